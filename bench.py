@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the FRIRL hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run times the headline leg alone: set-up, W warm-up and exactly K timed steps of the rule-distance sweep, the
+result line (ms_per_step = wall time of the K steps / K).  --dump-outputs DIR writes what the last timed step computed
+(dump_sample) as DIR/<name>.npy; the inputs depend only on the arguments.  --full adds everything else described below:
+the f64-layout timing and parity gates, the env-steps, learning and evaluation legs, the other configurations and the
+CPU baseline.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: before anything touches the
 GPU it starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`
@@ -139,6 +145,52 @@ def make_queries(prob, device, seed):
     return (lo + (hi - lo) * torch.rand((prob.E, prob.nant), generator=g, device=device, dtype=torch.float64)).contiguous()
 
 
+DUMP_BYTES = 48 << 20       # --dump-outputs: the sampled distance rows stay under this (the exact-hit vector comes on top)
+
+
+def dump_sample(dists, hit, R):
+    """What the timed sweep returns to its caller, copied to the host for --dump-outputs: "rule_distances" = the R distances of a
+    fixed, seeded sample of at most 64 environments (rows in ascending env order; the whole (E, R) array is up to several GB),
+    "exact_hit" = the exact-hit rule index of every environment (-1: none).  Both float64 (the hit indices are exact in it)."""
+    import numpy as np
+    import torch
+    E = dists.shape[0]
+    k = max(1, min(E, 64, DUMP_BYTES // (8 * R)))
+    rows = np.sort(np.random.default_rng(20240601).choice(E, size=k, replace=False))
+    d = dists[torch.from_numpy(rows).to(dists.device), :R].cpu().numpy()
+    return {"rule_distances": np.ascontiguousarray(d, dtype=np.float64), "exact_hit": hit.cpu().numpy().astype(np.float64)}
+
+
+def write_outputs(outdir, outputs):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+def roofline_record(name, w, compressed, kern_ms, evals, moved_bytes, contract_bytes):
+    """HBM roofline of the timed sweep from its average launch time (no run of its own)."""
+    achieved = moved_bytes / (kern_ms * 1e-3) / 1e9
+    roof = {"bound": "hbm", "kernel": "rule_distance_idx_kernel" if compressed else "rule_distance_kernel",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+            "algorithmic_bytes_per_launch": moved_bytes, "bytes_per_eval": moved_bytes / evals, "avg_launch_ms": kern_ms,
+            "layout": "u16 universe-index mirror + LDS VE tables (bit-identical to the f64 columns)" if compressed else "f64 SoA columns",
+            "contract_bytes_per_launch": contract_bytes, "contract_equiv_GBps": contract_bytes / (kern_ms * 1e-3) / 1e9,
+            "contract_frac": contract_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "note": ("achieved / frac = bytes this kernel moves (2*nant B of 16-bit indices read + 8 B written per eval) / avg launch time; "
+                     "contract_* prices the same launch at the reference's f64 layout (8*(nant+1) B per eval) and may exceed the peak: "
+                     "a compression effect, not a bandwidth") if compressed else "f64 layout: contract bytes == moved bytes"}
+    try:
+        tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json"))).get(name)
+        if tr and w["E"] == WORKLOADS[name]["E"]:
+            roof["traffic"] = tr["fetch_bytes"] + tr["write_bytes"]
+            roof["traffic_source"] = tr["source"]
+            roof["traffic_kernel"] = tr.get("kernel")
+    except (OSError, ValueError):
+        pass
+    return roof
+
+
 # ---- CPU baseline (rank 0, N = 1; time-boxed) ---------------------------------------------------------------------------
 def _harness_bench(harness, nant, U, R, nq):
     out = subprocess.run([harness, "bench", str(nant), str(U), str(R), str(nq)], check=True, capture_output=True, text=True).stdout
@@ -247,21 +299,31 @@ class Bench:
             return frirl_amd.demo_batch(w["env"], w["E"], w["R"], maxR, self.device, seed=env_start, keep_rant=keep_rant)
         return synth_problem(w, self.device, seed=env_start)
 
-    def rule_distance_leg(self, name, w, prob, x, steps, warmup):
-        """The metric's first half.  Returns (value record, roofline record)."""
+    def rule_distance_leg(self, name, w, prob, x, steps, warmup, full=True, keep_outputs=False):
+        """The metric's first half.  Returns (value record, roofline record).  full=False: the timed sweep alone (no f64-layout
+        timing, no parity gate).  keep_outputs: the value record carries "outputs", host copies of what the last timed step
+        computed (see dump_sample)."""
         import frirl_amd
         torch = self.torch
         E, R, nant = w["E"], w["R"], w["nant"]
         dists = torch.empty((E, prob.maxR), dtype=torch.float64, device=self.device)
         hit = torch.empty((E,), dtype=torch.int32, device=self.device)
         dt, kern_ms = self.timed(lambda: prob.rule_distance(x, ruledists=dists, hit=hit, stream=self.stream), steps, warmup)
+        outputs = dump_sample(dists, hit, R) if keep_outputs else None
         compressed = prob.uidx is not None and bool(frirl_amd.lib().five_hip_rule_distance_uses_uidx(prob.nant, prob.U))
+        nhits = float((hit >= 0).sum().item())
+        evals = float(E) * R
+        contract_bytes = 8.0 * (nant + 1) * evals              # SURVEY 8d U1: the reference's f64 SoA layout, 8*nant read + 8 written per eval
+        moved_bytes = (2.0 * nant + 8.0) * evals if compressed else contract_bytes
+        roof = roofline_record(name, w, compressed, kern_ms, evals, moved_bytes, contract_bytes)
+        val = {"evals_per_s_rank": evals * steps / dt, "wall_s": dt, "exact_hits_rank": nhits, "outputs": outputs}
+        if not full:
+            return val, roof
         f64_ms = None
         if compressed:
             # the same sweep on the reference's f64 SoA columns (no index mirror), timed beside the shipped path
             plain = frirl_amd.Problem(prob.u, prob.ve, prob.rb, prob.nrules)
             _, f64_ms = self.timed(lambda: plain.rule_distance(x, ruledists=dists, hit=hit, stream=self.stream), max(steps // 3, 5), 2)
-        nhits = float((hit >= 0).sum().item())
         # parity gate, outside the timed region: sampled environments (first, last, middle, either side of work-item batch edges)
         # against the oracle -- distances bit-exact and the exact-hit index, for every layout that was timed
         from tests import gates
@@ -278,32 +340,12 @@ class Bench:
             gate["layouts"].append("f64 columns")
             del d2, h2
         del dists
-        evals = float(E) * R
-        contract_bytes = 8.0 * (nant + 1) * evals              # the reference's f64 SoA layout, 8*nant read + 8 written per eval
-        moved_bytes = (2.0 * nant + 8.0) * evals if compressed else contract_bytes
-        achieved = moved_bytes / (kern_ms * 1e-3) / 1e9
-        roof = {"bound": "hbm", "kernel": "rule_distance_idx_kernel" if compressed else "rule_distance_kernel",
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                "algorithmic_bytes_per_launch": moved_bytes, "bytes_per_eval": moved_bytes / evals, "avg_launch_ms": kern_ms,
-                "layout": "u16 universe-index mirror + LDS VE tables (bit-identical to the f64 columns)" if compressed else "f64 SoA columns",
-                "contract_bytes_per_launch": contract_bytes, "contract_equiv_GBps": contract_bytes / (kern_ms * 1e-3) / 1e9,
-                "contract_frac": contract_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "note": ("achieved / frac = bytes this kernel moves (2*nant B of 16-bit indices read + 8 B written per eval) / avg launch time; "
-                         "contract_* prices the same launch at the reference's f64 layout (8*(nant+1) B per eval) and may exceed the peak: "
-                         "a compression effect, not a bandwidth") if compressed else "f64 layout: contract bytes == moved bytes"}
         if f64_ms:
             roof["f64_layout"] = {"kernel": "rule_distance_kernel", "avg_launch_ms": f64_ms, "evals_per_s": evals / (f64_ms * 1e-3),
                                   "achieved": contract_bytes / (f64_ms * 1e-3) / 1e9, "frac": contract_bytes / (f64_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                   "note": "same sweep streaming the reference's f64 columns (contract bytes == moved bytes)"}
-        try:
-            tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json"))).get(name)
-            if tr and w["E"] == WORKLOADS[name]["E"]:
-                roof["traffic"] = tr["fetch_bytes"] + tr["write_bytes"]
-                roof["traffic_source"] = tr["source"]
-                roof["traffic_kernel"] = tr.get("kernel")
-        except (OSError, ValueError):
-            pass
-        return {"evals_per_s_rank": evals * steps / dt, "wall_s": dt, "exact_hits_rank": nhits, "parity_gate": gate}, roof
+        val["parity_gate"] = gate
+        return val, roof
 
     def env_steps_leg(self, w, prob, agent, envs, nsteps, warmup, name=None):
         """The metric's second half: whole environment steps (do_action, reward, quantise, greedy sweep, SARSA update)."""
@@ -628,8 +670,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=0, help="override environments per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; rank 0's shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the f64-layout timing and parity gate of the headline sweep, the env-steps, learning and evaluation legs, "
+                         "the other configurations and the CPU baseline (the --no-* options below trim this)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--env-steps", type=int, default=20, help="timed environment steps of the fused SARSA leg")
+    ap.add_argument("--env-steps", type=int, default=20, help="timed environment steps of the fused SARSA leg (--full)")
     ap.add_argument("--no-env-steps", action="store_true")
     ap.add_argument("--no-learn", action="store_true", help="skip the real-learning and evaluation legs")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the cfg2 / cfg3 / cfg5 sub-records")
@@ -675,28 +722,31 @@ def main():
     E, R, nant = w["E"], w["R"], w["nant"]
     env_start, _ = D.shard(E * world, world, rank)            # this rank's slice of the global env ids
 
-    # ---- legs 1 + 2 on the headline workload -------------------------------------------------------------------------
-    prob, agent, envs = B.build(w, env_start)
+    # ---- leg 1 (the headline; all a plain run does) + leg 2 on the headline workload ------------------------------------
+    prob, agent, envs = B.build(w, env_start, keep_rant=args.full)     # raw antecedents: kept for the env-steps leg alone
     x = make_queries(prob, device, seed=env_start)
-    val, roof = B.rule_distance_leg(args.workload, w, prob, x, args.steps, args.warmup)
+    val, roof = B.rule_distance_leg(args.workload, w, prob, x, args.steps, args.warmup, full=args.full,
+                                    keep_outputs=args.dump_outputs is not None and rank == 0)
+    if val["outputs"] is not None:
+        write_outputs(args.dump_outputs, val["outputs"])
     nhits = torch.tensor([val["exact_hits_rank"]], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(nhits)
     env_leg = None
-    if agent is not None and not args.no_env_steps:
+    if args.full and agent is not None and not args.no_env_steps:
         env_leg = B.env_steps_leg(w, prob, agent, envs, args.env_steps, min(args.warmup, 3), args.workload)
     del prob, agent, envs, x
     torch.cuda.empty_cache()
 
     # ---- legs 3 + 4 ----------------------------------------------------------------------------------------------
     legs = None
-    if w["env"] and not args.no_learn:
+    if args.full and w["env"] and not args.no_learn:
         legs = learning_and_evaluation(B, w, world, rank)
         torch.cuda.empty_cache()
 
     # ---- the other BASELINE configurations, same two legs, shorter (N = 1 only: they are per-GPU workloads) -----------
     others = None
-    if world == 1 and not args.no_other_configs and not args.envs:
+    if args.full and world == 1 and not args.no_other_configs and not args.envs:
         others = {}
         for name, ow in WORKLOADS.items():
             if name == args.workload:
@@ -733,12 +783,13 @@ def main():
         }
         if env_leg:
             out["env_steps"] = env_leg
-        out["parity_gate"] = val["parity_gate"]
+        if args.full:
+            out["parity_gate"] = val["parity_gate"]
         if legs:
             out.update(legs)
         if others:
             out["other_configs"] = others
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,10 +1,13 @@
 """bench.py's own rank launcher (no GPU needed): `python bench.py --gpus N` with no WORLD_SIZE in the environment must
 start N ranks itself (torch.distributed.run as a CHILD process, started before anything touches the GPU), relay rank 0's
-JSON line and the child's exit code.  --rank-probe replaces the GPU legs by a gloo all-reduce that counts the ranks."""
+JSON line and the child's exit code.  --rank-probe replaces the GPU legs by a gloo all-reduce that counts the ranks.
+The one GPU test here runs a small plain benchmark with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,3 +40,36 @@ def test_launcher_parent_does_not_import_torch():
     assert "launch_ranks(args.gpus" in head
     launcher = src.split("def launch_ranks")[1].split("def rank_probe")[0]
     assert "import torch" not in launcher and "os.exec" not in launcher
+
+
+def test_plain_and_full_options_exist():
+    p = run(["--help"])
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """A plain run times exactly --steps steps of the headline sweep, prints the contract keys and none of the --full legs;
+    --dump-outputs writes float64 arrays under 64 MB that two runs with the same arguments reproduce bit for bit."""
+    import numpy as np
+    recs = []
+    for tag in ("a", "b"):
+        p = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--envs", "96", "--dump-outputs", str(tmp_path / tag)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64"
+    for k in ("env_steps", "learning", "evaluation", "other_configs", "cpu_baseline", "parity_gate"):
+        assert k not in rec, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["exact_hit.npy", "rule_distances.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and (a.view(np.uint64) == b.view(np.uint64)).all(), n
+    d, hit = np.load(tmp_path / "a" / "rule_distances.npy"), np.load(tmp_path / "a" / "exact_hit.npy")
+    assert d.shape == (64, rec["config"]["rules_per_env"]) and hit.shape == (96,) and np.isfinite(d).all() and (d >= 0).all()

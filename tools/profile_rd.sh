@@ -7,7 +7,7 @@ TAG=$1; WL=$2; shift 2
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-ARGS="--workload $WL --no-cpu-baseline --no-learn --no-env-steps --no-other-configs"
+ARGS="--workload $WL --full --no-cpu-baseline --no-learn --no-env-steps --no-other-configs"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$REPO/bench.py" $ARGS --steps 20 --warmup 3 "$@" > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 "$REPO/bench.py" $ARGS --steps 4 --warmup 1 "$@" > "$OUT/bench_pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
