@@ -93,6 +93,10 @@ SIGNATURES = {
     "five_hip_rule_distance_uses_uidx": (C.c_int, [C.c_int32, C.c_int32]),
     "frirl_hip_step_uses_uidx": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "five_hip_rule_distance": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "five_hip_rule_distance_packed_words": (C.c_int, [C.c_int32, C.c_int32]),
+    "frirl_hip_pack_indices": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p]),
+    "five_hip_rule_distance_packed": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
     "five_hip_vag_concl": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "five_hip_vag_concl_weight": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_get_best_action": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -246,20 +250,53 @@ class Problem:
             assert uidx.is_cuda and uidx.dtype == torch.int16 and uidx.shape == (self.E, self.nant, self.maxR) and self.U <= 32767
             self.uidx = uidx.contiguous()
         self.tables = Tables(self.nant, self.U, self.u.data_ptr(), self.ve.data_ptr())
-        self.bases = RuleBases(self.E, self.maxR, self.rb.data_ptr(), self.nrules.data_ptr(),
-                               self.uidx.data_ptr() if self.uidx is not None else None)
+        self._bases = RuleBases(self.E, self.maxR, self.rb.data_ptr(), self.nrules.data_ptr(),
+                                self.uidx.data_ptr() if self.uidx is not None else None)
+        # packed copy of the index mirror (6-bit fields, five_hip_rule_distance_packed) for the shapes that form serves: derived
+        # data, repacked before the next scan whenever uidx may have changed (see `bases` and _pidx_current)
+        self.pidx = None
+        self._pidx_key = None
+        W = lib().five_hip_rule_distance_packed_words(self.nant, self.U) if self.uidx is not None else 0
+        if W > 0:
+            self.pidx = torch.empty((self.E, W, self.maxR), dtype=torch.int32, device=self.uidx.device)
+            self._pack(None)
+
+    @property
+    def bases(self):
+        """The frirl_hip_rulebases handle for native calls.  Any of them may append, merge or compact rules (uidx changes
+        under the packed mirror), so handing it out marks the mirror stale; the read-only scans below use the private one.
+        Take it afresh for every native call: a handle kept across a rule_distance would escape the staleness mark."""
+        self._pidx_key = None
+        return self._bases
+
+    def _pack(self, stream):
+        check(lib().frirl_hip_pack_indices(C.byref(self.tables), C.byref(self._bases), _ptr(self.pidx), _stream(stream)),
+              "frirl_hip_pack_indices")
+        self._pidx_key = (self.uidx.data_ptr(), self.uidx._version)
+
+    def _pidx_current(self, stream):
+        """The packed mirror, repacked on `stream` first if uidx was handed to native code (bases) or edited in place since."""
+        if self._pidx_key != (self.uidx.data_ptr(), self.uidx._version):
+            self._pack(stream)
+        return self.pidx
 
     def rule_distance(self, x, ruledists=None, hit=None, materialise=True, stream=None):
-        """five_hip_rule_distance: returns (ruledists [E,maxR] or None, hit [E] int32 with -1 = none)."""
+        """five_hip_rule_distance (five_hip_rule_distance_packed while the packed mirror exists): returns (ruledists [E,maxR]
+        or None, hit [E] int32 with -1 = none)."""
         import torch
         assert x.is_cuda and x.dtype == torch.float64 and x.shape == (self.E, self.nant) and x.is_contiguous()
         if materialise and ruledists is None:
             ruledists = torch.empty((self.E, self.maxR), dtype=torch.float64, device=x.device)
         if hit is None:
             hit = torch.empty((self.E,), dtype=torch.int32, device=x.device)
-        rc = lib().five_hip_rule_distance(C.byref(self.tables), C.byref(self.bases), _ptr(x),
-                                          _ptr(ruledists) if materialise else None, _ptr(hit), _stream(stream))
-        check(rc, "five_hip_rule_distance")
+        if self.pidx is not None:
+            rc = lib().five_hip_rule_distance_packed(C.byref(self.tables), C.byref(self._bases), _ptr(self._pidx_current(stream)), _ptr(x),
+                                                     _ptr(ruledists) if materialise else None, _ptr(hit), _stream(stream))
+            check(rc, "five_hip_rule_distance_packed")
+        else:
+            rc = lib().five_hip_rule_distance(C.byref(self.tables), C.byref(self._bases), _ptr(x),
+                                              _ptr(ruledists) if materialise else None, _ptr(hit), _stream(stream))
+            check(rc, "five_hip_rule_distance")
         return (ruledists if materialise else None), hit
 
     def vag_concl(self, x, p=0, stream=None):
@@ -268,7 +305,7 @@ class Problem:
         assert x.is_cuda and x.dtype == torch.float64 and x.shape == (self.E, self.nant) and x.is_contiguous()
         conc = torch.empty((self.E,), dtype=torch.float64, device=x.device)
         hit = torch.empty((self.E,), dtype=torch.int32, device=x.device)
-        check(lib().five_hip_vag_concl(C.byref(self.tables), C.byref(self.bases), p, _ptr(x), _ptr(conc), _ptr(hit), _stream(stream)),
+        check(lib().five_hip_vag_concl(C.byref(self.tables), C.byref(self._bases), p, _ptr(x), _ptr(conc), _ptr(hit), _stream(stream)),
               "five_hip_vag_concl")
         return conc, hit
 
@@ -279,7 +316,7 @@ class Problem:
         if weights is None:
             weights = torch.full((self.E, self.maxR), float("nan"), dtype=torch.float64, device=x.device)
         hit = torch.empty((self.E,), dtype=torch.int32, device=x.device)
-        check(lib().five_hip_vag_concl_weight(C.byref(self.tables), C.byref(self.bases), p, _ptr(x), _ptr(weights), _ptr(hit),
+        check(lib().five_hip_vag_concl_weight(C.byref(self.tables), C.byref(self._bases), p, _ptr(x), _ptr(weights), _ptr(hit),
                                               _stream(stream)), "five_hip_vag_concl_weight")
         return weights, hit
 
@@ -290,7 +327,7 @@ class Problem:
         A = action_ve.numel()
         actconc = torch.empty((self.E, A), dtype=torch.float64, device=states.device)
         best = torch.empty((self.E,), dtype=torch.int32, device=states.device)
-        check(lib().frirl_hip_get_best_action(C.byref(self.tables), C.byref(self.bases), p, _ptr(states), _ptr(action_ve), A,
+        check(lib().frirl_hip_get_best_action(C.byref(self.tables), C.byref(self._bases), p, _ptr(states), _ptr(action_ve), A,
                                               _ptr(actconc), _ptr(best), _stream(stream)), "frirl_hip_get_best_action")
         return actconc, best
 
@@ -301,7 +338,7 @@ class Problem:
         Q = x.shape[0]
         conc = torch.empty((Q,), dtype=torch.float64, device=x.device)
         hit = torch.empty((Q,), dtype=torch.int32, device=x.device)
-        check(lib().five_hip_vag_concl_shared(C.byref(self.tables), C.byref(self.bases), p, Q, _ptr(x), _ptr(conc), _ptr(hit), _stream(stream)),
+        check(lib().five_hip_vag_concl_shared(C.byref(self.tables), C.byref(self._bases), p, Q, _ptr(x), _ptr(conc), _ptr(hit), _stream(stream)),
               "five_hip_vag_concl_shared")
         return conc, hit
 
@@ -312,7 +349,7 @@ class Problem:
         Q, A = states.shape[0], action_ve.numel()
         actconc = torch.empty((Q, A), dtype=torch.float64, device=states.device)
         best = torch.empty((Q,), dtype=torch.int32, device=states.device)
-        check(lib().frirl_hip_get_best_action_shared(C.byref(self.tables), C.byref(self.bases), p, Q, _ptr(states), _ptr(action_ve), A, _ptr(actconc),
+        check(lib().frirl_hip_get_best_action_shared(C.byref(self.tables), C.byref(self._bases), p, Q, _ptr(states), _ptr(action_ve), A, _ptr(actconc),
                                                      _ptr(best), _stream(stream)), "frirl_hip_get_best_action_shared")
         return actconc, best
 

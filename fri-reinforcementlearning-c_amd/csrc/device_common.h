@@ -66,6 +66,14 @@ __device__ __forceinline__ double2 lds_table_pair(const double *tab_k, uint32_t 
     return v;
 }
 
+// Packed antecedent record: the universe indices of one rule as BITS-bit fields, FPW per 32-bit word, field k in word k / FPW at
+// shift BITS * (k % FPW) (the learner's tile records, learn_kernel.h, and the rule-distance scan's pidx mirror, five_rule_distance.hip).
+template <int BITS>
+struct Packed {
+    static constexpr int FPW = 32 / BITS;                       // fields per 32-bit word
+    static constexpr int words(int nant) { return (nant + FPW - 1) / FPW; }
+};
+
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v)
 {
 #pragma unroll
@@ -157,6 +165,7 @@ struct Options {
     int rd_nt;            // rule-distance scan: non-temporal variant, -1 = shipped              (FRIRL_HIP_RD_NT)
     int rd_persist;       // compressed rule-distance scan: -1 = by table size, 0 = one workgroup per item, 1 = persistent (FRIRL_HIP_RD_PERSIST)
     int rd_order;         // rule-distance scan item order: 0 = chunk index fastest (shipped), 1 = environment fastest (FRIRL_HIP_RD_ORDER)
+    int rd_packed;        // five_hip_rule_distance_packed: 1 = stream the packed 6-bit index words (shipped), 0 = the 16-bit mirror (FRIRL_HIP_RD_PACKED)
     int step_wave;        // episode step: 1 = one wave per environment, 0 = 256 threads, -1 = by shape (FRIRL_HIP_STEP_WAVE)
     int step_track;       // episode step: spread candidates tracked in the fused sweep: 1 / 0, -1 = large rule bases only (FRIRL_HIP_STEP_TRACK)
     int lanes_slices;     // lane groups: rule slices per conclusion, 0 = by shape               (FRIRL_HIP_LANES_SLICES)

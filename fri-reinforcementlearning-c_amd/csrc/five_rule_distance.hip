@@ -14,7 +14,7 @@
 //   every lane loads two rules per column and instruction (16 B of f64 / 4 B of u16 indices): a wave instruction reads
 //   1 KiB / 256 contiguous bytes and stores 1 KiB of contiguous distances; wider per-lane index loads (8 / 16 B) leave
 //   the stores only half / quarter dense and measured 0.42 / 0.19.
-// Three kernels, the same arithmetic on the same doubles (bit-identical results):
+// Four kernels, the same arithmetic on the same doubles (bit-identical results):
 //   rule_distance_kernel          f64 VE columns (the reference's layout); one workgroup per item, hardware dispatch
 //                                 order = item order;
 //   rule_distance_idx_kernel      16-bit universe-index mirror, VE values gathered from an LDS copy of the tables;
@@ -28,6 +28,9 @@
 //                                 VE values of every environment are computed once by observe_reset_kernel (which also
 //                                 resets the hit words and the counter): no barrier, no LDS write and no dependent
 //                                 global chain per item.  0.74-0.79 moved at cfg3 (round 1: 0.55), 0.69 at cfg5 (0.56).
+//   rule_distance_pk_kernel       PACKED index mirror (pidx: 6-bit fields, five per 32-bit word; five_hip_rule_distance_packed)
+//                                 for small tables with U <= 64: the idx kernel's items and stores, 4 B of indices per rule
+//                                 for nant <= 5 instead of 2 * nant -- at cfg4 12 B moved per evaluation instead of 18.
 // First exact hit: per-lane minimum index -> wave butterfly -> (LDS ->) one integer atomicMin per workgroup / item
 // (deterministic; only taken when a hit exists).
 // "rd_*" / "no_uidx" options (frirl_hip_set_option) are experiment hooks (tools/ab_rd.py); unset, the shipped configuration runs.
@@ -198,6 +201,135 @@ __global__ __launch_bounds__(BLOCK) void rule_distance_idx_kernel(
         unsigned m = red_s[0];
         for (int w = 1; w < BLOCK / FRIRL_WAVE; w++) m = red_s[w] < m ? red_s[w] : m;
         if (m != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], m);
+    }
+}
+
+// Packed-antecedent form (pidx mirror, five_hip_rule_distance_packed): the universe indices of a rule as BITS-bit fields of
+// W = Packed<BITS>::words(NANT) 32-bit words, pidx[e][w][r] -- 4 B per rule for nant <= 5 at BITS 6 instead of 2 * nant.  Small
+// tables only (one workgroup per item, the table refilled per workgroup), laid out in LDS with a row stride of 2^BITS entries:
+// a field becomes its table entry's byte offset with one shift and one mask, and the row offset is the LDS read's immediate.
+// Same item order, two adjacent rules per lane (one 8 B load per word and column set: 512 contiguous bytes per wave), the
+// same 16 B distance stores, the same subtract / multiply / add sequence as the kernels above (bit-identical results).
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+
+template <int BITS>
+__device__ __forceinline__ double pk_table_entry(const double *__restrict__ tab_k, uint32_t w, int sh)
+{
+    constexpr uint32_t FM = ((1u << BITS) - 1u) << 3;
+    const uint32_t off = (sh >= 3 ? (w >> (sh - 3)) : (w << (3 - sh))) & FM;     // 8 * index
+    return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(tab_k) + off);
+}
+
+template <int NANT, int BITS>
+__device__ __forceinline__ double2 pk_pair_distance(const u32x2_t (&w)[Packed<BITS>::words(NANT)], const double (&q)[NANT],
+                                                    const double *__restrict__ tab_s)
+{
+    constexpr int FPW = Packed<BITS>::FPW, TS = 1 << BITS;
+    double d0 = q[0] - pk_table_entry<BITS>(tab_s, w[0].x, 0), d1 = q[0] - pk_table_entry<BITS>(tab_s, w[0].y, 0);
+    double a0 = d0 * d0, a1 = d1 * d1;
+#pragma unroll
+    for (int k = 1; k < NANT; k++) {
+        const int sh = BITS * (k % FPW);
+        d0 = q[k] - pk_table_entry<BITS>(tab_s + k * TS, w[k / FPW].x, sh);
+        d1 = q[k] - pk_table_entry<BITS>(tab_s + k * TS, w[k / FPW].y, sh);
+        const double s0 = d0 * d0, s1 = d1 * d1;
+        a0 = a0 + s0;
+        a1 = a1 + s1;
+    }
+    double2 d;
+    d.x = __dsqrt_rn(a0);
+    d.y = __dsqrt_rn(a1);
+    return d;
+}
+
+template <int NANT, bool WRITE, int UNROLL, int BITS>
+__global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
+    const double *__restrict__ u, const double *__restrict__ ve, int U, const uint32_t *__restrict__ pidx,
+    const int32_t *__restrict__ nrules, int maxR, const double *__restrict__ x, double *__restrict__ dists,
+    uint32_t *__restrict__ hit, int rules_per_block, int cpe, int E, int env_fastest)
+{
+    constexpr int W = Packed<BITS>::words(NANT), TS = 1 << BITS;
+    __shared__ double tab_s[NANT * TS];          // [NANT][2^BITS] vague environments (static: row offsets are immediates)
+    __shared__ double q_s[NANT];
+    __shared__ unsigned red_s[FRIRL_WAVES_PER_BLOCK];
+    int e, c;
+    item_to_env_chunk(blockIdx.x, cpe, E, env_fastest != 0, e, c);
+    const int R = nrules[e];
+    const int r0 = c * rules_per_block;
+    if (r0 >= R) return;
+    int r_end = r0 + rules_per_block;
+    if (r_end > R) r_end = R;
+
+    const uint32_t *__restrict__ base = pidx + (size_t)e * W * maxR;
+    constexpr int STEP = FRIRL_BLOCK * 2;
+    u32x2_t w[UNROLL][W];
+    auto load = [&](int r) {
+#pragma unroll
+        for (int j = 0; j < UNROLL; j++) {
+            const int rr = r + j * STEP;
+            if (rr < r_end) {                    // rr even and maxR even: the pair is 8-byte aligned and inside the row
+#pragma unroll
+                for (int k = 0; k < W; k++) w[j][k] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(base + (size_t)k * maxR + rr));
+            }
+        }
+    };
+    int r = r0 + 2 * (int)threadIdx.x;
+    load(r);                                     // the first sweep's indices are in flight while the table is filled and x is snapped
+
+    for (int i = threadIdx.x; i < NANT * TS; i += FRIRL_BLOCK) {
+        const int k = i >> BITS, j = i & (TS - 1);
+        tab_s[i] = j < U ? ve[k * U + j] : 0.0;  // padding: what the odd last rule's unused column may point at
+    }
+    if (threadIdx.x < NANT) q_s[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
+    __syncthreads();
+    double q[NANT];
+#pragma unroll
+    for (int k = 0; k < NANT; k++) q[k] = q_s[k];
+
+    double *__restrict__ out = WRITE ? dists + (size_t)e * maxR : nullptr;
+    unsigned best = FRIRL_HIP_NO_HIT;
+
+    for (; r < r_end; r += STEP * UNROLL) {
+        if (r != r0 + 2 * (int)threadIdx.x) load(r);
+#pragma unroll
+        for (int j = 0; j < UNROLL; j++) {
+            const int rr = r + j * STEP;
+            if (rr < r_end) {
+                const double2 d = pk_pair_distance<NANT, BITS>(w[j], q, tab_s);
+                if (WRITE) { __builtin_nontemporal_store(d.x, out + rr); __builtin_nontemporal_store(d.y, out + rr + 1); }
+                if (d.y == 0.0 && rr + 1 < R) best = min(best, (unsigned)(rr + 1));
+                if (d.x == 0.0) best = min(best, (unsigned)rr);
+            }
+        }
+    }
+    best = wave_min_u32(best);
+    if ((threadIdx.x & (FRIRL_WAVE - 1)) == 0) red_s[threadIdx.x / FRIRL_WAVE] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned m = red_s[0];
+        for (int v = 1; v < FRIRL_WAVES_PER_BLOCK; v++) m = red_s[v] < m ? red_s[v] : m;
+        if (m != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], m);
+    }
+}
+
+// pidx[e][w][r] from uidx[e][k][r] for every one of the maxR columns (fields masked to BITS bits, unused high bits zero).
+template <int BITS>
+__global__ __launch_bounds__(FRIRL_BLOCK) void pack_indices_kernel(const uint16_t *__restrict__ uidx, int nant, int maxR, long total,
+                                                                   uint32_t *__restrict__ pidx)
+{
+    constexpr int FPW = Packed<BITS>::FPW;
+    const int W = (nant + FPW - 1) / FPW;
+    for (long i = (long)blockIdx.x * FRIRL_BLOCK + threadIdx.x; i < total; i += (long)gridDim.x * FRIRL_BLOCK) {
+        const long e = i / maxR;
+        const long r = i - e * maxR;
+        const uint16_t *__restrict__ src = uidx + (size_t)e * nant * maxR + r;
+        uint32_t *__restrict__ dst = pidx + (size_t)e * W * maxR + r;
+        for (int w = 0; w < W; w++) {
+            uint32_t v = 0u;
+            for (int f = 0; f < FPW && w * FPW + f < nant; f++)
+                v |= ((uint32_t)src[(size_t)(w * FPW + f) * maxR] & ((1u << BITS) - 1u)) << (BITS * f);
+            dst[(size_t)w * maxR] = v;
+        }
     }
 }
 
@@ -450,6 +582,52 @@ static int launch_nant(const frirl_hip_tables *t, const frirl_hip_rulebases *b, 
     return check_launch("five_hip_rule_distance");
 }
 
+// Packed form: BITS = 6 (U <= 64), small tables.  chunk = ONE sweep of the workgroup (256 threads x 2 rules x UNROLL column sets).
+// 8 column sets per lane (4096-rule items) for nant <= 5: tools/ab_rd.py, cfg4 / cfg2, medians of 5 x 20 launches on one box --
+// unroll 8: 1.175 / 0.135 ms, 4: 1.263 / 0.145, 2: 1.517 / 0.178; unroll 8 with 8192-rule items 1.180 / 0.204, with 16384 1.234;
+// unroll 4 with 4096-rule items 1.202 / 0.139, with 8192 1.212 (the 16-bit mirror: 1.585 / 0.149).
+static constexpr int RD_PK_BITS = 6;
+
+static int packed_words(int nant, int U)
+{
+    if (nant < 1 || nant > FRIRL_HIP_MAX_NANT || U < 2 || U > (1 << RD_PK_BITS)) return 0;
+    if (sizeof(double) * nant * (size_t)U > RD_SMALL_TABLE_BYTES) return 0;
+    return Packed<RD_PK_BITS>::words(nant);
+}
+
+template <int NANT>
+struct RdPkConfig {
+    static constexpr int UNROLL = NANT <= 5 ? 8 : 4;
+};
+
+template <int NANT>
+static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                         double *ruledists, uint32_t *hit, hipStream_t s)
+{
+    using namespace frirl_host;
+    constexpr int UP = RdPkConfig<NANT>::UNROLL;
+    const RdTune tn = rd_tune();
+    const int un = (NANT <= 5 && tn.unroll) ? tn.unroll : UP;              // tuning hook (experiments only)
+    RdGrid g;
+    if (!make_grid(b, tn.chunk > 0 ? tn.chunk : 2 * FRIRL_BLOCK * un, g)) { set_error("five_hip_rule_distance_packed: too many work items"); return FRIRL_HIP_EINVAL; }
+    if (hipMemsetAsync(hit, 0xFF, sizeof(uint32_t) * (size_t)b->E, s) != hipSuccess) return check_launch("five_hip_rule_distance_packed(memset)");
+#define VP(U_)                                                                                                                                          \
+    do {                                                                                                                                                \
+        if (ruledists)                                                                                                                                  \
+            hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, true, U_, RD_PK_BITS>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,  \
+                               b->nrules, b->maxR, x, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);                                   \
+        else                                                                                                                                            \
+            hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, false, U_, RD_PK_BITS>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx, \
+                               b->nrules, b->maxR, x, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);                                   \
+    } while (0)
+    if (NANT <= 5 && un == 8) VP(8);
+    else if (NANT <= 5 && un == 2) VP(2);
+    else if (NANT <= 5 && un == 1) VP(1);
+    else VP(UP);
+#undef VP
+    return check_launch("five_hip_rule_distance_packed");
+}
+
 }  // namespace frirl
 
 extern "C" int five_hip_rule_distance_uses_uidx(int32_t nant, int32_t U)
@@ -475,5 +653,52 @@ extern "C" int five_hip_rule_distance(const frirl_hip_tables *t, const frirl_hip
 #undef FRIRL_CASE
     }
     set_error("five_hip_rule_distance: unsupported nant=%d", t->nant);
+    return FRIRL_HIP_EINVAL;
+}
+
+extern "C" int five_hip_rule_distance_packed_words(int32_t nant, int32_t U)
+{
+    return frirl::packed_words(nant, U);
+}
+
+extern "C" int frirl_hip_pack_indices(const frirl_hip_tables *t, const frirl_hip_rulebases *b, uint32_t *pidx, void *stream)
+{
+    using namespace frirl_host;
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    if (!b->uidx || !pidx) { set_error("frirl_hip_pack_indices: NULL uidx/pidx"); return FRIRL_HIP_EINVAL; }
+    if (!frirl::packed_words(t->nant, t->U)) { set_error("frirl_hip_pack_indices: nant=%d U=%d is not served by the packed form", t->nant, t->U); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_device())) return rc;
+    const long total = (long)b->E * b->maxR;
+    long grid = (total + FRIRL_BLOCK - 1) / FRIRL_BLOCK;
+    if (grid > (long)frirl::device_cus() * 32) grid = (long)frirl::device_cus() * 32;
+    hipLaunchKernelGGL(frirl::pack_indices_kernel<frirl::RD_PK_BITS>, dim3((unsigned)grid), dim3(FRIRL_BLOCK), 0, as_stream(stream), b->uidx, t->nant,
+                       b->maxR, total, pidx);
+    return check_launch("frirl_hip_pack_indices");
+}
+
+extern "C" int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                             double *ruledists, uint32_t *hit, void *stream)
+{
+    using namespace frirl_host;
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    // shapes the packed form does not serve, and the A/B / test switches: the scan of five_hip_rule_distance (16-bit mirror or f64 columns)
+    const Options &o = opts();
+    if (!frirl::packed_words(t->nant, t->U) || !o.rd_packed || o.no_uidx || o.rd_persist == 1)
+        return five_hip_rule_distance(t, b, x, ruledists, hit, stream);
+    if (!pidx || !x || !hit) { set_error("five_hip_rule_distance_packed: NULL pidx/x/hit"); return FRIRL_HIP_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(pidx) & 7) { set_error("five_hip_rule_distance_packed: pidx must be 8-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if (ruledists && (reinterpret_cast<uintptr_t>(ruledists) & 15)) { set_error("five_hip_rule_distance_packed: ruledists must be 16-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_device())) return rc;
+    hipStream_t s = as_stream(stream);
+
+    switch (t->nant) {
+#define FRIRL_CASE(N) case N: return frirl::launch_packed<N>(t, b, pidx, x, ruledists, hit, s);
+        FRIRL_CASE(1) FRIRL_CASE(2) FRIRL_CASE(3) FRIRL_CASE(4) FRIRL_CASE(5) FRIRL_CASE(6) FRIRL_CASE(7) FRIRL_CASE(8)
+        FRIRL_CASE(9) FRIRL_CASE(10) FRIRL_CASE(11) FRIRL_CASE(12) FRIRL_CASE(13) FRIRL_CASE(14) FRIRL_CASE(15) FRIRL_CASE(16)
+#undef FRIRL_CASE
+    }
+    set_error("five_hip_rule_distance_packed: unsupported nant=%d", t->nant);
     return FRIRL_HIP_EINVAL;
 }

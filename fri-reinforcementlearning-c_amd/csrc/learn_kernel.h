@@ -72,12 +72,6 @@ struct LearnArgs {
 #define LT_MARK(i) do { } while (0)
 #endif
 
-template <int BITS>
-struct Packed {
-    static constexpr int FPW = 32 / BITS;                       // fields per 32-bit word
-    static constexpr int words(int nant) { return (nant + FPW - 1) / FPW; }
-};
-
 // ---- import / export: canonical rb[e][nant][r], uidx[e][k][r], prev_rconc[e][r]  <->  tiles --------------------------------
 template <int NANT, int BITS>
 __global__ __launch_bounds__(256) void learn_import_kernel(const LearnArgs la, int H, const double *__restrict__ prev_rconc)

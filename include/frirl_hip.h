@@ -97,7 +97,7 @@ int frirl_hip_device_count(void);                 /* number of visible gfx950 de
 int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, int64_t *hbm_bytes);
 
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
- * "rd_persist", "rd_order", "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -119,6 +119,19 @@ int frirl_hip_step_uses_uidx(int32_t nant, int32_t U, int32_t maxR, int32_t E);
  */
 int five_hip_rule_distance(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const double *x,
                            double *ruledists, uint32_t *hit, void *stream);
+
+/* The same scan streaming a PACKED copy of the index mirror: the universe indices of a rule as 6-bit fields, five per 32-bit
+ * word (field k in word k / 5 at shift 6 * (k % 5)), pidx[e][w][r] for w < W = ceil(nant / 5) -- 4 B per rule for nant <= 5
+ * instead of 2 * nant.  Same contract and bits as five_hip_rule_distance; pidx must be 8-byte aligned and packed from the
+ * CURRENT uidx (frirl_hip_pack_indices): the library does not keep it in sync when rules are appended, merged or removed.
+ * five_hip_rule_distance_packed_words(nant, U) = W for the shapes this form serves (U <= 64, nant * U * 8 <= 4 KiB), 0 for
+ * the rest; for those, and under the options rd_packed = 0, no_uidx = 1 or rd_persist = 1, the call runs
+ * five_hip_rule_distance on `b` (pidx is not read).
+ *   pidx [dev] [E][W][maxR] uint32 */
+int five_hip_rule_distance_packed_words(int32_t nant, int32_t U);
+int frirl_hip_pack_indices(const frirl_hip_tables *t, const frirl_hip_rulebases *b, uint32_t *pidx, void *stream);
+int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                  double *ruledists, uint32_t *hit, void *stream);
 
 /* ---- FIVE_vag_concl (reference src/five/FIVEVagConcl.c:64-351, default-flag live path) ------
  * Q value of one observation per rule base: the consequent of the first exact-hit rule, else the
