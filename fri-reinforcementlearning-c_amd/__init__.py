@@ -35,6 +35,7 @@ class RuleBases(C.Structure):
 
 MAX_GRID = 64
 ENV_KINDS = {"mountaincar": 0, "cartpole": 1, "acrobot": 2}
+ENV_EXTERNAL = 3          # FRIRL_HIP_ENV_EXTERNAL: the caller steps the environment (agent_begin / agent_observe)
 UPD_INACTIVE, UPD_EXACT, UPD_SPREAD, UPD_INSERTED, UPD_SKIPPED, UPD_FULL = range(6)
 
 
@@ -70,6 +71,12 @@ class ReduceResult(C.Structure):
     """struct frirl_hip_reduce_result (include/frirl_hip.h)."""
     _fields_ = [("rules_before", C.c_int32), ("rules_after", C.c_int32), ("rounds", C.c_int32), ("rollouts", C.c_int32),
                 ("steps_incremental", C.c_int32), ("reserved", C.c_int32), ("reward", C.c_double)]
+
+
+class AgentIO(C.Structure):
+    """struct frirl_hip_agent_io (include/frirl_hip.h)."""
+    _fields_ = [("obs", C.c_void_p), ("q_obs", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p), ("reset", C.c_void_p),
+                ("action_out", C.c_void_p), ("action_idx", C.c_void_p)]
 
 
 class ConvergenceDesc(C.Structure):
@@ -130,6 +137,9 @@ SIGNATURES = {
     "frirl_hip_episode_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p]),
     "frirl_hip_episode_step": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p]),
     "frirl_hip_episode_steps": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_void_p]),
+    "frirl_hip_agent_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]),
+    "frirl_hip_agent_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
+                                          C.c_void_p]),
     "frirl_hip_episode_run": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_int32, C.c_void_p]),
     "frirl_hip_convergence_init": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(ConvergenceDesc), C.c_void_p]),
     "frirl_hip_convergence_update": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
@@ -491,6 +501,49 @@ def episode_step(problem, agent, envs, stream=None):
                                        _stream(stream)), "frirl_hip_episode_step")
 
 
+def _agent_io(problem, obs, q_obs=None, reward=None, success=None, reset=None):
+    import torch
+    E, ns = problem.E, problem.nant - 1
+    assert obs.is_cuda and obs.dtype == torch.float64 and obs.shape == (E, ns) and obs.is_contiguous()
+    io = AgentIO()
+    io.obs = obs.data_ptr()
+    if q_obs is not None:
+        assert q_obs.dtype == torch.float64 and q_obs.shape == (E, ns) and q_obs.is_contiguous()
+        io.q_obs = q_obs.data_ptr()
+    if reward is not None:
+        assert reward.dtype == torch.float64 and reward.shape == (E,) and reward.is_contiguous()
+        assert success.dtype == torch.int32 and success.shape == (E,) and success.is_contiguous()
+        io.reward, io.success = reward.data_ptr(), success.data_ptr()
+    if reset is not None:
+        assert reset.dtype in (torch.uint8, torch.bool) and reset.shape == (E,) and reset.is_contiguous()
+        io.reset = reset.data_ptr()
+    action = torch.empty((E,), dtype=torch.float64, device=obs.device)
+    action_idx = torch.empty((E,), dtype=torch.int32, device=obs.device)
+    io.action_out, io.action_idx = action.data_ptr(), action_idx.data_ptr()
+    return io, action, action_idx
+
+
+def agent_begin(problem, agent, envs, obs, reset=None, stream=None):
+    """frirl_hip_agent_begin: start an episode from the caller's observations obs [E, nant-1] (float64, on the device) for the rows
+    selected by `reset` ([E] uint8 / bool, None = all).  Returns (action values [E] float64, action indices [E] int32): the first
+    action of every restarted row (the other rows' entries are not written).  Does not synchronise."""
+    io, action, action_idx = _agent_io(problem, obs, reset=reset)
+    check(lib().frirl_hip_agent_begin(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
+                                      _stream(stream)), "frirl_hip_agent_begin")
+    return action, action_idx
+
+
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None):
+    """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
+    last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
+    quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
+    rows that were done are not written.  Does not synchronise."""
+    io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
+    check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
+                                        _stream(stream)), "frirl_hip_agent_observe")
+    return action, action_idx
+
+
 def dist():
     """The multi-GPU helper module (fri-reinforcementlearning-c_amd/dist.py)."""
     import importlib.util
@@ -519,6 +572,10 @@ def dropin():
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
         D.frirl_demo_describe.restype = C.c_int
         D.frirl_demo_describe.argtypes = [C.c_char_p, ip, ip, ip, dp, dp, dp, ip, dp, dp, dp, dp, ip]
+        D.frirl_describe_tables.restype = C.c_int
+        D.frirl_describe_tables.argtypes = [C.c_int, C.c_int, ip, dp, dp, dp, dp, dp, dp]
+        D.frirl_gen_fixres_arr.restype = None
+        D.frirl_gen_fixres_arr.argtypes = [dp, C.c_int, C.c_double]
         _dropin = D
     return _dropin
 
@@ -753,13 +810,54 @@ def demo_agent(d, device, max_steps=None, p=0, **kw):
                  reward_good_above=d["reward_good_above"], qdiff_final_tolerance=d["qdiff_final_tolerance"], **kw)
 
 
-def demo_fresh_batch(env, E, maxR, device, start_states=None, **agent_kw):
-    """E agents of a demo starting from the reference's initial rule base: the 2^nant corner rules with Q = 0
-    (frirl_init_rb.c:99-126), grid min/max as antecedents.  Returns (Problem, Agent, Envs)."""
+def describe(states, actions, U, alpha, gamma, qdiff_pos, qdiff_neg, weight_thr=0.05, skip_rules=1, reward_good_above=0.0,
+             qdiff_final_tolerance=250.0, max_steps=1000, name="external"):
+    """Tables, grids and hyper-parameters of the caller's own environment, in the form demo_describe returns (kind = ENV_EXTERNAL),
+    built by the drop-in library's frirl_describe_tables (the reference's frirl_init_ve etc.); no GPU needed.
+      states:  one dict per state dimension (struct frirl_dimension_desc): "values" (its grid of possible rule places) or "n" (that
+               many values at step "div" around 0, frirl_gen_fixres_arr), "div" (values_div: the generic quantiser's step),
+               "steep" (values_steep, default 1.0), "default" (values_def, default 0.0), "universe_div" (step of its universe)
+      actions: dict with "values" (the action values) or "n" + "div", and "universe_div"
+      U:       points per universe (universe_len, the same for every dimension)"""
+    import numpy as np
+    D = dropin()
+    dims = list(states) + [dict(actions, steep=0.0, default=0.0)]
+    nant = len(dims)
+    assert 2 <= nant <= MAX_NANT - 1
+    grid = np.zeros((nant, MAX_GRID))
+    grid_len = np.zeros(nant, dtype=np.int32)
+    grid_div, values_def, steep, udiv = np.zeros(nant), np.zeros(nant), np.zeros(nant), np.zeros(nant)
+    for k, d in enumerate(dims):
+        if d.get("values") is not None:
+            v = np.asarray(d["values"], dtype=np.float64)
+        else:
+            v = np.zeros(int(d["n"]))
+            D.frirl_gen_fixres_arr(v.ctypes.data_as(C.POINTER(C.c_double)), len(v), float(d["div"]))
+        assert 1 <= len(v) <= MAX_GRID
+        grid[k, : len(v)] = v
+        grid_len[k] = len(v)
+        grid_div[k], values_def[k] = float(d.get("div", 0.0)), float(d.get("default", 0.0))
+        steep[k], udiv[k] = float(d.get("steep", 1.0)), float(d["universe_div"])
+    A = int(grid_len[-1])
+    u, ve, action_ve = np.zeros((nant, U)), np.zeros((nant, U)), np.zeros(A)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    if D.frirl_describe_tables(nant - 1, U, grid_len.ctypes.data_as(ip), grid.ctypes.data_as(dp), steep.ctypes.data_as(dp), udiv.ctypes.data_as(dp),
+                               u.ctypes.data_as(dp), ve.ctypes.data_as(dp), action_ve.ctypes.data_as(dp)) != 0:
+        raise ValueError("frirl_describe_tables refused the description (nant 2..15, U >= 2, 1..64 grid values, 1..32 actions, universe_div > 0)")
+    return dict(env=name, kind=ENV_EXTERNAL, nstates=nant - 1, nant=nant, U=U, A=A, u=u, ve=ve,
+                grids=[grid[k, : grid_len[k]].copy() for k in range(nant)], grid_div=grid_div, values_def=values_def, action_ve=action_ve,
+                alpha=float(alpha), gamma=float(gamma), qdiff_pos=float(qdiff_pos), qdiff_neg=float(qdiff_neg), weight_thr=float(weight_thr),
+                skip_rules=int(skip_rules), reward_good_above=float(reward_good_above), qdiff_final_tolerance=float(qdiff_final_tolerance),
+                max_steps=int(max_steps))
+
+
+def fresh_batch(desc, E, maxR, device, start_states=None, **agent_kw):
+    """E agents of the environment `desc` (describe / demo_describe) starting from the reference's initial rule base: the 2^nant
+    corner rules with Q = 0 (frirl_init_rb.c:99-126), grid min/max as antecedents.  Returns (Problem, Agent, Envs)."""
     import numpy as np
     import torch
-    d = demo_describe(env)
-    nant, U = d["nant"], d["U"]
+    d = desc
+    nant = d["nant"]
     ncorner = 2 ** nant
     assert maxR % 2 == 0 and maxR >= ncorner
     u_d, ve_d = torch.from_numpy(d["u"]).to(device), torch.from_numpy(d["ve"]).to(device)
@@ -776,3 +874,8 @@ def demo_fresh_batch(env, E, maxR, device, start_states=None, **agent_kw):
         ra = torch.from_numpy(np.ascontiguousarray(rant0[:, j])).to(device).expand(E, nant).contiguous()
         prob.add_rule(ra, torch.zeros((E,), dtype=torch.float64, device=device), rant_store=envs.rant)
     return prob, agent, envs
+
+
+def demo_fresh_batch(env, E, maxR, device, start_states=None, **agent_kw):
+    """E agents of a demo starting from the reference's initial rule base (fresh_batch).  Returns (Problem, Agent, Envs)."""
+    return fresh_batch(demo_describe(env), E, maxR, device, start_states=start_states, **agent_kw)

@@ -1,0 +1,54 @@
+// agent.hip -- frirl_episode with the caller's environment: frirl_hip_agent_begin / frirl_hip_agent_observe (include/frirl_hip.h).
+// The kernels are the fused episode kernels of sarsa.hip with EXT = true (episode_kernel.h), instantiated per antecedent count in
+// agent_i<N>.hip.
+#include "device_common.h"
+
+using namespace frirl_host;
+
+#define FRIRL_AGENT_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
+#define M(N) void frirl_agent_launch_##N(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
+                                         const frirl_hip_envs *ev, const frirl_hip_agent_io &io, hipStream_t s);
+FRIRL_AGENT_NANT_CASES(M)
+#undef M
+
+static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const frirl_hip_envs *ev,
+                            const frirl_hip_agent_io *io, bool begin, const char *who)
+{
+    if (!t || t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t ? t->nant : 0); return FRIRL_HIP_EINVAL; }
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    if (!a || !a->grid_values || !a->action_ve) { set_error("%s: NULL agent / grid_values / action_ve", who); return FRIRL_HIP_EINVAL; }
+    if (a->A < 1 || a->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, a->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
+    for (int k = 0; k < t->nant; k++)
+        if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    if (a->grid_len[t->nant - 1] != a->A) { set_error("%s: the action grid has %d values, A=%d", who, a->grid_len[t->nant - 1], a->A); return FRIRL_HIP_EINVAL; }
+    if (!ev || !ev->states || !ev->q_ant || !ev->fus || !ev->done || !ev->ep_steps || !ev->ep_reward) { set_error("%s: NULL env state", who); return FRIRL_HIP_EINVAL; }
+    if (!io || !io->obs || !io->action_out) { set_error("%s: NULL io / io->obs / io->action_out", who); return FRIRL_HIP_EINVAL; }
+    if (!begin && (!io->reward || !io->success)) { set_error("%s: NULL io->reward / io->success", who); return FRIRL_HIP_EINVAL; }
+    return check_device();
+}
+
+static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
+                      const frirl_hip_agent_io *io, void *stream, bool begin, const char *who)
+{
+    int rc = check_agent_call(t, b, agent, envs, io, begin, who);
+    if (rc) return rc;
+    switch (t->nant) {
+#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, as_stream(stream)); break;
+        FRIRL_AGENT_NANT_CASES(M)
+#undef M
+    }
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_agent_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                     const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream)
+{
+    return agent_call(t, b, agent, envs, io, stream, true, "frirl_hip_agent_begin");
+}
+
+extern "C" int frirl_hip_agent_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                       const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream)
+{
+    return agent_call(t, b, agent, envs, io, stream, false, "frirl_hip_agent_observe");
+}

@@ -1,0 +1,9 @@
+// agent_i4.hip -- the caller's-environment episode kernels (episode_kernel.h, EXT = true) for 4 antecedents, one file per count for a parallel build.
+#include "episode_kernel.h"
+
+void frirl_agent_launch_4(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                          const frirl_hip_agent_io &io, hipStream_t s)
+{
+    if (begin) frirl::launch_episode<4, true, true>(t, b, ag, ev, s, io);
+    else frirl::launch_episode<4, false, true>(t, b, ag, ev, s, io);
+}

@@ -6,114 +6,11 @@
 // runs inside one launch without inter-workgroup communication or atomics.
 #include <string.h>
 
-#include "envs.h"
-#include "sweeps.h"
+#include "episode_kernel.h"
 
 namespace frirl {
 
-struct StepShared {
-    double q_ant[FRIRL_HIP_MAX_NANT];      // raw antecedent values of (s, a)
-    double cur_q_ant[FRIRL_HIP_MAX_NANT];  // raw antecedent values of (s', a')
-    double ve1[FRIRL_HIP_MAX_NANT];        // VE values of q_ant
-    double ve2[FRIRL_HIP_MAX_NANT];        // VE values of cur_q_ant
-    double rant[FRIRL_HIP_MAX_NANT];       // grid-snapped antecedents of a would-be new rule
-    double ve3[FRIRL_HIP_MAX_NANT];        // their VE values
-    double cur_states[FRIRL_HIP_MAX_NANT];
-    unsigned idx3[FRIRL_HIP_MAX_NANT];    // universe indices of the snapped antecedents
-    double reward;
-    int success;
-    int same;
-};
-
-// test hook: frirl_hip_agent.debug_flags bit 0 forces update_rules' second sweep (the candidate path must give the same bits)
-__device__ __forceinline__ bool frirl_no_spread_candidates(const frirl_hip_agent &ag) { return (ag.debug_flags & 1) != 0; }
-
-// frirl_update_sarsa + update_rules (reference src/frirl/frirl_update_sarsa.c:348-385, :22-143).
-// `qp_known`: Q(s',a') already available (fused step: the greedy sweep produced it, identical
-// operands and order -- SURVEY 7(i)); otherwise it is computed by a sweep over ve2.
-template <int NANT, int BLOCK, bool TRACK = false, class COLS, class POW>
-__device__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u, const double *__restrict__ ve, int U, double *__restrict__ base,
-                                  int maxR, int32_t *nrules_e, const frirl_hip_agent &ag, StepShared &sh, double reward,
-                                  bool qp_known, double qp, int32_t *fus_e, double *rant_e, BlockRed<BLOCK> &red,
-                                  const QResult *rn_known, uint16_t *uidx_e, POW p, SpreadCand *slot, double *spread_ant_e = nullptr, int32_t *spread_R_e = nullptr)
-{
-    const int R = *nrules_e;
-    double q1[NANT], q2[NANT];
-#pragma unroll
-    for (int k = 0; k < NANT; k++) { q1[k] = sh.ve1[k]; q2[k] = sh.ve2[k]; }
-    double *qcol = base + (size_t)NANT * maxR;
-
-    if (!qp_known) {                                                        // :356  Q(s',a')
-        const QResult rp = sweep_q<NANT, BLOCK>(cols, qcol, R, q2, p, red);
-        qp = (rp.hit != FRIRL_HIP_NO_HIT) ? qcol[rp.hit] : rp.vagc / rp.ws;
-    }
-    const QResult rn = rn_known ? *rn_known : sweep_q<NANT, BLOCK, TRACK>(cols, qcol, R, q1, p, red, ag.weight_significant, slot);    // :357  Q(s,a)
-    const double qnow = (rn.hit != FRIRL_HIP_NO_HIT) ? qcol[rn.hit] : rn.vagc / rn.ws;
-    const double qdiff = ag.alpha * (reward + ag.gamma * qp - qnow);        // :358
-    int fus = *fus_e;
-    __syncthreads();   // every thread has read *fus_e / *nrules_e before thread 0 may rewrite them
-
-    if (qdiff > ag.qdiff_pos_boundary || qdiff < ag.qdiff_neg_boundary) {   // :363
-        // snap the antecedents to the allowed grid (check_possible_states, :146-170)
-        if (threadIdx.x < NANT) {
-            const int k = threadIdx.x;
-            const double r = check_possible_states(sh.q_ant[k], ag.grid_values + (size_t)k * FRIRL_HIP_MAX_GRID, ag.grid_len[k]);
-            sh.rant[k] = r;
-            const double *uni = u + (size_t)k * U;
-            const unsigned j = snap_index(uni, U, r, universe_div(uni, U));
-            sh.idx3[k] = j;
-            sh.ve3[k] = ve[(size_t)k * U + j];
-        }
-        __syncthreads();
-        double q3[NANT];
-        bool same = true;
-#pragma unroll
-        for (int k = 0; k < NANT; k++) { q3[k] = sh.ve3[k]; same = same && (q3[k] == q1[k]); }
-        QResult rr = rn;                                                    // :370 (same VE point => same sweep result)
-        if (!same) rr = sweep_q<NANT, BLOCK>(cols, qcol, R, q3, p, red);
-        if (rr.hit == FRIRL_HIP_NO_HIT) {                                   // :373-377 append and leave
-            if (R >= maxR) return FRIRL_HIP_UPD_FULL;
-            const double rconc = rr.vagc / rr.ws;
-            if (threadIdx.x < NANT) {
-                base[(size_t)threadIdx.x * maxR + R] = q3[threadIdx.x];      // five_add_rule.c:80-81
-                if (uidx_e) uidx_e[(size_t)threadIdx.x * maxR + R] = (uint16_t)sh.idx3[threadIdx.x];   // five_add_rule.c:76
-                if (rant_e) rant_e[(size_t)threadIdx.x * maxR + R] = sh.rant[threadIdx.x];
-            }
-            if (threadIdx.x == 0) {
-                qcol[R] = rconc + qdiff;
-                *nrules_e = R + 1;
-                *fus_e = 1;
-            }
-            return FRIRL_HIP_UPD_INSERTED;
-        }
-        fus = 0;                                                            // :378
-    }
-
-    // update_rules (:22-143); FIVE_vag_concl_weight(q_ant) sees the distances of the sweep above
-    int rules = R;
-    if (fus) rules--;                                                       // :30-33
-    int status;
-    if (rn.hit != FRIRL_HIP_NO_HIT && (ag.skip_rules == 0 || (ag.skip_rules == 1 && (int)rn.hit < rules))) {
-        if (threadIdx.x == 0) qcol[rn.hit] = qnow + qdiff;                  // :55
-        status = FRIRL_HIP_UPD_EXACT;
-    } else if (ag.skip_rules == 1 && rn.hit != FRIRL_HIP_NO_HIT && (int)rn.hit == rules) {
-        status = FRIRL_HIP_UPD_SKIPPED;                                     // :61-63
-    } else {
-        if (ag.skip_rules == 0) fus = 0;                                    // :70-73
-        const int r_skip = fus ? R - 1 : -1;                                // :76,124-126: the just-inserted rule keeps its Q
-        if (rn.hit == FRIRL_HIP_NO_HIT) {      // FIVE_vag_concl_weight interpolated (:40): this call defines FIVERB.weights from now on
-            if (spread_ant_e && threadIdx.x < NANT) spread_ant_e[threadIdx.x] = sh.q_ant[threadIdx.x];
-            if (spread_R_e && threadIdx.x == 0) *spread_R_e = R;
-        }
-        // K6+K7: from the candidates tracked during the Q(s,a) sweep when possible (no second pass over the slab), else the sweep
-        const bool from_cand = TRACK && rn.tracked && rn.hit == FRIRL_HIP_NO_HIT && !frirl_no_spread_candidates(ag) &&
-                               spread_from_candidates<BLOCK>(slot[threadIdx.x], qcol, rn.ws, qnow, qdiff, ag.weight_significant, r_skip, red);
-        if (!from_cand) sweep_update<NANT, BLOCK>(cols, qcol, R, q1, p, rn.ws, qnow, qdiff, ag.weight_significant, r_skip);
-        status = FRIRL_HIP_UPD_SPREAD;
-    }
-    if (threadIdx.x == 0) *fus_e = fus;
-    return status;
-}
+// (StepShared, update_sarsa_block, the episode begin / step kernels and their launchers: episode_kernel.h)
 
 template <int NANT, int BLOCK, bool IDX>
 __global__ __launch_bounds__(BLOCK) void update_sarsa_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
@@ -197,171 +94,6 @@ __global__ void env_step_kernel(const frirl_hip_agent ag, int E, int ns, const d
     success[e] = f;
 }
 
-// frirl_episode(): start of an episode (reference src/frirl/frirl_episode.c:46-82).
-template <int NANT, int AMAX, int BLOCK, bool IDX, bool PN>
-__global__ __launch_bounds__(BLOCK) void episode_begin_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
-                                                               const double *__restrict__ rb, const uint16_t *__restrict__ uidx,
-                                                               const int32_t *__restrict__ nrules,
-                                                               int maxR, const frirl_hip_agent ag, const frirl_hip_envs ev)
-{
-    constexpr int NS = NANT - 1;
-    const int e = blockIdx.x;
-    extern __shared__ double tab_s[];
-    __shared__ double q_s[NS];
-    __shared__ GbaScratch<AMAX, BLOCK> gs;
-    if (IDX) for (int i = threadIdx.x; i < NANT * U; i += BLOCK) tab_s[i] = ve[i];
-    if (threadIdx.x < NS) {
-        const double v = ev.start_states ? ev.start_states[(size_t)e * NS + threadIdx.x] : ag.values_def[threadIdx.x];   // q_states = states = values_def (:46-48)
-        ev.states[(size_t)e * NS + threadIdx.x] = v;
-        ev.q_ant[(size_t)e * NANT + threadIdx.x] = v;
-        q_s[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, v);
-    }
-    if ((int)threadIdx.x < ag.A) gs.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
-    __syncthreads();
-    double q[NS];
-#pragma unroll
-    for (int k = 0; k < NS; k++) q[k] = q_s[k];
-    const double *base = rb + (size_t)e * (NANT + 1) * maxR;
-    const double *qcol = base + (size_t)NANT * maxR;
-    const auto cols = ColsSel<IDX>::make(base, uidx + (IDX ? (size_t)e * NANT * maxR : 0), tab_s, maxR, U);
-    const auto pw = PowSel<PN, NANT>::make(ag.p > 0 ? ag.p : NANT);
-    int a0;
-    if constexpr (AMAX == 24) {
-        __shared__ BlockRed<BLOCK> red;
-        double dummy[NANT] = {};
-        a0 = sweep_gba_many<NANT, AMAX, BLOCK, false>(cols, qcol, nrules[e], q, dummy, pw, ag.A, gs, red, nullptr);   // :78
-    } else if constexpr (AMAX > 8) {
-        __shared__ BlockRed<BLOCK> red;
-        double dummy[NANT] = {};
-        a0 = sweep_gba_wide<NANT, 8, AMAX, BLOCK, false>(cols, qcol, nrules[e], q, dummy, pw, ag.A, gs, red, nullptr);   // :78
-    } else {
-        a0 = sweep_gba<NANT, AMAX, BLOCK>(cols, qcol, nrules[e], q, pw, ag.A, gs);   // :78
-    }
-    if (threadIdx.x == 0) {
-        const uint32_t epi = ev.episode ? (uint32_t)(ev.episode[e] + 1) : 0u;
-        if (ev.episode) ev.episode[e] = (int32_t)epi;
-        a0 = e_greedy(ag, a0, (uint32_t)e, epi, 0u);
-        ev.q_ant[(size_t)e * NANT + NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + a0];                 // :82
-        ev.done[e] = 0;
-        ev.ep_steps[e] = 0;
-        ev.ep_reward[e] = 0.0;
-        if (ev.status) ev.status[e] = FRIRL_HIP_UPD_INACTIVE;
-    }
-}
-
-// frirl_episode(): one step of the loop (reference src/frirl/frirl_episode.c:86-185), fused.
-// register budget of the step kernel: 6 waves per SIMD (<= 80 VGPRs) for the 3-antecedent / <= 4-action shape (it needs ~64 now that
-// the observations sit in SGPRs and exact hits need no registers; 8 waves -- all 8192 one-wave environments of the 8192 x 8192 shape
-// resident at once -- measured the same 0.24 ms: the kernel is issue-bound, profiles/r02_step_timeline.txt), 4 (<= 128) for the
-// others: without the bound the 5-antecedent, many-action variants sit just above 128 and lose a wave
-// (the action-parallel kernel, amax > 8: 3 waves = 168 VGPRs -- its branch-free conclusion terms keep more chains in flight, and with
-// cartpole's 40 KB of LDS tables only three workgroups fit a CU anyway)
-#ifndef FRIRL_STEP_WAVES_N3
-#define FRIRL_STEP_WAVES_N3 6
-#endif
-#ifndef FRIRL_STEP_SAME_CELL
-#define FRIRL_STEP_SAME_CELL 1     // 0: always the full pending distance (A/B builds)
-#endif
-constexpr int step_min_waves(int nant, int amax) { return (nant <= 3 && amax <= 4) ? FRIRL_STEP_WAVES_N3 : (amax > 8 ? 3 : 4); }
-
-// TRACK: the candidates of update_rules' write-back are collected during the fused sweep (sweeps.h: SpreadCand) -- for LARGE rule
-// bases, where the second sweep it saves is a second pass over HBM; small slabs are re-read from L2 and the plain form is faster.
-#ifdef FRIRL_STEP_TIMING
-// experiment build only (tools/build_variant.sh timing -DFRIRL_STEP_TIMING): when each workgroup of the step kernel started, finished its
-// fused sweep and left, in 10 ns ticks of the device wall clock -- read back with frirl_hip_debug_step_timing
-__device__ long long g_step_timing[4 * 65536];
-#endif
-
-template <int NANT, int AMAX, int BLOCK, bool IDX, bool PN, bool TRACK>
-__global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_step_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
-                                                              double *__restrict__ rb, uint16_t *__restrict__ uidx, int32_t *__restrict__ nrules,
-                                                              int maxR, const frirl_hip_agent ag, const frirl_hip_envs ev)
-{
-    constexpr int NS = NANT - 1;
-    const int e = blockIdx.x;
-#ifdef FRIRL_STEP_TIMING
-    const long long tm0 = wall_clock64();
-#endif
-    if (ev.done[e]) {
-        if (threadIdx.x == 0 && ev.status) ev.status[e] = FRIRL_HIP_UPD_INACTIVE;
-        return;
-    }
-    extern __shared__ double tab_s[];
-    __shared__ StepShared sh;
-    __shared__ BlockRed<BLOCK> red;
-    __shared__ GbaScratch<AMAX, BLOCK> gs;
-    __shared__ SpreadCand cand_s[TRACK ? BLOCK : 1];       // one slot per lane: candidates of update_rules' write-back (sweeps.h)
-    if (IDX) for (int i = threadIdx.x; i < NANT * U; i += BLOCK) tab_s[i] = ve[i];
-    if (threadIdx.x == 0) {
-        double s[FRIRL_HIP_MAX_NANT], q[FRIRL_HIP_MAX_NANT];
-        for (int i = 0; i < NS; i++) s[i] = ev.states[(size_t)e * NS + i];
-        for (int i = 0; i < NANT; i++) sh.q_ant[i] = ev.q_ant[(size_t)e * NANT + i];
-        env_do_action(ag.env_kind, sh.q_ant[NS], s, sh.cur_states);                                   // :97
-        env_get_reward(ag.env_kind, sh.cur_states, sh.reward, sh.success);                            // :106
-        env_quantize(ag.env_kind, NS, ag.grid_values, ag.grid_len, ag.grid_div, sh.cur_states, q);   // :112
-        for (int i = 0; i < NS; i++) sh.cur_q_ant[i] = q[i];
-    }
-    if ((int)threadIdx.x < ag.A) gs.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x < NANT) sh.ve1[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, sh.q_ant[threadIdx.x]);
-    if (threadIdx.x < NS) sh.ve2[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, sh.cur_q_ant[threadIdx.x]);
-    __syncthreads();
-    double q[NS];
-#pragma unroll
-    for (int k = 0; k < NS; k++) q[k] = sh.ve2[k];
-    double *base = rb + (size_t)e * (NANT + 1) * maxR;
-    const double *qcol = base + (size_t)NANT * maxR;
-    uint16_t *uidx_e = uidx ? uidx + (size_t)e * NANT * maxR : nullptr;
-    const auto cols = ColsSel<IDX>::make(base, uidx_e, tab_s, maxR, U);
-    double q1[NANT];
-#pragma unroll
-    for (int k = 0; k < NANT; k++) q1[k] = sh.ve1[k];
-    const auto pw = PowSel<PN, NANT>::make(ag.p > 0 ? ag.p : NANT);
-    QResult rn;
-    // one pass over the slab: greedy action for s' (:148) AND Q(s,a) of the pending update (frirl_update_sarsa.c:357)
-    int ap;
-    if constexpr (AMAX == 24) ap = sweep_gba_many<NANT, AMAX, BLOCK, true>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, &rn);
-    else if constexpr (AMAX > 8) ap = sweep_gba_wide<NANT, 8, AMAX, BLOCK, true, TRACK>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, &rn, ag.weight_significant, cand_s);
-    else {
-        // the agent has not left its quantisation cell (workgroup-uniform): Q(s, a) of the pending update is the greedy sweep's conclusion
-        // for action a at the new observation (sweeps.h: SAMES)
-        bool same_cell = NS > 0 && FRIRL_STEP_SAME_CELL != 0;
-#pragma unroll
-        for (int k = 0; k < NS; k++) same_cell = same_cell && (q[k] == q1[k]);
-        int apend = -1;
-        for (int a = ag.A - 1; a >= 0; a--) if (gs.ave[a] == q1[NS]) apend = a;
-        if (same_cell && apend >= 0) ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, true>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, ag.weight_significant, cand_s, apend);
-        else ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, false>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, ag.weight_significant, cand_s);
-    }
-#ifdef FRIRL_STEP_TIMING
-    const long long tm1 = wall_clock64();
-#endif
-    if (threadIdx.x == 0) {
-        const int chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
-        gs.best = chosen;
-        sh.cur_q_ant[NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + chosen];                  // :151
-        sh.ve2[NS] = gs.ave[chosen];
-    }
-    __syncthreads();
-    const double qp = gs.actconc[gs.best];     // Q(s',a') of the chosen action == FIVE_vag_concl(cur_q_ant), frirl_update_sarsa.c:356
-    double *rant_e = ev.rant ? ev.rant + (size_t)e * NANT * maxR : nullptr;
-    int st = FRIRL_HIP_UPD_INACTIVE;
-    if (!ag.evaluate)                                                                                 // :155 (reduction_state == 0)
-        st = update_sarsa_block<NANT, BLOCK, TRACK>(cols, u, ve, U, base, maxR, nrules + e, ag, sh, sh.reward, true, qp, ev.fus + e, rant_e, red, &rn, uidx_e, pw, cand_s,
-                                                    ev.spread_ant ? ev.spread_ant + (size_t)e * NANT : nullptr, ev.spread_R ? ev.spread_R + e : nullptr);  // :159
-    if (threadIdx.x < NS) ev.states[(size_t)e * NS + threadIdx.x] = sh.cur_states[threadIdx.x];      // :163-165
-    if (threadIdx.x < NANT) ev.q_ant[(size_t)e * NANT + threadIdx.x] = sh.cur_q_ant[threadIdx.x];    // :166-168
-    if (threadIdx.x == 0) {
-        const int steps = ev.ep_steps[e] + 1;                                                         // :174
-        ev.ep_steps[e] = steps;
-        ev.ep_reward[e] = ev.ep_reward[e] + sh.reward;                                                // :107
-        if (sh.success == 1 || steps >= ag.max_steps) ev.done[e] = 1;                                 // :183, :86
-        if (ev.status) ev.status[e] = st;
-#ifdef FRIRL_STEP_TIMING
-        if (e < 65536) { g_step_timing[4 * e] = tm0; g_step_timing[4 * e + 1] = tm1; g_step_timing[4 * e + 2] = wall_clock64(); g_step_timing[4 * e + 3] = st; }
-#endif
-    }
-}
 
 #ifdef FRIRL_STEP_TIMING
 }  // namespace frirl
@@ -684,63 +416,6 @@ extern "C" int frirl_hip_env_step(const frirl_hip_agent *agent, int32_t E, int32
     return check_launch("frirl_hip_env_step");
 }
 
-template <int N, int AMAX, int BLOCK, bool BEGIN>
-static void launch_episode_v(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                             hipStream_t s)
-{
-    // compressed index mirror: large rule bases only (use_uidx); with one wave per environment only while the per-workgroup
-    // LDS copy of the VE tables is small (<= 4 KiB: it does not limit the waves per CU)
-    const bool idx = frirl::use_uidx(t, b) && (BLOCK >= 256 || sizeof(double) * t->nant * (size_t)t->U <= 4096);
-    const size_t tab = idx ? sizeof(double) * t->nant * (size_t)t->U : 0;
-    const bool pn = ag->p <= 0 || ag->p == N;                     // the Shepard power is the default nant: straight-line power (PowC<N>)
-    // Spread candidates tracked in the fused sweep (sweeps.h: SpreadCand): where the second sweep would be a second pass over HBM
-    // (large slabs) AND the sweep has registers to spare -- measured (tools/step_ab.py): acrobot 65 536 rules x 8 192 envs
-    // 2.47 -> 2.26 ms per step; the 3-antecedent kernels (80-VGPR budget) and the 21-action kernel (already at 128) spill in the hot
-    // loop with it (0.23 -> 0.57 ms, 3.0 -> 5.8 ms) and their second sweep is cheap beside A + 1 Shepard sums per rule, so they keep it.
-    constexpr bool CAN_TRACK = (N >= 4 && AMAX <= 4);
-    const int st_opt = frirl_host::opts().step_track;
-    const bool track = CAN_TRACK && (st_opt == 1 || (st_opt < 0 && b->maxR > 16384 + 512));
-#define EP_GO(KERNEL, DYN, ...)                                                                                                                  \
-    hipLaunchKernelGGL((frirl::KERNEL<N, AMAX, BLOCK, __VA_ARGS__>), dim3(b->E), dim3(BLOCK), DYN, s, t->u, t->ve, t->U, b->rb, b->uidx, b->nrules, \
-                       b->maxR, *ag, *ev)
-    if constexpr (BEGIN) {
-        if (idx) { if (pn) EP_GO(episode_begin_kernel, tab, true, true); else EP_GO(episode_begin_kernel, tab, true, false); }
-        else { if (pn) EP_GO(episode_begin_kernel, 0, false, true); else EP_GO(episode_begin_kernel, 0, false, false); }
-    } else {
-        if constexpr (CAN_TRACK) {
-            if (track) {
-                if (idx) { if (pn) EP_GO(episode_step_kernel, tab, true, true, true); else EP_GO(episode_step_kernel, tab, true, false, true); }
-                else { if (pn) EP_GO(episode_step_kernel, 0, false, true, true); else EP_GO(episode_step_kernel, 0, false, false, true); }
-                return;
-            }
-        }
-        if (idx) { if (pn) EP_GO(episode_step_kernel, tab, true, true, false); else EP_GO(episode_step_kernel, tab, true, false, false); }
-        else { if (pn) EP_GO(episode_step_kernel, 0, false, true, false); else EP_GO(episode_step_kernel, 0, false, false, false); }
-    }
-#undef EP_GO
-}
-
-// Workgroup shape: 256 threads per environment for large rule bases (bandwidth); ONE wave per environment while
-// the rule bases are small (<= 2048 rules: the demos' real learning regime, <= 367 rules) -- no cross-wave
-// reductions or barriers on the critical path and 4x more environments resident per CU.  More than 8 actions
-// always use 256 threads (the action-parallel sweep needs the waves).
-template <int N, bool BEGIN>
-static void launch_episode(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                           hipStream_t s)
-{
-    // one wave per environment: small rule bases, or mid-size ones when the environments alone fill the chip (>= 4 waves
-    // per SIMD): measured at 8192 rules x 8192 envs 0.320 -> 0.295 ms per step; at 65 536 rules the 256-thread form wins
-    bool small = b->maxR <= 2048 || (b->maxR <= 16384 && b->E >= 4096);
-    // (1024 threads per environment -- fewer environments in flight, fewer concurrent DRAM streams -- measured slower at 65 536 rules:
-    //  2.27 -> 2.79 ms per step, tools/step_ab.py)
-    const int sw = frirl_host::opts().step_wave;
-    if (sw >= 0) small = sw == 1;
-    // (two waves per environment -- 16 384 half-size waves instead of 8192, a finer last round -- measured 0.225 vs 0.217 ms at 8192 x 8192)
-    if (ag->A <= 4) { if (small) launch_episode_v<N, 4, 64, BEGIN>(t, b, ag, ev, s); else launch_episode_v<N, 4, 256, BEGIN>(t, b, ag, ev, s); }
-    else if (ag->A <= 8) { if (small) launch_episode_v<N, 8, 64, BEGIN>(t, b, ag, ev, s); else launch_episode_v<N, 8, 256, BEGIN>(t, b, ag, ev, s); }
-    else if (ag->A <= 24 && !frirl_host::opts().no_many) launch_episode_v<N, 24, 256, BEGIN>(t, b, ag, ev, s);   // 9..24 actions: all in registers (sweep_gba_many)
-    else launch_episode_v<N, 32, 256, BEGIN>(t, b, ag, ev, s);            // more: action-parallel waves (sweep_gba_wide)
-}
 
 // 1 when frirl_hip_episode_step streams the 16-bit index mirror for this shape (given that the caller provides one)
 extern "C" int frirl_hip_step_uses_uidx(int32_t nant, int32_t U, int32_t maxR, int32_t E)
@@ -777,8 +452,8 @@ extern "C" int frirl_hip_episode_begin(const frirl_hip_tables *t, const frirl_hi
 {
     int rc = check_episode(t, b, agent, envs, "frirl_hip_episode_begin");
     if (rc) return rc;
-    if (t->nant == 3) launch_episode<3, true>(t, b, agent, envs, as_stream(stream));
-    else launch_episode<5, true>(t, b, agent, envs, as_stream(stream));
+    if (t->nant == 3) frirl::launch_episode<3, true>(t, b, agent, envs, as_stream(stream));
+    else frirl::launch_episode<5, true>(t, b, agent, envs, as_stream(stream));
     return check_launch("frirl_hip_episode_begin");
 }
 
@@ -787,8 +462,8 @@ extern "C" int frirl_hip_episode_step(const frirl_hip_tables *t, const frirl_hip
 {
     int rc = check_episode(t, b, agent, envs, "frirl_hip_episode_step");
     if (rc) return rc;
-    if (t->nant == 3) launch_episode<3, false>(t, b, agent, envs, as_stream(stream));
-    else launch_episode<5, false>(t, b, agent, envs, as_stream(stream));
+    if (t->nant == 3) frirl::launch_episode<3, false>(t, b, agent, envs, as_stream(stream));
+    else frirl::launch_episode<5, false>(t, b, agent, envs, as_stream(stream));
     return check_launch("frirl_hip_episode_step");
 }
 
@@ -798,8 +473,8 @@ extern "C" int frirl_hip_episode_steps(const frirl_hip_tables *t, const frirl_hi
     int rc = check_episode(t, b, agent, envs, "frirl_hip_episode_steps");
     if (rc) return rc;
     for (int i = 0; i < nsteps; i++) {
-        if (t->nant == 3) launch_episode<3, false>(t, b, agent, envs, as_stream(stream));
-        else launch_episode<5, false>(t, b, agent, envs, as_stream(stream));
+        if (t->nant == 3) frirl::launch_episode<3, false>(t, b, agent, envs, as_stream(stream));
+        else frirl::launch_episode<5, false>(t, b, agent, envs, as_stream(stream));
     }
     return check_launch("frirl_hip_episode_steps");
 }

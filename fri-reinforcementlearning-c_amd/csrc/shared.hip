@@ -265,14 +265,30 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_shared_kernel(const double *
 
 using namespace frirl_host;
 
-static int check_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, int Q, const char *who)
+static int check_shared_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, int Q, const char *who)
 {
     int rc = check_rulebases(t, b);
     if (rc) return rc;
     if (b->E != 1) { set_error("%s: needs ONE shared rule base (E == 1), got E=%d", who, b->E); return FRIRL_HIP_EINVAL; }
     if (Q < 1) { set_error("%s: Q=%d < 1", who, Q); return FRIRL_HIP_EINVAL; }
     if (t->nant < 2 || t->nant > 9) { set_error("%s: nant=%d outside 2..9", who, t->nant); return FRIRL_HIP_EINVAL; }
-    return check_device();
+    return FRIRL_HIP_OK;
+}
+
+static int check_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, int Q, const char *who)
+{
+    int rc = check_shared_args(t, b, Q, who);
+    return rc ? rc : check_device();
+}
+
+// the roll-outs run the demo dynamics on the device: env_kind must name one of them, with its antecedent count
+static int check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who)
+{
+    if (agent->env_kind < 0 || agent->env_kind > 2 || (agent->env_kind == FRIRL_HIP_ENV_MOUNTAINCAR ? t->nant != 3 : t->nant != 5)) {
+        set_error("%s: env_kind %d does not match nant=%d (the demo environments only)", who, agent->env_kind, t->nant);
+        return FRIRL_HIP_EINVAL;
+    }
+    return FRIRL_HIP_OK;
 }
 
 extern "C" int five_hip_vag_concl_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, int p, int32_t Q, const double *x,
@@ -378,17 +394,14 @@ int frirl_rollout_resident(const frirl_hip_tables *t, const frirl_hip_rulebases 
 extern "C" int frirl_hip_rollout_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, int32_t Q,
                                         const frirl_hip_rollout *ro, void *stream)
 {
-    int rc = check_shared(t, b, Q, "frirl_hip_rollout_shared");
+    int rc = check_shared_args(t, b, Q, "frirl_hip_rollout_shared");
     if (rc) return rc;
     if (!agent || !ro || !ro->steps || !ro->reward || !agent->grid_values || !agent->action_ve) { set_error("frirl_hip_rollout_shared: NULL argument"); return FRIRL_HIP_EINVAL; }
     if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("frirl_hip_rollout_shared: A=%d / max_steps=%d out of range", agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
     for (int k = 0; k < t->nant; k++)
         if (agent->grid_len[k] < 1 || agent->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("frirl_hip_rollout_shared: grid_len[%d]=%d outside 1..%d", k, agent->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
     if ((ro->exclude_mask == nullptr) != (ro->rule_slot == nullptr)) { set_error("frirl_hip_rollout_shared: exclude_mask and rule_slot go together"); return FRIRL_HIP_EINVAL; }
-    if (agent->env_kind == FRIRL_HIP_ENV_MOUNTAINCAR ? t->nant != 3 : t->nant != 5) {
-        set_error("frirl_hip_rollout_shared: env_kind %d does not match nant=%d", agent->env_kind, t->nant);
-        return FRIRL_HIP_EINVAL;
-    }
+    if ((rc = check_demo_kind(t, agent, "frirl_hip_rollout_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     // small rule bases: the LDS-resident, queue-fed form (rollout.hip); the tiled kernel below serves every other shape, and a rule
     // base that turns out not to fit the LDS image (known on the device only: `too_big`)
@@ -419,12 +432,13 @@ struct DevBuf {
 extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant, int strategy,
                                        double reward_tolerance, int depth, int32_t *kept, frirl_hip_reduce_result *result, void *stream)
 {
-    int rc = check_shared(t, b, 1, "frirl_hip_reduce_shared");
+    int rc = check_shared_args(t, b, 1, "frirl_hip_reduce_shared");
     if (rc) return rc;
     if (!agent || !result) { set_error("frirl_hip_reduce_shared: NULL argument"); return FRIRL_HIP_EINVAL; }
     if (strategy != 1 && strategy != 2) { set_error("frirl_hip_reduce_shared: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", strategy); return FRIRL_HIP_EINVAL; }
     if (depth == 0) depth = 10;
     if (depth < 1 || depth > 12) { set_error("frirl_hip_reduce_shared: depth %d outside 1..12", depth); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_demo_kind(t, agent, "frirl_hip_reduce_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     const int nant = t->nant, maxR = b->maxR;
     const size_t col = (size_t)maxR;

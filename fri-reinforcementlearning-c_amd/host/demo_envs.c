@@ -206,38 +206,64 @@ void frirl_demo_release(struct frirl_desc *fr)
     fr->statedims = NULL;
 }
 
-/* Flat description of a demo for bindings (bench.py, tests): tables built by the same host functions
- * frirl_init() uses (frirl_init_ve; per-action VE values as frirl_init.c:156-158).  Needs no GPU. */
+/* Tables of an agent from a flat description of its dimensions (any environment; needs no GPU): dimension k < nstates is a
+ * state, k = nstates the action.  Universes as the demos' setup builds them (frirl_gen_fixres_arr over U points of step
+ * universe_div[k]), VE rows by frirl_init_ve from the grid values / steepness (the action row's steepness is derived from
+ * A, frirl_init_ve.c:91-92), VE value of every action as frirl_init.c:156-158.
+ *   values_len [nstates+1], values [nstates+1][FRIRL_HIP_MAX_GRID] (row k: its first values_len[k] entries), values_steep,
+ *   universe_div [nstates+1]  ->  u, ve [nstates+1][U], action_ve [values_len[nstates]].  0, or -1 on a bad argument. */
+int frirl_describe_tables(int nstates, int U, const int *values_len, const double *values, const double *values_steep,
+                          const double *universe_div, double *u, double *ve, double *action_ve)
+{
+    struct frirl_desc fr = frirl_desc_default;
+    struct frirl_dimension_desc sd[FRIRL_HIP_MAX_NANT];
+    int k, j;
+    if (nstates < 1 || nstates >= FRIRL_HIP_MAX_NANT || U < 2 || !values_len || !values || !values_steep || !universe_div || !u || !ve || !action_ve) return -1;
+    for (k = 0; k <= nstates; k++)
+        if (values_len[k] < 1 || values_len[k] > FRIRL_HIP_MAX_GRID || !(universe_div[k] > 0.0)) return -1;
+    if (values_len[nstates] > FRIRL_HIP_MAX_ACTIONS) return -1;
+    for (k = 0; k <= nstates; k++) {
+        struct frirl_dimension_desc *d = (k < nstates) ? &sd[k] : &fr.actiondim;
+        memset(d, 0, sizeof *d);
+        d->values_len = values_len[k]; d->values = (fri_float *)(values + (size_t)k * FRIRL_HIP_MAX_GRID); d->values_steep = values_steep[k];
+        d->universe_len = U; d->universe_div = universe_div[k];
+        frirl_gen_fixres_arr(u + (size_t)k * U, U, universe_div[k]);                     /* set_dim */
+    }
+    fr.statedims = sd; fr.statedims_len = nstates; fr.numofantecedents = nstates + 1;
+    if (frirl_init_ve(&fr, ve, u, U) != 0) return -1;
+    {
+        const double *ua = u + (size_t)nstates * U, *vea = ve + (size_t)nstates * U;
+        const double udiv = (ua[U - 1] - ua[0]) / (U - 1);
+        for (j = 0; j < values_len[nstates]; j++) action_ve[j] = vea[five_dropin_snap(ua, U - 1, fr.actiondim.values[j], udiv)];
+    }
+    return 0;
+}
+
+/* Flat description of a demo for bindings (bench.py, tests): the demo's setup, then frirl_describe_tables.  Needs no GPU. */
 int frirl_demo_describe(const char *env, int *nstates, int *U, int *A, double *u, double *ve, double *grid, int *grid_len,
                         double *grid_div, double *values_def, double *action_ve, double *hparams, int *max_steps)
 {
     struct frirl_desc fr = frirl_desc_default;
-    int k, j, n, usize;
+    int k, j, n, usize, rc = 0;
     if (frirl_demo_setup(&fr, env) != 0) return -1;
     n = fr.statedims_len + 1;
     usize = fr.statedims[0].universe_len;
     *nstates = fr.statedims_len; *U = usize; *A = fr.actiondim.values_len; *max_steps = fr.max_steps;
     if (u && ve) {
-        for (k = 0; k < fr.statedims_len; k++) memcpy(u + k * usize, fr.statedims[k].universe, sizeof(double) * usize);
-        memcpy(u + fr.statedims_len * usize, fr.actiondim.universe, sizeof(double) * usize);
-        fr.numofantecedents = n;
-        if (frirl_init_ve(&fr, ve, u, usize) != 0) return -1;
+        double steep[FRIRL_HIP_MAX_NANT], udiv[FRIRL_HIP_MAX_NANT];
         for (k = 0; k < n; k++) {
             const struct frirl_dimension_desc *d = (k < fr.statedims_len) ? &fr.statedims[k] : &fr.actiondim;
             grid_len[k] = d->values_len; grid_div[k] = d->values_div; values_def[k] = d->values_def;
-            for (j = 0; j < d->values_len; j++) grid[k * 64 + j] = d->values[j];
+            steep[k] = d->values_steep; udiv[k] = d->universe_div;
+            for (j = 0; j < d->values_len; j++) grid[k * FRIRL_HIP_MAX_GRID + j] = d->values[j];
         }
-        {
-            const double *ua = u + fr.statedims_len * usize, *vea = ve + fr.statedims_len * usize;
-            const double udiv = (ua[usize - 1] - ua[0]) / (usize - 1);
-            for (j = 0; j < fr.actiondim.values_len; j++) action_ve[j] = vea[five_dropin_snap(ua, usize - 1, fr.actiondim.values[j], udiv)];
-        }
+        rc = frirl_describe_tables(fr.statedims_len, usize, grid_len, grid, steep, udiv, u, ve, action_ve);
         hparams[0] = fr.alpha; hparams[1] = fr.gamma; hparams[2] = fr.qdiff_pos_boundary; hparams[3] = fr.qdiff_neg_boundary;
         hparams[4] = fr.rule_weight_considered_significant_for_update; hparams[5] = fr.skip_rules; hparams[6] = fr.reward_good_above;
         hparams[7] = fr.qdiff_final_tolerance;
     }
     frirl_demo_release(&fr);
-    return 0;
+    return rc;
 }
 
 /* E agents of a demo, batched on the device: the C-level counterpart of the reference's many-agent run modes

@@ -11,6 +11,11 @@
 int frirl_demo_setup(struct frirl_desc *fr, const char *env);     /* "mountaincar" | "cartpole" | "acrobot" */
 void frirl_demo_release(struct frirl_desc *fr);
 /* flat description for bindings; u/ve [ (nstates+1) * U ], grid [ (nstates+1) * 64 ]; pass u = ve = NULL to query sizes */
+/* tables of ANY environment from its dimensions (state dims 0..nstates-1, the action dim nstates): universes, VE rows
+ * (frirl_init_ve) and the actions' VE values (frirl_init.c:156-158); values [nstates+1][64].  frirl_demo_describe = a demo's
+ * setup + this.  0, or -1 on a bad argument. */
+int frirl_describe_tables(int nstates, int U, const int *values_len, const double *values, const double *values_steep,
+                          const double *universe_div, double *u, double *ve, double *action_ve);
 int frirl_demo_describe(const char *env, int *nstates, int *U, int *A, double *u, double *ve, double *grid, int *grid_len,
                         double *grid_div, double *values_def, double *action_ve, double *hparams, int *max_steps);
 

@@ -51,6 +51,7 @@ extern "C" {
 #define FRIRL_HIP_ENV_MOUNTAINCAR 0   /* reference examples/mountaincar/mountaincar.c */
 #define FRIRL_HIP_ENV_CARTPOLE    1   /* reference examples/cartpole/cartpole.c       */
 #define FRIRL_HIP_ENV_ACROBOT     2   /* reference examples/acrobot/acrobot.c         */
+#define FRIRL_HIP_ENV_EXTERNAL    3   /* the caller's own environment: frirl_hip_agent_begin / _observe only */
 
 /* outcome of one SARSA update per environment (frirl_hip_envs.status) */
 #define FRIRL_HIP_UPD_INACTIVE   0    /* environment masked out / episode already ended              */
@@ -167,7 +168,7 @@ typedef struct frirl_hip_agent {
     int32_t skip_rules;                        /* frirl_desc.skip_rules (MATLAB compatibility, 1 in demos) */
     int32_t p;                                 /* Shepard power, <= 0 -> nant (FIVEInit.c:89-93)           */
     int32_t A;                                 /* number of discrete actions                               */
-    int32_t env_kind;                          /* FRIRL_HIP_ENV_*                                          */
+    int32_t env_kind;                          /* FRIRL_HIP_ENV_*; the entry points that run the demo dynamics refuse EXTERNAL */
     int32_t max_steps;                         /* frirl_desc.max_steps                                     */
     int32_t no_random;                         /* frirl_desc.no_random: 1 = always greedy (every demo)     */
     int32_t grid_len[FRIRL_HIP_MAX_NANT];      /* possible rule places per antecedent (states.., action)   */
@@ -256,6 +257,20 @@ typedef struct frirl_hip_envs {
                                 frirl_hip_weights_from_spread rebuilds it where the rule-base merge needs it */
 } frirl_hip_envs;
 
+/* The caller's side of one step of frirl_episode for frirl_hip_agent_begin / frirl_hip_agent_observe: what the application's
+ * do_action / get_reward / quantize_observations callbacks return in the reference (frirl_episode.c:97-112; the three callbacks
+ * of struct frirl_desc, frirl_types.h), for every environment of the batch, plus the action chosen in reply. */
+typedef struct frirl_hip_agent_io {
+    const double *obs;       /* [dev] [E][nant-1] observation after the last action (begin: the episode's start state)      */
+    const double *q_obs;     /* [dev] [E][nant-1] its quantised form (quantize_observations), or NULL = the generic grid rule
+                                q = grid[k][clamp(round((obs + |grid[k][0]|) / grid_div[k]))] of the reference's examples   */
+    const double *reward;    /* [dev] [E] reward.value of the step (observe only)                                           */
+    const int32_t *success;  /* [dev] [E] reward.success: 1 ends the episode (observe only)                                 */
+    const uint8_t *reset;    /* [dev] [E] begin only: rows != 0 start an episode, the others are untouched; NULL = every row */
+    double *action_out;      /* [dev] [E] value of the action chosen for the next step (grid row nant-1)                    */
+    int32_t *action_idx;     /* [dev] [E] its index 0..A-1, or NULL                                                         */
+} frirl_hip_agent_io;
+
 /* Per-environment convergence state of the construct loop (reference frirl_sequential_run.c:55-165). */
 typedef struct frirl_hip_convergence {
     int32_t *prev_nrules;    /* [dev] [E] rule count after the previous episode                           */
@@ -323,6 +338,28 @@ int frirl_hip_episode_step(const frirl_hip_tables *t, const frirl_hip_rulebases 
 /* nsteps consecutive frirl_hip_episode_step launches (finished environments are skipped inside the kernel) */
 int frirl_hip_episode_steps(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                             const frirl_hip_envs *envs, int32_t nsteps, void *stream);
+
+/* ---- frirl_episode with the CALLER'S environment (env_kind is not read: FRIRL_HIP_ENV_EXTERNAL, or a demo driven from outside)
+ * The same fused kernels as frirl_hip_episode_begin / _step, with the environment's three callbacks (frirl_episode.c:97,106,112)
+ * replaced by the caller's data in `io`; nant 2..8 (FIVE_MAX_NUM_OF_UNIVERSES, FIVE.h:19), A 1..32.  Gym-style loop:
+ *     frirl_hip_agent_begin(obs = start states)        -> io.action_out: first action of every row (:46-48,78-82)
+ *     repeat: step the environments with action_out, then
+ *     frirl_hip_agent_observe(obs, reward, success)    -> one SARSA step per row that is not done (:86-185), next action
+ * frirl_hip_agent_begin: for rows with io->reset[e] != 0 (io->reset NULL: all) states = q_ant = io->obs (un-quantised, :46-48),
+ * episode[e] + 1 (RNG stream position), first action greedy on that state (:78) then epsilon-greedy, counters cleared, done = 0,
+ * status = FRIRL_HIP_UPD_INACTIVE.  Needs io->obs, io->action_out.
+ * frirl_hip_agent_observe: for rows with done[e] == 0: cur_states = io->obs, reward / success from io, quantised state io->q_obs
+ * (NULL: the generic grid rule on the device), then exactly frirl_hip_episode_step: greedy action for the new state with
+ * Q(s,a) of the pending update from the same sweep (:148, frirl_update_sarsa.c:357), epsilon-greedy on the stream (episode[e],
+ * ep_steps[e] + 1), the SARSA update (:155-159, skipped under agent->evaluate), states = io->obs, ep_steps + 1,
+ * ep_reward + reward, done = (success == 1 || ep_steps >= max_steps) (:183,:86).  Rows with done != 0 are skipped (io->action_out
+ * not written, status = FRIRL_HIP_UPD_INACTIVE).  Needs io->obs, io->reward, io->success, io->action_out.
+ * Driving a demo through these with frirl_hip_env_step as the environment gives the bits of frirl_hip_episode_begin / _step.
+ * Neither call synchronises.  Arguments are checked before the device (FRIRL_HIP_EINVAL before FRIRL_HIP_ENODEV). */
+int frirl_hip_agent_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                          const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream);
+int frirl_hip_agent_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                            const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream);
 
 /* Lane-group form for MANY agents with SMALL rule bases (the demos' learning regime; the reference's frirl_omp_run model
  * of one agent per core, frirl_agent.c:294-325, at GPU width): G = 4 or 8 consecutive lanes own one environment, each

@@ -1,0 +1,181 @@
+"""Host side of the caller's-environment API (no GPU needed): tables for any environment (frirl_amd.describe ->
+frirl_describe_tables) against the demos' own descriptions and against the oracle's restatement of the reference's VE
+construction, the new ABI symbols, and the argument checks of frirl_hip_agent_begin / _observe (EINVAL before ENODEV)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import frirl_amd
+from oracle import binding as ob
+
+DEMOS = ["mountaincar", "cartpole", "acrobot"]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    frirl_amd.build()
+    return frirl_amd.lib()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def oracle_dims(env):
+    """The demo's dimension descriptors as the oracle (pinned to the reference's examples) holds them."""
+    fr = ob.Frirl(env)
+    states = []
+    for k in range(fr.nstates):
+        d = fr.dim(k)
+        states.append(dict(values=d["values"], div=d["values_div"], steep=d["values_steep"], default=d["values_def"], universe_div=d["universe_div"]))
+    a = fr.dim(fr.nstates)
+    return fr, states, dict(values=a["values"], div=a["values_div"], universe_div=a["universe_div"])
+
+
+@pytest.mark.parametrize("env", DEMOS)
+def test_describe_reproduces_demo_describe(lib, env):
+    ref = frirl_amd.demo_describe(env)
+    fr, states, actions = oracle_dims(env)
+    hp = fr.hparams
+    d = frirl_amd.describe(states, actions, fr.five.U, hp["alpha"], hp["gamma"], hp["qdiff_pos"], hp["qdiff_neg"], hp["weight_thr"], hp["skip_rules"],
+                           hp["reward_good_above"], hp["qdiff_final_tolerance"], ref["max_steps"], name=env)
+    assert d["kind"] == frirl_amd.ENV_EXTERNAL == 3
+    assert set(d) == set(ref)
+    for key in ("nstates", "nant", "U", "A", "skip_rules", "max_steps"):
+        assert d[key] == ref[key], key
+    for key in ("u", "ve", "grid_div", "values_def", "action_ve"):
+        assert d[key].shape == ref[key].shape and (bits(d[key]) == bits(ref[key])).all(), key
+    for key in ("alpha", "gamma", "qdiff_pos", "qdiff_neg", "weight_thr", "reward_good_above", "qdiff_final_tolerance"):
+        assert bits(d[key]) == bits(ref[key]), key
+    assert len(d["grids"]) == len(ref["grids"]) and all((bits(g) == bits(r)).all() for g, r in zip(d["grids"], ref["grids"]))
+    # and the oracle's own tables of the demo
+    assert (bits(d["u"]) == bits(fr.five.u)).all() and (bits(d["ve"]) == bits(fr.five.ve)).all()
+    assert (bits(d["action_ve"]) == bits(fr.action_vevalues)).all()
+
+
+def fixres(n, div):
+    v = np.zeros(n)
+    ob.lib().orc_gen_fixres_arr(ob.dp(v), n, div)
+    return v
+
+
+def oracle_ve_row(u_row, sp, n):
+    U = len(u_row)
+    scf, ve = np.zeros(U), np.zeros(U)
+    sp = np.ascontiguousarray(sp, dtype=np.float64)
+    assert ob.lib().orc_gsc_func(ob.dp(u_row), 1, U, ob.dp(sp), n, 3, ob.dp(scf)) == 0
+    ob.lib().orc_gvagenv(ob.dp(u_row), 1, U, ob.dp(scf), ob.dp(ve))
+    return ve
+
+
+CUSTOM = [  # (state dims as (grid values, steepness, universe step), action values, U)
+    ([(np.linspace(-1.0, 1.0, 7), 1.0, 0.06)], [-1.0, 0.0, 1.0], 41),
+    ([(np.linspace(-2.0, 2.0, 5), 2.5, 0.05), (np.linspace(-0.5, 0.5, 9), 1.0, 0.012), (np.array([-0.3, 0.1, 0.4]), 0.75, 0.01)],
+     [-2.0, -1.0, 0.0, 1.0, 2.0], 101),
+    ([(np.linspace(-1.0, 1.0, 3 + k), 0.5 + 0.25 * k, 0.03 + 0.01 * k) for k in range(7)], np.linspace(-1.0, 1.0, 11), 101),
+    ([(np.linspace(-0.8, 0.8, 4), 1.0 + k, 0.05) for k in range(7)], [-0.5, 0.5, 1.0], 41),
+]
+
+
+@pytest.mark.parametrize("case", range(len(CUSTOM)))
+def test_describe_custom_dims_match_oracle(lib, case):
+    sdims, avals, U = CUSTOM[case]
+    states = [dict(values=v, div=float(v[1] - v[0]) if len(v) > 1 else 1.0, steep=st, default=float(v[len(v) // 2]), universe_div=ud) for v, st, ud in sdims]
+    actions = dict(values=np.asarray(avals, dtype=np.float64), div=0.1, universe_div=0.05)
+    d = frirl_amd.describe(states, actions, U, 0.5, 1.0, 1.0, -4.0)
+    nant, A = len(sdims) + 1, len(avals)
+    assert d["nant"] == nant and d["A"] == A and d["u"].shape == (nant, U)
+    for k, (v, st, ud) in enumerate(sdims):
+        u_row = fixres(U, ud)
+        assert (bits(d["u"][k]) == bits(u_row)).all()
+        sp = np.array([[x, st, st] for x in v]).ravel()
+        assert (bits(d["ve"][k]) == bits(oracle_ve_row(u_row, sp, len(v)))).all(), k
+        assert (bits(d["grids"][k]) == bits(v)).all() and d["values_def"][k] == v[len(v) // 2]
+    ua = fixres(U, 0.05)
+    divratio = 1.0 / (A - 1) * 2.0
+    sp = np.array([[i * divratio - 1.0, (A - 1) // 2, (A - 1) // 2] for i in range(A)], dtype=np.float64).ravel()   # frirl_init_ve.c:91-92
+    vea = oracle_ve_row(ua, sp, A)
+    assert (bits(d["u"][nant - 1]) == bits(ua)).all() and (bits(d["ve"][nant - 1]) == bits(vea)).all()
+    udiv = (ua[U - 1] - ua[0]) / (U - 1)
+    want = np.array([vea[ob.lib().orc_snap(ob.dp(ua), U - 1, float(a), udiv)] for a in avals])        # frirl_init.c:156-158
+    assert (bits(d["action_ve"]) == bits(want)).all()
+
+
+def test_describe_generated_grid_and_bad_input(lib):
+    d = frirl_amd.describe([dict(n=5, div=0.25, universe_div=0.05)], dict(n=3, div=1.0, universe_div=0.1), 41, 0.5, 1.0, 1.0, -4.0)
+    assert (bits(d["grids"][0]) == bits(fixres(5, 0.25))).all() and (bits(d["grids"][1]) == bits(fixres(3, 1.0))).all()
+    with pytest.raises(ValueError):
+        frirl_amd.describe([dict(values=[0.0], universe_div=0.0)], dict(values=[0.0, 1.0], universe_div=0.1), 41, 0.5, 1.0, 1.0, -4.0)
+
+
+def test_new_symbols_exported(lib):
+    assert frirl_amd.ENV_EXTERNAL == 3
+    for n in ("frirl_hip_agent_begin", "frirl_hip_agent_observe"):
+        assert hasattr(lib, n) and n in frirl_amd.SIGNATURES
+    assert hasattr(frirl_amd.dropin(), "frirl_describe_tables")
+    assert C.sizeof(frirl_amd.AgentIO) == 56 and frirl_amd.AgentIO.reset.offset == 32 and frirl_amd.AgentIO.action_idx.offset == 48
+
+
+def _valid_call(nant, A):
+    buf = (C.c_double * 16384)()
+    addr = (C.addressof(buf) + 15) & ~15
+    t = frirl_amd.Tables(nant, 41, addr, addr)
+    b = frirl_amd.RuleBases(4, 8, addr, addr)
+    ag = frirl_amd.AgentDesc()
+    ag.A, ag.env_kind, ag.max_steps, ag.grid_values, ag.action_ve = A, frirl_amd.ENV_EXTERNAL, 10, addr, addr
+    for k in range(min(nant, frirl_amd.MAX_NANT)):
+        ag.grid_len[k] = 3
+    if 1 <= nant <= frirl_amd.MAX_NANT:
+        ag.grid_len[nant - 1] = min(A, frirl_amd.MAX_GRID)
+    ev = frirl_amd.EnvsDesc()
+    ev.states = ev.q_ant = ev.fus = ev.done = ev.ep_steps = ev.ep_reward = addr
+    io = frirl_amd.AgentIO(addr, None, addr, addr, None, addr, None)
+    return buf, t, b, ag, ev, io
+
+
+def test_agent_observe_argument_checks_before_the_device(lib):
+    import torch
+    observe, begin = lib.frirl_hip_agent_observe, lib.frirl_hip_agent_begin
+    for nant, A, what in ((1, 3, b"nant"), (9, 3, b"nant"), (4, 33, b"A=33")):
+        keep, t, b, ag, ev, io = _valid_call(nant, A)
+        assert observe(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -2
+        assert what in lib.frirl_hip_last_error(), lib.frirl_hip_last_error()
+        assert begin(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -2
+    keep, t, b, ag, ev, io = _valid_call(4, 5)
+    io.obs = None
+    assert observe(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -2 and b"NULL" in lib.frirl_hip_last_error()
+    keep, t, b, ag, ev, io = _valid_call(4, 5)
+    io.reward = None
+    assert observe(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -2 and b"reward" in lib.frirl_hip_last_error()
+    keep, t, b, ag, ev, io = _valid_call(4, 5)
+    ag.grid_len[1] = 0
+    assert observe(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -2 and b"grid_len" in lib.frirl_hip_last_error()
+    keep, t, b, ag, ev, io = _valid_call(4, 5)
+    assert observe(C.byref(t), C.byref(b), None, C.byref(ev), C.byref(io), None) == -2
+    if not torch.cuda.is_available():       # valid arguments: no CPU fallback, the device check answers
+        for nant, A in ((2, 1), (4, 5), (8, 32)):
+            keep, t, b, ag, ev, io = _valid_call(nant, A)
+            assert observe(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -1
+            assert b"no CPU fallback" in lib.frirl_hip_last_error()
+            assert begin(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), C.byref(io), None) == -1
+
+
+def test_demo_dynamics_entry_points_refuse_the_external_kind(lib):
+    """Entry points that run the built-in dynamics reject env_kind = FRIRL_HIP_ENV_EXTERNAL before touching the device."""
+    keep, t, b, ag, ev, io = _valid_call(5, 3)
+    b1 = frirl_amd.RuleBases(1, 8, b.rb, b.nrules)
+    addr = b.rb
+    ro = frirl_amd.RolloutDesc()
+    ro.steps, ro.reward = addr, addr
+    assert lib.frirl_hip_rollout_shared(C.byref(t), C.byref(b1), C.byref(ag), 4, C.byref(ro), None) == -2
+    assert b"env_kind 3" in lib.frirl_hip_last_error()
+    res = frirl_amd.ReduceResult()
+    assert lib.frirl_hip_reduce_shared(C.byref(t), C.byref(b1), C.byref(ag), None, 1, 0.0, 0, None, C.byref(res), None) == -2
+    assert lib.frirl_hip_episode_begin(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), None) == -2
+    assert lib.frirl_hip_episode_step(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), None) == -2
+    assert lib.frirl_hip_episode_run(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), 5, 256, None) == -2
+    assert lib.frirl_hip_episode_run_lanes(C.byref(t), C.byref(b), C.byref(ag), C.byref(ev), 5, addr, 1 << 20, None) == -2
+    assert lib.frirl_hip_env_step(C.byref(ag), 4, 4, addr, addr, addr, addr, addr, addr, None) == -2
+    assert lib.frirl_hip_learn_supported(5, 41, 3, 0, frirl_amd.ENV_EXTERNAL) == 0
+    assert lib.frirl_hip_rollout_resident_rules(5, 3, 0, frirl_amd.ENV_EXTERNAL) == 0
