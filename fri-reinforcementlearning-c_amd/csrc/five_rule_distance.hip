@@ -31,10 +31,19 @@
 //   rule_distance_pk_kernel       PACKED index mirror (pidx: 6-bit fields, five per 32-bit word; five_hip_rule_distance_packed)
 //                                 for small tables with U <= 64: the idx kernel's items and stores, 4 B of indices per rule
 //                                 for nant <= 5 instead of 2 * nant -- at cfg4 12 B moved per evaluation instead of 18.
+//                                 Shipped form (SQ, option rd_sqdiff): what does not depend on the rule is done once per
+//                                 workgroup -- an LDS table of the squared differences (q_k - ve[k][i])^2 replaces the VE
+//                                 copy, so a rule costs NANT LDS reads + NANT - 1 adds, and when every entry of that table is
+//                                 0 or in [2^-767, 2^1000] (one workgroup-uniform flag) the square root skips __dsqrt_rn's
+//                                 rescale and special-case steps (sqrt_unscaled); otherwise __dsqrt_rn.  The same operations
+//                                 on the same doubles in the same order: bit-identical.  cfg4: 27 % fewer VALU instructions,
+//                                 1.18 -> 1.12 ms (profiles/r05_cfg4_sqdiff.md).
 // First exact hit: per-lane minimum index -> wave butterfly -> (LDS ->) one integer atomicMin per workgroup / item
 // (deterministic; only taken when a hit exists).
 // "rd_*" / "no_uidx" options (frirl_hip_set_option) are experiment hooks (tools/ab_rd.py); unset, the shipped configuration runs.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "device_common.h"
 
@@ -242,10 +251,100 @@ __device__ __forceinline__ double2 pk_pair_distance(const u32x2_t (&w)[Packed<BI
     return d;
 }
 
-template <int NANT, bool WRITE, int UNROLL, int BITS>
+// __dsqrt_rn's gfx950 expansion for an input it does not rescale (x >= 2^-767, finite): v_rsq_f64, the same two multiplies and
+// seven Newton FMAs in the same order, and 0 passed through.  For such x the result has the bits of __dsqrt_rn(x); below 2^-767,
+// at +inf or for NaN / negative x it does not (the full expansion rescales tiny inputs and passes +inf through).
+__device__ __forceinline__ double sqrt_unscaled(double x)
+{
+    const double y = __builtin_amdgcn_rsq(x);
+    const double s0 = x * y;
+    const double h0 = y * 0.5;
+    const double r0 = __builtin_fma(-h0, s0, 0.5);
+    const double h1 = __builtin_fma(h0, r0, h0);
+    const double s1 = __builtin_fma(s0, r0, s0);
+    const double d0 = __builtin_fma(-s1, s1, x);
+    const double s2 = __builtin_fma(d0, h1, s1);
+    const double d1 = __builtin_fma(-s2, s2, x);
+    const double r = __builtin_fma(d1, h1, s2);
+    return x == 0.0 ? x : r;
+}
+
+// Bounds on one squared difference under which every sum of at most FRIRL_HIP_MAX_NANT of them is exactly 0 or a finite value
+// >= 2^-767 (a sum of non-negative terms is at least its largest term; 16 * 2^1000 stays finite): sqrt_unscaled is then exact.
+__device__ __forceinline__ bool sq_in_unscaled_range(double s)
+{
+    return s == 0.0 || (s >= 0x1p-767 && s <= 0x1p1000);       // false for NaN
+}
+
+// Rule-independent half of the packed scan (rd_sqdiff, shipped): the workgroup's squared differences sq_s[k][i] = (q_k - t)^2,
+// t = the table's VE value i (0.0 on the padding entries i >= U, as above), in LDS; a rule then costs NANT LDS reads and NANT - 1
+// ordered adds -- the same subtract, multiply and dimension-ordered adds on the same doubles as pk_pair_distance.  The square
+// root is sqrt_unscaled when every entry of the workgroup's table is in range (one flag per workgroup: __syncthreads_or), else
+// __dsqrt_rn: bit-identical either way.
+template <int NANT, int BITS, bool FAST>
+__device__ __forceinline__ void pk_pair_sq(const u32x2_t (&w)[Packed<BITS>::words(NANT)], const double *__restrict__ sq_s, double2 &d,
+                                           bool &z0, bool &z1)
+{
+    constexpr int FPW = Packed<BITS>::FPW, TS = 1 << BITS;
+    double a0 = pk_table_entry<BITS>(sq_s, w[0].x, 0), a1 = pk_table_entry<BITS>(sq_s, w[0].y, 0);
+#pragma unroll
+    for (int k = 1; k < NANT; k++) {
+        const int sh = BITS * (k % FPW);
+        a0 = a0 + pk_table_entry<BITS>(sq_s + k * TS, w[k / FPW].x, sh);
+        a1 = a1 + pk_table_entry<BITS>(sq_s + k * TS, w[k / FPW].y, sh);
+    }
+    if (FAST) {
+        d.x = sqrt_unscaled(a0);
+        d.y = sqrt_unscaled(a1);
+        z0 = a0 == 0.0;                          // sqrt(a) == 0 exactly when a == 0: the select above and the hit test share it
+        z1 = a1 == 0.0;
+    } else {
+        d.x = __dsqrt_rn(a0);
+        d.y = __dsqrt_rn(a1);
+        z0 = d.x == 0.0;
+        z1 = d.y == 0.0;
+    }
+}
+
+// One environment's squared-difference table (above) from its snapped observations q_s; returns true when every entry is in
+// the range of sqrt_unscaled.  Shared by rule_distance_pk_kernel and the probe five_hip_rule_distance_sq_guard.
+template <int NANT, int BITS, int BLOCK>
+__device__ __forceinline__ bool fill_sq_table(const double *q_s, double *sq_s, const double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK])
+{
+    constexpr int TS = 1 << BITS, N = NANT * TS;
+    bool ok = true;
+#pragma unroll
+    for (int m = 0; m < (N + BLOCK - 1) / BLOCK; m++) {
+        const int i = (int)threadIdx.x + m * BLOCK;
+        if (N % BLOCK == 0 || i < N) {
+            const double d = q_s[i >> BITS] - tv[m];
+            const double s = d * d;
+            sq_s[i] = s;
+            ok = ok && sq_in_unscaled_range(s);
+        }
+    }
+    return ok;
+}
+
+// tv[m] = the table value of entry threadIdx.x + m * BLOCK of fill_sq_table (loaded before the observations are known)
+template <int NANT, int BITS, int BLOCK>
+__device__ __forceinline__ void load_sq_sources(const double *__restrict__ ve, int U, double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK])
+{
+    constexpr int TS = 1 << BITS, N = NANT * TS;
+#pragma unroll
+    for (int m = 0; m < (N + BLOCK - 1) / BLOCK; m++) {
+        const int i = (int)threadIdx.x + m * BLOCK;
+        const int k = i >> BITS, j = i & (TS - 1);
+        tv[m] = (i < N && j < U) ? ve[k * U + j] : 0.0;
+    }
+}
+
+// SQ = false: the kernel as it was before the squared-difference tables (option rd_sqdiff = 0, A/B only).
+// qv != nullptr: the snapped observations qv[e][k] of observe_reset_kernel (option rd_qpass) instead of observe_ve in the prologue.
+template <int NANT, bool WRITE, int UNROLL, int BITS, bool SQ>
 __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
     const double *__restrict__ u, const double *__restrict__ ve, int U, const uint32_t *__restrict__ pidx,
-    const int32_t *__restrict__ nrules, int maxR, const double *__restrict__ x, double *__restrict__ dists,
+    const int32_t *__restrict__ nrules, int maxR, const double *__restrict__ x, const double *__restrict__ qv, double *__restrict__ dists,
     uint32_t *__restrict__ hit, int rules_per_block, int cpe, int E, int env_fastest)
 {
     constexpr int W = Packed<BITS>::words(NANT), TS = 1 << BITS;
@@ -275,6 +374,47 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
     };
     int r = r0 + 2 * (int)threadIdx.x;
     load(r);                                     // the first sweep's indices are in flight while the table is filled and x is snapped
+    double *__restrict__ out = WRITE ? dists + (size_t)e * maxR : nullptr;
+    unsigned best = FRIRL_HIP_NO_HIT;
+
+    if constexpr (SQ) {
+        double *sq_s = tab_s;                    // [NANT][2^BITS] squared differences
+        double tv[(NANT * TS + FRIRL_BLOCK - 1) / FRIRL_BLOCK];
+        load_sq_sources<NANT, BITS, FRIRL_BLOCK>(ve, U, tv);
+        if (threadIdx.x < NANT)
+            q_s[threadIdx.x] = qv ? qv[(size_t)e * NANT + threadIdx.x] : observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
+        __syncthreads();
+        const bool fast = !__syncthreads_or(!fill_sq_table<NANT, BITS, FRIRL_BLOCK>(q_s, sq_s, tv));   // uniform
+        auto sweep = [&](auto fast_tag) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            for (; r < r_end; r += STEP * UNROLL) {
+                if (r != r0 + 2 * (int)threadIdx.x) load(r);
+#pragma unroll
+                for (int j = 0; j < UNROLL; j++) {
+                    const int rr = r + j * STEP;
+                    if (rr < r_end) {
+                        double2 d;
+                        bool z0, z1;
+                        pk_pair_sq<NANT, BITS, FAST>(w[j], sq_s, d, z0, z1);
+                        if (WRITE) { __builtin_nontemporal_store(d.x, out + rr); __builtin_nontemporal_store(d.y, out + rr + 1); }
+                        if (z1 && rr + 1 < R) best = min(best, (unsigned)(rr + 1));
+                        if (z0) best = min(best, (unsigned)rr);
+                    }
+                }
+            }
+        };
+        if (fast) sweep(std::true_type{});
+        else sweep(std::false_type{});
+        best = wave_min_u32(best);
+        if ((threadIdx.x & (FRIRL_WAVE - 1)) == 0) red_s[threadIdx.x / FRIRL_WAVE] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned m = red_s[0];
+            for (int v = 1; v < FRIRL_WAVES_PER_BLOCK; v++) m = red_s[v] < m ? red_s[v] : m;
+            if (m != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], m);
+        }
+        return;
+    }
 
     for (int i = threadIdx.x; i < NANT * TS; i += FRIRL_BLOCK) {
         const int k = i >> BITS, j = i & (TS - 1);
@@ -285,9 +425,6 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
     double q[NANT];
 #pragma unroll
     for (int k = 0; k < NANT; k++) q[k] = q_s[k];
-
-    double *__restrict__ out = WRITE ? dists + (size_t)e * maxR : nullptr;
-    unsigned best = FRIRL_HIP_NO_HIT;
 
     for (; r < r_end; r += STEP * UNROLL) {
         if (r != r0 + 2 * (int)threadIdx.x) load(r);
@@ -583,6 +720,11 @@ static int launch_nant(const frirl_hip_tables *t, const frirl_hip_rulebases *b, 
 }
 
 // Packed form: BITS = 6 (U <= 64), small tables.  chunk = ONE sweep of the workgroup (256 threads x 2 rules x UNROLL column sets).
+// Squared-difference form (rd_sqdiff, profiles/r05_cfg4_sqdiff.md), cfg4 / cfg2 medians of 5-7 x 20 launches: unroll 8 with 4096-rule
+// items 1.116-1.119 / 0.138-0.142 ms (rd_sqdiff=0: 1.177-1.181 / 0.138-0.139); unroll 4 with 2048-rule items 1.174 / 0.147, with 4096
+// 1.179 / 0.144; unroll 8 with 8192-rule items 1.163 / 0.203.  The observation pre-pass (rd_qpass=1: observe_reset_kernel in place of
+// the memset) measured 1.138 / 0.142 and is off.  It runs at 82 VGPRs (5 waves per SIMD); capping the kernel at 6 or 7 waves per SIMD
+// (amdgpu_waves_per_eu) measured 1.132 / 1.145 ms at cfg4.
 // 8 column sets per lane (4096-rule items) for nant <= 5: tools/ab_rd.py, cfg4 / cfg2, medians of 5 x 20 launches on one box --
 // unroll 8: 1.175 / 0.135 ms, 4: 1.263 / 0.145, 2: 1.517 / 0.178; unroll 8 with 8192-rule items 1.180 / 0.204, with 16384 1.234;
 // unroll 4 with 4096-rule items 1.202 / 0.139, with 8192 1.212 (the 16-bit mirror: 1.585 / 0.149).
@@ -600,6 +742,26 @@ struct RdPkConfig {
     static constexpr int UNROLL = NANT <= 5 ? 8 : 4;
 };
 
+template <int NANT, int UN, bool SQ>
+static void launch_pk(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x, const double *qv,
+                      double *ruledists, uint32_t *hit, hipStream_t s, const RdGrid &g)
+{
+    if (ruledists)
+        hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, true, UN, RD_PK_BITS, SQ>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,
+                           b->nrules, b->maxR, x, qv, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);
+    else
+        hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, false, UN, RD_PK_BITS, SQ>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,
+                           b->nrules, b->maxR, x, qv, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);
+}
+
+template <int NANT, int UN>
+static void launch_pk_form(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x, const double *qv,
+                           double *ruledists, uint32_t *hit, hipStream_t s, const RdGrid &g, bool sq)
+{
+    if (sq) launch_pk<NANT, UN, true>(t, b, pidx, x, qv, ruledists, hit, s, g);
+    else launch_pk<NANT, UN, false>(t, b, pidx, x, nullptr, ruledists, hit, s, g);
+}
+
 template <int NANT>
 static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
                          double *ruledists, uint32_t *hit, hipStream_t s)
@@ -608,24 +770,59 @@ static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     constexpr int UP = RdPkConfig<NANT>::UNROLL;
     const RdTune tn = rd_tune();
     const int un = (NANT <= 5 && tn.unroll) ? tn.unroll : UP;              // tuning hook (experiments only)
+    const bool sq = opts().rd_sqdiff != 0;
+    const bool qpass = sq && opts().rd_qpass == 1;
     RdGrid g;
     if (!make_grid(b, tn.chunk > 0 ? tn.chunk : 2 * FRIRL_BLOCK * un, g)) { set_error("five_hip_rule_distance_packed: too many work items"); return FRIRL_HIP_EINVAL; }
-    if (hipMemsetAsync(hit, 0xFF, sizeof(uint32_t) * (size_t)b->E, s) != hipSuccess) return check_launch("five_hip_rule_distance_packed(memset)");
-#define VP(U_)                                                                                                                                          \
-    do {                                                                                                                                                \
-        if (ruledists)                                                                                                                                  \
-            hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, true, U_, RD_PK_BITS>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,  \
-                               b->nrules, b->maxR, x, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);                                   \
-        else                                                                                                                                            \
-            hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, false, U_, RD_PK_BITS>), dim3(g.items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx, \
-                               b->nrules, b->maxR, x, ruledists, hit, g.rules_per_block, g.cpe, b->E, g.env_fastest);                                   \
-    } while (0)
-    if (NANT <= 5 && un == 8) VP(8);
-    else if (NANT <= 5 && un == 2) VP(2);
-    else if (NANT <= 5 && un == 1) VP(1);
-    else VP(UP);
-#undef VP
+    void *scratch = nullptr;
+    const double *qv = nullptr;
+    if (qpass) {
+        // [counter | qv[E][NANT]] from the stream's pool, as in launch_persist; observe_reset_kernel also resets the hit words
+        const size_t qv_off = 256, bytes = qv_off + sizeof(double) * (size_t)b->E * NANT;
+        const hipError_t e1 = hipMallocAsync(&scratch, bytes, s);
+        if (e1 != hipSuccess) { (void)hipGetLastError(); set_error("five_hip_rule_distance_packed: hipMallocAsync(%zu B) failed: %s", bytes, hipGetErrorString(e1)); return FRIRL_HIP_ELAUNCH; }
+        double *q = reinterpret_cast<double *>(static_cast<char *>(scratch) + qv_off);
+        const int nq = b->E * NANT;
+        hipLaunchKernelGGL(observe_reset_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, t->u, t->ve, t->U, NANT, b->E, x, q, hit, static_cast<unsigned *>(scratch));
+        qv = q;
+    } else if (hipMemsetAsync(hit, 0xFF, sizeof(uint32_t) * (size_t)b->E, s) != hipSuccess) {
+        return check_launch("five_hip_rule_distance_packed(memset)");
+    }
+    if constexpr (NANT <= 5) {
+        if (un == 4) launch_pk_form<NANT, 4>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+        else if (un == 2) launch_pk_form<NANT, 2>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+        else if (un == 1) launch_pk_form<NANT, 1>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+        else launch_pk_form<NANT, UP>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+    } else {
+        launch_pk_form<NANT, UP>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+    }
+    if (scratch && hipFreeAsync(scratch, s) != hipSuccess) { set_error("five_hip_rule_distance_packed: hipFreeAsync failed"); return FRIRL_HIP_ELAUNCH; }
     return check_launch("five_hip_rule_distance_packed");
+}
+
+// Probes for the tests (five_hip_sqrt_unscaled_check, five_hip_rule_distance_sq_guard): the device functions the packed scan uses.
+__global__ void sqrt_unscaled_check_kernel(const double *__restrict__ a, double *__restrict__ fast, double *__restrict__ ref, long n)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fast[i] = sqrt_unscaled(a[i]);
+    ref[i] = __dsqrt_rn(a[i]);
+}
+
+template <int NANT>
+__global__ __launch_bounds__(FRIRL_BLOCK) void sq_guard_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
+                                                             const double *__restrict__ x, int32_t *__restrict__ ok)
+{
+    constexpr int TS = 1 << RD_PK_BITS;
+    __shared__ double sq_s[NANT * TS];
+    __shared__ double q_s[NANT];
+    const int e = blockIdx.x;
+    double tv[(NANT * TS + FRIRL_BLOCK - 1) / FRIRL_BLOCK];
+    load_sq_sources<NANT, RD_PK_BITS, FRIRL_BLOCK>(ve, U, tv);
+    if (threadIdx.x < NANT) q_s[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
+    __syncthreads();
+    const bool fast = !__syncthreads_or(!fill_sq_table<NANT, RD_PK_BITS, FRIRL_BLOCK>(q_s, sq_s, tv));
+    if (threadIdx.x == 0) ok[e] = fast ? 1 : 0;
 }
 
 }  // namespace frirl
@@ -675,6 +872,34 @@ extern "C" int frirl_hip_pack_indices(const frirl_hip_tables *t, const frirl_hip
     hipLaunchKernelGGL(frirl::pack_indices_kernel<frirl::RD_PK_BITS>, dim3((unsigned)grid), dim3(FRIRL_BLOCK), 0, as_stream(stream), b->uidx, t->nant,
                        b->maxR, total, pidx);
     return check_launch("frirl_hip_pack_indices");
+}
+
+extern "C" int five_hip_sqrt_unscaled_check(const double *a, double *fast, double *ref, int64_t n, void *stream)
+{
+    using namespace frirl_host;
+    if (n < 0 || (n && (!a || !fast || !ref))) { set_error("five_hip_sqrt_unscaled_check: bad arguments"); return FRIRL_HIP_EINVAL; }
+    int rc = check_device();
+    if (rc) return rc;
+    if (n) hipLaunchKernelGGL(frirl::sqrt_unscaled_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), a, fast, ref, (long)n);
+    return check_launch("five_hip_sqrt_unscaled_check");
+}
+
+extern "C" int five_hip_rule_distance_sq_guard(const frirl_hip_tables *t, int32_t E, const double *x, int32_t *ok, void *stream)
+{
+    using namespace frirl_host;
+    int rc = check_tables(t);
+    if (rc) return rc;
+    if (!frirl::packed_words(t->nant, t->U)) { set_error("five_hip_rule_distance_sq_guard: nant=%d U=%d is not served by the packed form", t->nant, t->U); return FRIRL_HIP_EINVAL; }
+    if (E < 0 || (E && (!x || !ok))) { set_error("five_hip_rule_distance_sq_guard: bad arguments"); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_device())) return rc;
+    if (!E) return 0;
+    switch (t->nant) {
+#define FRIRL_CASE(N) case N: hipLaunchKernelGGL(frirl::sq_guard_kernel<N>, dim3((unsigned)E), dim3(FRIRL_BLOCK), 0, as_stream(stream), t->u, t->ve, t->U, x, ok); break;
+        FRIRL_CASE(1) FRIRL_CASE(2) FRIRL_CASE(3) FRIRL_CASE(4) FRIRL_CASE(5) FRIRL_CASE(6) FRIRL_CASE(7) FRIRL_CASE(8)
+        FRIRL_CASE(9) FRIRL_CASE(10) FRIRL_CASE(11) FRIRL_CASE(12) FRIRL_CASE(13) FRIRL_CASE(14) FRIRL_CASE(15) FRIRL_CASE(16)
+#undef FRIRL_CASE
+    }
+    return check_launch("five_hip_rule_distance_sq_guard");
 }
 
 extern "C" int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,

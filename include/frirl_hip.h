@@ -98,7 +98,8 @@ int frirl_hip_device_count(void);                 /* number of visible gfx950 de
 int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, int64_t *hbm_bytes);
 
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
- * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
+ * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -133,6 +134,15 @@ int five_hip_rule_distance_packed_words(int32_t nant, int32_t U);
 int frirl_hip_pack_indices(const frirl_hip_tables *t, const frirl_hip_rulebases *b, uint32_t *pidx, void *stream);
 int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
                                   double *ruledists, uint32_t *hit, void *stream);
+/* Test probes of the packed scan's squared-difference form (option rd_sqdiff, shipped).  The scan sums per-workgroup tables of
+ * (q_k - ve[k][i])^2 and, when every entry of the workgroup's tables is 0 or within [2^-767, 2^1000], takes the square root
+ * without __dsqrt_rn's rescaling and special-case steps; otherwise it calls __dsqrt_rn.
+ * five_hip_sqrt_unscaled_check: fast[i] = that short square root of a[i], ref[i] = __dsqrt_rn(a[i]), on the device, n >= 0.
+ * five_hip_rule_distance_sq_guard: ok[e] = 1 when the tables of environment e (observation x[e]) take the short square root, 0
+ * when the scan falls back to __dsqrt_rn; shapes served by the packed form only.
+ *   a, fast, ref [dev] [n] double;  x [dev] [E][nant];  ok [dev] [E] int32 */
+int five_hip_sqrt_unscaled_check(const double *a, double *fast, double *ref, int64_t n, void *stream);
+int five_hip_rule_distance_sq_guard(const frirl_hip_tables *t, int32_t E, const double *x, int32_t *ok, void *stream);
 
 /* ---- FIVE_vag_concl (reference src/five/FIVEVagConcl.c:64-351, default-flag live path) ------
  * Q value of one observation per rule base: the consequent of the first exact-hit rule, else the
