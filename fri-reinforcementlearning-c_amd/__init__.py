@@ -104,6 +104,9 @@ SIGNATURES = {
     "frirl_hip_pack_indices": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p]),
     "five_hip_rule_distance_packed": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "five_hip_rule_distance_packed_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "five_hip_rule_distance_packed_ws": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "five_hip_sqrt_unscaled_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "five_hip_rule_distance_sq_guard": (C.c_int, [C.POINTER(Tables), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "five_hip_vag_concl": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -272,6 +275,9 @@ class Problem:
         if W > 0:
             self.pidx = torch.empty((self.E, W, self.maxR), dtype=torch.int32, device=self.uidx.device)
             self._pack(None)
+        # workspaces of five_hip_rule_distance_packed_ws (per-call squared-difference tables), one per stream the scan is called on:
+        # calls on different streams may run at the same time and must not share one
+        self._rd_ws = {}
 
     @property
     def bases(self):
@@ -292,8 +298,17 @@ class Problem:
             self._pack(stream)
         return self.pidx
 
+    def _rd_workspace(self, stream):
+        """The packed scan's workspace for `stream` (uint8 tensor, allocated on first use), or None for a shape without one."""
+        import torch
+        key = _stream(stream).value
+        if key not in self._rd_ws:
+            n = lib().five_hip_rule_distance_packed_workspace_bytes(self.nant, self.U, self.E)
+            self._rd_ws[key] = torch.empty((n,), dtype=torch.uint8, device=self.pidx.device) if n else None
+        return self._rd_ws[key]
+
     def rule_distance(self, x, ruledists=None, hit=None, materialise=True, stream=None):
-        """five_hip_rule_distance (five_hip_rule_distance_packed while the packed mirror exists): returns (ruledists [E,maxR]
+        """five_hip_rule_distance (five_hip_rule_distance_packed_ws while the packed mirror exists): returns (ruledists [E,maxR]
         or None, hit [E] int32 with -1 = none)."""
         import torch
         assert x.is_cuda and x.dtype == torch.float64 and x.shape == (self.E, self.nant) and x.is_contiguous()
@@ -302,9 +317,11 @@ class Problem:
         if hit is None:
             hit = torch.empty((self.E,), dtype=torch.int32, device=x.device)
         if self.pidx is not None:
-            rc = lib().five_hip_rule_distance_packed(C.byref(self.tables), C.byref(self._bases), _ptr(self._pidx_current(stream)), _ptr(x),
-                                                     _ptr(ruledists) if materialise else None, _ptr(hit), _stream(stream))
-            check(rc, "five_hip_rule_distance_packed")
+            ws = self._rd_workspace(stream)
+            rc = lib().five_hip_rule_distance_packed_ws(C.byref(self.tables), C.byref(self._bases), _ptr(self._pidx_current(stream)), _ptr(x),
+                                                        _ptr(ruledists) if materialise else None, _ptr(hit), _ptr(ws),
+                                                        ws.numel() if ws is not None else 0, _stream(stream))
+            check(rc, "five_hip_rule_distance_packed_ws")
         else:
             rc = lib().five_hip_rule_distance(C.byref(self.tables), C.byref(self._bases), _ptr(x),
                                               _ptr(ruledists) if materialise else None, _ptr(hit), _stream(stream))

@@ -38,6 +38,13 @@
 //                                 rescale and special-case steps (sqrt_unscaled); otherwise __dsqrt_rn.  The same operations
 //                                 on the same doubles in the same order: bit-identical.  cfg4: 27 % fewer VALU instructions,
 //                                 1.18 -> 1.12 ms (profiles/r05_cfg4_sqdiff.md).
+//                                 With a caller's workspace (five_hip_rule_distance_packed_ws, option rd_prepass, PRE) the tables,
+//                                 the flags and the hit reset are done once per call by sq_tables_kernel (in place of the memset),
+//                                 the scan's prologue is a copy, the workgroups of an environment share an XCD (one L2 fetches the
+//                                 table) and items are 2048 rules: 1.124 -> 1.087 ms (profiles/r06_cfg4_prepass.md).
+//                                 Floor: reads (~7 TB/s) and the 16-B write stream (5.5-5.9 TB/s) share HBM's one data bus, so their
+//                                 times ADD (0.30 + 0.73...0.78 ms at cfg4); what is left above that sum is issue work and the
+//                                 shape of the window the resident workgroups touch, not a lack of overlap.
 // First exact hit: per-lane minimum index -> wave butterfly -> (LDS ->) one integer atomicMin per workgroup / item
 // (deterministic; only taken when a hit exists).
 // "rd_*" / "no_uidx" options (frirl_hip_set_option) are experiment hooks (tools/ab_rd.py); unset, the shipped configuration runs.
@@ -220,6 +227,7 @@ __global__ __launch_bounds__(BLOCK) void rule_distance_idx_kernel(
 // Same item order, two adjacent rules per lane (one 8 B load per word and column set: 512 contiguous bytes per wave), the
 // same 16 B distance stores, the same subtract / multiply / add sequence as the kernels above (bit-identical results).
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+static constexpr int RD_XCDS = 8;                // MI355X: workgroups are dealt round-robin over 8 XCDs, each with an L2 of its own
 
 template <int BITS>
 __device__ __forceinline__ double pk_table_entry(const double *__restrict__ tab_k, uint32_t w, int sh)
@@ -306,16 +314,17 @@ __device__ __forceinline__ void pk_pair_sq(const u32x2_t (&w)[Packed<BITS>::word
     }
 }
 
-// One environment's squared-difference table (above) from its snapped observations q_s; returns true when every entry is in
-// the range of sqrt_unscaled.  Shared by rule_distance_pk_kernel and the probe five_hip_rule_distance_sq_guard.
+// One environment's squared-difference table (above) from its snapped observations q_s, by BLOCK threads numbered tid (sq_s: LDS in
+// the scan, the environment's rows of the workspace in sq_tables_kernel); returns true when every entry is in the range of
+// sqrt_unscaled.  Shared by rule_distance_pk_kernel, sq_tables_kernel and the probe five_hip_rule_distance_sq_guard.
 template <int NANT, int BITS, int BLOCK>
-__device__ __forceinline__ bool fill_sq_table(const double *q_s, double *sq_s, const double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK])
+__device__ __forceinline__ bool fill_sq_table(const double *q_s, double *sq_s, const double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK], int tid)
 {
     constexpr int TS = 1 << BITS, N = NANT * TS;
     bool ok = true;
 #pragma unroll
     for (int m = 0; m < (N + BLOCK - 1) / BLOCK; m++) {
-        const int i = (int)threadIdx.x + m * BLOCK;
+        const int i = tid + m * BLOCK;
         if (N % BLOCK == 0 || i < N) {
             const double d = q_s[i >> BITS] - tv[m];
             const double s = d * d;
@@ -326,33 +335,77 @@ __device__ __forceinline__ bool fill_sq_table(const double *q_s, double *sq_s, c
     return ok;
 }
 
-// tv[m] = the table value of entry threadIdx.x + m * BLOCK of fill_sq_table (loaded before the observations are known)
+// tv[m] = the table value of entry tid + m * BLOCK of fill_sq_table (loaded before the observations are known)
 template <int NANT, int BITS, int BLOCK>
-__device__ __forceinline__ void load_sq_sources(const double *__restrict__ ve, int U, double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK])
+__device__ __forceinline__ void load_sq_sources(const double *__restrict__ ve, int U, double (&tv)[(NANT * (1 << BITS) + BLOCK - 1) / BLOCK], int tid)
 {
     constexpr int TS = 1 << BITS, N = NANT * TS;
 #pragma unroll
     for (int m = 0; m < (N + BLOCK - 1) / BLOCK; m++) {
-        const int i = (int)threadIdx.x + m * BLOCK;
+        const int i = tid + m * BLOCK;
         const int k = i >> BITS, j = i & (TS - 1);
         tv[m] = (i < N && j < U) ? ve[k * U + j] : 0.0;
     }
 }
 
+// Per-call pre-pass of the packed scan (option rd_prepass, five_hip_rule_distance_packed_ws): what the workgroups of an environment
+// would each redo in their prologue, done once -- one wave per environment, with the device functions of that prologue (same bits):
+//   sqtab[e][k][i] = (q_k - ve[k][i])^2, q_k = observe_ve(x[e][k]) (0.0 table values on the padding entries i >= U),
+//   fastv[e] = 1 when every entry is in the range of sqrt_unscaled, else 0,   hit[e] = "none" (in place of the memset).
+template <int NANT, int BITS>
+__global__ __launch_bounds__(FRIRL_BLOCK) void sq_tables_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U, int E,
+                                                              const double *__restrict__ x, double *__restrict__ sqtab,
+                                                              uint32_t *__restrict__ fastv, uint32_t *__restrict__ hit)
+{
+    constexpr int TS = 1 << BITS, N = NANT * TS;
+    __shared__ double q_s[FRIRL_WAVES_PER_BLOCK][NANT];
+    const int lane = threadIdx.x & (FRIRL_WAVE - 1), wave = threadIdx.x / FRIRL_WAVE;
+    const int e = blockIdx.x * FRIRL_WAVES_PER_BLOCK + wave;
+    const bool live = e < E;                     // uniform for the wave; every wave reaches the barrier
+    double tv[(N + FRIRL_WAVE - 1) / FRIRL_WAVE];
+    load_sq_sources<NANT, BITS, FRIRL_WAVE>(ve, U, tv, lane);
+    if (live && lane < NANT) q_s[wave][lane] = observe_ve(u, ve, U, lane, x[(size_t)e * NANT + lane]);
+    __syncthreads();
+    if (!live) return;
+    const bool ok = fill_sq_table<NANT, BITS, FRIRL_WAVE>(q_s[wave], sqtab + (size_t)e * N, tv, lane);
+    const bool fast = __all(ok);
+    if (lane == 0) {
+        fastv[e] = fast ? 1u : 0u;
+        hit[e] = FRIRL_HIP_NO_HIT;
+    }
+}
+
 // SQ = false: the kernel as it was before the squared-difference tables (option rd_sqdiff = 0, A/B only).
 // qv != nullptr: the snapped observations qv[e][k] of observe_reset_kernel (option rd_qpass) instead of observe_ve in the prologue.
-template <int NANT, bool WRITE, int UNROLL, int BITS, bool SQ>
+// PRE (with SQ; option rd_prepass, shipped where the caller gives a workspace): the prologue is a copy -- the environment's table
+// sqtab[e] of sq_tables_kernel goes to LDS with plain loads (its sibling workgroups read the same 2^BITS * NANT doubles) and the
+// flag fastv[e] is one scalar load: no u / ve / x, no division, one barrier.  Sweep, stores and hit reduction are those of SQ.
+// env_fastest: 0 = chunk fastest (PRE: within groups of RD_XCDS environments, see below), 1 = environment fastest, 2 = PRE with the
+// plain chunk-fastest order (A/B).
+template <int NANT, bool WRITE, int UNROLL, int BITS, bool SQ, bool PRE = false>
 __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
     const double *__restrict__ u, const double *__restrict__ ve, int U, const uint32_t *__restrict__ pidx,
     const int32_t *__restrict__ nrules, int maxR, const double *__restrict__ x, const double *__restrict__ qv, double *__restrict__ dists,
-    uint32_t *__restrict__ hit, int rules_per_block, int cpe, int E, int env_fastest)
+    uint32_t *__restrict__ hit, int rules_per_block, int cpe, int E, int env_fastest, const double *__restrict__ sqtab = nullptr,
+    const uint32_t *__restrict__ fastv = nullptr)
 {
+    static_assert(SQ || !PRE, "the pre-pass serves the squared-difference form");
     constexpr int W = Packed<BITS>::words(NANT), TS = 1 << BITS;
-    __shared__ double tab_s[NANT * TS];          // [NANT][2^BITS] vague environments (static: row offsets are immediates)
+    __shared__ __attribute__((aligned(16))) double tab_s[NANT * TS];      // [NANT][2^BITS] vague environments (static: row offsets are immediates)
     __shared__ double q_s[NANT];
     __shared__ unsigned red_s[FRIRL_WAVES_PER_BLOCK];
     int e, c;
-    item_to_env_chunk(blockIdx.x, cpe, E, env_fastest != 0, e, c);
+    if (PRE && env_fastest == 0) {
+        // The workgroups of an environment on ONE XCD, so that its table is fetched into one L2 and not into eight: workgroups b and
+        // b + RD_XCDS share an XCD, so RD_XCDS consecutive environments take the RD_XCDS * cpe workgroups of a group, environment =
+        // workgroup index mod RD_XCDS, chunks ascending.  The grid is rounded up to whole groups: e >= E leaves at once.
+        const unsigned grp = blockIdx.x / (unsigned)(RD_XCDS * cpe), j = blockIdx.x - grp * (unsigned)(RD_XCDS * cpe);
+        e = (int)(grp * RD_XCDS + j % RD_XCDS);
+        c = (int)(j / RD_XCDS);
+        if (e >= E) return;
+    } else {
+        item_to_env_chunk(blockIdx.x, cpe, E, env_fastest == 1, e, c);
+    }
     const int R = nrules[e];
     const int r0 = c * rules_per_block;
     if (r0 >= R) return;
@@ -379,12 +432,21 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_pk_kernel(
 
     if constexpr (SQ) {
         double *sq_s = tab_s;                    // [NANT][2^BITS] squared differences
-        double tv[(NANT * TS + FRIRL_BLOCK - 1) / FRIRL_BLOCK];
-        load_sq_sources<NANT, BITS, FRIRL_BLOCK>(ve, U, tv);
-        if (threadIdx.x < NANT)
-            q_s[threadIdx.x] = qv ? qv[(size_t)e * NANT + threadIdx.x] : observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
-        __syncthreads();
-        const bool fast = !__syncthreads_or(!fill_sq_table<NANT, BITS, FRIRL_BLOCK>(q_s, sq_s, tv));   // uniform
+        bool fast;                               // uniform
+        if constexpr (PRE) {
+            constexpr int N2 = NANT * TS / 2;    // 16 B per lane; sqtab + e * NANT * TS is 16-byte aligned (TS even, workspace checked)
+            const double2 *__restrict__ src = reinterpret_cast<const double2 *>(sqtab + (size_t)e * (NANT * TS));
+            for (int i = threadIdx.x; i < N2; i += FRIRL_BLOCK) reinterpret_cast<double2 *>(sq_s)[i] = src[i];
+            fast = fastv[e] != 0u;
+            __syncthreads();
+        } else {
+            double tv[(NANT * TS + FRIRL_BLOCK - 1) / FRIRL_BLOCK];
+            load_sq_sources<NANT, BITS, FRIRL_BLOCK>(ve, U, tv, (int)threadIdx.x);
+            if (threadIdx.x < NANT)
+                q_s[threadIdx.x] = qv ? qv[(size_t)e * NANT + threadIdx.x] : observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
+            __syncthreads();
+            fast = !__syncthreads_or(!fill_sq_table<NANT, BITS, FRIRL_BLOCK>(q_s, sq_s, tv, (int)threadIdx.x));
+        }
         auto sweep = [&](auto fast_tag) {
             constexpr bool FAST = decltype(fast_tag)::value;
             for (; r < r_end; r += STEP * UNROLL) {
@@ -723,7 +785,7 @@ static int launch_nant(const frirl_hip_tables *t, const frirl_hip_rulebases *b, 
 // Squared-difference form (rd_sqdiff, profiles/r05_cfg4_sqdiff.md), cfg4 / cfg2 medians of 5-7 x 20 launches: unroll 8 with 4096-rule
 // items 1.116-1.119 / 0.138-0.142 ms (rd_sqdiff=0: 1.177-1.181 / 0.138-0.139); unroll 4 with 2048-rule items 1.174 / 0.147, with 4096
 // 1.179 / 0.144; unroll 8 with 8192-rule items 1.163 / 0.203.  The observation pre-pass (rd_qpass=1: observe_reset_kernel in place of
-// the memset) measured 1.138 / 0.142 and is off.  It runs at 82 VGPRs (5 waves per SIMD); capping the kernel at 6 or 7 waves per SIMD
+// the memset) measured 1.138 / 0.142 and is off (rd_prepass supersedes it: it is an A/B hook of the rd_prepass = 0 path only).  It runs at 82 VGPRs (5 waves per SIMD); capping the kernel at 6 or 7 waves per SIMD
 // (amdgpu_waves_per_eu) measured 1.132 / 1.145 ms at cfg4.
 // 8 column sets per lane (4096-rule items) for nant <= 5: tools/ab_rd.py, cfg4 / cfg2, medians of 5 x 20 launches on one box --
 // unroll 8: 1.175 / 0.135 ms, 4: 1.263 / 0.145, 2: 1.517 / 0.178; unroll 8 with 8192-rule items 1.180 / 0.204, with 16384 1.234;
@@ -740,7 +802,19 @@ static int packed_words(int nant, int U)
 template <int NANT>
 struct RdPkConfig {
     static constexpr int UNROLL = NANT <= 5 ? 8 : 4;
+    // with the pre-pass (rd_prepass) the prologue is a copy and 2048-rule items win: 52 VGPRs (8 waves per SIMD) instead of 80 (6).
+    // cfg4 / cfg2, medians of 7 x 20 launches on one box (profiles/r06_cfg4_prepass.md): per-workgroup tables 1.077 / 0.139 ms;
+    // pre-pass with unroll 8 1.074 / 0.142, unroll 4 1.053 / 0.138, unroll 4 with 4096-rule items 1.101 / 0.148, unroll 2 1.095 / 0.140,
+    // unroll 2 with 2048-rule items 1.074 / 0.139, unroll 1 1.401 / 0.182; unroll 8 WITHOUT the XCD grouping of the items 1.143 / 0.143.
+    static constexpr int UNROLL_PRE = 4;
 };
+
+// Workspace of the pre-pass form: [sqtab[E][NANT][2^BITS] f64 | fastv[E] u32], 16-byte aligned, owned by the caller.
+static size_t packed_ws_bytes(int nant, int U, long E)
+{
+    if (!packed_words(nant, U) || E < 1) return 0;
+    return (sizeof(double) * (size_t)nant * (1u << RD_PK_BITS) + sizeof(uint32_t)) * (size_t)E;
+}
 
 template <int NANT, int UN, bool SQ>
 static void launch_pk(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x, const double *qv,
@@ -762,18 +836,51 @@ static void launch_pk_form(const frirl_hip_tables *t, const frirl_hip_rulebases 
     else launch_pk<NANT, UN, false>(t, b, pidx, x, nullptr, ruledists, hit, s, g);
 }
 
+// Pre-pass form: sq_tables_kernel (tables, flags, hit reset) + the scan whose prologue copies its environment's table.
+template <int NANT, int UN>
+static void launch_pk_pre(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x, double *ruledists,
+                          uint32_t *hit, void *ws, hipStream_t s, const RdGrid &g)
+{
+    double *sqtab = static_cast<double *>(ws);
+    uint32_t *fastv = reinterpret_cast<uint32_t *>(sqtab + (size_t)b->E * NANT * (1 << RD_PK_BITS));
+    const int order = frirl_host::opts().rd_order;                          // 0: environments grouped by XCD (grid of whole groups)
+    const unsigned items = order == 0 ? (unsigned)g.cpe * (unsigned)((b->E + RD_XCDS - 1) / RD_XCDS * RD_XCDS) : g.items;
+    hipLaunchKernelGGL((sq_tables_kernel<NANT, RD_PK_BITS>), dim3((unsigned)((b->E + FRIRL_WAVES_PER_BLOCK - 1) / FRIRL_WAVES_PER_BLOCK)), dim3(FRIRL_BLOCK),
+                       0, s, t->u, t->ve, t->U, b->E, x, sqtab, fastv, hit);
+    if (ruledists)
+        hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, true, UN, RD_PK_BITS, true, true>), dim3(items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,
+                           b->nrules, b->maxR, x, nullptr, ruledists, hit, g.rules_per_block, g.cpe, b->E, order, sqtab, fastv);
+    else
+        hipLaunchKernelGGL((rule_distance_pk_kernel<NANT, false, UN, RD_PK_BITS, true, true>), dim3(items), dim3(FRIRL_BLOCK), 0, s, t->u, t->ve, t->U, pidx,
+                           b->nrules, b->maxR, x, nullptr, ruledists, hit, g.rules_per_block, g.cpe, b->E, order, sqtab, fastv);
+}
+
+// ws: the caller's workspace (five_hip_rule_distance_packed_ws, already checked) or nullptr (five_hip_rule_distance_packed)
 template <int NANT>
 static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
-                         double *ruledists, uint32_t *hit, hipStream_t s)
+                         double *ruledists, uint32_t *hit, void *ws, hipStream_t s)
 {
     using namespace frirl_host;
-    constexpr int UP = RdPkConfig<NANT>::UNROLL;
     const RdTune tn = rd_tune();
-    const int un = (NANT <= 5 && tn.unroll) ? tn.unroll : UP;              // tuning hook (experiments only)
     const bool sq = opts().rd_sqdiff != 0;
-    const bool qpass = sq && opts().rd_qpass == 1;
+    const bool pre = ws && sq && opts().rd_prepass != 0;
+    const int UP = pre ? RdPkConfig<NANT>::UNROLL_PRE : RdPkConfig<NANT>::UNROLL;
+    const int un = (NANT <= 5 && tn.unroll) ? tn.unroll : UP;              // tuning hook (experiments only)
+    const bool qpass = sq && !pre && opts().rd_qpass == 1;
     RdGrid g;
     if (!make_grid(b, tn.chunk > 0 ? tn.chunk : 2 * FRIRL_BLOCK * un, g)) { set_error("five_hip_rule_distance_packed: too many work items"); return FRIRL_HIP_EINVAL; }
+    if (pre) {
+        if ((long)g.cpe * ((long)b->E + RD_XCDS) > 0x7FFFFFFFL) { set_error("five_hip_rule_distance_packed_ws: too many work items"); return FRIRL_HIP_EINVAL; }
+        if constexpr (NANT <= 5) {
+            if (un == 8) launch_pk_pre<NANT, 8>(t, b, pidx, x, ruledists, hit, ws, s, g);
+            else if (un == 2) launch_pk_pre<NANT, 2>(t, b, pidx, x, ruledists, hit, ws, s, g);
+            else if (un == 1) launch_pk_pre<NANT, 1>(t, b, pidx, x, ruledists, hit, ws, s, g);
+            else launch_pk_pre<NANT, 4>(t, b, pidx, x, ruledists, hit, ws, s, g);
+        } else {
+            launch_pk_pre<NANT, RdPkConfig<NANT>::UNROLL_PRE>(t, b, pidx, x, ruledists, hit, ws, s, g);
+        }
+        return check_launch("five_hip_rule_distance_packed_ws");
+    }
     void *scratch = nullptr;
     const double *qv = nullptr;
     if (qpass) {
@@ -792,9 +899,9 @@ static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b
         if (un == 4) launch_pk_form<NANT, 4>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
         else if (un == 2) launch_pk_form<NANT, 2>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
         else if (un == 1) launch_pk_form<NANT, 1>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
-        else launch_pk_form<NANT, UP>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+        else launch_pk_form<NANT, RdPkConfig<NANT>::UNROLL>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
     } else {
-        launch_pk_form<NANT, UP>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
+        launch_pk_form<NANT, RdPkConfig<NANT>::UNROLL>(t, b, pidx, x, qv, ruledists, hit, s, g, sq);
     }
     if (scratch && hipFreeAsync(scratch, s) != hipSuccess) { set_error("five_hip_rule_distance_packed: hipFreeAsync failed"); return FRIRL_HIP_ELAUNCH; }
     return check_launch("five_hip_rule_distance_packed");
@@ -818,10 +925,10 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void sq_guard_kernel(const double *__r
     __shared__ double q_s[NANT];
     const int e = blockIdx.x;
     double tv[(NANT * TS + FRIRL_BLOCK - 1) / FRIRL_BLOCK];
-    load_sq_sources<NANT, RD_PK_BITS, FRIRL_BLOCK>(ve, U, tv);
+    load_sq_sources<NANT, RD_PK_BITS, FRIRL_BLOCK>(ve, U, tv, (int)threadIdx.x);
     if (threadIdx.x < NANT) q_s[threadIdx.x] = observe_ve(u, ve, U, threadIdx.x, x[(size_t)e * NANT + threadIdx.x]);
     __syncthreads();
-    const bool fast = !__syncthreads_or(!fill_sq_table<NANT, RD_PK_BITS, FRIRL_BLOCK>(q_s, sq_s, tv));
+    const bool fast = !__syncthreads_or(!fill_sq_table<NANT, RD_PK_BITS, FRIRL_BLOCK>(q_s, sq_s, tv, (int)threadIdx.x));
     if (threadIdx.x == 0) ok[e] = fast ? 1 : 0;
 }
 
@@ -902,12 +1009,11 @@ extern "C" int five_hip_rule_distance_sq_guard(const frirl_hip_tables *t, int32_
     return check_launch("five_hip_rule_distance_sq_guard");
 }
 
-extern "C" int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
-                                             double *ruledists, uint32_t *hit, void *stream)
+static int rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                double *ruledists, uint32_t *hit, void *ws, void *stream)
 {
     using namespace frirl_host;
-    int rc = check_rulebases(t, b);
-    if (rc) return rc;
+    int rc;
     // shapes the packed form does not serve, and the A/B / test switches: the scan of five_hip_rule_distance (16-bit mirror or f64 columns)
     const Options &o = opts();
     if (!frirl::packed_words(t->nant, t->U) || !o.rd_packed || o.no_uidx || o.rd_persist == 1)
@@ -919,11 +1025,41 @@ extern "C" int five_hip_rule_distance_packed(const frirl_hip_tables *t, const fr
     hipStream_t s = as_stream(stream);
 
     switch (t->nant) {
-#define FRIRL_CASE(N) case N: return frirl::launch_packed<N>(t, b, pidx, x, ruledists, hit, s);
+#define FRIRL_CASE(N) case N: return frirl::launch_packed<N>(t, b, pidx, x, ruledists, hit, ws, s);
         FRIRL_CASE(1) FRIRL_CASE(2) FRIRL_CASE(3) FRIRL_CASE(4) FRIRL_CASE(5) FRIRL_CASE(6) FRIRL_CASE(7) FRIRL_CASE(8)
         FRIRL_CASE(9) FRIRL_CASE(10) FRIRL_CASE(11) FRIRL_CASE(12) FRIRL_CASE(13) FRIRL_CASE(14) FRIRL_CASE(15) FRIRL_CASE(16)
 #undef FRIRL_CASE
     }
     set_error("five_hip_rule_distance_packed: unsupported nant=%d", t->nant);
     return FRIRL_HIP_EINVAL;
+}
+
+extern "C" int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                             double *ruledists, uint32_t *hit, void *stream)
+{
+    const int rc = frirl_host::check_rulebases(t, b);
+    return rc ? rc : rule_distance_packed(t, b, pidx, x, ruledists, hit, nullptr, stream);
+}
+
+extern "C" size_t five_hip_rule_distance_packed_workspace_bytes(int32_t nant, int32_t U, int32_t E)
+{
+    return frirl::packed_ws_bytes(nant, U, E);
+}
+
+extern "C" int five_hip_rule_distance_packed_ws(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                                double *ruledists, uint32_t *hit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace frirl_host;
+    const int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    const size_t need = frirl::packed_ws_bytes(t->nant, t->U, b->E);      // 0: a shape the packed form does not serve (no workspace)
+    if (need) {
+        if (!workspace || workspace_bytes < need) {
+            set_error("five_hip_rule_distance_packed_ws: workspace of %zu B at %p, nant=%d U=%d E=%d needs %zu B "
+                      "(five_hip_rule_distance_packed_workspace_bytes)", workspace_bytes, workspace, t->nant, t->U, b->E, need);
+            return FRIRL_HIP_EINVAL;
+        }
+        if (reinterpret_cast<uintptr_t>(workspace) & 15) { set_error("five_hip_rule_distance_packed_ws: workspace must be 16-byte aligned"); return FRIRL_HIP_EINVAL; }
+    }
+    return rule_distance_packed(t, b, pidx, x, ruledists, hit, need ? workspace : nullptr, stream);
 }

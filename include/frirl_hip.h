@@ -99,7 +99,8 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
- * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -134,6 +135,18 @@ int five_hip_rule_distance_packed_words(int32_t nant, int32_t U);
 int frirl_hip_pack_indices(const frirl_hip_tables *t, const frirl_hip_rulebases *b, uint32_t *pidx, void *stream);
 int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
                                   double *ruledists, uint32_t *hit, void *stream);
+/* five_hip_rule_distance_packed with a caller-owned workspace: the squared-difference tables of every environment (below) and the
+ * hit reset are done once per call by a pre-pass kernel into `workspace`, and the scan's workgroups copy their environment's table
+ * instead of rebuilding it (option rd_prepass, shipped; 0 = the per-workgroup tables of five_hip_rule_distance_packed).  Same contract
+ * and bits.  five_hip_rule_distance_packed_workspace_bytes(nant, U, E) is the size the call needs (0 for the shapes the packed form
+ * does not serve: workspace may then be NULL).  The workspace is scratch: nothing is kept in it between calls, but two calls that may
+ * run concurrently (different streams) need one each.  A NULL, misaligned (16 bytes) or too small workspace is FRIRL_HIP_EINVAL and
+ * nothing is launched.  After the call it holds sqtab[E][nant][64] f64 = (q_k - ve[k][i])^2 (table value 0.0 for i >= U), then
+ * fast[E] uint32 (1 = every entry of the environment's table is 0 or within [2^-767, 2^1000]).
+ *   workspace [dev] workspace_bytes bytes */
+size_t five_hip_rule_distance_packed_workspace_bytes(int32_t nant, int32_t U, int32_t E);
+int five_hip_rule_distance_packed_ws(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
+                                     double *ruledists, uint32_t *hit, void *workspace, size_t workspace_bytes, void *stream);
 /* Test probes of the packed scan's squared-difference form (option rd_sqdiff, shipped).  The scan sums per-workgroup tables of
  * (q_k - ve[k][i])^2 and, when every entry of the workgroup's tables is 0 or within [2^-767, 2^1000], takes the square root
  * without __dsqrt_rn's rescaling and special-case steps; otherwise it calls __dsqrt_rn.
