@@ -79,6 +79,12 @@ class AgentIO(C.Structure):
                 ("action_out", C.c_void_p), ("action_idx", C.c_void_p)]
 
 
+class PolicyRowsDesc(C.Structure):
+    """struct frirl_hip_policy_rows (include/frirl_hip.h)."""
+    _fields_ = [("Q", C.c_int32), ("done", C.c_void_p), ("ep_steps", C.c_void_p), ("success", C.c_void_p), ("ep_reward", C.c_void_p),
+                ("exclude_mask", C.c_void_p), ("rule_slot", C.c_void_p)]
+
+
 class ConvergenceDesc(C.Structure):
     """struct frirl_hip_convergence (include/frirl_hip.h)."""
     _fields_ = [("prev_nrules", C.c_void_p), ("prev_steps", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_rconc", C.c_void_p),
@@ -145,6 +151,17 @@ SIGNATURES = {
     "frirl_hip_agent_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]),
     "frirl_hip_agent_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
                                           C.c_void_p]),
+    "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
+    "frirl_hip_policy_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO),
+                                           C.c_void_p]),
+    "frirl_hip_reducer_create": (C.c_void_p, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_int, C.c_double, C.c_int,
+                                              C.c_void_p]),
+    "frirl_hip_reducer_next_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "frirl_hip_reducer_begin": (C.c_int, [C.c_void_p, C.POINTER(AgentIO)]),
+    "frirl_hip_reducer_observe": (C.c_int, [C.c_void_p, C.POINTER(AgentIO), C.POINTER(C.c_int32)]),
+    "frirl_hip_reducer_end_round": (C.c_int, [C.c_void_p]),
+    "frirl_hip_reducer_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReduceResult)]),
+    "frirl_hip_reducer_destroy": (None, [C.c_void_p]),
     "frirl_hip_episode_run": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_int32, C.c_void_p]),
     "frirl_hip_convergence_init": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(ConvergenceDesc), C.c_void_p]),
     "frirl_hip_convergence_update": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
@@ -417,6 +434,23 @@ class Problem:
               "frirl_hip_reduce_shared")
         return kept[: res.rules_after], res
 
+    def policy_begin(self, agent, rows, obs, reset=None, stream=None):
+        """frirl_hip_policy_begin: rows (PolicyRows) selected by `reset` ([Q] uint8 / bool, None = all) start a greedy episode on this ONE
+        rule base from the caller's observations obs [Q, nant-1].  Returns (action values [Q], action indices [Q]); rows that were not
+        restarted are not written.  Does not synchronise."""
+        io, action, action_idx = _agent_io(self, obs, reset=reset, E=rows.Q)
+        check(lib().frirl_hip_policy_begin(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(rows.desc), C.byref(io),
+                                           _stream(stream)), "frirl_hip_policy_begin")
+        return action, action_idx
+
+    def policy_observe(self, agent, rows, obs, reward, success, q_obs=None, stream=None):
+        """frirl_hip_policy_observe: one greedy step of every row that is not done, from what the caller's environment returned for the
+        last action (as agent_observe).  Returns (action values, action indices); rows that were done are not written."""
+        io, action, action_idx = _agent_io(self, obs, q_obs, reward, success, E=rows.Q)
+        check(lib().frirl_hip_policy_observe(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(rows.desc), C.byref(io),
+                                             _stream(stream)), "frirl_hip_policy_observe")
+        return action, action_idx
+
     def merge_rb(self, agent, sndr_rant, sndr_rconc, weights, rant_store=None, active=None, stream=None):
         """frirl_hip_merge_rb: every (active) rule base of this batch takes over the sender rules sndr_rant [S][nant] (AoS),
         sndr_rconc [S]; weights [E][maxR] persists between calls (zeros at first).  Returns full [E] int32."""
@@ -520,9 +554,9 @@ def episode_step(problem, agent, envs, stream=None):
                                        _stream(stream)), "frirl_hip_episode_step")
 
 
-def _agent_io(problem, obs, q_obs=None, reward=None, success=None, reset=None):
+def _agent_io(problem, obs, q_obs=None, reward=None, success=None, reset=None, E=None, out=None):
     import torch
-    E, ns = problem.E, problem.nant - 1
+    E, ns = (problem.E if E is None else E), problem.nant - 1
     assert obs.is_cuda and obs.dtype == torch.float64 and obs.shape == (E, ns) and obs.is_contiguous()
     io = AgentIO()
     io.obs = obs.data_ptr()
@@ -536,8 +570,11 @@ def _agent_io(problem, obs, q_obs=None, reward=None, success=None, reset=None):
     if reset is not None:
         assert reset.dtype in (torch.uint8, torch.bool) and reset.shape == (E,) and reset.is_contiguous()
         io.reset = reset.data_ptr()
-    action = torch.empty((E,), dtype=torch.float64, device=obs.device)
-    action_idx = torch.empty((E,), dtype=torch.int32, device=obs.device)
+    if out is not None:         # the caller's buffers: rows the call skips keep what they hold
+        action, action_idx = out
+    else:
+        action = torch.empty((E,), dtype=torch.float64, device=obs.device)
+        action_idx = torch.empty((E,), dtype=torch.int32, device=obs.device)
     io.action_out, io.action_idx = action.data_ptr(), action_idx.data_ptr()
     return io, action, action_idx
 
@@ -561,6 +598,99 @@ def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream
     check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
                                         _stream(stream)), "frirl_hip_agent_observe")
     return action, action_idx
+
+
+class PolicyRows:
+    """Device-resident per-row episode state of a caller-stepped roll-out on one shared rule base (struct frirl_hip_policy_rows)."""
+
+    def __init__(self, Q, device, exclude_mask=None, rule_slot=None):
+        import torch
+        self.Q = Q
+        self.done = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.ep_steps = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.success = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.ep_reward = torch.zeros((Q,), dtype=torch.float64, device=device)
+        self.exclude_mask, self.rule_slot = exclude_mask, rule_slot
+        if exclude_mask is not None:
+            assert exclude_mask.shape == (Q,) and exclude_mask.dtype == torch.int32 and rule_slot.dtype == torch.uint8
+        self.desc = PolicyRowsDesc(Q, self.done.data_ptr(), self.ep_steps.data_ptr(), self.success.data_ptr(), self.ep_reward.data_ptr(),
+                                   _ptr(exclude_mask), _ptr(rule_slot))
+
+
+class Reducer:
+    """frirl_hip_reducer: the rule-base reduction of ONE rule base (problem.E == 1) with the caller's environment, round by round."""
+
+    def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, stream=None):
+        assert problem.E == 1
+        self.problem, self.R0 = problem, int(problem.nrules[0].item())
+        self.h = lib().frirl_hip_reducer_create(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _ptr(rant), strategy,
+                                                reward_tolerance, depth, _stream(stream))
+        if not self.h:
+            raise FrirlHipError(f"frirl_hip_reducer_create: {lib().frirl_hip_last_error().decode()}")
+        self.Q = 0
+
+    def next_round(self):
+        """Rows to replay from the start state in the next round (round 0: the baseline replay, 1 row); 0 = finished."""
+        q = C.c_int32()
+        check(lib().frirl_hip_reducer_next_round(self.h, C.byref(q)), "frirl_hip_reducer_next_round")
+        self.Q = q.value
+        return q.value
+
+    def begin(self, obs):
+        io, action, action_idx = _agent_io(self.problem, obs, E=self.Q)
+        check(lib().frirl_hip_reducer_begin(self.h, C.byref(io)), "frirl_hip_reducer_begin")
+        self._out = (action, action_idx)
+        return action, action_idx
+
+    def observe(self, obs, reward, success, q_obs=None, count_live=True):
+        """Returns (action values, action indices, rows still live or None when count_live is False: no synchronisation).  The
+        action tensors are those begin returned, updated in place: rows whose replay has ended keep their last action."""
+        io, action, action_idx = _agent_io(self.problem, obs, q_obs, reward, success, E=self.Q, out=getattr(self, "_out", None))
+        live = C.c_int32()
+        check(lib().frirl_hip_reducer_observe(self.h, C.byref(io), C.byref(live) if count_live else None), "frirl_hip_reducer_observe")
+        return action, action_idx, (live.value if count_live else None)
+
+    def end_round(self):
+        check(lib().frirl_hip_reducer_end_round(self.h), "frirl_hip_reducer_end_round")
+
+    def result(self):
+        """(kept original indices, ReduceResult) so far."""
+        import numpy as np
+        kept = np.zeros(self.R0, dtype=np.int32)
+        res = ReduceResult()
+        check(lib().frirl_hip_reducer_result(self.h, kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)), "frirl_hip_reducer_result")
+        return kept[: res.rules_after], res
+
+    def close(self):
+        if self.h:
+            lib().frirl_hip_reducer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            self.close()
+
+
+def reduce_external(problem, agent, reset_fn, step_fn, strategy, reward_tolerance=0.0, depth=0, rant=None):
+    """The reduction's round loop with the caller's environment: reset_fn(Q) -> obs [Q, nant-1] (Q environments at the start state),
+    step_fn(states, action) -> obs, reward, success or obs, reward, success, q_obs (q_obs: the environment's own quantiser).
+    Returns (kept original indices, ReduceResult); compacts problem's rule base in place."""
+    import torch
+    red = Reducer(problem, agent, strategy, reward_tolerance, depth, rant)
+    try:
+        while red.next_round() > 0:
+            states = reset_fn(red.Q).contiguous()
+            action, _ = red.begin(states)
+            live = red.Q
+            while live > 0:
+                out = step_fn(states, action)
+                obs, reward, success = out[0].contiguous(), out[1].contiguous(), out[2].to(torch.int32).contiguous()
+                nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
+                states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
+            red.end_round()
+        return red.result()
+    finally:
+        red.close()
 
 
 def dist():

@@ -1,0 +1,157 @@
+// reduce_plan.h -- host side of the speculative try-remove reduction (frirl_sequential_run.c:170-350; include/frirl_hip.h):
+// candidate order, the mask table of a round's accept/reject tree, the tree walk and the compaction.  One helper for both forms:
+// frirl_hip_reduce_shared (shared.hip: the replays run the demo dynamics in the kernel) and frirl_hip_reducer_* (policy.hip: the
+// caller steps the environment).  Neither form owns a second copy of this logic.
+#pragma once
+#include "device_common.h"
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <vector>
+
+namespace frirl_host {
+
+struct ReducePlan {
+    const char *who = "";
+    int nant = 0, maxR = 0, depth = 0;
+    frirl_hip_rulebases b = {};
+    double *rant = nullptr;                   // [dev] raw antecedents compacted alongside, or NULL
+    std::vector<double> slab, rants;          // host copies of the rule base (and rant), compacted round by round
+    std::vector<uint16_t> idx;
+    std::vector<int> order;                   // candidates in trial order (original rule indices)
+    std::vector<int> alive;                   // original index of the rule in each current slot
+    std::vector<int> where;                   // current slot of each original rule, -1 = removed
+    std::vector<uint8_t> slot;                // [maxR] candidate slot of every current rule, 255 = none (this round)
+    std::vector<uint32_t> mask;               // [lanes_max] exclude mask of every tree node (this round)
+    int R0 = 0, R = 0, j = 0, d = 0, rounds = 0, rollouts = 0, steps_inc = 0;
+    double prev_reward = 0.0;
+
+    int lanes_max() const { return (1 << depth) - 1; }
+    bool finished() const { return j >= R0; }
+
+#define FRIRL_PLAN_TRY(expr)                                                                                       \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
+    } while (0)
+
+    // host copies of the rule base and the candidate order; synchronises `s`
+    int load(const char *who_, const frirl_hip_tables *t, const frirl_hip_rulebases *b_, double *rant_, int strategy, int depth_, hipStream_t s)
+    {
+        who = who_; nant = t->nant; maxR = b_->maxR; depth = depth_; b = *b_; rant = rant_;
+        const size_t col = (size_t)maxR;
+        int32_t r0 = 0;
+        FRIRL_PLAN_TRY(hipMemcpyAsync(&r0, b.nrules, sizeof r0, hipMemcpyDeviceToHost, s));
+        FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+        if (r0 < 1 || r0 > maxR) { set_error("%s: nrules=%d outside 1..maxR=%d", who, r0, maxR); return FRIRL_HIP_EINVAL; }
+        R0 = R = r0;
+        slab.resize((size_t)(nant + 1) * col);
+        FRIRL_PLAN_TRY(hipMemcpyAsync(slab.data(), b.rb, slab.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (rant) { rants.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(rants.data(), rant, rants.size() * sizeof(double), hipMemcpyDeviceToHost, s)); }
+        if (b.uidx) { idx.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(idx.data(), b.uidx, idx.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s)); }
+        FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+        // candidate order: the reference rescans for the first minimum (strategy 1, `mvalue > fabs(..)` :268) or the first
+        // maximum (strategy 2, :286) of the not-yet-tested consequents after every episode; the consequents never change and
+        // removals keep the relative rule order, so that is a stable sort, fixed up front
+        const double *qcol = slab.data() + (size_t)nant * col;
+        order.resize(R0);
+        std::iota(order.begin(), order.end(), 0);
+        if (strategy == 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) < std::fabs(qcol[c]); });
+        else std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) > std::fabs(qcol[c]); });
+        alive.resize(R0);
+        std::iota(alive.begin(), alive.end(), 0);
+        where.resize(R0);
+        slot.resize(col);
+        mask.resize(lanes_max());
+        j = d = rounds = 0;
+        return FRIRL_HIP_OK;
+    }
+
+    // baseline replay on the un-reduced rule base (:196-198 and the first loop iteration, :204-206)
+    void set_baseline(int steps, double reward) { steps_inc = steps; prev_reward = reward; rollouts = 1; }
+
+    // replays of a round are capped at steps_incremental + 1 steps (a longer episode is rejected anyway, :212)
+    int capped_steps(int max_steps) const { return max_steps > steps_inc + 1 ? steps_inc + 1 : max_steps; }
+
+    // slots and masks of the next round's tree, uploaded to d_slot [maxR] / d_mask [lanes]; returns its lanes (0: finished) in *lanes
+    int open_round(void *d_slot, void *d_mask, hipStream_t s, int *lanes)
+    {
+        *lanes = 0;
+        if (finished()) return FRIRL_HIP_OK;
+        d = std::min(depth, R0 - j);
+        const int n = (1 << d) - 1;
+        std::fill(where.begin(), where.end(), -1);
+        for (int i = 0; i < R; i++) where[alive[i]] = i;
+        std::fill(slot.begin(), slot.end(), (uint8_t)255);
+        for (int i = 0; i < d; i++) slot[where[order[j + i]]] = (uint8_t)i;
+        for (int k = 0; k < d; k++)                                   // node (k, bits): candidates j..j+k-1 had outcomes `bits`, candidate j+k is on trial
+            for (uint32_t bits = 0; bits < (1u << k); bits++) mask[(1u << k) - 1 + bits] = bits | (1u << k);
+        FRIRL_PLAN_TRY(hipMemcpyAsync(d_slot, slot.data(), (size_t)maxR, hipMemcpyHostToDevice, s));
+        FRIRL_PLAN_TRY(hipMemcpyAsync(d_mask, mask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        *lanes = n;
+        return FRIRL_HIP_OK;
+    }
+
+    // walk the tree along the outcomes that happened (steps / reward: host, one entry per node), compact the rule base; synchronises `s`
+    int close_round(const int32_t *steps, const double *reward, double reward_good_above, double reward_tolerance, hipStream_t s)
+    {
+        const size_t col = (size_t)maxR;
+        rounds++;
+        rollouts += (1 << d) - 1;
+        uint32_t bits = 0;
+        for (int k = 0; k < d; k++) {
+            const uint32_t lane = (1u << k) - 1 + bits;
+            const double diff = prev_reward - reward[lane];
+            if (reward[lane] > reward_good_above && steps[lane] == steps_inc && std::fabs(diff) <= reward_tolerance) {   // :212
+                bits |= 1u << k;
+                prev_reward = reward[lane];                           // :222
+            }
+        }
+        if (bits) {                                                   // five_remove_rule of every accepted candidate: compact all columns
+            std::vector<char> drop(R, 0);
+            for (int i = 0; i < d; i++) if ((bits >> i) & 1u) drop[where[order[j + i]]] = 1;
+            int w = 0;
+            for (int r = 0; r < R; r++) {
+                if (drop[r]) continue;
+                if (w != r) {
+                    for (int k = 0; k <= nant; k++) slab[(size_t)k * col + w] = slab[(size_t)k * col + r];
+                    if (rant) for (int k = 0; k < nant; k++) rants[(size_t)k * col + w] = rants[(size_t)k * col + r];
+                    if (b.uidx) for (int k = 0; k < nant; k++) idx[(size_t)k * col + w] = idx[(size_t)k * col + r];
+                    alive[w] = alive[r];
+                }
+                w++;
+            }
+            for (int r = w; r < R; r++) {                             // vacated tail: zero like the reference's memset (five_remove_rule.c:64-80)
+                for (int k = 0; k <= nant; k++) slab[(size_t)k * col + r] = 0.0;
+                if (rant) for (int k = 0; k < nant; k++) rants[(size_t)k * col + r] = 0.0;
+                if (b.uidx) for (int k = 0; k < nant; k++) idx[(size_t)k * col + r] = 0;
+            }
+            R = w;
+            alive.resize(R);
+            const int32_t Rn = R;
+            FRIRL_PLAN_TRY(hipMemcpyAsync(b.rb, slab.data(), slab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            if (rant) FRIRL_PLAN_TRY(hipMemcpyAsync(rant, rants.data(), rants.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            if (b.uidx) FRIRL_PLAN_TRY(hipMemcpyAsync(b.uidx, idx.data(), idx.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+            FRIRL_PLAN_TRY(hipMemcpyAsync(b.nrules, &Rn, sizeof Rn, hipMemcpyHostToDevice, s));
+            FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+        }
+        j += d;
+        return FRIRL_HIP_OK;
+    }
+#undef FRIRL_PLAN_TRY
+
+    void result(int32_t *kept, frirl_hip_reduce_result *res) const
+    {
+        if (kept) for (int i = 0; i < R; i++) kept[i] = alive[i];
+        if (!res) return;
+        res->rules_before = R0;
+        res->rules_after = R;
+        res->rounds = rounds;
+        res->rollouts = rollouts;
+        res->steps_incremental = steps_inc;
+        res->reserved = 0;
+        res->reward = prev_reward;
+    }
+};
+
+}  // namespace frirl_host

@@ -44,6 +44,8 @@ static const OptName k_opts[] = {
     {"rollout_cap", "FRIRL_HIP_ROLLOUT_CAP", &Options::rollout_cap, 0},
     {"rollout_pair", "FRIRL_HIP_ROLLOUT_PAIR", &Options::rollout_pair, -1},
     {"rollout_wps", "FRIRL_HIP_ROLLOUT_WPS", &Options::rollout_wps, 0},
+    {"policy_group", "FRIRL_HIP_POLICY_GROUP", &Options::policy_group, 0},
+    {"policy_slices", "FRIRL_HIP_POLICY_SLICES", &Options::policy_slices, 0},
     {"learn_slices", "FRIRL_HIP_LEARN_SLICES", &Options::learn_slices, 0},
     {"learn_alone", "FRIRL_HIP_LEARN_ALONE", &Options::learn_alone, 0},
     {"learn_persistent", "FRIRL_HIP_LEARN_PERSISTENT", &Options::learn_persistent, -1},

@@ -6,8 +6,9 @@
 // accumulates its own Shepard sums sequentially -- the reference's summation order (FIVEVagConcl.c:224-235,
 // FIVEVagConcl_FRIRL_BestAct.c:212-217) -- so no reductions are needed.  Compute-bound: ~24 FP64 instructions per
 // (lane, rule, action).
-#include "sweeps.h"
+#include "shared_sweep.h"
 #include "envs.h"
+#include "reduce_plan.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -16,129 +17,6 @@
 #include <vector>
 
 namespace frirl {
-
-constexpr int SH_TILE = 256;   // rules per LDS tile
-constexpr int SH_BLOCK = 256;
-
-template <int NANT>
-struct SharedTile {
-    double col[(NANT + 1) * SH_TILE];
-    uint8_t slot[SH_TILE];
-    double ave[FRIRL_HIP_MAX_ACTIONS];
-};
-
-// One lane's conclusions against the whole shared rule base; every lane of the workgroup must call it (barriers).
-//   GBA: q[] holds the nant-1 state VE points, the action VE points come from tl.ave; conclusions of all A actions go
-//        to conc[0..A) (if non-NULL) and the first maximum (frirl_get_best_action.c:60-75) is returned in bi.
-//   !GBA: q[] holds all nant VE points; conc[0] / hit0 are FIVE_vag_concl's result.
-//   EXCL: rules whose candidate slot s (slot_g[r], 255 = none) has bit s set in `mask` are treated as removed
-//        (same sums and same first-hit ORDER as the compacted rule base: removal keeps the relative rule order,
-//        five_remove_rule.c:29-85).
-//   H > 1: H lanes (G apart, slice index h) share every conclusion of this lane: lane h takes the rules r = h (mod H); the
-//        partial sums are added in slice order and the lowest exact hit wins (latency form for few environments).
-template <int NANT, int AMAX, bool GBA, bool EXCL, int G = 1, int H = 1, class POW = PowU>
-__device__ __forceinline__ void shared_sweep(SharedTile<NANT> &tl, const double *__restrict__ rb, const uint8_t *__restrict__ slot_g, int R,
-                                             int maxR, POW p, int abeg, int aend, int nchunks, const double *q, bool live, uint32_t mask,
-                                             double *conc, unsigned &hit0, int &bi, double &bvout, int h = 0)
-{
-    constexpr int NS = NANT - 1;
-    constexpr int ND = GBA ? NS : NANT;
-    const double *qcol = rb + (size_t)NANT * maxR;
-    const int nact = GBA ? aend : 1;
-    // running first maximum over this lane's actions [abeg, aend): `bv < c` as max.inl:21; action 0 always seeds it (so a
-    // NaN there sticks, as in the reference), a lane that starts later seeds with -inf and skips NaNs
-    double bv = -__builtin_inf();
-    bi = abeg;
-    hit0 = FRIRL_HIP_NO_HIT;
-    const auto pk = pin_pow(p);            // series coefficients of the Shepard weight in registers (sweeps.h)
-    // actions in chunks of AMAX accumulators (A = 21: three passes over the L2-resident rule base keep the kernel at
-    // ~90 VGPRs instead of 254)
-    // `nchunks` is uniform over the workgroup (the tile staging below has barriers); a lane with fewer actions idles
-    for (int c = 0; c < nchunks; c++) {
-        const int a0 = (GBA ? abeg : 0) + c * AMAX;
-        const int left = nact - a0;
-        const int nacc = left < 0 ? 0 : (left < AMAX ? left : AMAX);
-        double sv[AMAX], sw[AMAX];
-        unsigned sh[AMAX];
-#pragma unroll
-        for (int a = 0; a < AMAX; a++) { sv[a] = 0.0; sw[a] = 0.0; sh[a] = FRIRL_HIP_NO_HIT; }
-        for (int r0 = 0; r0 < R; r0 += SH_TILE) {
-            const int n = (R - r0 < SH_TILE) ? R - r0 : SH_TILE;
-            __syncthreads();
-            for (int i = threadIdx.x; i < (NANT + 1) * SH_TILE; i += SH_BLOCK) {
-                const int k = i / SH_TILE, r = i - k * SH_TILE;
-                tl.col[i] = (r < n) ? rb[(size_t)k * maxR + r0 + r] : 0.0;
-            }
-            if (EXCL) for (int r = threadIdx.x; r < SH_TILE; r += SH_BLOCK) tl.slot[r] = (r < n) ? slot_g[r0 + r] : (uint8_t)255;
-            __syncthreads();
-            if (live && nacc > 0) {
-                // branch-free body (selects on the exact-hit test and on the try-remove mask): straight-line code per rule
-                for (int r = h; r < n; r += H) {
-                    bool valid = true;
-                    if (EXCL) { const unsigned sl = tl.slot[r]; valid = !(sl < 32u && ((mask >> sl) & 1u)); }
-                    double d0 = q[0] - tl.col[r];
-                    double s = d0 * d0;
-#pragma unroll
-                    for (int k = 1; k < ND; k++) { const double d = q[k] - tl.col[k * SH_TILE + r]; s = __fma_rn(d, d, s); }
-                    const double cq = tl.col[NANT * SH_TILE + r];
-                    // a removed rule gets a huge squared distance once (its weight vanishes: the sums keep the bits of the compacted
-                    // rule base); an exact hit is noted with a select and poisons the sums of its own conclusion, which are then not
-                    // read (sweeps.h: q_pair) -- no select around the weight
-                    if (EXCL) s = valid ? s : NO_RULE_STATE_PART;
-                    if (GBA) {
-                        const double va = tl.col[NS * SH_TILE + r];
-#pragma unroll
-                        for (int a = 0; a < AMAX; a++) {
-                            if (a < nacc) {
-                                const double e = tl.ave[a0 + a] - va;
-                                const double d2 = __fma_rn(e, e, s);
-                                const double wi = shepard_w(d2, pk);
-                                sv[a] = __fma_rn(wi, cq, sv[a]);
-                                sw[a] = sw[a] + wi;
-                                sh[a] = (d2 == 0.0 && sh[a] == FRIRL_HIP_NO_HIT) ? (unsigned)(r0 + r) : sh[a];
-                            }
-                        }
-                    } else {
-                        const double wi = shepard_w(s, pk);
-                        sv[0] = __fma_rn(wi, cq, sv[0]);
-                        sw[0] = sw[0] + wi;
-                        sh[0] = (s == 0.0 && sh[0] == FRIRL_HIP_NO_HIT) ? (unsigned)(r0 + r) : sh[0];
-                    }
-                }
-            }
-        }
-        if (H > 1 && live) {             // combine the H rule slices (all lanes of an environment are live together)
-            const int lane = threadIdx.x & (FRIRL_WAVE - 1);
-            const int first = lane - h * G;
-#pragma unroll
-            for (int a = 0; a < AMAX; a++) {
-                double tv = __shfl(sv[a], first), tw = __shfl(sw[a], first);
-                unsigned th = (unsigned)__shfl((int)sh[a], first);
-#pragma unroll
-                for (int hh = 1; hh < H; hh++) {
-                    const double v = __shfl(sv[a], first + hh * G), w = __shfl(sw[a], first + hh * G);
-                    const unsigned x = (unsigned)__shfl((int)sh[a], first + hh * G);
-                    tv = tv + v;
-                    tw = tw + w;
-                    th = x < th ? x : th;
-                }
-                sv[a] = tv; sw[a] = tw; sh[a] = th;
-            }
-        }
-        if (live) {
-#pragma unroll
-            for (int a = 0; a < AMAX; a++) {
-                if (a < nacc) {
-                    const double c = (sh[a] != FRIRL_HIP_NO_HIT) ? qcol[sh[a]] : sv[a] / sw[a];
-                    if (conc) conc[a0 + a] = c;
-                    if (a0 + a == 0 || bv < c) { bv = c; bi = a0 + a; }
-                }
-            }
-            if (c == 0) hit0 = sh[0];
-        }
-    }
-    bvout = bv;
-}
 
 template <int NANT, int AMAX, bool GBA>
 __global__ __launch_bounds__(SH_BLOCK) void shared_q_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
@@ -162,26 +40,6 @@ __global__ __launch_bounds__(SH_BLOCK) void shared_q_kernel(const double *__rest
     if (!live) return;
     if (GBA) best[qi] = bi;
     else hit[qi] = h0;
-}
-
-// First maximum over the G lanes that share one environment (consecutive lanes of one wave, each holding the first
-// maximum of its own block of actions): combined in block order with the reference's `bv < c` (max.inl:21).
-template <int G>
-__device__ __forceinline__ void group_first_max(double &bv, int &bi)
-{
-    if (G == 1) return;
-    const int lane = threadIdx.x & (FRIRL_WAVE - 1);
-    const int base = lane - (lane % G);
-    double cb = __shfl(bv, base);
-    int ci = __shfl(bi, base);
-#pragma unroll
-    for (int g = 1; g < G; g++) {
-        const double v = __shfl(bv, base + g);
-        const int i = __shfl(bi, base + g);
-        if (cb < v) { cb = v; ci = i; }
-    }
-    bv = cb;
-    bi = ci;
 }
 
 // frirl_test_run's episode (src/frirl/frirl_test_run.c:66-70: construct_rb = 0, reduction_state = 1, frirl_episode) for
@@ -440,40 +298,19 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
     if (depth < 1 || depth > 12) { set_error("frirl_hip_reduce_shared: depth %d outside 1..12", depth); return FRIRL_HIP_EINVAL; }
     if ((rc = check_demo_kind(t, agent, "frirl_hip_reduce_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
-    const int nant = t->nant, maxR = b->maxR;
-    const size_t col = (size_t)maxR;
 #define HIP_TRY(expr)                                                                                              \
     do {                                                                                                           \
         hipError_t e_ = (expr);                                                                                    \
         if (e_ != hipSuccess) { set_error("frirl_hip_reduce_shared: %s: %s", #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
     } while (0)
 
-    int32_t R0 = 0;
-    HIP_TRY(hipMemcpyAsync(&R0, b->nrules, sizeof R0, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (R0 < 1 || R0 > maxR) { set_error("frirl_hip_reduce_shared: nrules=%d outside 1..maxR=%d", R0, maxR); return FRIRL_HIP_EINVAL; }
-    std::vector<double> slab((size_t)(nant + 1) * col), rants;
-    std::vector<uint16_t> idx;
-    HIP_TRY(hipMemcpyAsync(slab.data(), b->rb, slab.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (rant) { rants.resize((size_t)nant * col); HIP_TRY(hipMemcpyAsync(rants.data(), rant, rants.size() * sizeof(double), hipMemcpyDeviceToHost, s)); }
-    if (b->uidx) { idx.resize((size_t)nant * col); HIP_TRY(hipMemcpyAsync(idx.data(), b->uidx, idx.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s)); }
-    HIP_TRY(hipStreamSynchronize(s));
-
-    // candidate order: the reference rescans for the first minimum (strategy 1, `mvalue > fabs(..)` :268) or the first
-    // maximum (strategy 2, :286) of the not-yet-tested consequents after every episode; the consequents never change and
-    // removals keep the relative rule order, so that is a stable sort, fixed up front
-    const double *qcol = slab.data() + (size_t)nant * col;
-    std::vector<int> order(R0);
-    std::iota(order.begin(), order.end(), 0);
-    if (strategy == 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) < std::fabs(qcol[c]); });
-    else std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) > std::fabs(qcol[c]); });
-
-    const int lanes_max = (1 << depth) - 1;
+    // candidate order, mask tables, tree walk and compaction: reduce_plan.h (shared with the caller-stepped form, policy.hip)
+    ReducePlan plan;
+    if ((rc = plan.load("frirl_hip_reduce_shared", t, b, rant, strategy, depth, s))) return rc;
+    const int lanes_max = plan.lanes_max();
     DevBuf d_slot, d_mask, d_steps, d_reward;
-    if (!d_slot.alloc(col) || !d_mask.alloc(sizeof(uint32_t) * lanes_max) || !d_steps.alloc(sizeof(int32_t) * lanes_max) ||
+    if (!d_slot.alloc((size_t)b->maxR) || !d_mask.alloc(sizeof(uint32_t) * lanes_max) || !d_steps.alloc(sizeof(int32_t) * lanes_max) ||
         !d_reward.alloc(sizeof(double) * lanes_max)) { set_error("frirl_hip_reduce_shared: hipMalloc failed"); return FRIRL_HIP_ELAUNCH; }
-    std::vector<uint8_t> slot(col);
-    std::vector<uint32_t> mask(lanes_max);
     std::vector<int32_t> steps(lanes_max);
     std::vector<double> reward(lanes_max);
 
@@ -488,82 +325,24 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
     HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const int steps_inc = steps[0];
-    double prev_reward = reward[0];
+    plan.set_baseline(steps[0], reward[0]);
     frirl_hip_agent capped = greedy;
-    if (capped.max_steps > steps_inc + 1) capped.max_steps = steps_inc + 1;
+    capped.max_steps = plan.capped_steps(capped.max_steps);
 
-    std::vector<int> alive(R0);                                       // original index of the rule in each current slot
-    std::iota(alive.begin(), alive.end(), 0);
-    std::vector<int> where(R0);                                       // current slot of each original rule, -1 = removed
-    int R = R0, rounds = 0, rollouts = 1;
     ro.exclude_mask = static_cast<const uint32_t *>(d_mask.p);
     ro.rule_slot = static_cast<const uint8_t *>(d_slot.p);
-    for (int j = 0; j < R0;) {
-        const int d = std::min(depth, R0 - j);
-        const int lanes = (1 << d) - 1;
-        std::fill(where.begin(), where.end(), -1);
-        for (int i = 0; i < R; i++) where[alive[i]] = i;
-        std::fill(slot.begin(), slot.end(), (uint8_t)255);
-        for (int i = 0; i < d; i++) slot[where[order[j + i]]] = (uint8_t)i;
-        for (int k = 0; k < d; k++)                                   // node (k, bits): candidates j..j+k-1 had outcomes `bits`, candidate j+k is on trial
-            for (uint32_t bits = 0; bits < (1u << k); bits++) mask[(1u << k) - 1 + bits] = bits | (1u << k);
-        HIP_TRY(hipMemcpyAsync(d_slot.p, slot.data(), col, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_mask.p, mask.data(), sizeof(uint32_t) * lanes, hipMemcpyHostToDevice, s));
+    for (;;) {
+        int lanes = 0;
+        if ((rc = plan.open_round(d_slot.p, d_mask.p, s, &lanes))) return rc;
+        if (lanes == 0) break;
         rc = frirl_hip_rollout_shared(t, b, &capped, lanes, &ro, stream);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t) * lanes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double) * lanes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        rounds++;
-        rollouts += lanes;
-        uint32_t bits = 0;
-        for (int k = 0; k < d; k++) {
-            const uint32_t lane = (1u << k) - 1 + bits;
-            const double diff = prev_reward - reward[lane];
-            if (reward[lane] > agent->reward_good_above && steps[lane] == steps_inc && std::fabs(diff) <= reward_tolerance) {   // :212
-                bits |= 1u << k;
-                prev_reward = reward[lane];                           // :222
-            }
-        }
-        if (bits) {                                                   // five_remove_rule of every accepted candidate: compact all columns
-            std::vector<char> drop(R, 0);
-            for (int i = 0; i < d; i++) if ((bits >> i) & 1u) drop[where[order[j + i]]] = 1;
-            int w = 0;
-            for (int r = 0; r < R; r++) {
-                if (drop[r]) continue;
-                if (w != r) {
-                    for (int k = 0; k <= nant; k++) slab[(size_t)k * col + w] = slab[(size_t)k * col + r];
-                    if (rant) for (int k = 0; k < nant; k++) rants[(size_t)k * col + w] = rants[(size_t)k * col + r];
-                    if (b->uidx) for (int k = 0; k < nant; k++) idx[(size_t)k * col + w] = idx[(size_t)k * col + r];
-                    alive[w] = alive[r];
-                }
-                w++;
-            }
-            for (int r = w; r < R; r++) {                             // vacated tail: zero like the reference's memset (five_remove_rule.c:64-80)
-                for (int k = 0; k <= nant; k++) slab[(size_t)k * col + r] = 0.0;
-                if (rant) for (int k = 0; k < nant; k++) rants[(size_t)k * col + r] = 0.0;
-                if (b->uidx) for (int k = 0; k < nant; k++) idx[(size_t)k * col + r] = 0;
-            }
-            R = w;
-            alive.resize(R);
-            const int32_t Rn = R;
-            HIP_TRY(hipMemcpyAsync(b->rb, slab.data(), slab.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            if (rant) HIP_TRY(hipMemcpyAsync(rant, rants.data(), rants.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            if (b->uidx) HIP_TRY(hipMemcpyAsync(b->uidx, idx.data(), idx.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(b->nrules, &Rn, sizeof Rn, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        j += d;
+        if ((rc = plan.close_round(steps.data(), reward.data(), agent->reward_good_above, reward_tolerance, s))) return rc;
     }
 #undef HIP_TRY
-    if (kept) for (int i = 0; i < R; i++) kept[i] = alive[i];
-    result->rules_before = R0;
-    result->rules_after = R;
-    result->rounds = rounds;
-    result->rollouts = rollouts;
-    result->steps_incremental = steps_inc;
-    result->reserved = 0;
-    result->reward = prev_reward;
+    plan.result(kept, result);
     return FRIRL_HIP_OK;
 }

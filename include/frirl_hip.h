@@ -100,7 +100,7 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
  * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
- * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -383,6 +383,65 @@ int frirl_hip_agent_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *
                           const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream);
 int frirl_hip_agent_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                             const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream);
+
+/* ---- frirl_test_run's greedy episode with the CALLER'S environment, Q rows on ONE shared rule base (b->E == 1) ----------------
+ * frirl_hip_rollout_shared cut at the step boundary: frirl_episode with reduction_state == 1 (frirl_episode.c:28-194 without the
+ * update at :155, so the rule base is read-only), the environment's three callbacks (:97,106,112) replaced by the caller's data in
+ * `io` (meaning as for frirl_hip_agent_begin / _observe, one row per environment); env_kind is not read.  nant 2..8, A 1..32; the
+ * default Shepard power is a compile-time constant of the kernels, any other agent->p runs the run-time-power variants.  The per-row
+ * episode state lives in the caller's device arrays below.  One launch per call, plus the caller's environment step: for the three
+ * demo environments this is slower than frirl_hip_rollout_shared, which keeps the dynamics inside its kernel.
+ * frirl_hip_policy_begin: rows with io->reset[q] != 0 (NULL: all) start an episode: greedy action of the UN-quantised observation
+ * io->obs (:46-48,78), epsilon-greedy on the stream (env_id_base + q, episode 0, step 0) -- the keys of frirl_hip_rollout_shared --,
+ * ep_steps = 0, ep_reward = 0, success = 0, done = 0.  Needs io->obs, io->action_out.
+ * frirl_hip_policy_observe: rows with done[q] == 0: quantised observation io->q_obs (NULL: the generic grid rule on the device, :112),
+ * greedy action (:148), epsilon-greedy at step ep_steps + 1, ep_steps + 1, ep_reward + io->reward (:107), success = io->success,
+ * done = (success == 1 || ep_steps >= max_steps) (:183,:86).  Rows with done != 0 are skipped: io->action_out is not written.
+ * Needs io->obs, io->reward, io->success, io->action_out.
+ * Optional try-remove view exactly as frirl_hip_rollout: row q ignores the rules whose slot bit is set in exclude_mask[q].
+ * Many rows: one lane per row; few rows (the reduction's replays): 4 / 8 lanes split the actions and 4 / 8 lanes the rules of every
+ * conclusion (options "policy_group", "policy_slices"); every shape chooses the same actions.  Neither call synchronises.
+ * Arguments are checked before the device (FRIRL_HIP_EINVAL before FRIRL_HIP_ENODEV). */
+typedef struct frirl_hip_policy_rows {
+    int32_t Q;                     /* rows                                                                 */
+    int32_t *done;                 /* [dev] [Q] 1 once the episode ended (success or max_steps)            */
+    int32_t *ep_steps;             /* [dev] [Q] reward.ep_total_steps                                      */
+    int32_t *success;              /* [dev] [Q] reward.success of the last step                            */
+    double *ep_reward;             /* [dev] [Q] reward.ep_total_value                                      */
+    const uint32_t *exclude_mask;  /* [dev] [Q] or NULL                                                    */
+    const uint8_t *rule_slot;      /* [dev] [maxR] or NULL (together with exclude_mask)                    */
+} frirl_hip_policy_rows;
+int frirl_hip_policy_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                           const frirl_hip_policy_rows *rows, const frirl_hip_agent_io *io, void *stream);
+int frirl_hip_policy_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                             const frirl_hip_policy_rows *rows, const frirl_hip_agent_io *io, void *stream);
+
+/* ---- the rule-base reduction (frirl_sequential_run.c:170-350) with the CALLER'S environment: frirl_hip_reduce_shared as a resumable
+ * object, because the caller owns the environment loop.  Same semantics: candidate order = stable sort by |Q|, one row per node
+ * (k, bits) of the accept/reject tree of the next `depth` candidates, replays greedy (no_random = 1) and capped at
+ * steps_incremental + 1 steps, the acceptance test of :212, compaction with the vacated tail zeroed.
+ *     r = frirl_hip_reducer_create(t, b, agent, rant, strategy, tolerance, depth, stream);
+ *     while (frirl_hip_reducer_next_round(r, &Q) == 0 && Q > 0) {        -- round 0: the baseline replay, Q = 1 (:196-198)
+ *         reset Q environments to the start state; io.obs = their observations
+ *         frirl_hip_reducer_begin(r, &io);
+ *         do { step the environments with io.action_out; frirl_hip_reducer_observe(r, &io, &live); } while (live > 0);
+ *         frirl_hip_reducer_end_round(r);                                -- walks the tree, compacts b (and rant, uidx)
+ *     }
+ *     frirl_hip_reducer_result(r, kept, &result);  frirl_hip_reducer_destroy(r);
+ * create returns NULL and sets frirl_hip_last_error on bad arguments (those of frirl_hip_reduce_shared; nant 2..8, any env_kind) or
+ * without a device; t, b and agent are copied, the device arrays they name must outlive the reducer.  The reducer owns its masks,
+ * slots and row state (allocated at create).  observe with rows_live == NULL does not synchronise; otherwise *rows_live = rows
+ * whose replay has not ended.  Calls out of order (begin before next_round or twice, observe outside a round, end_round while rows
+ * are live, next_round inside a round) return FRIRL_HIP_EINVAL and change nothing.  kept / result as frirl_hip_reduce_shared. */
+typedef struct frirl_hip_reducer frirl_hip_reducer;
+frirl_hip_reducer *frirl_hip_reducer_create(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                                            int strategy, double reward_tolerance, int depth, void *stream);
+int frirl_hip_reducer_next_round(frirl_hip_reducer *r, int32_t *Q);
+int frirl_hip_reducer_begin(frirl_hip_reducer *r, const frirl_hip_agent_io *io);
+int frirl_hip_reducer_observe(frirl_hip_reducer *r, const frirl_hip_agent_io *io, int32_t *rows_live);
+int frirl_hip_reducer_end_round(frirl_hip_reducer *r);
+int frirl_hip_reducer_result(const frirl_hip_reducer *r, int32_t *kept, frirl_hip_reduce_result *result);
+void frirl_hip_reducer_destroy(frirl_hip_reducer *r);
 
 /* Lane-group form for MANY agents with SMALL rule bases (the demos' learning regime; the reference's frirl_omp_run model
  * of one agent per core, frirl_agent.c:294-325, at GPU width): G = 4 or 8 consecutive lanes own one environment, each
