@@ -119,6 +119,7 @@ SIGNATURES = {
     "five_hip_vag_concl_weight": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_get_best_action": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "five_hip_shepard_weight_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "five_hip_vag_concl_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_get_best_action_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -104,6 +104,19 @@ __global__ __launch_bounds__(BLOCK) void get_best_action_kernel(const double *__
 template <template <int, int> class K>
 struct Dummy {};
 
+// Probe for the tests (five_hip_shepard_weight_check): the Shepard weight in the forms the sweeps call it (sweeps.h).  FORM 0 / 1 take the
+// power as a kernel argument (run-time loop, PowU shortcuts); FORM 2 / 3 are the straight-line series for the compile-time power P.
+template <int FORM, int P>
+__global__ void shepard_weight_check_kernel(const double *__restrict__ s, long n, int p, double *__restrict__ w)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (FORM == 0) w[i] = shepard_w(s[i], p);
+    else if constexpr (FORM == 1) w[i] = shepard_w(s[i], PowU{p});
+    else if constexpr (FORM == 2) w[i] = shepard_w(s[i], PowC<P>());
+    else w[i] = shepard_w(s[i], pin_pow(PowC<P>()));
+}
+
 }  // namespace frirl
 
 using namespace frirl_host;
@@ -213,4 +226,31 @@ extern "C" int frirl_hip_get_best_action(const frirl_hip_tables *t, const frirl_
         default: set_error("frirl_hip_get_best_action: nant=%d outside 2..9", t->nant); return FRIRL_HIP_EINVAL;
     }
     return check_launch("frirl_hip_get_best_action");
+}
+
+extern "C" int five_hip_shepard_weight_check(const double *s, int64_t n, int p, int form, double *w, void *stream)
+{
+    if (p < 1 || p > 16 || form < 0 || form > 3 || n < 0 || (n && (!s || !w))) {
+        set_error("five_hip_shepard_weight_check: bad arguments (p=%d outside 1..16, form=%d outside 0..3, n < 0 or NULL s/w)", p, form);
+        return FRIRL_HIP_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    if (!n) return 0;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (form == 0) hipLaunchKernelGGL((frirl::shepard_weight_check_kernel<0, 0>), grid, block, 0, st, s, (long)n, p, w);
+    else if (form == 1) hipLaunchKernelGGL((frirl::shepard_weight_check_kernel<1, 0>), grid, block, 0, st, s, (long)n, p, w);
+    else {
+        switch (p) {
+#define M(N)                                                                                                                  \
+    case N:                                                                                                                   \
+        if (form == 2) hipLaunchKernelGGL((frirl::shepard_weight_check_kernel<2, N>), grid, block, 0, st, s, (long)n, p, w);  \
+        else hipLaunchKernelGGL((frirl::shepard_weight_check_kernel<3, N>), grid, block, 0, st, s, (long)n, p, w);            \
+        break;
+            FRIRL_NANT_CASES(M)
+#undef M
+        }
+    }
+    return check_launch("five_hip_shepard_weight_check");
 }

@@ -36,8 +36,8 @@ __device__ __forceinline__ double pow_int(double b, int p)
 template <bool UNROLLED_POWERS = false>
 __device__ __forceinline__ double inv_dist_pow(double s, int p)
 {
-    // v_rsq_f64 is good to 5.2e-8; ONE third-order step y (1 + e/2 + 3 e^2/8), e = 1 - s y^2, brings it to 1.4e-16
-    // (measured, tools/exp/rsq_prec.hip: the same as two Newton steps) in 5 instead of 8 FP64 instructions
+    // v_rsq_f64 is good to 5.2e-8; ONE third-order step y (1 + e/2 + 3 e^2/8), e = 1 - s y^2, brings it to 1.7e-16
+    // (measured, profiles/r08_shepard_power.md: the same as two Newton steps) in 5 instead of 8 FP64 instructions
     double y = __builtin_amdgcn_rsq(s);
     const double t = s * y;
     const double e = __fma_rn(-t, y, 1.0);

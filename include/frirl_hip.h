@@ -181,6 +181,14 @@ int five_hip_vag_concl_weight(const frirl_hip_tables *t, const frirl_hip_rulebas
 int frirl_hip_get_best_action(const frirl_hip_tables *t, const frirl_hip_rulebases *b, int p, const double *states,
                               const double *action_ve, int A, double *actconc, int32_t *best, void *stream);
 
+/* Test probe of the Shepard weight every Q value passes through: w[i] = s[i]^(-p/2) from the SQUARED distance s[i] > 0, in the
+ * form the kernels call: form 0 = the run-time loop (per-environment sweeps at any power), 1 = the run-time form with the p = 3 / 5
+ * shortcuts (lane-group, shared-base and policy kernels at p != nant), 2 = the straight-line series for a compile-time power (every
+ * kernel at p = nant), 3 = the same with its coefficients pinned in registers (action-parallel sweep).  p is 1..16, n >= 0;
+ * FRIRL_HIP_EINVAL for any other p or form, n < 0, or NULL s / w with n > 0 (checked before the device).
+ *   s, w [dev] [n] double */
+int five_hip_shepard_weight_check(const double *s, int64_t n, int p, int form, double *w, void *stream);
+
 /* Agent hyper-parameters and grids (reference struct frirl_desc, src/frirl/frirl_types.h:62-169;
  * defaults src/frirl/frirl_types_def.h:22-77).  Passed by pointer, copied by value into the launch. */
 typedef struct frirl_hip_agent {

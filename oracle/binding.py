@@ -372,6 +372,11 @@ class Frirl:
             lib().orc_frirl_set_max_episodes(self.h, max_episodes)
         return lib().orc_sequential_run(self.h, 0)
 
+    def set_power(self, p):
+        """Shepard power of this agent's rule base from now on (FIVERB.p; the demos' own FIVEInit call leaves the default, nant)."""
+        assert p >= 1
+        self.five.c.p = int(p)
+
     def set_start_state(self, states):
         for k, v in enumerate(states):
             lib().orc_frirl_set_values_def(self.h, k, float(v))
@@ -413,8 +418,8 @@ class Frirl:
         return lib().orc_save_rb_text(self.h, path.encode())
 
 
-def synth_problem(nant, U, R, A, seed, maxR=None):
-    """Synthetic tables + duplicate-free on-grid rule base.  Returns a Five."""
+def synth_problem(nant, U, R, A, seed, maxR=None, p=0):
+    """Synthetic tables + duplicate-free on-grid rule base with Shepard power p (0 = nant).  Returns a Five."""
     u = np.zeros(nant * U)
     ve = np.zeros(nant * U)
     lib().orc_synth_tables(nant, U, seed, dp(u), dp(ve))
@@ -423,7 +428,7 @@ def synth_problem(nant, U, R, A, seed, maxR=None):
     lib().orc_synth_rules(nant, U, R, A, seed, up(uidx), dp(rc))
     uidx = uidx.reshape(nant, R)
     rant = np.ascontiguousarray(u.reshape(nant, U)[np.arange(nant)[:, None], uidx].T)
-    return Five(u, ve, nant, U, maxR or (R + 8), rant, rc)
+    return Five(u, ve, nant, U, maxR or (R + 8), rant, rc, p=p)
 
 
 def synth_query(five, rng_state, q):

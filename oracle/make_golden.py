@@ -20,7 +20,8 @@ reference's exported C API and each example's own main().  What is committed is 
                                       after merging in both directions
   tests/golden/synth_*.jsonl          hashes for large synthetic rule bases (inputs are re-created
                                       in the tests by oracle orc_synth_*; nant <= 8 only, the
-                                      reference's cap is FIVE_MAX_NUM_OF_UNIVERSES = 8)
+                                      reference's cap is FIVE_MAX_NUM_OF_UNIVERSES = 8); synth_*_p<p>.jsonl: the same
+                                      with the rule base's Shepard power set to p != nant
 """
 import json, os, shutil, subprocess, sys
 
@@ -40,6 +41,11 @@ SYNTH = [  # nant, U, R, A, seed, nq
     (8, 101, 4096, 0, 14, 32),
     (5, 41, 65536, 3, 15, 16),
     (3, 41, 8192, 3, 16, 24),
+]
+SYNTH_POWER = [  # nant, U, R, A, seed, nq, p: Shepard powers other than nant (the default of the bases above)
+    (3, 41, 33, 3, 11, 64, 1),
+    (3, 41, 33, 3, 11, 64, 2),
+    (5, 41, 367, 3, 12, 64, 3),
 ]
 
 
@@ -89,6 +95,9 @@ def main():
     for (nant, U, R, A, seed, nq) in SYNTH:
         run(HARNESS, "synth", str(nant), str(U), str(R), str(A), str(seed), str(nq),
             os.path.join(GOLD, f"synth_n{nant}_u{U}_r{R}.jsonl"))
+    for (nant, U, R, A, seed, nq, p) in SYNTH_POWER:
+        run(HARNESS, "synth", str(nant), str(U), str(R), str(A), str(seed), str(nq),
+            os.path.join(GOLD, f"synth_n{nant}_u{U}_r{R}_p{p}.jsonl"), str(p))
     sz = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(GOLD) for f in fs)
     print(f"golden fixtures: {sz / 1e6:.2f} MB")
 

@@ -14,7 +14,8 @@
  *                                     own main) + <env>.trace.jsonl (first steps, per-episode records,
  *                                     running FNV-1a hash over every step of the run)
  *   vectors <env> <outfile> <nep>     run <nep> episodes, then function-level vectors on that rule base
- *   synth   <nant> <U> <R> <A> <seed> <nq> <outfile>   large synthetic bases (inputs from orc_synth_*)
+ *   synth   <nant> <U> <R> <A> <seed> <nq> <outfile> [p]   large synthetic bases (inputs from orc_synth_*); p = Shepard power of
+ *                                     the queries (omitted or 0: the reference's default p = nant, header without a "p" field)
  *   bench   <nant> <U> <R> <nq>       times five_rule_distance / FIVE_vag_concl (cpu_baseline "reference")
  *   reduce  <env> <outdir> <strategy> construct run, then the reference's rule-base reduction
  *                                     (frirl_sequential_run.c:170-350) on the result; <env>.reduced<strategy>.frirlrb.txt
@@ -353,10 +354,12 @@ static int run_synth(int argc, char **argv)
 {
     int nant = atoi(argv[2]), U = atoi(argv[3]), R = atoi(argv[4]), A = atoi(argv[5]);
     uint64_t seed = strtoull(argv[6], NULL, 0); int nq = atoi(argv[7]);
+    int p = (argc >= 10) ? atoi(argv[9]) : 0;
     FILE *fp = fopen(argv[8], "w");
     double *u, *ve; struct FIVERB *f = synth_base(nant, U, R, A, seed, &u, &ve);
-    fprintf(fp, "{\"k\":\"synth\",\"nant\":%d,\"U\":%d,\"R\":%d,\"A\":%d,\"seed\":%llu,\"nq\":%d,\"veval_hash\":\"%016llx\"}\n", nant, U, R, A,
-            (unsigned long long)seed, nq, (unsigned long long)orc_hash_doubles(0, f->rseqant_veval[nant - 1], R));
+    fprintf(fp, "{\"k\":\"synth\",\"nant\":%d,\"U\":%d,\"R\":%d,\"A\":%d,\"seed\":%llu,\"nq\":%d,", nant, U, R, A, (unsigned long long)seed, nq);
+    if (p > 0) { f->p = p; fprintf(fp, "\"p\":%d,", p); }      /* the rule base's power, as FIVEInit stores a given p (FIVEInit.c:89-93) */
+    fprintf(fp, "\"veval_hash\":\"%016llx\"}\n", (unsigned long long)orc_hash_doubles(0, f->rseqant_veval[nant - 1], R));
     uint64_t rng = seed * 77 + 5;
     for (int q = 0; q < nq; q++) {
         double x[FIVE_MAX_NUM_OF_UNIVERSES], conc = 0;

@@ -71,12 +71,12 @@ class Batch:
                                          ob.dp(x.reshape(-1)), ob.dp(d.reshape(-1)), ob.ip(hit), nthreads)
         return d, hit
 
-    def five(self, e):
-        """Oracle rule base of environment e (its own copy)."""
+    def five(self, e, p=0):
+        """Oracle rule base of environment e (its own copy) with Shepard power p (0 = nant)."""
         n = int(self.nrules[e])
         rant = np.ascontiguousarray(self.u[np.arange(self.nant)[:, None], self.uidx[e, :, :n]].T)
         f = ob.Five(self.u.ravel(), self.ve.ravel(), self.nant, self.U, self.maxR, rant if n else None,
-                    np.ascontiguousarray(self.rb[e, self.nant, :n]) if n else None)
+                    np.ascontiguousarray(self.rb[e, self.nant, :n]) if n else None, p=p)
         assert f.R == n
         return f
 
@@ -121,11 +121,11 @@ def demo_device_batch(env, episodes, E, seed=0):
     return b, fr
 
 
-def device_agent(fr, device="cuda", max_steps=1000):
+def device_agent(fr, device="cuda", max_steps=1000, p=0):
     """frirl_amd.Agent mirroring an oracle Frirl (its grids, hyper-parameters, per-action VE values)."""
     import frirl_amd
     hp = fr.hparams
     dims = [fr.dim(k) for k in range(fr.nant)]
     return frirl_amd.Agent(device, fr.nant, [d["values"] for d in dims], [d["values_div"] for d in dims],
                            [d["values_def"] for d in dims], np.array(fr.action_vevalues), hp["alpha"], hp["gamma"], hp["qdiff_pos"],
-                           hp["qdiff_neg"], hp["weight_thr"], hp["skip_rules"], 0, fr.env, max_steps)
+                           hp["qdiff_neg"], hp["weight_thr"], hp["skip_rules"], p, fr.env, max_steps)

@@ -139,3 +139,19 @@ def test_learner_launch_plan_and_coverage(lib):
     assert lib.frirl_hip_learn_plan(0, 0, C.byref(H), C.byref(take)) != 0
     a = lib.frirl_hip_learn_workspace_bytes(5, 4096, 512, 3)
     assert lib.frirl_hip_learn_train_workspace_bytes(5, 4096, 512, 3) >= a + 3 * 4096 * 4 > 0
+
+
+def test_shepard_weight_probe_argument_checks(lib):
+    """five_hip_shepard_weight_check validates p (1..16), form (0..3), n and its pointers before it looks for a device."""
+    import torch
+    buf = (C.c_double * 16)()
+    addr = C.addressof(buf)
+    probe = lib.five_hip_shepard_weight_check
+    for p, form, n, s, w in ((0, 0, 4, addr, addr), (17, 0, 4, addr, addr), (-3, 2, 4, addr, addr), (3, -1, 4, addr, addr), (3, 4, 4, addr, addr),
+                             (3, 0, -1, addr, addr), (3, 0, 4, None, addr), (3, 0, 4, addr, None), (17, 2, 0, None, None), (3, 5, 0, None, None)):
+        assert probe(s, n, p, form, w, None) == -2, (p, form, n)
+        assert b"five_hip_shepard_weight_check" in lib.frirl_hip_last_error()
+    if not torch.cuda.is_available():
+        for form in range(4):
+            assert probe(addr, 4, 16, form, addr, None) == -1 and b"no CPU fallback" in lib.frirl_hip_last_error()
+        assert probe(None, 0, 1, 0, None, None) == -1, "valid arguments reach the device check even for n = 0"

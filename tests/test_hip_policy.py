@@ -15,7 +15,7 @@ import pytest
 
 import frirl_amd
 from oracle import binding as ob
-from tests.test_hip_external import PointEnv, generic_quantize, point_desc
+from tests.test_hip_external import Mirror, PointEnv, generic_quantize, point_desc
 from tests.test_hip_shared import shared_problem, start_states, trained
 from tests.test_policy_host import SequentialReduction
 
@@ -286,6 +286,123 @@ def test_external_reduction_of_new_shapes_follows_the_sequential_loop():
             assert (rant_d[:, :R1].cpu().numpy() == rant0[kept].T).all() and bool((rant_d[:, R1:] == 0).all())
         clean_shapes += shape_ties == 0
     assert clean_shapes >= 3, report
+
+
+# ---- 3b. a Shepard power other than nant --------------------------------------------------------------------------------------
+def oracle_trained_point_base(nant, A, p, episodes=30):
+    """A rule base of the caller's environment learned by the oracle alone at Shepard power p (no GPU needed): description, environment,
+    start state, oracle rule base."""
+    d = point_desc(nant, A)
+    env = PointEnv(nant - 1)
+    start = np.ascontiguousarray(np.random.default_rng(nant * 100 + A).uniform(-0.9, 0.9, nant - 1))
+    m = Mirror(d, start, 1024, p=p)
+    for _ in range(episodes):
+        m.episode(env, None)
+        if m.converged:
+            break
+    return d, env, start, m.five
+
+
+def sequential_reduction_at_power(nant, A, p, strategy, device_pick=None):
+    d, env, start, f = oracle_trained_point_base(nant, A, p)
+    R0 = f.R
+
+    def env_fn(states, action):
+        x, r, ok = env.step(np, states[None], np.array([action]))
+        return x[0], float(r[0]), int(ok[0]), generic_quantize(d, x[0])
+
+    seq = SequentialReduction(d["u"], d["ve"], np.array(f.rant[:R0]), np.array(f.rconc[:R0]), d["action_ve"], d["grids"][nant - 1], start, env_fn,
+                              d["max_steps"], d["reward_good_above"], device_pick=device_pick, p=p)
+    return d, env, start, f, seq, seq.run(strategy)
+
+
+@pytest.mark.parametrize("nant,A", [(3, 3), (5, 11)])
+def test_external_reduction_at_power_2_follows_the_sequential_loop(nant, A):
+    """frirl_hip_reducer_* with agent.p = 2 (the policy kernels' run-time-power variants) on a rule base the oracle learned at p = 2, with
+    policy_group forced to 1 and to 4 / 8, against SequentialReduction(p=2).  Picks that follow the device inside a 1e-12 tie of the
+    oracle: at most 10 % (the oracle alone has such near-ties at 0 of 512 picks for nant 3 / A 3 and 0 of 5266 for nant 5 / A 11, which the test asserts too)."""
+    import torch
+    p, strategy = 2, 1
+    d, env, start, f, alone, kept_alone = sequential_reduction_at_power(nant, A, p, strategy)
+    assert alone.near_ties * 10 <= alone.picks
+    R0 = f.R
+    rb = torch.from_numpy(f.device_layout(R0 + 8 + (R0 & 1))[None].copy()).to(DEV)
+    agent = frirl_amd.demo_agent(d, DEV, p=p)
+    start_d = torch.from_numpy(start).to(DEV)
+    u, ve = torch.from_numpy(d["u"]).to(DEV), torch.from_numpy(d["ve"]).to(DEV)
+    for group in (1, 4 if A <= 4 else 8):
+        prob = frirl_amd.Problem(u, ve, rb.clone(), torch.tensor([R0], dtype=torch.int32, device=DEV))
+        old = frirl_amd.set_option("policy_group", group)
+        try:
+            kept, res, rounds = external_reduction_with_trace(prob, agent, env, start_d, strategy, None)
+            torch.cuda.synchronize()
+        finally:
+            frirl_amd.set_option("policy_group", old)
+
+        def device_pick(i, bits, step):
+            tr = rounds[0] if i < 0 else rounds[1 + i // 10]
+            lane = 0 if i < 0 else (1 << (i % 10)) - 1 + bits
+            return int(tr[step, lane]) if step < tr.shape[0] else None
+
+        _, _, _, _, seq, kept_seq = sequential_reduction_at_power(nant, A, p, strategy, device_pick=device_pick)
+        assert seq.ties * 10 <= seq.picks, (seq.ties, seq.picks)
+        assert list(kept) == kept_seq, (nant, A, group)
+        assert res.rules_before == R0 and res.rules_after == len(kept_seq) == int(prob.nrules[0])
+        assert res.steps_incremental == seq.steps_incremental and res.rounds == -(-R0 // 10)
+        assert 1 <= res.rules_after < R0, "the case must remove at least one rule and keep at least one"
+        R1 = res.rules_after
+        got = prob.rb[0].cpu().numpy()
+        assert (got[:nant, :R1] == np.array(f.veval[:, :R0])[:, kept]).all() and (got[nant, :R1] == np.array(f.rconc[:R0])[kept]).all()
+        assert (got[:, R1:] == 0).all()
+
+
+def test_stepped_rollout_with_exclude_masks_at_power_2():
+    """The twelve masks of test_stepped_rollout_with_exclude_masks at agent.p = 2 on a mountaincar rule base the oracle learned at p = 2:
+    the stepped roll-out equals the in-kernel one and the oracle's greedy episode on the COMPACTED rule base, for policy_group 1 and 4
+    and policy_slices 1, 4 and 8.  With p != nant the launcher ignores policy_slices (the variants without rule slices run), so slices = 8
+    must give the actions of slices = 1 step by step."""
+    import torch
+    env = "mountaincar"
+
+    def learned():
+        fr = ob.Frirl(env, trig_mode=1)
+        fr.set_power(2)
+        fr.run(max_episodes=13)
+        return fr
+
+    fr = learned()
+    R = fr.five.R
+    prob, maxR = shared_problem(fr, DEV)
+    agent = frirl_amd.demo_agent(frirl_amd.demo_describe(env), DEV, p=2)
+    order = np.argsort(np.abs(fr.five.rconc[:R]), kind="stable")
+    cand = [int(r) for r in order[-16:][::-1]] + [int(r) for r in order[:16]]
+    slot = np.full(maxR, 255, dtype=np.uint8)
+    for sl, r in enumerate(cand):
+        slot[r] = sl
+    masks = np.array([0, 1, 0x80000000, 0xffff, 0xffff0000, 0xffffffff, 0x00ff00ff, 0x0f0f0f0f, 0x3f, 0xfff, 0xffffff, 0xa5a5a5a5],
+                     dtype=np.uint32).view(np.int32)
+    masks_d, slot_d = torch.from_numpy(masks).to(DEV), torch.from_numpy(slot).to(DEV)
+    Q = len(masks)
+    steps, reward, success, _ = prob.rollout_shared(agent, Q, exclude_mask=masks_d, rule_slot=slot_d)
+    torch.cuda.synchronize()
+    s = torch.from_numpy(np.ascontiguousarray(np.tile(np.array(agent.desc.values_def[: fr.nstates]), (Q, 1)))).to(DEV)
+    traces = {}
+    for shape in group_shapes(agent.A):
+        rows, traces[shape] = drive_demo(prob, agent, env, s, masks=masks_d, slot=slot_d, shape=shape, record=True)
+        assert torch.equal(rows.ep_steps, steps) and torch.equal(rows.success, success), shape
+        rel = ((rows.ep_reward - reward).abs() / reward.abs().clamp(min=1.0)).max().item()
+        assert rel <= 1e-9, (shape, rel)
+    first = traces[(1, 1)]
+    for shape, tr in traces.items():
+        assert len(tr) == len(first) and all(torch.equal(a, b) for a, b in zip(tr, first)), f"actions differ for shape {shape}"
+    st, rw = steps.cpu().numpy(), reward.cpu().numpy()
+    assert ((st != st[0]) | (rw != rw[0])).any(), "removals did not change the episode: the masks are not exercised"
+    for i, m in enumerate(masks):
+        fr2 = learned()
+        for r in sorted([cand[sl] for sl in range(32) if (int(np.uint32(m)) >> sl) & 1], reverse=True):
+            fr2.five.remove_rule(r)
+        fr2.episode_eval()
+        assert int(st[i]) == fr2.ep_steps and abs(float(rw[i]) - fr2.ep_reward) <= 1e-9 * max(1.0, abs(fr2.ep_reward)), (i, st[i], fr2.ep_steps)
 
 
 # ---- 4. masks and skipping ---------------------------------------------------------------------------------------------------

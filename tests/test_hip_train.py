@@ -238,3 +238,74 @@ def test_rollout_on_shared_rule_base_with_non_default_power():
     same = (steps == envs2.ep_steps)
     assert same.float().mean() > 0.98, same.float().mean()        # sequential vs tree sums: a near-tie may flip an action
     assert ((reward - envs2.ep_reward).abs()[same] <= 1e-9 * envs2.ep_reward.abs()[same].clamp_min(1.0)).all()
+
+
+# ---- p = 2 against the oracle (the two tests above compare kernels with kernels) ---------------------------------------------------
+@pytest.mark.parametrize("kernel", ["fused_step", "lane_group"])
+def test_power_2_learning_follows_the_oracle(kernel):
+    """Three mountaincar episodes at agent.p = 2 through the fused step kernel and through the lane-group learner (their variants
+    without rule slices), every environment followed by the oracle with its rule base's power set to 2 (portable trig on both sides):
+    steps, rewards, rule counts and appended antecedents exact, learned Q within 1e-6."""
+    import numpy as np
+    import torch
+    from oracle import binding as ob
+    dev = torch.device("cuda", 0)
+    fr = ob.Frirl("mountaincar", trig_mode=1)
+    fr.set_power(2)
+    E = 4
+    prob, agent, envs = frirl_amd.demo_fresh_batch("mountaincar", E, 512, dev, p=2)
+    assert agent.desc.p == 2 and fr.five.c.p == 2
+    for _ in range(3):
+        fr.episode()
+        frirl_amd.episode_begin(prob, agent, envs)
+        if kernel == "fused_step":
+            frirl_amd.episode_steps(prob, agent, envs, agent.desc.max_steps)
+        else:
+            frirl_amd.episode_run_lanes(prob, agent, envs, agent.desc.max_steps)
+        torch.cuda.synchronize()
+        assert (envs.done.cpu().numpy() == 1).all()
+        assert (envs.ep_steps.cpu().numpy() == fr.ep_steps).all() and (envs.ep_reward.cpu().numpy() == fr.ep_reward).all()
+        R = fr.five.R
+        assert (prob.nrules.cpu().numpy() == R).all()
+        assert (envs.rant[:, :, :R].cpu().numpy() == fr.five.rant[:R].T[None]).all(), "appended rule antecedents"
+        q, ref = prob.rb[:, prob.nant, :R].cpu().numpy(), np.array(fr.five.rconc[:R])
+        assert (np.abs(q - ref[None]) <= 1e-6 * np.maximum(np.abs(ref[None]), 1e-9)).all()
+    assert fr.five.R > 2 ** prob.nant, "rules were inserted"
+    other = ob.Frirl("mountaincar", trig_mode=1)          # the default power learns something else: p is really used by the oracle
+    for _ in range(3):
+        other.episode()
+    assert other.five.R != fr.five.R or (np.array(other.five.rconc[: fr.five.R]) != np.array(fr.five.rconc[: fr.five.R])).any()
+
+
+def test_power_2_rollouts_on_a_shared_rule_base_follow_the_oracle():
+    """frirl_hip_rollout_shared at agent.p = 2 (the shared roll-out's variants without rule slices, resident and tiled) on a rule base
+    the oracle learned at p = 2, against the oracle's greedy episode from the same start states: steps exact, reward 1e-9."""
+    import numpy as np
+    import torch
+    from oracle import binding as ob
+    from tests.test_hip_shared import shared_problem, start_states
+    dev = torch.device("cuda", 0)
+    fr = ob.Frirl("mountaincar", trig_mode=1)
+    fr.set_power(2)
+    fr.run(max_episodes=13)
+    assert fr.five.R > 40
+    prob, _ = shared_problem(fr, dev)
+    agent = frirl_amd.demo_agent(frirl_amd.demo_describe("mountaincar"), dev, p=2)
+    Q = 70                                                         # two workgroups, the second one ragged
+    s = start_states(fr, Q, 5)
+    outs = []
+    for resident in (1, 0):
+        old = frirl_amd.set_option("rollout_resident", resident)
+        try:
+            steps, reward, success, _ = prob.rollout_shared(agent, Q, start_states=torch.from_numpy(s).to(dev))
+            torch.cuda.synchronize()
+        finally:
+            frirl_amd.set_option("rollout_resident", old)
+        outs.append((steps.cpu().numpy(), reward.cpu().numpy()))
+    for steps, reward in outs:
+        for i in range(Q):
+            fr.set_start_state(s[i])
+            fr.episode_eval()
+            assert steps[i] == fr.ep_steps, (i, steps[i], fr.ep_steps)
+            assert abs(reward[i] - fr.ep_reward) <= 1e-9 * max(1.0, abs(fr.ep_reward)), (i, reward[i], fr.ep_reward)
+    assert len(set(outs[0][0].tolist())) > 3, "the start states lead to different episodes"

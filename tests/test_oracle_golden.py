@@ -230,15 +230,18 @@ def test_vec_update_sarsa_sequence(vec):
     assert inserted > 5
 
 
-SYNTH = [(3, 41, 33, 3, 11), (5, 41, 367, 3, 12), (5, 1001, 4096, 21, 13), (8, 101, 4096, 0, 14), (5, 41, 65536, 3, 15),
-         (3, 41, 8192, 3, 16)]
+SYNTH = [(3, 41, 33, 3, 11, 0), (5, 41, 367, 3, 12, 0), (5, 1001, 4096, 21, 13, 0), (8, 101, 4096, 0, 14, 0), (5, 41, 65536, 3, 15, 0),
+         (3, 41, 8192, 3, 16, 0),
+         (3, 41, 33, 3, 11, 1), (3, 41, 33, 3, 11, 2), (5, 41, 367, 3, 12, 3)]        # Shepard powers other than nant
 
 
-@pytest.mark.parametrize("nant,U,R,A,seed", SYNTH)
-def test_synth_bases(nant, U, R, A, seed, golden_dir):
-    recs = load_jsonl(os.path.join(golden_dir, f"synth_n{nant}_u{U}_r{R}.jsonl"))
+@pytest.mark.parametrize("nant,U,R,A,seed,p", [pytest.param(*c, id="-".join(map(str, c[:5])) + (f"-p{c[5]}" if c[5] else "")) for c in SYNTH])
+def test_synth_bases(nant, U, R, A, seed, p, golden_dir):
+    recs = load_jsonl(os.path.join(golden_dir, f"synth_n{nant}_u{U}_r{R}" + (f"_p{p}" if p else "") + ".jsonl"))
     hdr = recs[0]
-    f = ob.synth_problem(nant, U, R, A, seed)
+    assert hdr.get("p", 0) == p
+    f = ob.synth_problem(nant, U, R, A, seed, p=p)
+    assert f.c.p == (p or nant)
     assert f.R == R, "synthetic rule base must be duplicate-free and fully inserted"
     assert "%016x" % ob.hash_doubles(f.veval[nant - 1, :R]) == hdr["veval_hash"]
     rng = seed * 77 + 5
@@ -408,3 +411,23 @@ def test_omp_run_loop_matches_reference(env, max_episodes, golden_dir):
     assert sum(a.episodes_run for a in ag) == recs["stdout_counts"]["episode_lines"]
     assert pended == recs["stdout_counts"]["pended_lines"]
     assert rounds >= 1
+
+
+# ---- the Shepard weight on its own: the oracle's chain against a 60-digit reference ----------------------------------------------
+def test_shepard_weight_chain_meets_the_derived_bound():
+    """wi = 1 / fast_pow(sqrt(s), p) (FIVEVagConcl.c:226 as the oracle restates it: IEEE sqrt, orc_fast_pow, divide) against
+    s^(-p/2) from `decimal` at 60 digits, p = 1..16, on the inputs of the device probe test (tests/shepard_ref.py): relative error
+    <= p x 4e-16, the bound tests/test_hip_power.py holds every device form to.  A correct double implementation can meet that bound,
+    and the decimal reference agrees with an independent chain."""
+    from tests import shepard_ref as sr
+    L = ob.lib()
+    s = sr.inputs()
+    d = np.sqrt(s).tolist()
+    worst = {}
+    for p in sr.POWERS:
+        w = np.array([1.0 / L.orc_fast_pow(v, p) for v in d])
+        err, i = sr.rel_error(w, p)
+        worst[p] = err
+        assert err <= sr.bound(p), (p, err, float(s[i]))
+    assert max(worst.values()) > 1e-17, "the comparison must resolve single roundings"
+    assert sr.exact()[16][2].all() and len(s) >= 19000

@@ -33,20 +33,21 @@ class SequentialReduction:
     `near_ties` counts the greedy picks whose runner-up is that close, whatever the device did."""
 
     def __init__(self, u, ve, rant, rconc, action_ve, action_values, start, env_fn, max_steps, reward_good_above, device_pick=None,
-                 depth=10):
+                 depth=10, p=0):
         self.u, self.ve = np.array(u), np.array(ve)
         self.nant, self.U = self.u.shape
         self.rant0, self.rconc0 = np.array(rant, dtype=np.float64), np.array(rconc, dtype=np.float64)
         self.action_ve, self.action_values = np.array(action_ve), np.array(action_values)
         self.start, self.env_fn, self.max_steps, self.good_above = np.array(start, dtype=np.float64), env_fn, max_steps, reward_good_above
-        self.device_pick, self.depth = device_pick, depth
-        self.ties = self.near_ties = 0
+        self.device_pick, self.depth, self.p = device_pick, depth, p          # p: Shepard power of every rule base it builds (0 = nant)
+        self.ties = self.near_ties = self.picks = 0
 
     def five(self, alive):
-        return ob.Five(self.u, self.ve, self.nant, self.U, len(self.rconc0) + 8, rant=self.rant0[alive], rconc=self.rconc0[alive])
+        return ob.Five(self.u, self.ve, self.nant, self.U, len(self.rconc0) + 8, rant=self.rant0[alive], rconc=self.rconc0[alive], p=self.p)
 
     def pick(self, f, states, key, step):
         best, oc = f.best_action(states, self.action_ve)
+        self.picks += 1
         others = np.delete(oc, best)
         if len(others) and np.any(np.abs(others - oc[best]) <= 1e-12 * abs(oc[best])):
             self.near_ties += 1
