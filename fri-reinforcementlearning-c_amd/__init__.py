@@ -120,6 +120,8 @@ SIGNATURES = {
     "frirl_hip_get_best_action": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "five_hip_shepard_weight_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "frirl_hip_explore_check": (C.c_int, [C.POINTER(AgentDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "five_hip_vag_concl_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_get_best_action_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -543,6 +545,21 @@ def env_step(agent, action, states, stream=None):
     check(lib().frirl_hip_env_step(C.byref(agent.desc), E, ns, _ptr(action), _ptr(states), _ptr(new_states), _ptr(reward), _ptr(success),
                                    _ptr(q_states), _stream(stream)), "frirl_hip_env_step")
     return new_states, reward, success, q_states
+
+
+def explore_check(agent, env, episode, step, greedy, stream=None):
+    """frirl_hip_explore_check: the exploration stream and pick of `agent` (A, epsilon, no_random, seed, env_id_base) at the key
+    tuples env / episode / step [n] (int64 tensors holding uint32 values) with greedy actions greedy [n] int32.
+    Returns (picked action [n] int32, units [n, 2] float64: draw 0 and draw 1)."""
+    import torch
+    n = env.numel()
+    as_u32 = [k.to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.uint32).contiguous() for k in (env, episode, step)]
+    greedy = greedy.to(torch.int32).contiguous()
+    action = torch.empty((n,), dtype=torch.int32, device=greedy.device)
+    units = torch.empty((n, 2), dtype=torch.float64, device=greedy.device)
+    check(lib().frirl_hip_explore_check(C.byref(agent.desc), n, _ptr(as_u32[0]), _ptr(as_u32[1]), _ptr(as_u32[2]), _ptr(greedy), _ptr(action),
+                                        _ptr(units), _stream(stream)), "frirl_hip_explore_check")
+    return action, units
 
 
 def episode_begin(problem, agent, envs, stream=None):

@@ -94,6 +94,20 @@ __global__ void env_step_kernel(const frirl_hip_agent ag, int E, int ns, const d
     success[e] = f;
 }
 
+// Probe for the tests (frirl_hip_explore_check): rng_unit and e_greedy of envs.h exactly as every learning and roll-out kernel calls
+// them, one key tuple per thread.
+__global__ void explore_check_kernel(const frirl_hip_agent ag, long n, const uint32_t *__restrict__ env, const uint32_t *__restrict__ episode,
+                                     const uint32_t *__restrict__ step, const int32_t *__restrict__ greedy, int32_t *__restrict__ out_action,
+                                     double *__restrict__ out_unit)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t gid = ag.env_id_base + env[i];
+    out_unit[2 * i] = rng_unit(ag.seed, gid, episode[i], step[i], 0);
+    out_unit[2 * i + 1] = rng_unit(ag.seed, gid, episode[i], step[i], 1);
+    out_action[i] = e_greedy(ag, greedy[i], env[i], episode[i], step[i]);
+}
+
 
 #ifdef FRIRL_STEP_TIMING
 }  // namespace frirl
@@ -414,6 +428,22 @@ extern "C" int frirl_hip_env_step(const frirl_hip_agent *agent, int32_t E, int32
     hipLaunchKernelGGL(frirl::env_step_kernel, dim3((E + 255) / 256), dim3(256), 0, as_stream(stream), *agent, E, nstates, action, states,
                        new_states, reward, success, q_states);
     return check_launch("frirl_hip_env_step");
+}
+
+extern "C" int frirl_hip_explore_check(const frirl_hip_agent *agent, int64_t n, const uint32_t *env, const uint32_t *episode, const uint32_t *step,
+                                       const int32_t *greedy, int32_t *out_action, double *out_unit, void *stream)
+{
+    if (!agent || agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || n < 0 || n > (int64_t)1 << 30 ||
+        (n && (!env || !episode || !step || !greedy || !out_action || !out_unit))) {
+        set_error("frirl_hip_explore_check: bad arguments (NULL agent, A outside 1..%d, n outside 0..2^30 or a NULL array)", FRIRL_HIP_MAX_ACTIONS);
+        return FRIRL_HIP_EINVAL;
+    }
+    int rc = check_device();
+    if (rc) return rc;
+    if (!n) return 0;
+    hipLaunchKernelGGL(frirl::explore_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), *agent, (long)n, env, episode,
+                       step, greedy, out_action, out_unit);
+    return check_launch("frirl_hip_explore_check");
 }
 
 

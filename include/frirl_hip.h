@@ -216,8 +216,22 @@ typedef struct frirl_hip_agent {
     int32_t debug_flags;                       /* 0; bit 0 (tests only): update_rules always re-sweeps the rule base instead of using the
                                                   candidates tracked during the Q(s,a) sweep -- both give the same bits */
     uint64_t env_id_base;                      /* global id of environment 0 of this batch: RNG streams are keyed by the
-                                                  GLOBAL environment id, so trajectories do not depend on the sharding */
+                                                  GLOBAL environment id, so trajectories do not depend on the sharding.  The id
+                                                  enters the stream's key shifted left by 32 bits in 64-bit arithmetic, so only
+                                                  its low 32 bits count: streams repeat with a period of 2^32 global ids */
 } frirl_hip_agent;
+
+/* Test probe of the exploration stream, in the form every learning and roll-out kernel calls it.  For key tuple i the global id is
+ * agent->env_id_base + env[i] and the word is the SplitMix64 output function of
+ *     seed + 0x9E3779B97F4A7C15 * ((id << 32) | episode[i]) + 0xD1B54A32D192ED03 * ((step[i] << 8) | draw)      (mod 2^64);
+ * out_unit[2i + draw] = (word >> 11) * 2^-53 for draw 0 (explore when it is <= agent->epsilon) and draw 1 (the action), and
+ * out_action[i] = frirl_e_greedy_selection (frirl_e_greedy_selection.c:21-37) given the greedy action greedy[i]: greedy[i] when
+ * agent->no_random == 1, agent->epsilon == 0 or draw 0 > epsilon, else round(draw 1 * A) clamped to A - 1.  Of `agent` only A
+ * (1..32), epsilon, no_random, seed and env_id_base are read.  n >= 0; FRIRL_HIP_EINVAL for a NULL agent, any other A, n < 0 or
+ * n > 2^30, or a NULL array with n > 0 (checked before the device).
+ *   env, episode, step [dev] [n] uint32;  greedy, out_action [dev] [n] int32;  out_unit [dev] [2n] double */
+int frirl_hip_explore_check(const frirl_hip_agent *agent, int64_t n, const uint32_t *env, const uint32_t *episode, const uint32_t *step,
+                            const int32_t *greedy, int32_t *out_action, double *out_unit, void *stream);
 
 /* frirl_test_run's greedy roll-out (reference src/frirl/frirl_test_run.c:66-70 -> frirl_episode with reduction_state == 1,
  * frirl_episode.c:28-194 without the update at :155) for Q environments sharing ONE read-only rule base: lane =

@@ -93,6 +93,13 @@ def lib():
         "orc_frirl_ep_reward": (d, [vp]),
         "orc_frirl_hparams": (None, [vp, c_double_p]),
         "orc_frirl_set_trace": (None, [vp, vp]),
+        "orc_frirl_set_exploration": (None, [vp, d, i, u64, u64, C.c_uint]),
+        "orc_frirl_rng_episode": (C.c_uint, [vp]),
+        "orc_frirl_success": (i, [vp]),
+        "orc_frirl_last_states": (c_double_p, [vp]),
+        "orc_frirl_explore_stats": (None, [vp, c_double_p]),
+        "orc_rng_unit": (d, [u64, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64)]),
+        "orc_e_greedy_pick": (C.c_uint, [C.c_uint, i, d, i, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(i), C.POINTER(i)]),
         "orc_get_best_action": (C.c_uint, [vp, c_double_p]),
         "orc_check_possible_states": (d, [d, c_double_p, i]),
         "orc_update_sarsa": (None, [vp, c_double_p, d, c_double_p]),
@@ -145,6 +152,23 @@ def up(a):
 def hash_doubles(a, h=0):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return lib().orc_hash_bytes(h, a.ctypes.data, a.nbytes)
+
+
+def rng_word(seed, gid, episode, step, draw):
+    """The 64-bit word of the exploration stream at these keys (orc_rng_unit); gid is taken modulo 2^64 as the C ABI does."""
+    w = C.c_uint64()
+    lib().orc_rng_unit(seed, gid & (2 ** 64 - 1), episode, step, draw, C.byref(w))
+    return w.value
+
+
+def rng_unit(seed, gid, episode, step, draw):
+    """Its top 53 bits as a number of [0, 1)."""
+    return lib().orc_rng_unit(seed, gid & (2 ** 64 - 1), episode, step, draw, None)
+
+
+def e_greedy_pick(greedy, A, epsilon, no_random, seed, gid, episode, step):
+    """orc_e_greedy_pick: the action chosen at these keys given the greedy one."""
+    return int(lib().orc_e_greedy_pick(greedy, A, epsilon, no_random, seed, gid & (2 ** 64 - 1), episode, step, None, None))
 
 
 ENV_IDS = {"mountaincar": 0, "cartpole": 1, "acrobot": 2}
@@ -376,6 +400,34 @@ class Frirl:
         """Shepard power of this agent's rule base from now on (FIVERB.p; the demos' own FIVEInit call leaves the default, nant)."""
         assert p >= 1
         self.five.c.p = int(p)
+
+    def set_exploration(self, epsilon, no_random, seed, env_id, episode=0):
+        """Epsilon-greedy on the counter-based stream of global environment `env_id`; `episode` = episodes started so far."""
+        lib().orc_frirl_set_exploration(self.h, float(epsilon), int(no_random), int(seed), int(env_id) & (2 ** 64 - 1), int(episode))
+
+    @property
+    def rng_episode(self):
+        return lib().orc_frirl_rng_episode(self.h)
+
+    @property
+    def success(self):
+        return lib().orc_frirl_success(self.h)
+
+    @property
+    def last_states(self):
+        """Continuous state at the end of the last episode (a copy)."""
+        return np.array(np.ctypeslib.as_array(lib().orc_frirl_last_states(self.h), shape=(self.nstates,)))
+
+    @property
+    def explore_stats(self):
+        """Counters since init: picks, picks on the random branch, those that changed the action, those clamped from A to A - 1,
+        and the smallest relative gap between the two best conclusions at a pick that stayed greedy (NaN: none; bit-equal pairs apart)."""
+        out = np.zeros(5)
+        lib().orc_frirl_explore_stats(self.h, dp(out))
+        return dict(picks=int(out[0]), explored=int(out[1]), changed=int(out[2]), clamped=int(out[3]), min_gap=float(out[4]))
+
+    def set_max_steps(self, n):
+        lib().orc_frirl_set_max_steps(self.h, int(n))
 
     def set_start_state(self, states):
         for k, v in enumerate(states):

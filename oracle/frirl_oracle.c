@@ -653,6 +653,9 @@ int orc_frirl_init(orc_frirl *fr)
     fr->ep_total_value = -1; fr->ep_total_steps = -1;                /* frirl_init.c:149-150 */
     fr->fus_is_rule_inserted = 0; fr->episode_num = 1; fr->epended = 0;
     fr->step_hash = 0; fr->total_steps = 0;
+    fr->rng_episode = 0;
+    fr->picks = fr->explore_picks = fr->explore_changed = fr->explore_clamped = 0;
+    fr->min_greedy_gap = 0.0 / 0.0;
     return 0;
 }
 
@@ -707,11 +710,69 @@ unsigned orc_get_best_action(orc_frirl *fr, const double *states)
     return orc_five_best_action(fr->frb, states, fr->action_vevalues, fr->actiondim.values_len, fr->actconc);
 }
 
-/* src/frirl/frirl_e_greedy_selection.c:21-37.  Every shipped demo keeps no_random = 1, so the
- * libc rand() branch (:28-33) is never taken; the oracle restates the greedy branch only. */
-unsigned orc_e_greedy(orc_frirl *fr, const double *states)
+/* The exploring branch's random stream, restated from the contract in include/frirl_hip.h (the reference draws from libc
+ * rand(), frirl_e_greedy_selection.c:28-33, which cannot be reproduced per environment): a counter-based stream, the SplitMix64
+ * finaliser over the keys (seed, global environment id, episode, step, draw).  The id enters shifted left by 32 bits, so
+ * streams repeat with a period of 2^32 global ids.  *word (optional) receives the 64-bit output, the result is its top
+ * 53 bits as a number of [0, 1). */
+double orc_rng_unit(uint64_t seed, uint64_t gid, uint32_t episode, uint32_t step, uint32_t draw, uint64_t *word)
 {
-    return orc_get_best_action(fr, states);
+    const uint64_t stream = (gid << 32) | (uint64_t)episode;
+    const uint64_t counter = ((uint64_t)step << 8) | (uint64_t)draw;
+    uint64_t z = seed + 0x9E3779B97F4A7C15ULL * stream + 0xD1B54A32D192ED03ULL * counter;
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
+    z ^= z >> 27; z *= 0x94D049BB133111EBULL;
+    z ^= z >> 31;
+    if (word) *word = z;
+    return (double)(z >> 11) * 0x1p-53;
+}
+
+/* src/frirl/frirl_e_greedy_selection.c:21-37 on that stream: greedy when no_random == 1, epsilon == 0 (:24) or the first draw
+ * exceeds epsilon (:28-30); otherwise round(second draw * A) (:33), which the reference leaves one past the last action when
+ * it rounds to A -- clamped to A - 1 as the batched path does.  *clamped (optional): 1 when that happened,
+ * *explored (optional): 1 when the random branch was taken. */
+unsigned orc_e_greedy_pick(unsigned greedy, int A, double epsilon, int no_random, uint64_t seed, uint64_t gid,
+                           uint32_t episode, uint32_t step, int *explored, int *clamped)
+{
+    if (explored) *explored = 0;
+    if (clamped) *clamped = 0;
+    if (no_random == 1 || epsilon == 0.0) return greedy;
+    if (orc_rng_unit(seed, gid, episode, step, 0, NULL) > epsilon) return greedy;
+    long a = lround(orc_rng_unit(seed, gid, episode, step, 1, NULL) * (double)A);      /* half away from zero, as round() */
+    if (explored) *explored = 1;
+    if (a > A - 1) { a = A - 1; if (clamped) *clamped = 1; }
+    return (unsigned)a;
+}
+
+/* Every shipped demo keeps no_random = 1 (the default here too), which never consults the stream.  With no_random = 0 the
+ * pick at (episode, step) of the stream of environment fr->env_id replaces the greedy one; the counters record what the
+ * tests need to know about a run: picks on the random branch, those that changed the action, those that were clamped, and
+ * the smallest relative gap between the two best conclusions at a pick that stayed greedy.  A pair with equal bits is left out of
+ * that gap wherever it occurs (not only on the all-zero initial rule base, its usual cause): there the oracle and the device both
+ * take the first maximum, so the pick cannot go either way.  This bookkeeping runs on every pick, greedy defaults included. */
+unsigned orc_e_greedy(orc_frirl *fr, const double *states, uint32_t episode, uint32_t step)
+{
+    const int A = fr->actiondim.values_len;
+    const unsigned greedy = orc_get_best_action(fr, states);
+    int explored = 0, clamped = 0;
+    const unsigned pick = orc_e_greedy_pick(greedy, A, fr->epsilon, fr->no_random, fr->seed, fr->env_id, episode, step, &explored, &clamped);
+    fr->picks++;
+    if (explored) {
+        fr->explore_picks++;
+        if (pick != greedy) fr->explore_changed++;
+        if (clamped) fr->explore_clamped++;
+    } else if (A > 1) {
+        const double best = fr->actconc[greedy];
+        int have = 0;
+        double second = 0;
+        for (int a = 0; a < A; a++) if (a != (int)greedy && (!have || second < fr->actconc[a])) { second = fr->actconc[a]; have = 1; }
+        if (memcmp(&best, &second, sizeof(double)) != 0) {
+            const double scale = fabs(best) > fabs(second) ? fabs(best) : fabs(second);
+            const double gap = (best - second) / scale;
+            if (!(fr->min_greedy_gap <= gap)) fr->min_greedy_gap = gap;       /* starts as NaN: no gap seen yet */
+        }
+    }
+    return pick;
 }
 
 /* src/frirl/frirl_check_possible_states.c:96-122 with hit_between_possible_places (:53-88).
@@ -845,7 +906,8 @@ void orc_episode(orc_frirl *fr)
     double states[ORC_MAX_NANT], cur_states[ORC_MAX_NANT], q_ant[ORC_MAX_NANT], cur_q_ant[ORC_MAX_NANT];
     for (int i = 0; i < ns; i++) q_ant[i] = states[i] = fr->statedims[i].values_def;
     fr->ep_total_value = 0; fr->ep_total_steps = 0;
-    unsigned ai = orc_e_greedy(fr, states);
+    fr->rng_episode++;                                   /* stream position: the first episode draws from episode 1 */
+    unsigned ai = orc_e_greedy(fr, states, fr->rng_episode, 0);
     q_ant[ns] = fr->actiondim.values[ai];
     for (int step = 1; step <= fr->max_steps; step++) {
         orc_env_do_action(fr, q_ant[ns], states, cur_states);
@@ -857,7 +919,7 @@ void orc_episode(orc_frirl *fr)
         orc_env_quantize(fr, cur_states, cur_q_ant);
         { double nr = (double)fr->frb->R; fr->step_hash = orc_hash_doubles(fr->step_hash, cur_q_ant, ns);
           fr->step_hash = orc_hash_doubles(fr->step_hash, &nr, 1); }
-        unsigned pa = orc_e_greedy(fr, cur_q_ant);
+        unsigned pa = orc_e_greedy(fr, cur_q_ant, fr->rng_episode, (uint32_t)step);
         cur_q_ant[ns] = fr->actiondim.values[pa];
         if (fr->trace) fr->trace(fr, step, q_ant[ns], cur_states, cur_q_ant, fr->trace_ud);
         orc_update_sarsa(fr, q_ant, fr->reward_value, cur_q_ant);
@@ -866,6 +928,7 @@ void orc_episode(orc_frirl *fr)
         fr->ep_total_steps++; fr->total_steps++;
         if (fr->success == 1) break;
     }
+    for (int i = 0; i < ns; i++) fr->last_states[i] = states[i];
 }
 
 /* src/frirl/frirl_sequential_run.c:24-165 -- construct loop: at most max_episodes-1 episodes
@@ -1054,6 +1117,18 @@ int orc_demo_run(int env, int trig_mode, const char *rb_path, uint64_t *hash, lo
     orc_frirl_delete(fr);
     return ok;
 }
+void orc_frirl_set_exploration(orc_frirl *fr, double epsilon, int no_random, uint64_t seed, uint64_t env_id, unsigned episode)
+{
+    fr->epsilon = epsilon; fr->no_random = no_random; fr->seed = seed; fr->env_id = env_id; fr->rng_episode = episode;
+}
+unsigned orc_frirl_rng_episode(orc_frirl *fr) { return fr->rng_episode; }
+int orc_frirl_success(orc_frirl *fr) { return fr->success; }
+const double *orc_frirl_last_states(orc_frirl *fr) { return fr->last_states; }
+void orc_frirl_explore_stats(orc_frirl *fr, double *out5)
+{
+    out5[0] = (double)fr->picks; out5[1] = (double)fr->explore_picks; out5[2] = (double)fr->explore_changed;
+    out5[3] = (double)fr->explore_clamped; out5[4] = fr->min_greedy_gap;
+}
 void orc_frirl_set_trace(orc_frirl *fr, void (*cb)(orc_frirl *, int, double, const double *, const double *, void *))
 {
     fr->trace = cb;
@@ -1074,20 +1149,21 @@ static void orc_episode_noupdate(orc_frirl *fr)
     double states[ORC_MAX_NANT], cur_states[ORC_MAX_NANT], q_ant[ORC_MAX_NANT], cur_q_ant[ORC_MAX_NANT];
     for (int i = 0; i < ns; i++) q_ant[i] = states[i] = fr->statedims[i].values_def;
     fr->ep_total_value = 0; fr->ep_total_steps = 0;
-    unsigned ai = orc_e_greedy(fr, states);
+    unsigned ai = orc_e_greedy(fr, states, 0, 0);                  /* roll-outs on a finished rule base draw from episode 0 */
     q_ant[ns] = fr->actiondim.values[ai];
     for (int step = 1; step <= fr->max_steps; step++) {
         orc_env_do_action(fr, q_ant[ns], states, cur_states);
         orc_env_get_reward(fr, cur_states, &fr->reward_value, &fr->success);
         fr->ep_total_value += fr->reward_value;
         orc_env_quantize(fr, cur_states, cur_q_ant);
-        unsigned pa = orc_e_greedy(fr, cur_q_ant);
+        unsigned pa = orc_e_greedy(fr, cur_q_ant, 0, (uint32_t)step);
         cur_q_ant[ns] = fr->actiondim.values[pa];
         for (int i = 0; i < ns; i++) states[i] = cur_states[i];
         for (int i = 0; i < n; i++) q_ant[i] = cur_q_ant[i];
         fr->ep_total_steps++;
         if (fr->success == 1) break;
     }
+    for (int i = 0; i < ns; i++) fr->last_states[i] = states[i];
 }
 
 /* frirl_test_run's episode (src/frirl/frirl_test_run.c:20-86): one greedy roll-out, rule base untouched */
@@ -1106,6 +1182,8 @@ int orc_reduce_run(orc_frirl *fr, int strategy, double reward_tolerance)
     double prev_reward = fr->ep_total_value;
     unsigned mindex = 0;
     int redend = 0;
+    const int saved_no_random = fr->no_random;
+    fr->no_random = 1;                                          /* the replays are greedy whatever the agent explores with */
     orc_episode_noupdate(fr);                                   /* :196-197 */
     const int steps_incremental = fr->ep_total_steps;
     for (fr->episode_num = 1; (int)fr->episode_num <= iterations; fr->episode_num++) {
@@ -1143,5 +1221,6 @@ int orc_reduce_run(orc_frirl *fr, int strategy, double reward_tolerance)
         if (redend) break;
     }
     free(tmp_rconc); free(prev_rconc); free(snap_rant); free(snap_rconc);
+    fr->no_random = saved_no_random;
     return f->R;
 }

@@ -109,6 +109,13 @@ typedef struct orc_frirl {
     void (*trace)(struct orc_frirl *fr, int step, double action, const double *cur_states,
                   const double *cur_q_states, void *ud);
     void *trace_ud;
+    /* exploration (no_random == 0): the counter-based stream of include/frirl_hip.h */
+    uint64_t seed;                 /* frirl_hip_agent.seed */
+    uint64_t env_id;               /* GLOBAL environment id: frirl_hip_agent.env_id_base + row */
+    unsigned rng_episode;          /* episodes started by orc_episode (frirl_hip_envs.episode): the stream's episode key */
+    long picks, explore_picks, explore_changed, explore_clamped;   /* see orc_e_greedy */
+    double min_greedy_gap;
+    double last_states[ORC_MAX_NANT];   /* continuous state at the end of the last episode (learning or roll-out) */
 } orc_frirl;
 
 /* agent parameters of the SARSA update in bare form (any rule base) */
@@ -128,7 +135,10 @@ void orc_frirl_config(orc_frirl *fr, int env);     /* examples/<env>/<env>.c mai
 int  orc_frirl_init(orc_frirl *fr);                /* frirl_init.c:29-341, frirl_init_ve.c:25-121, frirl_init_rb.c:86-147 */
 void orc_frirl_deinit(orc_frirl *fr);
 unsigned orc_get_best_action(orc_frirl *fr, const double *states);                    /* frirl_get_best_action.c:31-341 */
-unsigned orc_e_greedy(orc_frirl *fr, const double *states);                           /* frirl_e_greedy_selection.c:21-37 */
+double orc_rng_unit(uint64_t seed, uint64_t gid, uint32_t episode, uint32_t step, uint32_t draw, uint64_t *word);
+unsigned orc_e_greedy_pick(unsigned greedy, int A, double epsilon, int no_random, uint64_t seed, uint64_t gid,
+                           uint32_t episode, uint32_t step, int *explored, int *clamped);    /* frirl_e_greedy_selection.c:21-37 */
+unsigned orc_e_greedy(orc_frirl *fr, const double *states, uint32_t episode, uint32_t step);
 double orc_check_possible_states(double obs, const double *values, int values_len);   /* frirl_check_possible_states.c:96-122 */
 void orc_update_sarsa(orc_frirl *fr, const double *q_ant, double reward, const double *cur_q_ant); /* frirl_update_sarsa.c:348-385 */
 void orc_episode(orc_frirl *fr);                                                      /* frirl_episode.c:28-194 */
@@ -183,6 +193,11 @@ unsigned orc_frirl_episode_num(orc_frirl *fr);
 int orc_frirl_ep_steps(orc_frirl *fr);
 double orc_frirl_ep_reward(orc_frirl *fr);
 void orc_frirl_hparams(orc_frirl *fr, double *out8);
+void orc_frirl_set_exploration(orc_frirl *fr, double epsilon, int no_random, uint64_t seed, uint64_t env_id, unsigned episode);
+unsigned orc_frirl_rng_episode(orc_frirl *fr);
+int orc_frirl_success(orc_frirl *fr);                       /* reward.success of the last step */
+const double *orc_frirl_last_states(orc_frirl *fr);
+void orc_frirl_explore_stats(orc_frirl *fr, double *out5);   /* picks, on the random branch, changed, clamped, smallest greedy gap */
 void orc_frirl_set_trace(orc_frirl *fr, void (*cb)(orc_frirl *, int, double, const double *, const double *, void *));
 int orc_demo_run(int env, int trig_mode, const char *rb_path, uint64_t *hash, long *steps, int *episodes, int *R);
 

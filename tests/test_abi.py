@@ -155,3 +155,25 @@ def test_shepard_weight_probe_argument_checks(lib):
         for form in range(4):
             assert probe(addr, 4, 16, form, addr, None) == -1 and b"no CPU fallback" in lib.frirl_hip_last_error()
         assert probe(None, 0, 1, 0, None, None) == -1, "valid arguments reach the device check even for n = 0"
+
+
+def test_explore_probe_argument_checks(lib):
+    """frirl_hip_explore_check validates the agent, A (1..32), n and its arrays before it looks for a device."""
+    import torch
+    buf = (C.c_double * 64)()
+    addr = C.addressof(buf)
+    probe = lib.frirl_hip_explore_check
+    ag = frirl_amd.AgentDesc()
+    ag.A, ag.epsilon, ag.no_random = 3, 0.3, 0
+    bad_a0, bad_a33 = frirl_amd.AgentDesc(), frirl_amd.AgentDesc()
+    bad_a0.A, bad_a33.A = 0, 33
+    ok = [addr] * 6
+    cases = [(None, 4, ok), (C.byref(bad_a0), 4, ok), (C.byref(bad_a33), 4, ok), (C.byref(ag), -1, ok), (C.byref(ag), 2 ** 30 + 1, ok),
+             (C.byref(bad_a33), 0, [None] * 6)]
+    cases += [(C.byref(ag), 4, [None if i == k else addr for i in range(6)]) for k in range(6)]
+    for agent, n, arrays in cases:
+        assert probe(agent, n, *arrays, None) == -2, (n, arrays)
+        assert b"frirl_hip_explore_check" in lib.frirl_hip_last_error()
+    if not torch.cuda.is_available():
+        assert probe(C.byref(ag), 4, *ok, None) == -1 and b"no CPU fallback" in lib.frirl_hip_last_error()
+        assert probe(C.byref(ag), 0, *([None] * 6), None) == -1, "valid arguments reach the device check even for n = 0"

@@ -15,6 +15,7 @@ import pytest
 
 import frirl_amd
 from oracle import binding as ob
+from tests import explore_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -153,8 +154,10 @@ def generic_quantize(d, s):
 class Mirror:
     """One agent of frirl_sequential_run's construct loop restated with the oracle's FIVE pieces."""
 
-    def __init__(self, d, start, maxR, p=0):
+    def __init__(self, d, start, maxR, p=0, explore=None, gid=0):
         nant = d["nant"]
+        self.explore, self.gid, self.episode_no = explore, gid, 0       # explore: dict(epsilon, seed, env_id_base) or None = greedy
+        self.explored = self.changed = self.clamped = 0                  # picks on the random branch / that changed the action / clamped
         R0 = 2 ** nant
         rant0 = np.array([[d["grids"][k].min() if ((j // (R0 >> (k + 1))) % 2) == 0 else d["grids"][k].max() for k in range(nant)] for j in range(R0)])
         self.five = ob.Five(d["u"], d["ve"], nant, d["U"], maxR, rant=rant0, rconc=np.zeros(R0), p=p)
@@ -166,13 +169,22 @@ class Mirror:
         self.picks = 0         # picks made
         self.near = 0          # picks at which the oracle's own two best conclusions lie within 1e-12 relative
 
-    def pick(self, states, device_pick):
+    def pick(self, states, device_pick, step=0):
         """Greedy action (frirl_get_best_action).  Where the oracle's conclusions tie the device's pick within 1e-12 relative --
         Q equal in real arithmetic, e.g. nant = 2, whose corner rules learn action-independent values -- the device's pick is
-        followed: tie-breaking below the 1e-6 contract is not part of it.  Any other difference is a failure."""
+        followed: tie-breaking below the 1e-6 contract is not part of it.  Any other difference is a failure.
+        With exploration the pick of tests/explore_ref.py at (episode, step) replaces the greedy one where the stream says so: such a
+        pick is never a tie and never follows the device."""
         best, oc = self.five.best_action(states, self.d["action_ve"])
-        srt = np.sort(oc)
         self.picks += 1
+        x = self.explore
+        if x is not None and explore_ref.explores(x["epsilon"], 0, x["seed"], self.gid, self.episode_no, step):
+            a, clamped = explore_ref.random_action(len(oc), x["seed"], self.gid, self.episode_no, step)
+            self.explored += 1
+            self.changed += int(a != best)
+            self.clamped += int(clamped)
+            return a
+        srt = np.sort(oc)
         self.near += int(len(srt) > 1 and srt[-1] - srt[-2] <= 1e-12 * abs(srt[-1]))
         if device_pick is None:          # dry run on the CPU: the oracle alone
             return best
@@ -186,16 +198,17 @@ class Mirror:
         NS = d["nant"] - 1
         av = d["grids"][NS]
         self.prev["R"], self.prev["q"] = f.R, np.array(f.rconc[: f.maxR]).copy()        # frirl_sequential_run.c:68-72
+        self.episode_no += 1                                                               # frirl_hip_agent_begin: episode[e] + 1
         states = self.start.copy()
         picks = picks if picks is not None else [None] * (d["max_steps"] + 1)
-        a0 = self.pick(states, picks[0])                                                   # frirl_episode.c:78, un-quantised
+        a0 = self.pick(states, picks[0], 0)                                                 # frirl_episode.c:78, un-quantised
         q_ant = np.concatenate([states, [av[a0]]])
         actions, steps, total = [a0], 0, 0.0
         while True:
             x, r, ok = env.step(np, states[None], np.array([q_ant[NS]]))
             cur, r, success = x[0], float(r[0]), int(ok[0])
             q = generic_quantize(d, cur)
-            best = self.pick(q, picks[steps + 1])
+            best = self.pick(q, picks[steps + 1], steps + 1)
             cur_q_ant = np.concatenate([q, [av[best]]])
             self.fus = f.update_sarsa(self.oa, self.fus, q_ant, r, cur_q_ant)
             states, q_ant = cur, cur_q_ant
@@ -211,12 +224,16 @@ class Mirror:
         return actions, steps, total
 
 
-def new_shape_case(nant, A, p=0):
+EXPLORE = dict(epsilon=0.2, seed=4321, env_id_base=2 ** 32 - 5)      # the batch's global ids cross 2^32
+
+
+def new_shape_case(nant, A, p=0, explore=None):
     """Description, environment, start states and the oracle mirrors of one new-shape case (no GPU needed)."""
     d = point_desc(nant, A)
     E, maxR = 16, 1024
     starts = np.ascontiguousarray(np.random.default_rng(nant * 100 + A).uniform(-0.9, 0.9, (E, nant - 1)))
-    return d, PointEnv(nant - 1), starts, [Mirror(d, starts[e], maxR, p=p) for e in range(E)]
+    base = explore["env_id_base"] if explore else 0
+    return d, PointEnv(nant - 1), starts, [Mirror(d, starts[e], maxR, p=p, explore=explore, gid=base + e) for e in range(E)]
 
 
 @pytest.mark.parametrize("nant", [2, 4, 6, 8])
@@ -240,11 +257,25 @@ def test_new_shapes_follow_the_oracle_at_other_powers(nant, A, power):
     assert ties * 10 <= picks, (ties, picks)
 
 
-def follow_the_oracle(nant, A, p):
+@pytest.mark.parametrize("nant", [2, 5, 8])
+@pytest.mark.parametrize("A", [3, 11])
+def test_new_shapes_explore_and_follow_the_oracle(nant, A):
+    """The construct loops with epsilon = 0.2 on streams whose global ids cross 2^32: the mirrors take the picks of
+    tests/explore_ref.py after the greedy pick.  The tie rule is the existing one (1e-12 relative, at most 10 % of a case's picks),
+    taken over the picks that stayed greedy: only those can tie.  tests/test_explore_ref.py::test_new_shape_cases_explore_enough
+    shows that every case has exploring picks that change the action."""
+    mirrors = follow_the_oracle(nant, A, 0, explore=EXPLORE)
+    ties, greedy_picks = sum(m.ties for m in mirrors), sum(m.picks - m.explored for m in mirrors)
+    assert ties * 10 <= greedy_picks, (ties, greedy_picks)
+    assert sum(m.changed for m in mirrors) >= 10
+
+
+def follow_the_oracle(nant, A, p, explore=None):
     import torch
-    d, env, starts, mirrors = new_shape_case(nant, A, p)
+    d, env, starts, mirrors = new_shape_case(nant, A, p, explore=explore)
     E, maxR, episodes = 16, 1024, 4
-    prob, agent, envs = frirl_amd.fresh_batch(d, E, maxR, DEV, p=p)
+    kw = dict(epsilon=explore["epsilon"], no_random=0, seed=explore["seed"], env_id_base=explore["env_id_base"]) if explore else {}
+    prob, agent, envs = frirl_amd.fresh_batch(d, E, maxR, DEV, p=p, **kw)
     assert agent.desc.p == p and mirrors[0].five.c.p == (p or nant)
     conv = frirl_amd.Convergence(prob, DEV)
     ss = torch.from_numpy(starts).to(DEV)
