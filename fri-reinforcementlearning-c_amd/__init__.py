@@ -113,6 +113,10 @@ SIGNATURES = {
     "five_hip_rule_distance_packed_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "five_hip_rule_distance_packed_ws": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "five_hip_rule_distance_coded_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "frirl_hip_pack_codes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "five_hip_rule_distance_coded_ws": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "five_hip_sqrt_unscaled_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "five_hip_rule_distance_sq_guard": (C.c_int, [C.POINTER(Tables), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "five_hip_vag_concl": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -295,6 +299,12 @@ class Problem:
         if W > 0:
             self.pidx = torch.empty((self.E, W, self.maxR), dtype=torch.int32, device=self.uidx.device)
             self._pack(None)
+        # coded copy (3-byte lane-tiled codes, five_hip_rule_distance_coded_ws) beside pidx, where the rule bases' dictionaries allow
+        # it: derived from uidx AND nrules, rebuilt with its dictionaries whenever either may have changed (_codes_current)
+        self.codes = self._code_dict = self._code_rank = self._code_d = None
+        self._codes_key = None
+        if self.pidx is not None and self.nant <= 5:
+            self._pack_codes(None)
         # workspaces of five_hip_rule_distance_packed_ws (per-call squared-difference tables), one per stream the scan is called on:
         # calls on different streams may run at the same time and must not share one
         self._rd_ws = {}
@@ -305,6 +315,7 @@ class Problem:
         under the packed mirror), so handing it out marks the mirror stale; the read-only scans below use the private one.
         Take it afresh for every native call: a handle kept across a rule_distance would escape the staleness mark."""
         self._pidx_key = None
+        self._codes_key = None
         return self._bases
 
     def _pack(self, stream):
@@ -317,6 +328,46 @@ class Problem:
         if self._pidx_key != (self.uidx.data_ptr(), self.uidx._version):
             self._pack(stream)
         return self.pidx
+
+    def _pack_codes(self, stream):
+        """Dictionaries of the coded copy from uidx and nrules (torch ops on `stream`'s device, one host read of their lengths) and the
+        copy itself (frirl_hip_pack_codes); codes = None where the coded form does not apply."""
+        import torch
+        dev = self.uidx.device
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            nr = self.nrules.to(torch.int64)
+            upto = (nr + (nr & 1)).clamp(max=self.maxR)                  # the odd last rule's partner column is scanned like a rule
+            cols = torch.arange(self.maxR, device=dev)
+            dimoff = (65 * torch.arange(self.nant, device=dev)).view(1, self.nant, 1)
+            counts = torch.zeros((self.nant * 65,), dtype=torch.int64, device=dev)
+            step = max(1, (1 << 26) // (self.nant * self.maxR))          # environments per pass: bounds the temporaries
+            for e0 in range(0, self.E, step):
+                v = self.uidx[e0:e0 + step].to(torch.int64) & 63
+                live = (cols.view(1, -1) < upto[e0:e0 + step].view(-1, 1)).unsqueeze(1)
+                v = torch.where(live, v, torch.full_like(v, 64)) + dimoff
+                counts += torch.bincount(v.flatten(), minlength=self.nant * 65)
+            present = counts.view(self.nant, 65)[:, :64] > 0
+            rank = (present.cumsum(1) - 1).clamp(min=0).to(torch.uint8).contiguous()
+            idx = torch.arange(64, device=dev).expand(self.nant, 64)
+            dct = torch.where(present, idx, torch.full_like(idx, 255)).sort(1).values.to(torch.uint8).contiguous()
+            d = present.sum(1).clamp(min=1).to(torch.int32).cpu().tolist()        # the one host read
+        darr = (C.c_int32 * self.nant)(*d)
+        n = lib().five_hip_rule_distance_coded_bytes(self.nant, self.U, self.E, self.maxR, darr)
+        if n:
+            if self.codes is None or self.codes.numel() != n:
+                self.codes = torch.empty((n,), dtype=torch.uint8, device=dev)
+            self._code_dict, self._code_rank, self._code_d = dct, rank, darr
+            check(lib().frirl_hip_pack_codes(C.byref(self.tables), C.byref(self._bases), _ptr(rank), darr, _ptr(self.codes), _stream(stream)),
+                  "frirl_hip_pack_codes")
+        else:
+            self.codes = self._code_dict = self._code_rank = self._code_d = None
+        self._codes_key = (self.uidx.data_ptr(), self.uidx._version, self.nrules.data_ptr(), self.nrules._version)
+
+    def _codes_current(self, stream):
+        """The coded copy (or None), rebuilt on `stream` first if uidx or nrules were handed to native code (bases) or edited in place since."""
+        if self.nant <= 5 and self._codes_key != (self.uidx.data_ptr(), self.uidx._version, self.nrules.data_ptr(), self.nrules._version):
+            self._pack_codes(stream)
+        return self.codes
 
     def _rd_workspace(self, stream):
         """The packed scan's workspace for `stream` (uint8 tensor, allocated on first use), or None for a shape without one."""
@@ -336,7 +387,13 @@ class Problem:
             ruledists = torch.empty((self.E, self.maxR), dtype=torch.float64, device=x.device)
         if hit is None:
             hit = torch.empty((self.E,), dtype=torch.int32, device=x.device)
-        if self.pidx is not None:
+        if self.pidx is not None and self._codes_current(stream) is not None:
+            ws = self._rd_workspace(stream)
+            rc = lib().five_hip_rule_distance_coded_ws(C.byref(self.tables), C.byref(self._bases), _ptr(self.codes), _ptr(self._code_dict), self._code_d,
+                                                       _ptr(self._pidx_current(stream)), _ptr(x), _ptr(ruledists) if materialise else None,
+                                                       _ptr(hit), _ptr(ws), ws.numel() if ws is not None else 0, _stream(stream))
+            check(rc, "five_hip_rule_distance_coded_ws")
+        elif self.pidx is not None:
             ws = self._rd_workspace(stream)
             rc = lib().five_hip_rule_distance_packed_ws(C.byref(self.tables), C.byref(self._bases), _ptr(self._pidx_current(stream)), _ptr(x),
                                                         _ptr(ruledists) if materialise else None, _ptr(hit), _ptr(ws),

@@ -169,6 +169,7 @@ struct Options {
     int rd_sqdiff;        // packed scan: 1 = per-workgroup squared-difference tables + guarded short sqrt (shipped), 0 = the scan without them (FRIRL_HIP_RD_SQDIFF)
     int rd_qpass;         // packed scan with rd_sqdiff and rd_prepass = 0: 1 = snap the observations in observe_reset_kernel, 0 = in every workgroup; superseded by rd_prepass (FRIRL_HIP_RD_QPASS)
     int rd_prepass;       // five_hip_rule_distance_packed_ws with rd_sqdiff: 1 = squared-difference tables built once per call in the workspace (shipped), 0 = per workgroup (FRIRL_HIP_RD_PREPASS)
+    int rd_coded;         // five_hip_rule_distance_coded_ws: 1 = stream the 3-byte lane-tiled codes (shipped), 0 = the 4-byte packed words (FRIRL_HIP_RD_CODED)
     int step_wave;        // episode step: 1 = one wave per environment, 0 = 256 threads, -1 = by shape (FRIRL_HIP_STEP_WAVE)
     int step_track;       // episode step: spread candidates tracked in the fused sweep: 1 / 0, -1 = large rule bases only (FRIRL_HIP_STEP_TRACK)
     int lanes_slices;     // lane groups: rule slices per conclusion, 0 = by shape               (FRIRL_HIP_LANES_SLICES)

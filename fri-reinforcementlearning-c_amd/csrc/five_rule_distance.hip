@@ -14,7 +14,7 @@
 //   every lane loads two rules per column and instruction (16 B of f64 / 4 B of u16 indices): a wave instruction reads
 //   1 KiB / 256 contiguous bytes and stores 1 KiB of contiguous distances; wider per-lane index loads (8 / 16 B) leave
 //   the stores only half / quarter dense and measured 0.42 / 0.19.
-// Four kernels, the same arithmetic on the same doubles (bit-identical results):
+// Five kernels, the same arithmetic on the same doubles (bit-identical results):
 //   rule_distance_kernel          f64 VE columns (the reference's layout); one workgroup per item, hardware dispatch
 //                                 order = item order;
 //   rule_distance_idx_kernel      16-bit universe-index mirror, VE values gathered from an LDS copy of the tables;
@@ -45,6 +45,13 @@
 //                                 Floor: reads (~7 TB/s) and the 16-B write stream (5.5-5.9 TB/s) share HBM's one data bus, so their
 //                                 times ADD (0.30 + 0.73...0.78 ms at cfg4); what is left above that sum is issue work and the
 //                                 shape of the window the resident workgroups touch, not a lack of overlap.
+//   rule_distance_cd_kernel       CODED copy (five_hip_rule_distance_coded_ws, option rd_coded, what Problem.rule_distance calls where it
+//                                 applies): 3 bytes of indices per rule.  A rule's indices are ranks in per-dimension dictionaries,
+//                                 two dimensions per field, at most 24 bits in all (cfg4: 11 + 11 + 2); the copy is lane-tiled, so a lane
+//                                 makes three aligned 8-byte loads per 2048-rule item where the packed scan makes four, and the tables
+//                                 of sq_tables_kernel<DIGIT> are laid out by rank: the scan is the pre-pass form of the packed one with
+//                                 another decode (one 24-bit multiply, a shift and a multiply-subtract per pair) -- bit-identical.
+//                                 cfg4: FETCH 2.17 -> 1.63 GB, 1.052-1.053 -> 1.017-1.020 ms; 28 VGPRs (profiles/r10_cfg4_coded.md).
 // First exact hit: per-lane minimum index -> wave butterfly -> (LDS ->) one integer atomicMin per workgroup / item
 // (deterministic; only taken when a hit exists).
 // "rd_*" / "no_uidx" options (frirl_hip_set_option) are experiment hooks (tools/ab_rd.py); unset, the shipped configuration runs.
@@ -352,10 +359,14 @@ __device__ __forceinline__ void load_sq_sources(const double *__restrict__ ve, i
 // would each redo in their prologue, done once -- one wave per environment, with the device functions of that prologue (same bits):
 //   sqtab[e][k][i] = (q_k - ve[k][i])^2, q_k = observe_ve(x[e][k]) (0.0 table values on the padding entries i >= U),
 //   fastv[e] = 1 when every entry is in the range of sqrt_unscaled, else 0,   hit[e] = "none" (in place of the memset).
-template <int NANT, int BITS>
+// DIGIT (the coded scan, rule_distance_cd_kernel): entry j of row k is the table value of universe index dict[k][j] -- the j-th index of
+// the rule bases' dictionary of dimension k, 0xFF beyond its length -- so sqtab[e][k][j] = (q_k - ve[k][dict[k][j]])^2, with the same 0.0
+// table value wherever the index is not below U.  Row stride, flag and hit reset are unchanged.
+template <int NANT, int BITS, bool DIGIT = false>
 __global__ __launch_bounds__(FRIRL_BLOCK) void sq_tables_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U, int E,
                                                               const double *__restrict__ x, double *__restrict__ sqtab,
-                                                              uint32_t *__restrict__ fastv, uint32_t *__restrict__ hit)
+                                                              uint32_t *__restrict__ fastv, uint32_t *__restrict__ hit,
+                                                              const uint8_t *__restrict__ dict = nullptr)
 {
     constexpr int TS = 1 << BITS, N = NANT * TS;
     __shared__ double q_s[FRIRL_WAVES_PER_BLOCK][NANT];
@@ -363,7 +374,17 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void sq_tables_kernel(const double *__
     const int e = blockIdx.x * FRIRL_WAVES_PER_BLOCK + wave;
     const bool live = e < E;                     // uniform for the wave; every wave reaches the barrier
     double tv[(N + FRIRL_WAVE - 1) / FRIRL_WAVE];
-    load_sq_sources<NANT, BITS, FRIRL_WAVE>(ve, U, tv, lane);
+    if constexpr (DIGIT) {
+#pragma unroll
+        for (int m = 0; m < (N + FRIRL_WAVE - 1) / FRIRL_WAVE; m++) {
+            const int i = lane + m * FRIRL_WAVE;
+            const int k = i >> BITS;
+            const int idx = i < N ? (int)dict[i] : U;                    // dict[NANT][2^BITS]
+            tv[m] = idx < U ? ve[k * U + idx] : 0.0;
+        }
+    } else {
+        load_sq_sources<NANT, BITS, FRIRL_WAVE>(ve, U, tv, lane);
+    }
     if (live && lane < NANT) q_s[wave][lane] = observe_ve(u, ve, U, lane, x[(size_t)e * NANT + lane]);
     __syncthreads();
     if (!live) return;
@@ -907,6 +928,230 @@ static int launch_packed(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     return check_launch("five_hip_rule_distance_packed");
 }
 
+// ---- Coded form (five_hip_rule_distance_coded_ws, option rd_coded): 3 bytes of indices per rule -------------------------------------
+// A rule's indices as ONE code of at most 24 bits.  Every dimension k has a dictionary (the sorted distinct 6-bit indices its column
+// holds, d_k of them) and a rule's digit j_k is the rank of its index in it.  Dimensions are paired in order: field f holds
+// v = j_b * d_a + j_a (a = 2f, b = 2f + 1) in ceil(log2(d_a * d_b)) bits, an odd last dimension j_a alone; fields lie low to high.  The
+// scan never sees the dictionaries: sq_tables_kernel<DIGIT> lays the squared differences out by digit, so a digit is a table offset
+// exactly as a 6-bit field is in rule_distance_pk_kernel.  Decode of a pair field: j_b = (v * M) >> 18 with M = ceil(2^18 / d_a) -- one
+// 24-bit multiply, exact for v < 4096 and d_a <= 64 (tests/test_rd_codes_host.py proves it exhaustively) -- and j_a = v - j_b * d_a.
+// Layout (lane-tiled): a tile is one item of the pre-pass scan, RD_CD_TILE = 2048 consecutive rules of one environment; thread t owns
+// rules 2t + p + 512 j (p < 2, j < 4) as there, its eight codes (code 2j + p at byte 3 (2j + p)) form one 24-byte little-endian string,
+// and piece m (8 bytes) of that string lies at tile + 2048 m + 8 t: three aligned 8-byte loads per lane and item, 512 contiguous bytes
+// per wave instruction -- the load shape of the packed scan with three loads where it has four.  codes[e][tile][3][256][8] bytes,
+// ceil(maxR / 2048) tiles per environment.
+static constexpr int RD_CD_TILE = 2 * FRIRL_BLOCK * 4;           // rules per tile
+static constexpr int RD_CD_TILE_BYTES = 3 * RD_CD_TILE;
+static constexpr int RD_CD_MAX_NANT = 5, RD_CD_FIELDS = (RD_CD_MAX_NANT + 1) / 2;
+
+struct CodeParams {                              // uniform kernel arguments
+    uint32_t shift[RD_CD_FIELDS], mask[RD_CD_FIELDS], da[RD_CD_FIELDS], magic[RD_CD_FIELDS];
+};
+
+static int ceil_log2(uint32_t n)
+{
+    int b = 0;
+    while ((1u << b) < n) b++;
+    return b;
+}
+
+// field parameters from the dictionary lengths; false when the coded form does not apply (a field over 12 bits, a code over 24)
+static bool code_params(int nant, const int32_t *d, CodeParams &cp)
+{
+    if (nant < 1 || nant > RD_CD_MAX_NANT || !d) return false;
+    int total = 0;
+    for (int f = 0; f < RD_CD_FIELDS; f++) cp.shift[f] = cp.mask[f] = 0u, cp.da[f] = 1u, cp.magic[f] = 1u << 18;
+    for (int k = 0; k < nant; k += 2) {
+        const int f = k / 2;
+        if (d[k] < 1 || d[k] > 64 || (k + 1 < nant && (d[k + 1] < 1 || d[k + 1] > 64))) return false;
+        const uint32_t da = (uint32_t)d[k], db = k + 1 < nant ? (uint32_t)d[k + 1] : 1u;
+        const int bits = ceil_log2(da * db);
+        if (bits > 12) return false;
+        cp.shift[f] = (uint32_t)total;
+        cp.mask[f] = (1u << bits) - 1u;
+        cp.da[f] = da;
+        cp.magic[f] = ((1u << 18) + da - 1u) / da;
+        total += bits;
+    }
+    return total <= 24;
+}
+
+static size_t coded_bytes(int nant, int U, long E, long maxR, const int32_t *d)
+{
+    CodeParams cp;
+    if (!packed_words(nant, U) || E < 1 || maxR < 2 || !code_params(nant, d, cp)) return 0;
+    return (size_t)E * (size_t)((maxR + RD_CD_TILE - 1) / RD_CD_TILE) * RD_CD_TILE_BYTES;
+}
+
+// codes from uidx: one thread per (tile, thread slot), writing its 24-byte string as three 8-byte pieces.  rank[k][i] = rank of the
+// 6-bit index i in the dictionary of dimension k.  Columns at or beyond nrules[e] rounded up to the next even index get code 0 (the
+// odd last rule's partner column is coded like a rule: the scans write its distance).
+__global__ __launch_bounds__(FRIRL_BLOCK) void pack_codes_kernel(const uint16_t *__restrict__ uidx, const int32_t *__restrict__ nrules, int nant, int maxR,
+                                                                 int tpe, long ntiles, const uint8_t *__restrict__ rank, CodeParams cp,
+                                                                 uint8_t *__restrict__ codes)
+{
+    const int t = threadIdx.x;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long e = tile / tpe;
+        const int c = (int)(tile - e * tpe);
+        const int R = nrules[e];
+        const int Rp = min(R + (R & 1), maxR);
+        const uint16_t *__restrict__ src = uidx + (size_t)e * nant * maxR;
+        uint32_t code[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int r = c * RD_CD_TILE + 2 * t + (i & 1) + 2 * FRIRL_BLOCK * (i >> 1);
+            uint32_t v = 0u;
+            if (r < Rp) {
+                for (int k = 0; k < nant; k += 2) {
+                    const uint32_t ja = rank[k * 64 + (src[(size_t)k * maxR + r] & 63u)];
+                    const uint32_t jb = k + 1 < nant ? rank[(k + 1) * 64 + (src[(size_t)(k + 1) * maxR + r] & 63u)] : 0u;
+                    v |= (jb * cp.da[k / 2] + ja) << cp.shift[k / 2];
+                }
+            }
+            code[i] = v & 0xFFFFFFu;
+        }
+        u32x2_t *__restrict__ dst = reinterpret_cast<u32x2_t *>(codes + (size_t)tile * RD_CD_TILE_BYTES + 8 * t);
+        u32x2_t p0, p1, p2;
+        p0.x = code[0] | code[1] << 24;  p0.y = code[1] >> 8 | code[2] << 16;
+        p1.x = code[2] >> 16 | code[3] << 8;  p1.y = code[4] | code[5] << 24;
+        p2.x = code[5] >> 8 | code[6] << 16;  p2.y = code[6] >> 16 | code[7] << 8;
+        dst[0] = p0;
+        dst[RD_CD_TILE / 8] = p1;                // + 2048 bytes
+        dst[2 * (RD_CD_TILE / 8)] = p2;
+    }
+}
+
+// the sum of a rule's NANT squared differences, dimensions ascending, from its code (bits above 24 are ignored: every field is masked)
+template <int NANT>
+__device__ __forceinline__ double cd_rule_sq(uint32_t code, const double *__restrict__ sq_s, const CodeParams &cp)
+{
+    constexpr int TS = 64;
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < NANT; k += 2) {
+        const int f = k / 2;
+        const uint32_t v = (code >> cp.shift[f]) & cp.mask[f];
+        if (k + 1 < NANT) {
+            const uint32_t jb = __umul24(v, cp.magic[f]) >> 18;
+            const uint32_t ja = v - __umul24(jb, cp.da[f]);
+            const double sa = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + k * TS) + (ja << 3));
+            const double sb = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + (k + 1) * TS) + (jb << 3));
+            a = k == 0 ? sa : a + sa;
+            a = a + sb;
+        } else {
+            const double sa = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + k * TS) + (v << 3));
+            a = k == 0 ? sa : a + sa;
+        }
+    }
+    return a;
+}
+
+// The coded scan: the pre-pass form of rule_distance_pk_kernel (items of 2048 rules grouped by XCD, four column sets per lane, the table
+// copy, the same adds, square roots, stores and hit reduction) reading three 8-byte pieces of codes per lane and item.
+template <int NANT, bool WRITE>
+__global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_cd_kernel(const uint8_t *__restrict__ codes, const int32_t *__restrict__ nrules, int maxR,
+                                                                     double *__restrict__ dists, uint32_t *__restrict__ hit, int cpe, int E,
+                                                                     const double *__restrict__ sqtab, const uint32_t *__restrict__ fastv, CodeParams cp)
+{
+    constexpr int TS = 64, STEP = FRIRL_BLOCK * 2;
+    __shared__ __attribute__((aligned(16))) double sq_s[NANT * TS];
+    __shared__ unsigned red_s[FRIRL_WAVES_PER_BLOCK];
+    const unsigned grp = blockIdx.x / (unsigned)(RD_XCDS * cpe), gj = blockIdx.x - grp * (unsigned)(RD_XCDS * cpe);
+    const int e = (int)(grp * RD_XCDS + gj % RD_XCDS);
+    const int c = (int)(gj / RD_XCDS);
+    if (e >= E) return;
+    const int R = nrules[e];
+    const int r0 = c * RD_CD_TILE;
+    if (r0 >= R) return;
+    int r_end = r0 + RD_CD_TILE;
+    if (r_end > R) r_end = R;
+
+    const int r = r0 + 2 * (int)threadIdx.x;
+    const bool any = r < r_end;                  // the lane's first pair is its lowest: without it the lane has no rule in this tile
+    u32x2_t w[3];
+    if (any) {                                   // the whole tile exists (codes are allocated in whole tiles): aligned, in bounds
+        const uint8_t *__restrict__ src = codes + ((size_t)e * cpe + c) * RD_CD_TILE_BYTES + 8 * threadIdx.x;
+#pragma unroll
+        for (int m = 0; m < 3; m++) w[m] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(src + m * RD_CD_TILE));
+    }
+    constexpr int N2 = NANT * TS / 2;
+    const double2 *__restrict__ tsrc = reinterpret_cast<const double2 *>(sqtab + (size_t)e * (NANT * TS));
+    for (int i = threadIdx.x; i < N2; i += FRIRL_BLOCK) reinterpret_cast<double2 *>(sq_s)[i] = tsrc[i];
+    const bool fast = fastv[e] != 0u;
+    __syncthreads();
+
+    double *__restrict__ out = WRITE ? dists + (size_t)e * maxR : nullptr;
+    unsigned best = FRIRL_HIP_NO_HIT;
+    auto sweep = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        if (!any) return;
+        uint32_t code[8];
+        code[0] = w[0].x;
+        code[1] = __builtin_amdgcn_alignbit(w[0].y, w[0].x, 24);
+        code[2] = __builtin_amdgcn_alignbit(w[1].x, w[0].y, 16);
+        code[3] = w[1].x >> 8;
+        code[4] = w[1].y;
+        code[5] = __builtin_amdgcn_alignbit(w[2].x, w[1].y, 24);
+        code[6] = __builtin_amdgcn_alignbit(w[2].y, w[2].x, 16);
+        code[7] = w[2].y >> 8;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int rr = r + j * STEP;
+            if (rr < r_end) {
+                const double a0 = cd_rule_sq<NANT>(code[2 * j], sq_s, cp), a1 = cd_rule_sq<NANT>(code[2 * j + 1], sq_s, cp);
+                double2 d;
+                bool z0, z1;
+                if (FAST) {
+                    d.x = sqrt_unscaled(a0);
+                    d.y = sqrt_unscaled(a1);
+                    z0 = a0 == 0.0;
+                    z1 = a1 == 0.0;
+                } else {
+                    d.x = __dsqrt_rn(a0);
+                    d.y = __dsqrt_rn(a1);
+                    z0 = d.x == 0.0;
+                    z1 = d.y == 0.0;
+                }
+                if (WRITE) { __builtin_nontemporal_store(d.x, out + rr); __builtin_nontemporal_store(d.y, out + rr + 1); }
+                if (z1 && rr + 1 < R) best = min(best, (unsigned)(rr + 1));
+                if (z0) best = min(best, (unsigned)rr);
+            }
+        }
+    };
+    if (fast) sweep(std::true_type{});
+    else sweep(std::false_type{});
+    best = wave_min_u32(best);
+    if ((threadIdx.x & (FRIRL_WAVE - 1)) == 0) red_s[threadIdx.x / FRIRL_WAVE] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned m = red_s[0];
+        for (int v = 1; v < FRIRL_WAVES_PER_BLOCK; v++) m = red_s[v] < m ? red_s[v] : m;
+        if (m != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], m);
+    }
+}
+
+template <int NANT>
+static int launch_coded(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint8_t *codes, const uint8_t *dict, const CodeParams &cp,
+                        const double *x, double *ruledists, uint32_t *hit, void *ws, hipStream_t s)
+{
+    using namespace frirl_host;
+    const long cpe = ((long)b->maxR + RD_CD_TILE - 1) / RD_CD_TILE;
+    if (cpe * ((long)b->E + RD_XCDS) > 0x7FFFFFFFL) { set_error("five_hip_rule_distance_coded_ws: too many work items"); return FRIRL_HIP_EINVAL; }
+    double *sqtab = static_cast<double *>(ws);
+    uint32_t *fastv = reinterpret_cast<uint32_t *>(sqtab + (size_t)b->E * NANT * (1 << RD_PK_BITS));
+    const unsigned items = (unsigned)cpe * (unsigned)((b->E + RD_XCDS - 1) / RD_XCDS * RD_XCDS);
+    hipLaunchKernelGGL((sq_tables_kernel<NANT, RD_PK_BITS, true>), dim3((unsigned)((b->E + FRIRL_WAVES_PER_BLOCK - 1) / FRIRL_WAVES_PER_BLOCK)), dim3(FRIRL_BLOCK),
+                       0, s, t->u, t->ve, t->U, b->E, x, sqtab, fastv, hit, dict);
+    if (ruledists)
+        hipLaunchKernelGGL((rule_distance_cd_kernel<NANT, true>), dim3(items), dim3(FRIRL_BLOCK), 0, s, codes, b->nrules, b->maxR, ruledists, hit, (int)cpe,
+                           b->E, sqtab, fastv, cp);
+    else
+        hipLaunchKernelGGL((rule_distance_cd_kernel<NANT, false>), dim3(items), dim3(FRIRL_BLOCK), 0, s, codes, b->nrules, b->maxR, ruledists, hit, (int)cpe,
+                           b->E, sqtab, fastv, cp);
+    return check_launch("five_hip_rule_distance_coded_ws");
+}
+
 // Probes for the tests (five_hip_sqrt_unscaled_check, five_hip_rule_distance_sq_guard): the device functions the packed scan uses.
 __global__ void sqrt_unscaled_check_kernel(const double *__restrict__ a, double *__restrict__ fast, double *__restrict__ ref, long n)
 {
@@ -1062,4 +1307,67 @@ extern "C" int five_hip_rule_distance_packed_ws(const frirl_hip_tables *t, const
         if (reinterpret_cast<uintptr_t>(workspace) & 15) { set_error("five_hip_rule_distance_packed_ws: workspace must be 16-byte aligned"); return FRIRL_HIP_EINVAL; }
     }
     return rule_distance_packed(t, b, pidx, x, ruledists, hit, need ? workspace : nullptr, stream);
+}
+
+extern "C" size_t five_hip_rule_distance_coded_bytes(int32_t nant, int32_t U, int32_t E, int32_t maxR, const int32_t *d)
+{
+    return frirl::coded_bytes(nant, U, E, maxR, d);
+}
+
+extern "C" int frirl_hip_pack_codes(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint8_t *rank, const int32_t *d, uint8_t *codes,
+                                    void *stream)
+{
+    using namespace frirl_host;
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    if (!b->uidx || !rank || !codes) { set_error("frirl_hip_pack_codes: NULL uidx/rank/codes"); return FRIRL_HIP_EINVAL; }
+    frirl::CodeParams cp;
+    if (!frirl::coded_bytes(t->nant, t->U, b->E, b->maxR, d) || !frirl::code_params(t->nant, d, cp)) {
+        set_error("frirl_hip_pack_codes: nant=%d U=%d with these dictionary lengths is not served by the coded form", t->nant, t->U);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(codes) & 7) { set_error("frirl_hip_pack_codes: codes must be 8-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_device())) return rc;
+    const int tpe = (b->maxR + frirl::RD_CD_TILE - 1) / frirl::RD_CD_TILE;
+    const long ntiles = (long)b->E * tpe;
+    long grid = ntiles;
+    if (grid > (long)frirl::device_cus() * 32) grid = (long)frirl::device_cus() * 32;
+    hipLaunchKernelGGL(frirl::pack_codes_kernel, dim3((unsigned)grid), dim3(FRIRL_BLOCK), 0, as_stream(stream), b->uidx, b->nrules, t->nant, b->maxR, tpe,
+                       ntiles, rank, cp, codes);
+    return check_launch("frirl_hip_pack_codes");
+}
+
+extern "C" int five_hip_rule_distance_coded_ws(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint8_t *codes, const uint8_t *dict,
+                                               const int32_t *d, const uint32_t *pidx, const double *x, double *ruledists, uint32_t *hit,
+                                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace frirl_host;
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    // the A/B hooks keep selecting the kernels they select without the coded form: any of them set, the 4-byte route runs
+    const Options &o = opts();
+    const bool plain = !o.rd_coded || !o.rd_packed || !o.rd_sqdiff || !o.rd_prepass || o.rd_persist == 1 || o.no_uidx || o.rd_order != 0 ||
+                       (o.rd_unroll != 0 && o.rd_unroll != 4) || (o.rd_chunk != 0 && o.rd_chunk != frirl::RD_CD_TILE);
+    frirl::CodeParams cp;
+    if (plain || !frirl::coded_bytes(t->nant, t->U, b->E, b->maxR, d) || !frirl::code_params(t->nant, d, cp))
+        return five_hip_rule_distance_packed_ws(t, b, pidx, x, ruledists, hit, workspace, workspace_bytes, stream);
+    const size_t need = frirl::packed_ws_bytes(t->nant, t->U, b->E);
+    if (!workspace || workspace_bytes < need) {
+        set_error("five_hip_rule_distance_coded_ws: workspace of %zu B at %p, nant=%d U=%d E=%d needs %zu B "
+                  "(five_hip_rule_distance_packed_workspace_bytes)", workspace_bytes, workspace, t->nant, t->U, b->E, need);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) { set_error("five_hip_rule_distance_coded_ws: workspace must be 16-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if (!codes || !dict || !x || !hit) { set_error("five_hip_rule_distance_coded_ws: NULL codes/dict/x/hit"); return FRIRL_HIP_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(codes) & 7) { set_error("five_hip_rule_distance_coded_ws: codes must be 8-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if (ruledists && (reinterpret_cast<uintptr_t>(ruledists) & 15)) { set_error("five_hip_rule_distance_coded_ws: ruledists must be 16-byte aligned"); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_device())) return rc;
+    hipStream_t s = as_stream(stream);
+    switch (t->nant) {
+#define FRIRL_CASE(N) case N: return frirl::launch_coded<N>(t, b, codes, dict, cp, x, ruledists, hit, workspace, s);
+        FRIRL_CASE(1) FRIRL_CASE(2) FRIRL_CASE(3) FRIRL_CASE(4) FRIRL_CASE(5)
+#undef FRIRL_CASE
+    }
+    set_error("five_hip_rule_distance_coded_ws: unsupported nant=%d", t->nant);
+    return FRIRL_HIP_EINVAL;
 }

@@ -34,6 +34,7 @@ static const OptName k_opts[] = {
     {"rd_sqdiff", "FRIRL_HIP_RD_SQDIFF", &Options::rd_sqdiff, 1},
     {"rd_qpass", "FRIRL_HIP_RD_QPASS", &Options::rd_qpass, 0},
     {"rd_prepass", "FRIRL_HIP_RD_PREPASS", &Options::rd_prepass, 1},
+    {"rd_coded", "FRIRL_HIP_RD_CODED", &Options::rd_coded, 1},
     {"step_wave", "FRIRL_HIP_STEP_WAVE", &Options::step_wave, -1},
     {"step_track", "FRIRL_HIP_STEP_TRACK", &Options::step_track, -1},
     {"lanes_slices", "FRIRL_HIP_LANES_SLICES", &Options::lanes_slices, 0},

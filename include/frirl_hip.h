@@ -100,7 +100,7 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
  * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
- * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -147,6 +147,26 @@ int five_hip_rule_distance_packed(const frirl_hip_tables *t, const frirl_hip_rul
 size_t five_hip_rule_distance_packed_workspace_bytes(int32_t nant, int32_t U, int32_t E);
 int five_hip_rule_distance_packed_ws(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint32_t *pidx, const double *x,
                                      double *ruledists, uint32_t *hit, void *workspace, size_t workspace_bytes, void *stream);
+/* The same scan streaming 3-BYTE CODES (option rd_coded, shipped): a rule's indices as one code of at most 24 bits in a lane-tiled
+ * copy that only this library reads.  Dimension k has a dictionary: the sorted distinct 6-bit indices (uidx & 63) of its columns
+ * r < nrules[e] rounded up to the next even index, over all environments; d[k] <= 64 is its length, dict[k][j] its j-th entry (0xFF for
+ * j >= d[k]) and rank[k][i] the position of index i in it.  Dimensions are paired in order, field f = digit(2f + 1) * d[2f] + digit(2f)
+ * in ceil(log2(d[2f] * d[2f + 1])) bits (an odd last dimension: its digit in ceil(log2 d) bits), fields low to high; every other
+ * column has code 0.  The form applies when every field has <= 12 bits, the code <= 24, nant <= 5 and the packed form serves the
+ * shape: five_hip_rule_distance_coded_bytes is then the size of the copy (whole tiles of 2048 rules, 6144 bytes each: thread t of a
+ * tile owns rules 2t + p + 512 j, p < 2, j < 4, its eight codes in the order 2j + p are one 24-byte little-endian string, and piece
+ * m < 3 of it lies at tile + 2048 m + 8 t), else 0.  frirl_hip_pack_codes builds the copy from the CURRENT uidx and nrules.
+ * five_hip_rule_distance_coded_ws has the contract, workspace and bits of five_hip_rule_distance_packed_ws; the workspace's tables are
+ * laid out by digit (sqtab[e][k][j] belongs to index dict[k][j]).  Where the form does not apply, and under rd_coded = 0, rd_packed = 0,
+ * rd_sqdiff = 0, rd_prepass = 0, rd_persist = 1, no_uidx = 1, rd_order != 0 or another rd_unroll / rd_chunk than 4 / 2048, it runs
+ * five_hip_rule_distance_packed_ws on pidx (codes, dict and d are not read).
+ *   d [host] [nant] int32;  rank, dict [dev] [nant][64] uint8;  codes [dev] 8-byte aligned */
+size_t five_hip_rule_distance_coded_bytes(int32_t nant, int32_t U, int32_t E, int32_t maxR, const int32_t *d);
+int frirl_hip_pack_codes(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint8_t *rank, const int32_t *d, uint8_t *codes,
+                         void *stream);
+int five_hip_rule_distance_coded_ws(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const uint8_t *codes, const uint8_t *dict,
+                                    const int32_t *d, const uint32_t *pidx, const double *x, double *ruledists, uint32_t *hit,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 /* Test probes of the packed scan's squared-difference form (option rd_sqdiff, shipped).  The scan sums per-workgroup tables of
  * (q_k - ve[k][i])^2 and, when every entry of the workgroup's tables is 0 or within [2^-767, 2^1000], takes the square root
  * without __dsqrt_rn's rescaling and special-case steps; otherwise it calls __dsqrt_rn.
