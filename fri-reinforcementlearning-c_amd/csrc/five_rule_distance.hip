@@ -50,10 +50,13 @@
 //                                 two dimensions per field, at most 24 bits in all (cfg4: 11 + 11 + 2); the copy is lane-tiled, so a lane
 //                                 makes three aligned 8-byte loads per 2048-rule item where the packed scan makes four, and the tables
 //                                 of sq_tables_kernel<DIGIT> are laid out by rank: the scan is the pre-pass form of the packed one with
-//                                 another decode (one 24-bit multiply, a shift and a multiply-subtract per pair) -- bit-identical.
-//                                 cfg4: FETCH 2.17 -> 1.63 GB, 1.052-1.053 -> 1.017-1.020 ms; 28 VGPRs (profiles/r10_cfg4_coded.md).
+//                                 another decode -- bit-identical.  cfg4: FETCH 2.17 -> 1.63 GB, 1.052-1.053 -> 1.017-1.020 ms
+//                                 (profiles/r10_cfg4_coded.md).  The decode works in byte offsets (5-6 instructions per pair field), 0
+//                                 leaves the short square root through one v_max_f64 and the exact hits are found off the common path:
+//                                 59 vector instructions per rule pair where there were 81, SQ_INSTS_VALU 3.99e8 -> 2.80e8 per launch,
+//                                 34 VGPRs (profiles/r11_cfg4_scan_valu.md).
 // First exact hit: per-lane minimum index -> wave butterfly -> (LDS ->) one integer atomicMin per workgroup / item
-// (deterministic; only taken when a hit exists).
+// (deterministic; only taken when a hit exists).  The coded scan looks for the index only in a wave that saw a zero (see there).
 // "rd_*" / "no_uidx" options (frirl_hip_set_option) are experiment hooks (tools/ab_rd.py); unset, the shipped configuration runs.
 #include <stdlib.h>
 
@@ -267,7 +270,7 @@ __device__ __forceinline__ double2 pk_pair_distance(const u32x2_t (&w)[Packed<BI
 }
 
 // __dsqrt_rn's gfx950 expansion for an input it does not rescale (x >= 2^-767, finite): v_rsq_f64, the same two multiplies and
-// seven Newton FMAs in the same order, and 0 passed through.  For such x the result has the bits of __dsqrt_rn(x); below 2^-767,
+// seven Newton FMAs in the same order, and 0 passed through (one v_max_f64).  For such x the result has the bits of __dsqrt_rn(x); below 2^-767,
 // at +inf or for NaN / negative x it does not (the full expansion rescales tiny inputs and passes +inf through).
 __device__ __forceinline__ double sqrt_unscaled(double x)
 {
@@ -281,7 +284,7 @@ __device__ __forceinline__ double sqrt_unscaled(double x)
     const double s2 = __builtin_fma(d0, h1, s1);
     const double d1 = __builtin_fma(-s2, s2, x);
     const double r = __builtin_fma(d1, h1, s2);
-    return x == 0.0 ? x : r;
+    return __builtin_fmax(r, 0.0);               // x = +0: rsq = +inf, r = 0 * inf = NaN, and the maximum of a quiet NaN and +0 is +0; x > 0: r > 0
 }
 
 // Bounds on one squared difference under which every sum of at most FRIRL_HIP_MAX_NANT of them is exactly 0 or a finite value
@@ -1022,42 +1025,85 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void pack_codes_kernel(const uint16_t 
     }
 }
 
-// the sum of a rule's NANT squared differences, dimensions ascending, from its code (bits above 24 are ignored: every field is masked)
+// What the scan derives from CodeParams once per wave (scalar registers): the decode of a pair field works in BYTE offsets.  The codes
+// are unpacked to bit 3 (code8 = code << 3, rubbish below bit 3 and above bit 27), so that for a field at `shift`
+//   v8  = (code8 >> shift) & (mask << 3)                   8 v: v < 2^bits <= 4096, v8 < 2^15           (field 0: shift = 0, the mask alone)
+//   jb8 = ((v8 * magic) >> 18) & RD_CD_Q8                  8 (v / d_a): v8 * magic = 8 (v * magic), so the shift by 18 leaves 8 j_b + three
+//                                                          bits of the fraction, which the mask drops; v_mul_u32_u24: v8 < 2^15 < 2^24,
+//                                                          magic <= 2^18 < 2^24, and v8 * magic < 2^32: 2^bits < 2 d_a d_b, so the product is
+//                                                          below 16 d_a d_b (2^18 / d_a + 1) <= 2^28 + 2^16
+//   ja8 = v8 - jb8 * d_a                                   8 (v mod d_a): one v_mad_i32_i24 with -d_a: jb8 < 2^10, |-d_a| <= 64, no overflow
+// all exact for every v below 2^bits (tests/test_rd_decode_host.py; v / d_a < 2 d_b <= 128 there, which RD_CD_Q8 holds); the pack kernel
+// writes v < d_a d_b only.  A single field is its shift and mask.
+static constexpr uint32_t RD_CD_Q8 = 127u << 3;
+struct CodeScan {
+    uint32_t shift[RD_CD_FIELDS], mask8[RD_CD_FIELDS], magic[RD_CD_FIELDS];
+    int32_t negda[RD_CD_FIELDS];
+    __device__ __forceinline__ explicit CodeScan(const CodeParams &cp)
+    {
+#pragma unroll
+        for (int f = 0; f < RD_CD_FIELDS; f++) shift[f] = cp.shift[f], mask8[f] = (cp.mask[f] & 0xFFFu) << 3, magic[f] = cp.magic[f], negda[f] = -(int32_t)cp.da[f];
+    }
+};
+
+__device__ __forceinline__ double cd_table_entry(const double *__restrict__ tab_k, uint32_t off8)
+{
+    return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(tab_k) + off8);
+}
+
+// the sum of a rule's NANT squared differences, dimensions ascending, from its code at bit 3 (other bits are ignored: every field is masked)
 template <int NANT>
-__device__ __forceinline__ double cd_rule_sq(uint32_t code, const double *__restrict__ sq_s, const CodeParams &cp)
+__device__ __forceinline__ double cd_rule_sq(uint32_t code8, const double *__restrict__ sq_s, const CodeScan &cs)
 {
     constexpr int TS = 64;
     double a = 0.0;
 #pragma unroll
     for (int k = 0; k < NANT; k += 2) {
         const int f = k / 2;
-        const uint32_t v = (code >> cp.shift[f]) & cp.mask[f];
+        const uint32_t v8 = (f == 0 ? code8 : code8 >> cs.shift[f]) & cs.mask8[f];       // code_params: shift[0] = 0
         if (k + 1 < NANT) {
-            const uint32_t jb = __umul24(v, cp.magic[f]) >> 18;
-            const uint32_t ja = v - __umul24(jb, cp.da[f]);
-            const double sa = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + k * TS) + (ja << 3));
-            const double sb = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + (k + 1) * TS) + (jb << 3));
+            const uint32_t jb8 = (__umul24(v8, cs.magic[f]) >> 18) & RD_CD_Q8;
+            const uint32_t ja8 = (uint32_t)(__mul24((int)jb8, cs.negda[f]) + (int)v8);
+            const double sa = cd_table_entry(sq_s + k * TS, ja8);
+            const double sb = cd_table_entry(sq_s + (k + 1) * TS, jb8);
             a = k == 0 ? sa : a + sa;
             a = a + sb;
         } else {
-            const double sa = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(sq_s + k * TS) + (v << 3));
+            const double sa = cd_table_entry(sq_s + k * TS, v8);
             a = k == 0 ? sa : a + sa;
         }
     }
     return a;
 }
 
+// blockIdx.x / d for the scan's grid: d = RD_XCDS * cpe >= 8 and fewer than 2^31 workgroups.  With l = ceil(log2 d) and
+// mul = ceil(2^(31 + l) / d) (d > 2^(l - 1): mul < 2^32), n / d = (n * mul) >> (31 + l) for every n < 2^31: the error of the product,
+// n * (mul * d - 2^(31 + l)) / d < 2^31 * d / d, stays below the 2^(31 + l) / d that one step of the quotient's fraction is worth.
+struct GroupDiv { uint32_t mul, shift; };        // quotient = __umulhi(n, mul) >> shift
+static GroupDiv group_div(uint32_t d)
+{
+    const int l = ceil_log2(d);
+    GroupDiv g;
+    g.mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
+    g.shift = (uint32_t)(l - 1);
+    return g;
+}
+
 // The coded scan: the pre-pass form of rule_distance_pk_kernel (items of 2048 rules grouped by XCD, four column sets per lane, the table
-// copy, the same adds, square roots, stores and hit reduction) reading three 8-byte pieces of codes per lane and item.
+// copy, the same adds, square roots and stores) reading three 8-byte pieces of codes per lane and item.
+// First exact hit, off the common path: the sweep only keeps the lane's minimum of the HIGH WORDS of the squared sums (FAST) or distances
+// (one v_min3_u32 per pair: +0 has a zero high word, a NaN has not), and the wave leaves unless one of its lanes saw a zero high word.
+// Such a wave (a handful per launch; a subnormal sum would bring it here too, and find nothing) decodes its codes again, takes the lowest zero rule per lane under the bounds of the sweep (the partner column of an odd last rule is
+// swept, and may bring the wave here, but is no rule), reduces over the wave and issues one atomicMin: no LDS, no second barrier.
 template <int NANT, bool WRITE>
 __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_cd_kernel(const uint8_t *__restrict__ codes, const int32_t *__restrict__ nrules, int maxR,
                                                                      double *__restrict__ dists, uint32_t *__restrict__ hit, int cpe, int E,
-                                                                     const double *__restrict__ sqtab, const uint32_t *__restrict__ fastv, CodeParams cp)
+                                                                     const double *__restrict__ sqtab, const uint32_t *__restrict__ fastv, CodeParams cp,
+                                                                     GroupDiv gd)
 {
     constexpr int TS = 64, STEP = FRIRL_BLOCK * 2;
     __shared__ __attribute__((aligned(16))) double sq_s[NANT * TS];
-    __shared__ unsigned red_s[FRIRL_WAVES_PER_BLOCK];
-    const unsigned grp = blockIdx.x / (unsigned)(RD_XCDS * cpe), gj = blockIdx.x - grp * (unsigned)(RD_XCDS * cpe);
+    const unsigned grp = __umulhi(blockIdx.x, gd.mul) >> gd.shift, gj = blockIdx.x - grp * (unsigned)(RD_XCDS * cpe);
     const int e = (int)(grp * RD_XCDS + gj % RD_XCDS);
     const int c = (int)(gj / RD_XCDS);
     if (e >= E) return;
@@ -1079,56 +1125,65 @@ __global__ __launch_bounds__(FRIRL_BLOCK) void rule_distance_cd_kernel(const uin
     const double2 *__restrict__ tsrc = reinterpret_cast<const double2 *>(sqtab + (size_t)e * (NANT * TS));
     for (int i = threadIdx.x; i < N2; i += FRIRL_BLOCK) reinterpret_cast<double2 *>(sq_s)[i] = tsrc[i];
     const bool fast = fastv[e] != 0u;
+    const CodeScan cs(cp);
     __syncthreads();
 
     double *__restrict__ out = WRITE ? dists + (size_t)e * maxR : nullptr;
-    unsigned best = FRIRL_HIP_NO_HIT;
+    uint32_t code[8];                            // at bit 3
+    uint32_t lo = ~0u;                           // minimum high word of what the lane's hit test compares with 0.0
     auto sweep = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        if (!any) return;
-        uint32_t code[8];
-        code[0] = w[0].x;
-        code[1] = __builtin_amdgcn_alignbit(w[0].y, w[0].x, 24);
-        code[2] = __builtin_amdgcn_alignbit(w[1].x, w[0].y, 16);
-        code[3] = w[1].x >> 8;
-        code[4] = w[1].y;
-        code[5] = __builtin_amdgcn_alignbit(w[2].x, w[1].y, 24);
-        code[6] = __builtin_amdgcn_alignbit(w[2].y, w[2].x, 16);
-        code[7] = w[2].y >> 8;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int rr = r + j * STEP;
             if (rr < r_end) {
-                const double a0 = cd_rule_sq<NANT>(code[2 * j], sq_s, cp), a1 = cd_rule_sq<NANT>(code[2 * j + 1], sq_s, cp);
+                const double a0 = cd_rule_sq<NANT>(code[2 * j], sq_s, cs), a1 = cd_rule_sq<NANT>(code[2 * j + 1], sq_s, cs);
                 double2 d;
-                bool z0, z1;
                 if (FAST) {
                     d.x = sqrt_unscaled(a0);
                     d.y = sqrt_unscaled(a1);
-                    z0 = a0 == 0.0;
-                    z1 = a1 == 0.0;
+                    lo = min(lo, min((uint32_t)__double2hiint(a0), (uint32_t)__double2hiint(a1)));     // sqrt(a) == 0 exactly when a == 0
                 } else {
                     d.x = __dsqrt_rn(a0);
                     d.y = __dsqrt_rn(a1);
-                    z0 = d.x == 0.0;
-                    z1 = d.y == 0.0;
+                    lo = min(lo, min((uint32_t)__double2hiint(d.x), (uint32_t)__double2hiint(d.y)));
                 }
                 if (WRITE) { __builtin_nontemporal_store(d.x, out + rr); __builtin_nontemporal_store(d.y, out + rr + 1); }
+            }
+        }
+    };
+    auto first_hit = [&](auto fast_tag) -> unsigned {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        unsigned best = FRIRL_HIP_NO_HIT;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int rr = r + j * STEP;
+            if (rr < r_end) {
+                const double a0 = cd_rule_sq<NANT>(code[2 * j], sq_s, cs), a1 = cd_rule_sq<NANT>(code[2 * j + 1], sq_s, cs);
+                const bool z0 = FAST ? a0 == 0.0 : __dsqrt_rn(a0) == 0.0, z1 = FAST ? a1 == 0.0 : __dsqrt_rn(a1) == 0.0;
                 if (z1 && rr + 1 < R) best = min(best, (unsigned)(rr + 1));
                 if (z0) best = min(best, (unsigned)rr);
             }
         }
+        return best;
     };
-    if (fast) sweep(std::true_type{});
-    else sweep(std::false_type{});
-    best = wave_min_u32(best);
-    if ((threadIdx.x & (FRIRL_WAVE - 1)) == 0) red_s[threadIdx.x / FRIRL_WAVE] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned m = red_s[0];
-        for (int v = 1; v < FRIRL_WAVES_PER_BLOCK; v++) m = red_s[v] < m ? red_s[v] : m;
-        if (m != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], m);
+    if (any) {
+        code[0] = w[0].x << 3;
+        code[1] = __builtin_amdgcn_alignbit(w[0].y, w[0].x, 21);
+        code[2] = __builtin_amdgcn_alignbit(w[1].x, w[0].y, 13);
+        code[3] = w[1].x >> 5;
+        code[4] = w[1].y << 3;
+        code[5] = __builtin_amdgcn_alignbit(w[2].x, w[1].y, 21);
+        code[6] = __builtin_amdgcn_alignbit(w[2].y, w[2].x, 13);
+        code[7] = w[2].y >> 5;
+        if (fast) sweep(std::true_type{});
+        else sweep(std::false_type{});
     }
+    if (!__any(lo == 0u)) return;                // uniform for the wave
+    unsigned best = FRIRL_HIP_NO_HIT;
+    if (any) best = fast ? first_hit(std::true_type{}) : first_hit(std::false_type{});
+    best = wave_min_u32(best);                   // every lane of the wave is here
+    if ((threadIdx.x & (FRIRL_WAVE - 1)) == 0 && best != FRIRL_HIP_NO_HIT) atomicMin(&hit[e], best);
 }
 
 template <int NANT>
@@ -1141,14 +1196,15 @@ static int launch_coded(const frirl_hip_tables *t, const frirl_hip_rulebases *b,
     double *sqtab = static_cast<double *>(ws);
     uint32_t *fastv = reinterpret_cast<uint32_t *>(sqtab + (size_t)b->E * NANT * (1 << RD_PK_BITS));
     const unsigned items = (unsigned)cpe * (unsigned)((b->E + RD_XCDS - 1) / RD_XCDS * RD_XCDS);
+    const GroupDiv gd = group_div((uint32_t)(RD_XCDS * cpe));
     hipLaunchKernelGGL((sq_tables_kernel<NANT, RD_PK_BITS, true>), dim3((unsigned)((b->E + FRIRL_WAVES_PER_BLOCK - 1) / FRIRL_WAVES_PER_BLOCK)), dim3(FRIRL_BLOCK),
                        0, s, t->u, t->ve, t->U, b->E, x, sqtab, fastv, hit, dict);
     if (ruledists)
         hipLaunchKernelGGL((rule_distance_cd_kernel<NANT, true>), dim3(items), dim3(FRIRL_BLOCK), 0, s, codes, b->nrules, b->maxR, ruledists, hit, (int)cpe,
-                           b->E, sqtab, fastv, cp);
+                           b->E, sqtab, fastv, cp, gd);
     else
         hipLaunchKernelGGL((rule_distance_cd_kernel<NANT, false>), dim3(items), dim3(FRIRL_BLOCK), 0, s, codes, b->nrules, b->maxR, ruledists, hit, (int)cpe,
-                           b->E, sqtab, fastv, cp);
+                           b->E, sqtab, fastv, cp, gd);
     return check_launch("five_hip_rule_distance_coded_ws");
 }
 
