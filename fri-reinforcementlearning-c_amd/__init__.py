@@ -132,6 +132,12 @@ SIGNATURES = {
     "frirl_hip_rollout_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_int32, C.POINTER(RolloutDesc), C.c_void_p]),
     "frirl_hip_reduce_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_int, C.c_double, C.c_int,
                                           C.POINTER(C.c_int32), C.POINTER(ReduceResult), C.c_void_p]),
+    "frirl_hip_reduce_batch_depth": (C.c_int, [C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_double, C.c_int, C.POINTER(C.c_int32), C.POINTER(ReduceResult), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_reduce_walk_check": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _DP, C.c_int, C.c_double, C.c_double, C.c_double,
+                                              C.POINTER(C.c_uint32), _DP]),
     "frirl_hip_lanes_preferred": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_lanes_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_episode_run_lanes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32,
@@ -185,6 +191,7 @@ SIGNATURES = {
     "frirl_hip_batch_save_rulebases": (C.c_int, [C.c_void_p, C.c_char_p]),
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult)]),
+    "frirl_hip_batch_reduce_all": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_train_merged": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "frirl_hip_merge_rb": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(SenderDesc), C.c_void_p,
@@ -493,6 +500,28 @@ class Problem:
                                             strategy, reward_tolerance, depth, kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res), _stream(stream)),
               "frirl_hip_reduce_shared")
         return kept[: res.rules_after], res
+
+    def reduce_batch(self, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, start_states=None, active=None, stream=None):
+        """frirl_hip_reduce_batch: the rule-base reduction of EVERY rule base of this problem in one run of rounds, agent e replaying
+        from start_states[e] ([E, nant-1] f64, None = agent.values_def); active: [E] uint8 / bool, None = all; rant: [E, nant, maxR]
+        compacted alongside.  Compacts the rule bases in place.  Returns (list of kept original indices, list of ReduceResult)."""
+        import numpy as np
+        import torch
+        dev_ = self.rb.device
+        if start_states is not None:
+            assert start_states.shape == (self.E, self.nant - 1) and start_states.dtype == torch.float64 and start_states.is_contiguous()
+        if active is not None:
+            assert active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous()
+        if rant is not None:
+            assert rant.shape == (self.E, self.nant, self.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
+        nbytes = lib().frirl_hip_reduce_batch_workspace_bytes(self.nant, self.E, self.maxR, depth)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev_)
+        kept = np.zeros((self.E, self.maxR), dtype=np.int32)
+        res = (ReduceResult * self.E)()
+        check(lib().frirl_hip_reduce_batch(C.byref(self.tables), C.byref(self.bases), C.byref(agent.desc), _ptr(rant), _ptr(start_states), _ptr(active),
+                                           strategy, reward_tolerance, depth, kept.ctypes.data_as(C.POINTER(C.c_int32)), res, _ptr(ws), nbytes,
+                                           _stream(stream)), "frirl_hip_reduce_batch")
+        return [kept[e, : res[e].rules_after].copy() for e in range(self.E)], list(res)
 
     def policy_begin(self, agent, rows, obs, reset=None, stream=None):
         """frirl_hip_policy_begin: rows (PolicyRows) selected by `reset` ([Q] uint8 / bool, None = all) start a greedy episode on this ONE

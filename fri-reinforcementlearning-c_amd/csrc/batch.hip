@@ -318,6 +318,26 @@ extern "C" int frirl_hip_batch_reduce(frirl_hip_batch *b, int32_t e, int strateg
     return frirl_hip_reduce_shared(&b->t, &one, &b->agent, b->d_rant + (size_t)e * n * M, strategy, reward_tolerance, depth, nullptr, result, b->s);
 }
 
+extern "C" int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, frirl_hip_reduce_result *results,
+                                          int32_t *agents_reduced)
+{
+    if (!b) { set_error("frirl_hip_batch_reduce_all: NULL batch"); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    std::vector<frirl_hip_reduce_result> res(b->E);
+    const size_t bytes = frirl_hip_reduce_batch_workspace_bytes(b->nant, b->E, b->maxR, depth);
+    void *ws = nullptr;
+    if (bytes) BCHK(hipMalloc(&ws, bytes), "reduction workspace");      // bytes == 0: a bad depth, refused below
+    const int rc = frirl_hip_reduce_batch(&b->t, &b->rb, &b->agent, b->d_rant, b->d_start, nullptr, strategy, reward_tolerance, depth, nullptr, res.data(),
+                                          ws, bytes, b->s);
+    if (ws) (void)hipFree(ws);
+    if (rc) return rc;
+    int32_t n = 0;
+    for (int e = 0; e < b->E; e++) n += res[e].rules_after < res[e].rules_before;
+    if (results) memcpy(results, res.data(), sizeof(frirl_hip_reduce_result) * b->E);
+    if (agents_reduced) *agents_reduced = n;
+    return FRIRL_HIP_OK;
+}
+
 // ---- multi-agent rule-base merge: one round of the reference's many-agent loop (frirl_agent.c:426-462) -------------------
 // (1) every agent id >= 1 takes over the master's (agent 0's) rules -- all receivers in ONE launch; (2) the master takes over the
 // rules of agent 1, 2, ... one after the other (sequential by definition: each merge changes the master).  Agents whose rule base

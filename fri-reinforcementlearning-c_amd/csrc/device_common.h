@@ -145,6 +145,7 @@ int check_device();                       // 0 or FRIRL_HIP_ENODEV
 int check_launch(const char *what);       // hipGetLastError -> code
 int check_tables(const frirl_hip_tables *t);
 int check_rulebases(const frirl_hip_tables *t, const frirl_hip_rulebases *b);
+int check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who);   // shared.hip: env_kind names a demo with t->nant antecedents
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // The library-owned batches switch to their own device; the caller's current device is put back on every exit path.

@@ -6,8 +6,7 @@
 // accumulates its own Shepard sums sequentially -- the reference's summation order (FIVEVagConcl.c:224-235,
 // FIVEVagConcl_FRIRL_BestAct.c:212-217) -- so no reductions are needed.  Compute-bound: ~24 FP64 instructions per
 // (lane, rule, action).
-#include "shared_sweep.h"
-#include "envs.h"
+#include "rollout_episode.h"
 #include "reduce_plan.h"
 #include <algorithm>
 #include <cstdlib>
@@ -58,59 +57,19 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_shared_kernel(const double *
     if (run_if && *run_if == 0u) return;          // the resident form (rollout.hip) has served this call
     __shared__ SharedTile<NANT> tl;
     __shared__ double grid_s[NANT * FRIRL_HIP_MAX_GRID];
-    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
+    const int gl = threadIdx.x % GH;
     const int qi = blockIdx.x * EPB + threadIdx.x / GH;
     const bool exists = qi < Q;
     const int R = nrules[0];
     using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
     POW p;
     if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
-    const int apl = (ag.A + G - 1) / G;                              // actions per lane
-    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
-    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
-    const int nchunks = (apl + AMAX - 1) / AMAX;
-    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
-    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
     const uint32_t mask = (EXCL && exists && ro.exclude_mask) ? ro.exclude_mask[qi] : 0u;
-    double states[NS], cur[NS], qs[NS], q[NS];
-#pragma unroll
-    for (int k = 0; k < NS; k++) {
-        states[k] = (exists && ro.start_states) ? ro.start_states[(size_t)qi * NS + k] : ag.values_def[k];   // frirl_episode.c:46-48
-        q[k] = observe_ve(u, ve, U, k, states[k]);
-    }
-    unsigned h0;
-    int a;
-    double bv;
-    shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, ro.rule_slot, R, maxR, p, abeg, aend, nchunks, q, exists, mask, nullptr, h0, a, bv, h);   // :78 (un-quantised start state)
-    group_first_max<G>(bv, a);
-    a = e_greedy(ag, a, (uint32_t)qi, 0u, 0u);
-    double action = grid_s[NS * FRIRL_HIP_MAX_GRID + a];                                                 // :82
-    int steps = 0, success = 0;
-    double total = 0.0;
-    bool active = exists;
-    for (int step = 1; step <= ag.max_steps; step++) {                                                   // :86
-        if (__syncthreads_count(active ? 1 : 0) == 0) break;                                             // every lane's episode has ended
-        if (active) {
-            double r;
-            env_do_action(ag.env_kind, action, states, cur);                                             // :97
-            env_get_reward(ag.env_kind, cur, r, success);                                                // :106
-            total = total + r;                                                                           // :107
-            env_quantize(ag.env_kind, NS, grid_s, ag.grid_len, ag.grid_div, cur, qs);                    // :112
-#pragma unroll
-            for (int k = 0; k < NS; k++) q[k] = observe_ve(u, ve, U, k, qs[k]);
-        }
-        int pa;
-        shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, ro.rule_slot, R, maxR, p, abeg, aend, nchunks, q, active, mask, nullptr, h0, pa, bv, h);   // :148
-        group_first_max<G>(bv, pa);
-        if (active) {
-            pa = e_greedy(ag, pa, (uint32_t)qi, 0u, (uint32_t)step);
-            action = grid_s[NS * FRIRL_HIP_MAX_GRID + pa];                                               // :151
-#pragma unroll
-            for (int k = 0; k < NS; k++) states[k] = cur[k];                                             // :163-165
-            steps++;                                                                                     // :174
-            if (success == 1) active = false;                                                            // :183
-        }
-    }
+    double states[NS], total;
+    int steps, success;
+    rollout_episode<NANT, AMAX, G, H, EXCL, POW>(tl, grid_s, u, ve, U, rb, ro.rule_slot, R, maxR, ag, p, exists, (uint32_t)qi, mask,
+                                                  ro.start_states ? ro.start_states + (size_t)(exists ? qi : 0) * NS : nullptr, ag.max_steps, steps,
+                                                  total, success, states);
     if (!exists || gl != 0) return;
     ro.steps[qi] = steps;
     ro.reward[qi] = total;
@@ -140,7 +99,7 @@ static int check_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b,
 }
 
 // the roll-outs run the demo dynamics on the device: env_kind must name one of them, with its antecedent count
-static int check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who)
+int frirl_host::check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who)
 {
     if (agent->env_kind < 0 || agent->env_kind > 2 || (agent->env_kind == FRIRL_HIP_ENV_MOUNTAINCAR ? t->nant != 3 : t->nant != 5)) {
         set_error("%s: env_kind %d does not match nant=%d (the demo environments only)", who, agent->env_kind, t->nant);

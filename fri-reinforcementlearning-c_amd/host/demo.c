@@ -21,7 +21,7 @@ int main(int argc, char **argv)
     struct frirl_desc fr = frirl_desc_default;
     const char *env = "mountaincar";
     char name[128];
-    int i, max_episodes = 0, fargc = 0, reduce = 0, agents = 0, gpus = -1, merge = 0;
+    int i, max_episodes = 0, fargc = 0, reduce = 0, agents = 0, gpus = -1, merge = 0, reduce_all = 0;
     const char *load_bin = NULL, *save_bin = NULL;
     char *fargv[16];
     fargv[fargc++] = argv[0];
@@ -34,6 +34,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--load") && i + 1 < argc) load_bin = argv[++i];             /* batched: start from a .frirlrb.bin file */
         else if (!strcmp(argv[i], "--save") && i + 1 < argc) save_bin = argv[++i];             /* batched: all agents' rule bases to one .bin */
         else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) reduce = atoi(argv[++i]);   /* construct, then reduce with strategy 1|2 */
+        else if (!strcmp(argv[i], "--reduce-all")) reduce_all = 1;                              /* with --agents and --reduce: every agent's rule base, not agent 0's alone */
         else if (fargc < 15) fargv[fargc++] = argv[i];
     }
     frirl_parse_cmdline(&fr, fargc, fargv);
@@ -52,6 +53,9 @@ int main(int argc, char **argv)
     if (agents > 0) {
         snprintf(name, sizeof name, "%s.batch.frirlrb.txt", env);
         if (reduce == 1 || reduce == 2) snprintf(name, sizeof name, "%s.batch.reduced%d.frirlrb.txt", env, reduce);
+        if (reduce_all && (reduce == 1 || reduce == 2))
+            return frirl_demo_batch_run_reduce_all(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), reduce, load_bin, save_bin,
+                                                   name, 1) >= 0 ? 0 : 3;
         if (load_bin) return frirl_demo_batch_run_ex(env, agents, 2, reduce, load_bin, save_bin, name, 1) >= 0 ? 0 : 3;
         return frirl_demo_batch_run_ex(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, reduce, NULL, save_bin, name, 1) == agents ? 0 : 3;
     }

@@ -458,8 +458,23 @@ int frirl_demo_multi_merged_run(const char *env, int agents, int gpus, int max_e
     return rounds;
 }
 
+static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
+                          const char *save_bin, const char *out_txt, int verbose);
+
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                             const char *out_txt, int verbose)
+{
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 0, load_bin, save_bin, out_txt, verbose);
+}
+
+int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                    const char *out_txt, int verbose)
+{
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, verbose);
+}
+
+static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
+                          const char *save_bin, const char *out_txt, int verbose)
 {
     int nant = 0, episodes = 0, rc;
     frirl_hip_batch_desc d;
@@ -494,7 +509,22 @@ int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int r
         rc = frirl_hip_batch_save_rulebases(b, save_bin);
         if (rc) five_dropin_fatal("frirl_demo_batch_run(save)", rc);
     }
-    if (reduce_strategy == 1 || reduce_strategy == 2) {
+    if ((reduce_strategy == 1 || reduce_strategy == 2) && reduce_all) {      /* every agent's rule base in one batched run */
+        frirl_hip_reduce_result *rr = malloc(sizeof *rr * (size_t)agents);
+        long long before = 0, after = 0, rollouts = 0;
+        int32_t reduced = 0, rounds = 0;
+        int e;
+        rc = rr ? frirl_hip_batch_reduce_all(b, reduce_strategy, 0.0, 0, rr, &reduced) : FRIRL_HIP_ELAUNCH;
+        if (rc) five_dropin_fatal("frirl_demo_batch_run(reduce all)", rc);
+        for (e = 0; e < agents; e++) {
+            before += rr[e].rules_before; after += rr[e].rules_after; rollouts += rr[e].rollouts;
+            if (rr[e].rounds > rounds) rounds = rr[e].rounds;
+        }
+        if (verbose)
+            printf("batch %s: %d of %d agents reduced, %lld -> %lld rules (strategy %d, %d rounds, %lld replays)\n", env, (int)reduced, agents, before,
+                   after, reduce_strategy, (int)rounds, rollouts);
+        free(rr);
+    } else if (reduce_strategy == 1 || reduce_strategy == 2) {
         frirl_hip_reduce_result rr;
         rc = frirl_hip_batch_reduce(b, 0, reduce_strategy, 0.0, 0, &rr);
         if (rc) five_dropin_fatal("frirl_demo_batch_run(reduce)", rc);

@@ -32,6 +32,10 @@ int frirl_demo_batch_run_reduce(const char *env, int agents, int max_episodes, i
  * (frirl_test_run), then the optional reduction */
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                             const char *out_txt, int verbose);   /* save_bin != NULL: all agents' rule bases (before the reduction) go there */
+/* the same, but the reduction covers EVERY agent's rule base in one batched run (frirl_hip_batch_reduce_all) instead of agent 0's
+ * alone; prints one summary line: agents reduced, rules before -> after summed over the agents, rounds, replays */
+int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                    const char *out_txt, int verbose);
 
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */

@@ -300,6 +300,41 @@ typedef struct frirl_hip_reduce_result {
 int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant, int strategy,
                             double reward_tolerance, int depth, int32_t *kept, frirl_hip_reduce_result *result, void *stream);
 
+/* The same reduction for EVERY rule base of a batch (b->E >= 1) in one run of rounds: per agent e exactly what
+ * frirl_hip_reduce_shared does on agent e's slab with agent->values_def replaced by start_states[e] -- same candidate order, baseline
+ * replay, tree of d_e = min(depth, R0_e - j_e) candidates per round, greedy replays capped at min(max_steps, steps_incremental[e] + 1)
+ * steps (per agent), acceptance test (:212) and compaction (rb columns, rant, uidx if present, nrules[e]; the vacated tail zeroed).
+ * Agents finish after different numbers of rounds and then sit out.  Everything stays on the device: an order kernel ranks every
+ * agent's |Q| once, and a round is three launches over the agents still reducing (slot tables; one replay per tree node, a workgroup
+ * serving rows of ONE agent; tree walk + in-place compaction + the next list of live agents).  Per round the host reads one 16-byte
+ * header; at the end it downloads `results` and `kept`.  The call synchronises `stream` before it returns.  Consequents must be finite
+ * (the loaders and the learner guarantee it): the candidate order of a rule base holding a NaN is undefined.
+ *   b            E rule bases, each compacted in place; nrules[e] in 1..maxR for every active agent (else FRIRL_HIP_EINVAL, nothing reduced)
+ *   rant         [dev] [E][nant][maxR] raw antecedents compacted alongside, or NULL
+ *   start_states [dev] [E][nant-1] start state of every agent's replays, or NULL = agent->values_def for all
+ *   active       [dev] [E] 0 = leave this agent untouched (results[e].rules_before == rules_after == nrules[e]), or NULL = all
+ *   depth        candidates per round, 1..12; 0 = frirl_hip_reduce_batch_depth(b->E, agent->A).  Results never depend on it
+ *   kept         [host] [E][maxR] original index of each surviving rule of agent e (first results[e].rules_after entries), or NULL
+ *   results      [host] [E]
+ *   workspace    [dev] 16-byte aligned, >= frirl_hip_reduce_batch_workspace_bytes(nant, E, maxR, depth) bytes; no other allocation
+ * Demo environments only, nant 3 / 5, as frirl_hip_reduce_shared.  Arguments are checked before the device is looked for.
+ * frirl_hip_reduce_batch_depth: the largest depth in 1..10 whose E * (2^depth - 1) replays per round all stay resident on the chip
+ * in the roll-out kernel's 8-slice shape (CUs x W workgroups x 256 / (G * 8) rows; G = 4 lanes per row and W = 3 for A <= 4, else
+ * G = 8 and W = 1, the kernels' register budgets; 256 CUs are assumed when no device is visible), at least 1: with many agents
+ * speculation is wasted work.
+ * frirl_hip_reduce_batch_workspace_bytes: a multiple of 16, non-decreasing in E, maxR and depth (depth 0: enough for any action
+ * count); 0 for E < 1, maxR < 1 or a depth outside 0..12. */
+int frirl_hip_reduce_batch_depth(int32_t E, int32_t A);
+size_t frirl_hip_reduce_batch_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t depth);
+int frirl_hip_reduce_batch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                           const double *start_states, const uint8_t *active, int strategy, double reward_tolerance, int depth, int32_t *kept,
+                           frirl_hip_reduce_result *results, void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only probe of the tree walk the close-round kernel runs (csrc/reduce_walk.h): d candidates (0..12), steps / reward HOST
+ * [2^d - 1], one entry per node (node (k, bits) = 2^k - 1 + bits); *bits_out = the removals, *prev_out = prev_reward after them.
+ * Needs no device. */
+int frirl_hip_reduce_walk_check(int d, const int32_t *steps, const double *reward, int steps_inc, double prev_reward, double good_above, double tol,
+                                uint32_t *bits_out, double *prev_out);
+
 /* Per-environment episode state (reference: fields of frirl_desc + frirl_reward_desc that
  * frirl_episode() carries from step to step, src/frirl/frirl_episode.c:28-194). */
 typedef struct frirl_hip_envs {
@@ -677,8 +712,15 @@ int frirl_hip_batch_get_rulebase(frirl_hip_batch *b, int32_t e, int32_t *R, doub
 int frirl_hip_batch_save_rulebases(frirl_hip_batch *b, const char *path);
 int frirl_hip_batch_load_rulebases(frirl_hip_batch *b, const char *path, int32_t *records_read);
 /* frirl_sequential_run's reduction phase (frirl_sequential_run.c:170-350) for agent e's rule base, in place, through
- * frirl_hip_reduce_shared (speculative batched try-remove); the other agents are untouched */
+ * frirl_hip_reduce_shared (speculative batched try-remove); the other agents are untouched.  The replays start from
+ * agent.values_def, NOT from the agent's own desc.start_states: use frirl_hip_batch_reduce_all for agents with diversified starts */
 int frirl_hip_batch_reduce(frirl_hip_batch *b, int32_t e, int strategy, double reward_tolerance, int depth, frirl_hip_reduce_result *result);
+/* The reduction phase for EVERY agent of the batch in one run of rounds (frirl_hip_reduce_batch), each agent replaying from its
+ * own desc.start_states row (agent.values_def where the batch has none).  All agents take part, converged or not, as the reference
+ * reduces whatever its construct loop left: an agent whose baseline episode is not good keeps every rule.  The workspace is
+ * allocated and freed inside the call.  results: HOST [E] or NULL; *agents_reduced (or NULL): agents that lost at least one rule. */
+int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, frirl_hip_reduce_result *results,
+                               int32_t *agents_reduced);
 /* One round of the reference's multi-agent rule-base exchange (frirl_omp_run, frirl_agent.c:426-462) inside the batch: every agent
  * id >= 1 takes over the master's (agent 0's) rules -- all of them in one launch of frirl_hip_merge_rb --, then the master takes
  * over the rules of agent 1, 2, ... in turn.  Agents whose rule base is complete do not send (:432,:444).  *full_agents (or NULL):

@@ -2,8 +2,12 @@
 """Evaluation-mode numbers on the three demo rule bases (learned here on the GPU, E = 1):
   * wall time of the speculative try-remove reduction (frirl_hip_reduce_shared), strategies 1 and 2
   * throughput of greedy roll-outs on the shared rule base (frirl_hip_rollout_shared), Q environments
-python tools/reduce_bench.py [--depth 10] [--envs 65536]"""
+python tools/reduce_bench.py [--depth 10] [--envs 65536]
+With --agents E (repeatable) instead: the batched reduction of E learned rule bases (frirl_hip_reduce_batch, every agent from its own
+start state) against a loop of frirl_hip_reduce_shared over the same rule bases with values_def set per agent, mountaincar and acrobot:
+python tools/reduce_bench.py --agents 64 --agents 4096 [--depth 0] [--loop-sample 64] [--reps 2]"""
 import argparse, json, os, sys, time
+import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import torch
 import frirl_amd
@@ -17,12 +21,85 @@ def learned(env, dev):
     return prob, agent, envs
 
 
+def batch_leg(env, E, a, dev):
+    """Host clock around calls that end in a device synchronise (both entry points synchronise before they return); the two sides
+    alternate, rule bases restored from a snapshot before every timed call (outside the window); first repetition = warm-up."""
+    d = frirl_amd.demo_describe(env)
+    ns = d["nstates"]
+    rng = np.random.default_rng(11)
+    start = np.zeros((E, ns))
+    for k in range(ns):
+        g = d["grids"][k]
+        start[:, k] = np.clip(d["values_def"][k] + rng.uniform(-0.1, 0.1, E) * (g.max() - g.min()), g.min(), g.max())
+        start[0, k] = d["values_def"][k]
+    ss = torch.from_numpy(np.ascontiguousarray(start)).to(dev)
+    prob, agent, envs = frirl_amd.demo_fresh_batch(env, E, 512, dev, start_states=ss)
+    run = frirl_amd.train_persistent(prob, agent, envs, max_episodes=400)
+    torch.cuda.synchronize()
+    snap = [t.clone() for t in (prob.rb, prob.nrules, prob.uidx, envs.rant)]
+
+    def restore():
+        for t, t0 in zip((prob.rb, prob.nrules, prob.uidx, envs.rant), snap):
+            t.copy_(t0)
+        torch.cuda.synchronize()
+
+    nr0 = snap[1].cpu().numpy()
+    depth = a.depth or frirl_amd.lib().frirl_hip_reduce_batch_depth(E, d["A"])
+    # the loop's side: one-base views of the same slabs, built outside the timed window; all agents, or an evenly spaced sample
+    # (--loop-sample 0: the batched side alone, for depth sweeps)
+    sample = list(range(E)) if 0 < a.loop_sample >= E else [int(i) for i in np.linspace(0, E - 1, a.loop_sample).astype(int)]
+    views = [frirl_amd.Problem(prob.u, prob.ve, prob.rb[e:e + 1], prob.nrules[e:e + 1], prob.uidx[e:e + 1]) for e in sample]
+    out = {"env": env, "agents": E, "converged": int((run.conv.converged == 1).sum()), "rules_before_sum": int(nr0.sum()), "depth": depth,
+           "loop_depth": a.depth or 10, "loop_agents_timed": len(sample), "batch_s": [], "loop_s": []}
+    for strategy in (1,):
+        for rep in range(a.reps + 1):
+            restore()
+            t0 = time.perf_counter()
+            kept, res = prob.reduce_batch(agent, strategy, 0.0, a.depth, rant=envs.rant, start_states=ss)
+            dt_b = time.perf_counter() - t0
+            after_b = np.array([r.rules_after for r in res])
+            restore()
+            after_l = []
+            t0 = time.perf_counter()
+            for e, view in zip(sample, views):
+                for k in range(ns):
+                    agent.desc.values_def[k] = float(start[e, k])
+                _, r1 = view.reduce_shared(agent, strategy, 0.0, a.depth, rant=envs.rant[e])
+                after_l.append(r1.rules_after)
+            dt_l = time.perf_counter() - t0
+            for k in range(ns):
+                agent.desc.values_def[k] = float(d["values_def"][k])
+            assert (after_b[sample] == np.array(after_l)).all(), "batched and single-base reductions disagree"
+            if rep:                                                  # rep 0 warms both sides up
+                out["batch_s"].append(round(dt_b, 4))
+                if sample:
+                    out["loop_s"].append(round(dt_l, 4))
+        out.update(strategy=strategy, rules_after_sum=int(after_b.sum()), rounds_max=max(r.rounds for r in res), rollouts_sum=int(sum(r.rollouts for r in res)))
+    if sample:
+        scale = E / len(sample)
+        out["loop_s_all_agents"] = [round(x * scale, 4) for x in out["loop_s"]]
+        out["loop_extrapolated"] = len(sample) < E
+        out["speedup_min_over_min"] = round(min(out["loop_s_all_agents"]) / min(out["batch_s"]), 2)
+    else:
+        del out["loop_s"], out["loop_depth"]
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--depth", type=int, default=0)
     ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--agents", type=int, action="append", default=[])
+    ap.add_argument("--loop-sample", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--only", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.agents:
+        for env in ([a.only] if a.only else ["mountaincar", "acrobot"]):
+            for E in a.agents:
+                batch_leg(env, E, a, dev)
+        return
     for env in ("mountaincar", "cartpole", "acrobot"):
         prob, agent, envs = learned(env, dev)
         R = int(prob.nrules[0])
