@@ -85,6 +85,13 @@ class PolicyRowsDesc(C.Structure):
                 ("exclude_mask", C.c_void_p), ("rule_slot", C.c_void_p)]
 
 
+class PolicyBatchRowsDesc(C.Structure):
+    """struct frirl_hip_policy_batch_rows (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("done", C.c_void_p), ("ep_steps", C.c_void_p), ("success", C.c_void_p), ("ep_reward", C.c_void_p),
+                ("row_count", C.c_void_p), ("step_cap", C.c_void_p), ("agents", C.c_void_p), ("nagents", C.c_int32),
+                ("exclude_mask", C.c_void_p), ("rule_slot", C.c_void_p), ("rows_live", C.c_void_p)]
+
+
 class ConvergenceDesc(C.Structure):
     """struct frirl_hip_convergence (include/frirl_hip.h)."""
     _fields_ = [("prev_nrules", C.c_void_p), ("prev_steps", C.c_void_p), ("prev_reward", C.c_void_p), ("prev_rconc", C.c_void_p),
@@ -175,6 +182,19 @@ SIGNATURES = {
     "frirl_hip_reducer_end_round": (C.c_int, [C.c_void_p]),
     "frirl_hip_reducer_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReduceResult)]),
     "frirl_hip_reducer_destroy": (None, [C.c_void_p]),
+    "frirl_hip_policy_batch_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyBatchRowsDesc),
+                                               C.POINTER(AgentIO), C.c_void_p]),
+    "frirl_hip_policy_batch_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyBatchRowsDesc),
+                                                 C.POINTER(AgentIO), C.c_void_p]),
+    "frirl_hip_batch_reducer_create": (C.c_void_p, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_double, C.c_int, C.c_void_p]),
+    "frirl_hip_batch_reducer_next_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_reducer_begin": (C.c_int, [C.c_void_p, C.POINTER(AgentIO)]),
+    "frirl_hip_batch_reducer_observe": (C.c_int, [C.c_void_p, C.POINTER(AgentIO), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_reducer_end_round": (C.c_int, [C.c_void_p]),
+    "frirl_hip_batch_reducer_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReduceResult)]),
+    "frirl_hip_batch_reducer_row_done": (C.c_void_p, [C.c_void_p]),
+    "frirl_hip_batch_reducer_destroy": (None, [C.c_void_p]),
     "frirl_hip_episode_run": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_int32, C.c_void_p]),
     "frirl_hip_convergence_init": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(ConvergenceDesc), C.c_void_p]),
     "frirl_hip_convergence_update": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
@@ -540,6 +560,23 @@ class Problem:
                                              _stream(stream)), "frirl_hip_policy_observe")
         return action, action_idx
 
+    def policy_batch_begin(self, agent, rows, obs, reset=None, out=None, stream=None):
+        """frirl_hip_policy_batch_begin: rows (PolicyBatchRows; row q on the rule base of agent q // rows.n) selected by `reset` start a
+        greedy episode from the caller's observations obs [E * n, nant-1].  Returns (action values, action indices); rows that were not
+        restarted are not written (out: the caller's (action, action_idx) tensors to write into).  Does not synchronise."""
+        io, action, action_idx = _agent_io(self, obs, reset=reset, E=rows.Q, out=out)
+        check(lib().frirl_hip_policy_batch_begin(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(rows.desc), C.byref(io),
+                                                 _stream(stream)), "frirl_hip_policy_batch_begin")
+        return action, action_idx
+
+    def policy_batch_observe(self, agent, rows, obs, reward, success, q_obs=None, out=None, stream=None):
+        """frirl_hip_policy_batch_observe: one greedy step of every row that is not done (as policy_observe, every agent on its own rule
+        base).  Returns (action values, action indices); rows that were done are not written."""
+        io, action, action_idx = _agent_io(self, obs, q_obs, reward, success, E=rows.Q, out=out)
+        check(lib().frirl_hip_policy_batch_observe(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(rows.desc), C.byref(io),
+                                                   _stream(stream)), "frirl_hip_policy_batch_observe")
+        return action, action_idx
+
     def merge_rb(self, agent, sndr_rant, sndr_rconc, weights, rant_store=None, active=None, stream=None):
         """frirl_hip_merge_rb: every (active) rule base of this batch takes over the sender rules sndr_rant [S][nant] (AoS),
         sndr_rconc [S]; weights [E][maxR] persists between calls (zeros at first).  Returns full [E] int32."""
@@ -721,6 +758,102 @@ class PolicyRows:
                                    _ptr(exclude_mask), _ptr(rule_slot))
 
 
+class PolicyBatchRows:
+    """Device-resident per-row episode state of caller-stepped roll-outs on EVERY agent's own rule base (struct
+    frirl_hip_policy_batch_rows): E * n rows, row q belongs to agent q // n.  row_count / step_cap / agents: int32 tensors or None;
+    exclude_mask [E * n] int32 with rule_slot [E, maxR] uint8; rows_live: [1] int32 the calls add the rows still running to."""
+
+    def __init__(self, E, n, device, row_count=None, step_cap=None, agents=None, exclude_mask=None, rule_slot=None, rows_live=None):
+        import torch
+        self.E, self.n, self.Q = E, n, E * n
+        Q = self.Q
+        self.done = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.ep_steps = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.success = torch.zeros((Q,), dtype=torch.int32, device=device)
+        self.ep_reward = torch.zeros((Q,), dtype=torch.float64, device=device)
+        for x, shape in ((row_count, (E,)), (step_cap, (E,)), (rows_live, (1,)), (exclude_mask, (Q,))):
+            assert x is None or (x.dtype == torch.int32 and x.shape == shape and x.is_contiguous())
+        assert agents is None or (agents.dtype == torch.int32 and agents.dim() == 1 and agents.is_contiguous())
+        if exclude_mask is not None:
+            assert rule_slot.dtype == torch.uint8 and rule_slot.is_contiguous() and rule_slot.shape[0] == E
+        self.row_count, self.step_cap, self.agents, self.rows_live = row_count, step_cap, agents, rows_live
+        self.exclude_mask, self.rule_slot = exclude_mask, rule_slot
+        self.desc = PolicyBatchRowsDesc(n, self.done.data_ptr(), self.ep_steps.data_ptr(), self.success.data_ptr(), self.ep_reward.data_ptr(),
+                                        _ptr(row_count), _ptr(step_cap), _ptr(agents), 0 if agents is None else agents.numel(),
+                                        _ptr(exclude_mask), _ptr(rule_slot), _ptr(rows_live))
+
+
+class BatchReducer:
+    """frirl_hip_batch_reducer: the rule-base reduction of EVERY rule base of `problem` with the caller's environment, round by round."""
+
+    def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None, stream=None):
+        import torch
+        if rant is not None:
+            assert rant.shape == (problem.E, problem.nant, problem.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
+        if active is not None:
+            assert active.shape == (problem.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous()
+        self.problem, self._keep = problem, (rant, active, agent)
+        self.h = lib().frirl_hip_batch_reducer_create(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _ptr(rant), _ptr(active),
+                                                      strategy, reward_tolerance, depth, _stream(stream))
+        if not self.h:
+            raise FrirlHipError(f"frirl_hip_batch_reducer_create: {lib().frirl_hip_last_error().decode()}")
+        self.Q = self.rows_per_agent = self.agents_live = 0
+
+    def next_round(self):
+        """Rows of the next round: E rows in round 0 (the baseline replays), then E * (2^depth - 1); 0 = finished.  Row q belongs to
+        agent q // rows_per_agent."""
+        q, n, live = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().frirl_hip_batch_reducer_next_round(self.h, C.byref(q), C.byref(n), C.byref(live)), "frirl_hip_batch_reducer_next_round")
+        self.Q, self.rows_per_agent, self.agents_live = q.value, n.value, live.value
+        return q.value
+
+    def begin(self, obs):
+        import torch
+        out = (torch.zeros((self.Q,), dtype=torch.float64, device=obs.device), torch.zeros((self.Q,), dtype=torch.int32, device=obs.device))
+        io, action, action_idx = _agent_io(self.problem, obs, E=self.Q, out=out)       # rows that are never stepped hold action 0.0
+        check(lib().frirl_hip_batch_reducer_begin(self.h, C.byref(io)), "frirl_hip_batch_reducer_begin")
+        self._out = (action, action_idx)
+        return action, action_idx
+
+    def observe(self, obs, reward, success, q_obs=None, count_live=True):
+        """Returns (action values, action indices, rows still live or None when count_live is False: no synchronisation).  The
+        action tensors are those begin returned, updated in place: rows whose replay has ended keep their last action."""
+        io, action, action_idx = _agent_io(self.problem, obs, q_obs, reward, success, E=self.Q, out=getattr(self, "_out", None))
+        live = C.c_int32()
+        check(lib().frirl_hip_batch_reducer_observe(self.h, C.byref(io), C.byref(live) if count_live else None), "frirl_hip_batch_reducer_observe")
+        return action, action_idx, (live.value if count_live else None)
+
+    def end_round(self):
+        check(lib().frirl_hip_batch_reducer_end_round(self.h), "frirl_hip_batch_reducer_end_round")
+
+    def row_done(self):
+        """[Q] int32 view of the reducer's own `done` array: 1 = the caller need not step this row."""
+        import torch
+        if self.Q == 0:
+            return torch.zeros((0,), dtype=torch.int32, device=self.problem.rb.device)
+        iface = {"shape": (self.Q,), "typestr": "<i4", "data": (lib().frirl_hip_batch_reducer_row_done(self.h), False), "version": 2}
+        holder = type("_DevArray", (), {"__cuda_array_interface__": iface})()
+        return torch.as_tensor(holder, device=self.problem.rb.device)
+
+    def result(self):
+        """(list of kept original indices, list of ReduceResult) so far; between rounds only."""
+        import numpy as np
+        E = self.problem.E
+        kept = np.zeros((E, self.problem.maxR), dtype=np.int32)
+        res = (ReduceResult * E)()
+        check(lib().frirl_hip_batch_reducer_result(self.h, kept.ctypes.data_as(C.POINTER(C.c_int32)), res), "frirl_hip_batch_reducer_result")
+        return [kept[e, : res[e].rules_after].copy() for e in range(E)], list(res)
+
+    def close(self):
+        if self.h:
+            lib().frirl_hip_batch_reducer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            self.close()
+
+
 class Reducer:
     """frirl_hip_reducer: the rule-base reduction of ONE rule base (problem.E == 1) with the caller's environment, round by round."""
 
@@ -784,6 +917,28 @@ def reduce_external(problem, agent, reset_fn, step_fn, strategy, reward_toleranc
     try:
         while red.next_round() > 0:
             states = reset_fn(red.Q).contiguous()
+            action, _ = red.begin(states)
+            live = red.Q
+            while live > 0:
+                out = step_fn(states, action)
+                obs, reward, success = out[0].contiguous(), out[1].contiguous(), out[2].to(torch.int32).contiguous()
+                nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
+                states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
+            red.end_round()
+        return red.result()
+    finally:
+        red.close()
+
+
+def reduce_external_batch(problem, agent, reset_fn, step_fn, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None):
+    """The batched reduction's round loop with the caller's environment, every rule base of `problem` at once:
+    reset_fn(Q, rows_per_agent) -> obs [Q, nant-1] with agent q // rows_per_agent's start state in row q; step_fn as for
+    reduce_external.  Returns (list of kept original indices, list of ReduceResult), as Problem.reduce_batch; compacts in place."""
+    import torch
+    red = BatchReducer(problem, agent, strategy, reward_tolerance, depth, rant, active)
+    try:
+        while red.next_round() > 0:
+            states = reset_fn(red.Q, red.rows_per_agent).contiguous()
             action, _ = red.begin(states)
             live = red.Q
             while live > 0:

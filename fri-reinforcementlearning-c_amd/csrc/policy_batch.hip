@@ -1,0 +1,304 @@
+// policy_batch.hip -- EVERY agent's own rule base in the caller's environment: frirl_hip_policy_batch_begin / _observe (one greedy step
+// of E * n caller-stepped rows, row q on the rule base of agent q / n) and the resumable batched reduction frirl_hip_batch_reducer_* on
+// top of them (include/frirl_hip.h).  The step kernels are policy_batch_kernel.h, instantiated per antecedent count in
+// policy_batch_i<N>.hip; the order, open, close and result kernels and the workspace are those of frirl_hip_reduce_batch
+// (reduce_batch_kernels.h).  A round of the reducer is: the caller's begin / observe loop, every step ONE launch over the rows of the
+// agents still reducing, then close (tree walk + compaction) and the next round's open kernel.  The host reads the 16-byte header
+// only: live agents of the next round, rows still live.
+#include "policy_batch_kernel.h"
+#include "reduce_batch_kernels.h"
+#include <new>
+
+#define FRIRL_POLICY_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
+#define M(N) void frirl_policy_batch_launch_##N(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
+                                                const frirl::PolicyBatchArgs *pa, const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s);
+FRIRL_POLICY_NANT_CASES(M)
+#undef M
+
+// Rule slices per conclusion.  The lanes per row are fixed by the action count (rb_group: 4 for up to 4 actions, else 8; the option
+// "policy_group" can name no other); "policy_slices" = 1 / 4 / 8 forces H.  Otherwise one row per agent (the baseline replay) takes a
+// full wave per row, and trees take the rule of frirl_hip_reduce_batch (rb_slices: 8 while every row stays resident, else 4, else 1).
+static int policy_batch_slices(long rows, int n, int A)
+{
+    { const int v = opts().policy_slices; if (v == 1 || v == 4 || v == 8) return v; }
+    if (n == 1) return FRIRL_WAVE / rb_group(A);
+    return rb_slices(rows, A);
+}
+
+static int check_policy_batch_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const char *who)
+{
+    if (!t || t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t ? t->nant : 0); return FRIRL_HIP_EINVAL; }
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    if (!a || !a->grid_values || !a->action_ve) { set_error("%s: NULL agent / grid_values / action_ve", who); return FRIRL_HIP_EINVAL; }
+    if (a->A < 1 || a->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, a->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
+    for (int k = 0; k < t->nant; k++)
+        if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    if (a->grid_len[t->nant - 1] != a->A) { set_error("%s: the action grid has %d values, A=%d", who, a->grid_len[t->nant - 1], a->A); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+static int check_policy_batch_io(const frirl_hip_agent_io *io, bool begin, const char *who)
+{
+    if (!io || !io->obs || !io->action_out) { set_error("%s: NULL io / io->obs / io->action_out", who); return FRIRL_HIP_EINVAL; }
+    if (!begin && (!io->reward || !io->success)) { set_error("%s: NULL io->reward / io->success", who); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+static void policy_batch_launch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl::PolicyBatchArgs *pa,
+                                const frirl_hip_agent_io *io, int begin, int nlist, hipStream_t s)
+{
+    const int H = policy_batch_slices((long)nlist * pa->rows.n, pa->rows.n, agent->A);
+    switch (t->nant) {
+#define M(N) case N: frirl_policy_batch_launch_##N(t, b, agent, pa, io, begin, nlist, H, s); break;
+        FRIRL_POLICY_NANT_CASES(M)
+#undef M
+    }
+}
+
+static int policy_batch_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_policy_batch_rows *rows,
+                             const frirl_hip_agent_io *io, void *stream, bool begin, const char *who)
+{
+    int rc = check_policy_batch_args(t, b, agent, who);
+    if (rc) return rc;
+    if (!rows || !rows->done || !rows->ep_steps || !rows->success || !rows->ep_reward) { set_error("%s: NULL row state", who); return FRIRL_HIP_EINVAL; }
+    if (rows->n < 1 || (long)rows->n * b->E > 0x7fffffffL) { set_error("%s: n=%d < 1 or E * n beyond 2^31 - 1", who, rows->n); return FRIRL_HIP_EINVAL; }
+    if ((rows->exclude_mask == nullptr) != (rows->rule_slot == nullptr)) { set_error("%s: exclude_mask and rule_slot go together", who); return FRIRL_HIP_EINVAL; }
+    if (rows->agents && (rows->nagents < 1 || rows->nagents > b->E)) { set_error("%s: nagents=%d outside 1..E=%d", who, rows->nagents, b->E); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_policy_batch_io(io, begin, who)) || (rc = check_device())) return rc;
+    frirl::PolicyBatchArgs pa = {};
+    pa.rows = *rows;
+    pa.list = rows->agents;
+    pa.E = b->E;
+    pa.state_stride = rows->n;
+    policy_batch_launch(t, b, agent, &pa, io, begin ? 1 : 0, rows->agents ? rows->nagents : b->E, as_stream(stream));
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_policy_batch_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                            const frirl_hip_policy_batch_rows *rows, const frirl_hip_agent_io *io, void *stream)
+{
+    return policy_batch_call(t, b, agent, rows, io, stream, true, "frirl_hip_policy_batch_begin");
+}
+
+extern "C" int frirl_hip_policy_batch_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                              const frirl_hip_policy_batch_rows *rows, const frirl_hip_agent_io *io, void *stream)
+{
+    return policy_batch_call(t, b, agent, rows, io, stream, false, "frirl_hip_policy_batch_observe");
+}
+
+// ---- the batched reduction with the caller's environment -------------------------------------------------------------------
+namespace frirl {
+__global__ void policy_batch_fill_kernel(int32_t *__restrict__ x, int n, int32_t v)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = v;
+}
+}  // namespace frirl
+
+struct frirl_hip_batch_reducer {
+    enum State { IDLE, OPEN, RUNNING };       // between rounds; next_round called; begin called
+    frirl_hip_tables t;
+    frirl_hip_rulebases b;
+    frirl_hip_agent agent;                    // greedy copy (no_random = 1)
+    double *rant = nullptr;
+    double reward_good_above = 0.0, reward_tolerance = 0.0;
+    int depth = 0, nodes = 0;
+    hipStream_t s = nullptr;
+    void *d_ws = nullptr, *d_done = nullptr, *d_success = nullptr;
+    ReduceBatchWs ws;
+    int32_t hdr[4] = {0, 0, 0, 0};            // host copy of ws.hdr: live agents of even / odd rounds, bad agent + 1, rows live
+    int round = 0;                            // round 0 = the baseline replays
+    State state = IDLE;
+    int n = 0, Q = 0;                         // rows per agent and rows of the open round
+    bool live_known = false;                  // hdr[3] holds the rows still live after the last launch
+
+    ~frirl_hip_batch_reducer()
+    {
+        for (void *p : {d_ws, d_done, d_success}) if (p) (void)hipFree(p);
+    }
+    int cur() const { return round & 1; }
+    frirl::PolicyBatchArgs args() const
+    {
+        frirl::PolicyBatchArgs pa = {};
+        pa.rows.n = n;
+        pa.rows.done = static_cast<int32_t *>(d_done);
+        pa.rows.success = static_cast<int32_t *>(d_success);
+        pa.rows.ep_steps = ws.steps;          // the arrays the close kernel reads: a round ends without a copy
+        pa.rows.ep_reward = ws.reward;
+        pa.rows.step_cap = ws.cap;
+        pa.rows.rows_live = ws.hdr + 3;
+        if (round > 0) {
+            pa.rows.exclude_mask = ws.mask;
+            pa.rows.rule_slot = ws.slot;
+            pa.depth_of = ws.d;
+            pa.mask_by_node = 1;
+        }
+        pa.list = ws.live[cur()];
+        pa.E = b.E;
+        pa.state_stride = ws.nodes;
+        return pa;
+    }
+};
+
+#define BR_TRY(expr, fail)                                                                                         \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); fail; }                \
+    } while (0)
+
+// the 16-byte header to the host; synchronises
+static int batch_reducer_header(frirl_hip_batch_reducer *r, const char *who)
+{
+    BR_TRY(hipMemcpyAsync(r->hdr, r->ws.hdr, sizeof r->hdr, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
+    BR_TRY(hipStreamSynchronize(r->s), return FRIRL_HIP_ELAUNCH);
+    return FRIRL_HIP_OK;
+}
+
+extern "C" frirl_hip_batch_reducer *frirl_hip_batch_reducer_create(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                                                   double *rant, const uint8_t *active, int strategy, double reward_tolerance, int depth,
+                                                                   void *stream)
+{
+    const char *who = "frirl_hip_batch_reducer_create";
+    if (check_policy_batch_args(t, b, agent, who)) return nullptr;
+    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return nullptr; }
+    if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return nullptr; }
+    if (agent->max_steps < 0) { set_error("%s: max_steps=%d < 0", who, agent->max_steps); return nullptr; }
+    if (depth == 0) depth = frirl_hip_reduce_batch_depth(b->E, agent->A);
+    const size_t E = (size_t)b->E, M = (size_t)b->maxR;
+    const int nodes = frirl::rw_nodes(depth);
+    if (E * (size_t)nodes > 0x7fffffffu) { set_error("%s: E=%d agents x %d rows per round beyond 2^31 - 1", who, b->E, nodes); return nullptr; }
+    if (check_device()) return nullptr;
+    frirl_hip_batch_reducer *r = new (std::nothrow) frirl_hip_batch_reducer;
+    if (!r) { set_error("%s: out of memory", who); return nullptr; }
+    r->t = *t; r->b = *b; r->agent = *agent;
+    r->agent.no_random = 1;                                           // the replays are greedy (reduction_state == 1)
+    r->rant = rant;
+    r->reward_good_above = agent->reward_good_above;
+    r->reward_tolerance = reward_tolerance;
+    r->depth = depth;
+    r->nodes = nodes;
+    r->s = as_stream(stream);
+    const size_t need = reduce_batch_layout(nullptr, E, M, depth, E * nodes, nullptr);
+    if (hipMalloc(&r->d_ws, need) != hipSuccess || hipMalloc(&r->d_done, sizeof(int32_t) * E * nodes) != hipSuccess ||
+        hipMalloc(&r->d_success, sizeof(int32_t) * E * nodes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: hipMalloc failed", who);
+        delete r;
+        return nullptr;
+    }
+    reduce_batch_layout(static_cast<char *>(r->d_ws), E, M, depth, E * nodes, &r->ws);
+    BR_TRY(hipMemsetAsync(r->ws.hdr, 0, sizeof r->hdr, r->s), { delete r; return nullptr; });
+    hipLaunchKernelGGL(frirl::reduce_batch_order_kernel, dim3((unsigned)E), dim3(256), 0, r->s, b->rb, b->nrules, t->nant, b->maxR, active, strategy,
+                       r->agent.max_steps, r->ws);
+    if (batch_reducer_header(r, who) || check_launch(who)) { delete r; return nullptr; }
+    if (r->hdr[2]) {
+        set_error("%s: agent %d: nrules outside 1..maxR=%d", who, r->hdr[2] - 1, b->maxR);
+        delete r;
+        return nullptr;
+    }
+    return r;
+}
+
+extern "C" void frirl_hip_batch_reducer_destroy(frirl_hip_batch_reducer *r) { delete r; }
+
+extern "C" int frirl_hip_batch_reducer_next_round(frirl_hip_batch_reducer *r, int32_t *Q, int32_t *rows_per_agent, int32_t *agents_live)
+{
+    const char *who = "frirl_hip_batch_reducer_next_round";
+    if (!r || !Q) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if (r->state != frirl_hip_batch_reducer::IDLE) { set_error("%s: the previous round has not been closed (frirl_hip_batch_reducer_end_round)", who); return FRIRL_HIP_EINVAL; }
+    const int nlive = r->hdr[r->cur()];
+    const int n = nlive == 0 ? 0 : (r->round == 0 ? 1 : r->nodes);
+    if (nlive > 0) {                                                  // rows of agents that sit out, and nodes that do not exist, stay done
+        const int q = r->b.E * n;
+        hipLaunchKernelGGL(frirl::policy_batch_fill_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, r->s, static_cast<int32_t *>(r->d_done), q, 1);
+        const int rc = check_launch(who);
+        if (rc) return rc;
+        r->state = frirl_hip_batch_reducer::OPEN;
+    }
+    r->n = n;
+    *Q = r->Q = r->b.E * n;
+    if (rows_per_agent) *rows_per_agent = n;
+    if (agents_live) *agents_live = nlive;
+    return FRIRL_HIP_OK;
+}
+
+static int batch_reducer_step(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io, int begin, const char *who)
+{
+    BR_TRY(hipMemsetAsync(r->ws.hdr + 3, 0, sizeof(int32_t), r->s), return FRIRL_HIP_ELAUNCH);
+    const frirl::PolicyBatchArgs pa = r->args();
+    policy_batch_launch(&r->t, &r->b, &r->agent, &pa, io, begin, r->hdr[r->cur()], r->s);
+    r->live_known = false;
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_batch_reducer_begin(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io)
+{
+    const char *who = "frirl_hip_batch_reducer_begin";
+    if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
+    if (r->state != frirl_hip_batch_reducer::OPEN) { set_error("%s: no open round (frirl_hip_batch_reducer_next_round first; one begin per round)", who); return FRIRL_HIP_EINVAL; }
+    int rc = check_policy_batch_io(io, true, who);
+    if (rc) return rc;
+    frirl_hip_agent_io all = *io;
+    all.reset = nullptr;                                              // every row of the round starts
+    if ((rc = batch_reducer_step(r, &all, 1, who))) return rc;
+    r->state = frirl_hip_batch_reducer::RUNNING;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_reducer_observe(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io, int32_t *rows_live)
+{
+    const char *who = "frirl_hip_batch_reducer_observe";
+    if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
+    if (r->state != frirl_hip_batch_reducer::RUNNING) { set_error("%s: no running round (frirl_hip_batch_reducer_begin first)", who); return FRIRL_HIP_EINVAL; }
+    int rc = check_policy_batch_io(io, false, who);
+    if (rc || (rc = batch_reducer_step(r, io, 0, who)) || !rows_live) return rc;
+    if ((rc = batch_reducer_header(r, who))) return rc;
+    r->live_known = true;
+    *rows_live = r->hdr[3];
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_reducer_end_round(frirl_hip_batch_reducer *r)
+{
+    const char *who = "frirl_hip_batch_reducer_end_round";
+    if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
+    if (r->state != frirl_hip_batch_reducer::RUNNING) { set_error("%s: no running round", who); return FRIRL_HIP_EINVAL; }
+    int rc;
+    if (!r->live_known) {
+        if ((rc = batch_reducer_header(r, who))) return rc;
+        r->live_known = true;
+    }
+    if (r->hdr[3] > 0) { set_error("%s: %d of %d replays have not ended", who, r->hdr[3], r->Q); return FRIRL_HIP_EINVAL; }
+    const int cur = r->cur(), first = r->round == 0, nlive = r->hdr[cur];
+    switch (r->t.nant) {
+#define M(N) case N: hipLaunchKernelGGL(frirl::reduce_batch_close_kernel<N>, dim3(nlive), dim3(256), 0, r->s, r->b.rb, r->b.nrules, r->b.uidx, r->rant, \
+                                        r->b.maxR, cur, first, r->agent.max_steps, r->reward_good_above, r->reward_tolerance, r->ws); break;
+        FRIRL_POLICY_NANT_CASES(M)
+#undef M
+    }
+    if ((rc = batch_reducer_header(r, who))) return rc;               // the next round's live count
+    r->round += 1;
+    r->state = frirl_hip_batch_reducer::IDLE;
+    const int next = r->hdr[r->cur()];
+    if (next > 0) hipLaunchKernelGGL(frirl::reduce_batch_open_kernel, dim3(next), dim3(256), 0, r->s, r->b.nrules, r->b.maxR, r->depth, r->cur(), r->ws);
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_batch_reducer_result(frirl_hip_batch_reducer *r, int32_t *kept, frirl_hip_reduce_result *results)
+{
+    const char *who = "frirl_hip_batch_reducer_result";
+    if (!r || !results) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if (r->state != frirl_hip_batch_reducer::IDLE) { set_error("%s: a round is open (frirl_hip_batch_reducer_end_round first)", who); return FRIRL_HIP_EINVAL; }
+    const size_t E = (size_t)r->b.E, M = (size_t)r->b.maxR;
+    hipLaunchKernelGGL(frirl::reduce_batch_result_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, r->s, r->b.nrules, (int)E, r->ws);
+    BR_TRY(hipMemcpyAsync(results, r->ws.res, sizeof(frirl_hip_reduce_result) * E, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
+    if (kept) BR_TRY(hipMemcpyAsync(kept, r->ws.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
+    BR_TRY(hipStreamSynchronize(r->s), return FRIRL_HIP_ELAUNCH);
+    return check_launch(who);
+}
+
+extern "C" const int32_t *frirl_hip_batch_reducer_row_done(const frirl_hip_batch_reducer *r)
+{
+    return r ? static_cast<const int32_t *>(r->d_done) : nullptr;
+}

@@ -1,0 +1,166 @@
+// policy_batch_kernel.h -- one greedy step of caller-stepped rows that belong to E DIFFERENT rule bases: policy_step_kernel
+// (policy_kernel.h) with the agent taken from the workgroup index, the way reduce_batch_rollout_kernel (reduce_batch.hip) takes it.
+// Row q = e * n + node is row `node` of agent e: it sweeps agent e's slab with agent e's slot table and step cap.  The step itself --
+// observation handling, sweep, first maximum, epsilon-greedy, bookkeeping -- is policy_step_kernel's (frirl_episode.c:28-194 with
+// reduction_state == 1).  Instantiated per antecedent count in policy_batch_i<N>.hip.
+#pragma once
+#include "shared_sweep.h"
+#include "envs.h"
+#include "reduce_walk.h"
+#include <type_traits>
+
+namespace frirl {
+
+// what the kernel needs beyond the public row description: frirl_hip_policy_batch_begin / _observe fill it from the caller's struct,
+// the batched reducer (policy_batch.hip) from its ReduceBatchWs
+struct PolicyBatchArgs {
+    frirl_hip_policy_batch_rows rows;
+    const int32_t *list;          // [dev] agents served by the launch, one per `wpa` workgroups (rows.agents or a live list); NULL = 0..
+    const int32_t *depth_of;      // [dev] [E] or NULL: agent e has the 2^depth_of[e] - 1 rows of its tree (instead of rows.row_count)
+    int32_t E;                    // rule bases: entries of `list` outside 0..E-1 are skipped
+    int32_t state_stride;         // ep_steps / ep_reward of row (e, node) sit at e * state_stride + node (the reducer: its tree size)
+    int32_t mask_by_node;         // != 0: exclude_mask is indexed by node (one table for every agent) instead of by row
+};
+
+// begin / observe as policy_step_kernel.  `wpa` workgroups per served agent, each with 256 / (G * H) rows of that agent only, so
+// everything in front of a barrier depends on the agent and on the workgroup's first row alone.  Rows node >= n_e do not exist:
+// nothing of theirs is read or written.  After the step the rows of the workgroup that are not done are counted into
+// *rows.rows_live: one integer atomic per workgroup.
+template <int NANT, int AMAX, int G, int H, bool EXCL, bool PN = true>
+__global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
+                                                                      const double *__restrict__ rb_all, const int32_t *__restrict__ nrules, int maxR,
+                                                                      const frirl_hip_agent ag, const PolicyBatchArgs pa,
+                                                                      const frirl_hip_agent_io io, int begin, int wpa)
+{
+    constexpr int NS = NANT - 1, GH = G * H, EPB = SH_BLOCK / GH;
+    __shared__ SharedTile<NANT> tl;
+    const frirl_hip_policy_batch_rows &rows = pa.rows;
+    const int slot_ix = blockIdx.x / wpa;
+    const int e = pa.list ? pa.list[slot_ix] : slot_ix;
+    if (e < 0 || e >= pa.E) return;                                  // uniform: not an agent of this batch
+    const int row0 = (blockIdx.x % wpa) * EPB;
+    const int n = rows.n;
+    int ne = pa.depth_of ? rw_nodes(pa.depth_of[e]) : (rows.row_count ? rows.row_count[e] : n);
+    ne = ne < 0 ? 0 : (ne > n ? n : ne);
+    if (row0 >= ne) return;                                          // the whole workgroup, before the first barrier
+    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
+    const int node = row0 + threadIdx.x / GH;
+    const bool exists = node < ne;
+    const size_t qi = (size_t)e * n + node, si = (size_t)e * pa.state_stride + node;
+    const bool live = exists && (begin ? (!io.reset || io.reset[qi] != 0) : rows.done[qi] == 0);
+    if (__syncthreads_count(live ? 1 : 0) == 0) {                    // no row of the workgroup takes this step: nothing is staged
+        if (begin && io.reset && rows.rows_live) {                   // uniform; rows that were not restarted may still be running
+            const int c = __syncthreads_count((exists && gl == 0 && rows.done[qi] == 0) ? 1 : 0);
+            if (threadIdx.x == 0 && c) atomicAdd(rows.rows_live, c);
+        }
+        return;
+    }
+    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
+    POW p;
+    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
+    const int apl = (ag.A + G - 1) / G;                              // actions per lane
+    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
+    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
+    const int nchunks = (apl + AMAX - 1) / AMAX;
+    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+    const uint32_t mask = (EXCL && exists) ? rows.exclude_mask[pa.mask_by_node ? (size_t)node : qi] : 0u;
+    double q[NS];
+    if (live) {
+        double s[NS], qs[NS];
+#pragma unroll
+        for (int k = 0; k < NS; k++) s[k] = io.obs[qi * NS + k];
+        if (begin) {
+#pragma unroll
+            for (int k = 0; k < NS; k++) qs[k] = s[k];                                                   // :78 (un-quantised start state)
+        } else if (io.q_obs) {
+#pragma unroll
+            for (int k = 0; k < NS; k++) qs[k] = io.q_obs[qi * NS + k];                                  // the caller's quantize_observations
+        } else {
+            env_quantize(FRIRL_HIP_ENV_EXTERNAL, NS, ag.grid_values, ag.grid_len, ag.grid_div, s, qs);   // :112, the generic rule
+        }
+#pragma unroll
+        for (int k = 0; k < NS; k++) q[k] = observe_ve(u, ve, U, k, qs[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NS; k++) q[k] = 0.0;
+    }
+    unsigned h0;
+    int a;
+    double bv;
+    int R = nrules[e] < maxR ? nrules[e] : maxR;
+    R = R < 0 ? 0 : R;
+    const double *rb = rb_all + (size_t)e * (NANT + 1) * maxR;
+    const uint8_t *slot_g = EXCL ? rows.rule_slot + (size_t)e * maxR : nullptr;
+    shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, slot_g, R, maxR, p, abeg, aend, nchunks, q, live, mask, nullptr, h0, a, bv, h);   // :78 / :148
+    group_first_max<G>(bv, a);
+    int running = 0;                                                 // this lane's row is not done after the step
+    if (exists && gl == 0) {
+        if (!live) {
+            running = (begin && rows.done[qi] == 0) ? 1 : 0;         // begin: a row that was not restarted
+        } else {
+            const int steps = begin ? 0 : rows.ep_steps[si] + 1;                                         // :174
+            a = e_greedy(ag, a, (uint32_t)qi, 0u, (uint32_t)steps);
+            io.action_out[qi] = ag.grid_values[NS * FRIRL_HIP_MAX_GRID + a];                             // :82 / :151
+            if (io.action_idx) io.action_idx[qi] = a;
+            if (begin) {
+                rows.ep_steps[si] = 0;
+                rows.ep_reward[si] = 0.0;
+                rows.success[qi] = 0;
+                rows.done[qi] = 0;
+                running = 1;
+            } else {
+                const int cap = rows.step_cap ? rows.step_cap[e] : ag.max_steps;
+                const int success = io.success[qi];                                                      // :106
+                const int done = (success == 1 || steps >= cap) ? 1 : 0;                                 // :183, :86
+                rows.ep_steps[si] = steps;
+                rows.ep_reward[si] = rows.ep_reward[si] + io.reward[qi];                                 // :107
+                rows.success[qi] = success;
+                rows.done[qi] = done;
+                running = done ? 0 : 1;
+            }
+        }
+    }
+    if (!rows.rows_live) return;                                     // uniform
+    const int c = __syncthreads_count(running);
+    if (threadIdx.x == 0 && c) atomicAdd(rows.rows_live, c);
+}
+
+template <int N, int AMAX, int G, int H, bool PN = true>
+static void launch_policy_batch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const PolicyBatchArgs *pa,
+                                const frirl_hip_agent_io *io, int begin, int nlist, hipStream_t s)
+{
+    constexpr int EPB = SH_BLOCK / (G * H);
+    const int wpa = (pa->rows.n + EPB - 1) / EPB;
+    const dim3 grid((unsigned)nlist * wpa);
+    if (pa->rows.exclude_mask && pa->rows.rule_slot)
+        hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, true, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa);
+    else
+        hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, false, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa);
+}
+
+// The lane shapes of the batched reduction's roll-out kernel (reduce_batch.hip: launch_rows_n): G = 4 lanes per row with one
+// conclusion each for up to 4 actions, else 8 lanes with chunks of 4; H = 1 / 4 / 8 rule slices, 16 (G = 4) = a full wave per row.
+// H is chosen by policy_batch.hip.
+template <int N>
+static void launch_policy_batch_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const PolicyBatchArgs *pa,
+                                  const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s)
+{
+    const bool few = ag->A <= 4;
+    if (ag->p > 0 && ag->p != N) {          // run-time Shepard power: the variants without rule slices
+        if (few) launch_policy_batch<N, 1, 4, 1, false>(t, b, ag, pa, io, begin, nlist, s);
+        else launch_policy_batch<N, 4, 8, 1, false>(t, b, ag, pa, io, begin, nlist, s);
+        return;
+    }
+    if (few) {
+        if (H == 16) launch_policy_batch<N, 1, 4, 16>(t, b, ag, pa, io, begin, nlist, s);
+        else if (H == 8) launch_policy_batch<N, 1, 4, 8>(t, b, ag, pa, io, begin, nlist, s);
+        else if (H == 4) launch_policy_batch<N, 1, 4, 4>(t, b, ag, pa, io, begin, nlist, s);
+        else launch_policy_batch<N, 1, 4, 1>(t, b, ag, pa, io, begin, nlist, s);
+    } else {
+        if (H == 8) launch_policy_batch<N, 4, 8, 8>(t, b, ag, pa, io, begin, nlist, s);
+        else if (H == 4) launch_policy_batch<N, 4, 8, 4>(t, b, ag, pa, io, begin, nlist, s);
+        else launch_policy_batch<N, 4, 8, 1>(t, b, ag, pa, io, begin, nlist, s);
+    }
+}
+
+}  // namespace frirl

@@ -1,0 +1,246 @@
+// reduce_batch_kernels.h -- what the two batched reductions share: the arrays of a run (ReduceBatchWs), the order, open-round,
+// close-round and result kernels, and the host helpers for lane shapes and the workspace layout.  frirl_hip_reduce_batch
+// (reduce_batch.hip) rolls the replays out inside its own kernel; frirl_hip_batch_reducer_* (policy_batch.hip) steps them in the
+// caller's environment.  Moved out of reduce_batch.hip as shared_sweep.h and rollout_episode.h were; the only change is that the
+// kernels that are no templates have internal linkage (`static`), since two translation units now hold them.
+#pragma once
+#include "shared_sweep.h"
+#include "reduce_walk.h"
+#include <cstring>
+#include <type_traits>
+
+namespace frirl {
+
+constexpr int RB_ORDER_TILE = 1024;      // |Q| values staged in LDS per pass of the rank count
+
+// the arrays of one call, carved out of the caller's workspace (reduce_batch_layout)
+struct ReduceBatchWs {
+    int32_t *hdr;                 // [4] live count of even rounds, of odd rounds, first agent with a bad rule count + 1, pad
+    uint32_t *mask;               // [nodes] exclude mask of every tree node: the same for every agent
+    int32_t *live[2];             // [E] agents still reducing, this round's list and the next one's
+    int32_t *order;               // [E][maxR] candidates in trial order (original rule indices)
+    int32_t *alive;               // [E][maxR] original index of the rule in each current slot
+    uint8_t *slot;                // [E][maxR] candidate slot of every current rule in this round, 255 = none
+    int32_t *steps;               // [E][nodes] replay results of this round
+    double *reward;               // [E][nodes]
+    int32_t *j, *d, *R0, *rounds, *rollouts, *steps_inc, *cap;      // [E]
+    double *prev;                 // [E] prev_reward
+    frirl_hip_reduce_result *res; // [E]
+    int nodes;                    // 2^depth - 1
+};
+
+// Order kernel: one workgroup per agent.  Per-agent state, and the stable rank of every |Q| by counting (rw_before) with the
+// consequents staged in LDS; workgroup 0 also builds the mask table.  Active agents join the first live list.
+static __global__ __launch_bounds__(256) void reduce_batch_order_kernel(const double *__restrict__ rb, const int32_t *__restrict__ nrules, int nant, int maxR,
+                                                                 const uint8_t *__restrict__ active, int strategy, int max_steps, ReduceBatchWs ws)
+{
+    __shared__ double aq[RB_ORDER_TILE];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const int R = nrules[e];
+    const bool act = !active || active[e] != 0;
+    const size_t row = (size_t)e * maxR;
+    if (e == 0)
+        for (int n = tid; n < ws.nodes; n += 256) ws.mask[n] = rw_node_mask((uint32_t)n);
+    if (tid == 0) {
+        ws.j[e] = 0; ws.d[e] = 0; ws.R0[e] = R; ws.rounds[e] = 0; ws.rollouts[e] = 0; ws.steps_inc[e] = 0; ws.cap[e] = max_steps;
+        ws.prev[e] = 0.0;
+    }
+    for (int r = tid; r < maxR; r += 256) { ws.alive[row + r] = r; ws.slot[row + r] = (uint8_t)255; ws.order[row + r] = 0; }
+    if (!act) return;                                                  // uniform over the workgroup
+    if (R < 1 || R > maxR) {                                           // uniform; reported by the host before anything is reduced
+        if (tid == 0) atomicCAS(&ws.hdr[2], 0, e + 1);
+        return;
+    }
+    const double *qcol = rb + ((size_t)e * (nant + 1) + nant) * maxR;
+    for (int r0 = 0; r0 < R; r0 += 256) {
+        const int r = r0 + tid;
+        const double ar = r < R ? fabs(qcol[r]) : 0.0;
+        int rank = 0;
+        for (int t0 = 0; t0 < R; t0 += RB_ORDER_TILE) {
+            const int n = R - t0 < RB_ORDER_TILE ? R - t0 : RB_ORDER_TILE;
+            __syncthreads();
+            for (int i = tid; i < n; i += 256) aq[i] = fabs(qcol[t0 + i]);
+            __syncthreads();
+            if (r < R)
+                for (int q = 0; q < n; q++) rank += rw_before(aq[q], t0 + q, ar, r, strategy) ? 1 : 0;
+        }
+        if (r < R) ws.order[row + rank] = r;                           // rank < R: at most R - 1 rules come before r
+    }
+    if (tid == 0) ws.live[0][atomicAdd(&ws.hdr[0], 1)] = e;
+}
+
+// Open-round kernel: one workgroup per live agent; d_e and the slot table of its next candidates.
+static __global__ __launch_bounds__(256) void reduce_batch_open_kernel(const int32_t *__restrict__ nrules, int maxR, int depth, int cur, ReduceBatchWs ws)
+{
+    __shared__ int cand[RW_MAX_DEPTH];
+    const int e = ws.live[cur][blockIdx.x], tid = threadIdx.x;
+    if (blockIdx.x == 0 && tid == 0) ws.hdr[cur ^ 1] = 0;             // the close kernel of this round appends to the other list
+    const int j = ws.j[e], left = ws.R0[e] - j;
+    const int d = left < depth ? left : depth;
+    const int R = nrules[e];
+    const size_t row = (size_t)e * maxR;
+    if (tid < d) cand[tid] = ws.order[row + j + tid];
+    if (tid == 0) ws.d[e] = d;
+    __syncthreads();
+    for (int r = tid; r < maxR; r += 256) {
+        unsigned s = 255u;
+        if (r < R) {
+            const int a = ws.alive[row + r];
+            for (int i = 0; i < d; i++) s = cand[i] == a ? (unsigned)i : s;
+        }
+        ws.slot[row + r] = (uint8_t)s;
+    }
+}
+
+// Close-round kernel: one workgroup per live agent.  first: the baseline replay sets steps_incremental, prev_reward and the
+// agent's step cap.  Otherwise: walk the tree (every thread, same result), compact the rule base in place -- chunks of 256 rules
+// in index order, every chunk read into registers by all threads before any of it is written, and a write never lands above
+// its read -- zero the vacated tail, advance the agent and append it to the next live list while candidates are left.
+template <int NANT>
+__global__ __launch_bounds__(256) void reduce_batch_close_kernel(double *__restrict__ rb, int32_t *__restrict__ nrules, uint16_t *__restrict__ uidx,
+                                                                 double *__restrict__ rant, int maxR, int cur, int first, int max_steps,
+                                                                 double good_above, double tol, ReduceBatchWs ws)
+{
+    __shared__ int wave_kept[4];
+    const int e = ws.live[cur][blockIdx.x], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t M = (size_t)maxR;
+    const int R = nrules[e], d = first ? 0 : ws.d[e];
+    const int steps_inc = first ? ws.steps[(size_t)e * ws.nodes] : ws.steps_inc[e];
+    double prev = first ? ws.reward[(size_t)e * ws.nodes] : ws.prev[e];
+    const uint32_t bits = rw_walk(d, ws.steps + (size_t)e * ws.nodes, ws.reward + (size_t)e * ws.nodes, steps_inc, prev, good_above, tol);
+    int Rn = R;
+    if (bits) {                                                        // uniform: every thread walked the same tree
+        double *cols = rb + (size_t)e * (NANT + 1) * M;
+        double *ra = rant ? rant + (size_t)e * NANT * M : nullptr;
+        uint16_t *ui = uidx ? uidx + (size_t)e * NANT * M : nullptr;
+        int32_t *al = ws.alive + (size_t)e * M;
+        const uint8_t *sl = ws.slot + (size_t)e * M;
+        int base = 0;
+        for (int r0 = 0; r0 < R; r0 += 256) {
+            const int r = r0 + tid;
+            const bool keep = r < R && !rw_dropped(sl[r], bits);
+            double v[NANT + 1], w[NANT];
+            uint16_t x[NANT];
+            int a = 0;
+            if (keep) {
+#pragma unroll
+                for (int k = 0; k <= NANT; k++) v[k] = cols[k * M + r];
+#pragma unroll
+                for (int k = 0; k < NANT; k++) { w[k] = ra ? ra[k * M + r] : 0.0; x[k] = ui ? ui[k * M + r] : (uint16_t)0; }
+                a = al[r];
+            }
+            const unsigned long long bal = __ballot(keep);
+            if (lane == 0) wave_kept[wave] = __popcll(bal);
+            __syncthreads();                                           // the chunk is in registers; the wave counts are visible
+            int pos = base + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+            for (int i = 0; i < 4; i++) { pos += i < wave ? wave_kept[i] : 0; tot += wave_kept[i]; }
+            if (keep && pos != r) {                                    // pos <= r
+#pragma unroll
+                for (int k = 0; k <= NANT; k++) cols[k * M + pos] = v[k];
+#pragma unroll
+                for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + pos] = w[k]; if (ui) ui[k * M + pos] = x[k]; }
+                al[pos] = a;
+            }
+            base += tot;
+            __syncthreads();                                           // wave_kept is rewritten by the next chunk
+        }
+        Rn = base;
+        for (int r = Rn + tid; r < R; r += 256) {                      // vacated tail: zero like five_remove_rule.c:64-80
+#pragma unroll
+            for (int k = 0; k <= NANT; k++) cols[k * M + r] = 0.0;
+#pragma unroll
+            for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + r] = 0.0; if (ui) ui[k * M + r] = 0; }
+        }
+    }
+    __syncthreads();                                                   // every thread has read the agent's state
+    if (tid != 0) return;
+    if (first) {
+        ws.steps_inc[e] = steps_inc;
+        ws.rollouts[e] = 1;
+        ws.cap[e] = max_steps > steps_inc + 1 ? steps_inc + 1 : max_steps;     // a longer replay is rejected anyway (:212)
+    } else {
+        ws.rounds[e] += 1;
+        ws.rollouts[e] += rw_nodes(d);
+        nrules[e] = Rn;
+    }
+    ws.prev[e] = prev;
+    const int j = ws.j[e] + d;
+    ws.j[e] = j;
+    if (j < ws.R0[e]) ws.live[cur ^ 1][atomicAdd(&ws.hdr[cur ^ 1], 1)] = e;
+}
+
+static __global__ void reduce_batch_result_kernel(const int32_t *__restrict__ nrules, int E, ReduceBatchWs ws)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    frirl_hip_reduce_result r;
+    r.rules_before = ws.R0[e];
+    r.rules_after = nrules[e];
+    r.rounds = ws.rounds[e];
+    r.rollouts = ws.rollouts[e];
+    r.steps_incremental = ws.steps_inc[e];
+    r.reserved = 0;
+    r.reward = ws.prev[e];
+    ws.res[e] = r;
+}
+
+}  // namespace frirl
+
+using namespace frirl_host;
+using frirl::ReduceBatchWs;
+
+// ---- shapes ----------------------------------------------------------------------------------------------------------------
+// Lanes per row: G action slots (4 for up to 4 actions, else 8) times H rule slices.  The rounds run H = 8 while that keeps every
+// row resident, the baseline replay (one row per agent) the widest group a wave holds.
+static constexpr int RB_H = 8;              // rule slices of the shape the depth rule counts with
+
+static int rb_group(int A) { return A <= 4 ? 4 : 8; }
+
+// Resident workgroups per CU of the H = 8 roll-out kernels (one wave of a workgroup per SIMD, so = waves per SIMD), from their
+// register counts: G = 4 needs 107 (nant 3) / 133 (nant 5) VGPRs -> 4 / 3 waves, G = 8 needs 235 / 255 -> 2 / 1.  The
+// smaller of the two antecedent counts is taken; the 15.6 KB of LDS per workgroup would allow 10.
+static int rb_wg_per_cu(int A) { return A <= 4 ? 3 : 1; }
+
+static int rb_cus()
+{
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) return n;
+    (void)hipGetLastError();
+    return 256;                              // no device visible: an MI355X is assumed
+}
+
+// rows the H = 8 shape keeps resident on the chip
+static long rb_resident_rows(int A) { return (long)rb_cus() * rb_wg_per_cu(A) * (frirl::SH_BLOCK / (rb_group(A) * RB_H)); }
+
+static size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+
+// carves the arrays of a call out of `base` (NULL: sizes only); `rows` = entries of steps / reward
+static size_t reduce_batch_layout(char *base, size_t E, size_t maxR, int depth, size_t rows, ReduceBatchWs *ws)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += up16(bytes); return p; };
+    ReduceBatchWs w;
+    w.nodes = frirl::rw_nodes(depth);
+    w.hdr = reinterpret_cast<int32_t *>(take(4 * sizeof(int32_t)));
+    w.mask = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * w.nodes));
+    w.live[0] = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
+    w.live[1] = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
+    w.order = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * maxR));
+    w.alive = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * maxR));
+    w.slot = reinterpret_cast<uint8_t *>(take(E * maxR));
+    w.steps = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * rows));
+    w.reward = reinterpret_cast<double *>(take(sizeof(double) * rows));
+    int32_t **per_agent[] = {&w.j, &w.d, &w.R0, &w.rounds, &w.rollouts, &w.steps_inc, &w.cap};
+    for (int32_t **p : per_agent) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
+    w.prev = reinterpret_cast<double *>(take(sizeof(double) * E));
+    w.res = reinterpret_cast<frirl_hip_reduce_result *>(take(sizeof(frirl_hip_reduce_result) * E));
+    if (ws) *ws = w;
+    return off;
+}
+
+// rule slices of a round with `rows` rows in all: 8 while every row stays resident, else 4, else 1
+static int rb_slices(long rows, int A)
+{
+    const long rows8 = rb_resident_rows(A);
+    return rows <= rows8 ? 8 : (rows <= 2 * rows8 ? 4 : 1);
+}

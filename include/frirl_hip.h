@@ -520,6 +520,67 @@ int frirl_hip_reducer_end_round(frirl_hip_reducer *r);
 int frirl_hip_reducer_result(const frirl_hip_reducer *r, int32_t *kept, frirl_hip_reduce_result *result);
 void frirl_hip_reducer_destroy(frirl_hip_reducer *r);
 
+/* ---- the same greedy step for EVERY agent's OWN rule base (b->E >= 1): E * n caller-stepped rows, row q = e * n + node on the rule
+ * base of agent e = q / n (slab e of b, nrules[e], rule_slot row e) -- e.g. every agent trained with frirl_hip_agent_begin / _observe
+ * evaluated from n start states of the caller's environment.  Arguments, checks and per-row semantics are those of
+ * frirl_hip_policy_begin / _observe (nant 2..8, A 1..32, env_kind not read, FRIRL_HIP_EINVAL before FRIRL_HIP_ENODEV, no
+ * synchronisation) without the E == 1 requirement; all arrays of `io` have E * n rows; the epsilon-greedy stream of row q is
+ * (env_id_base + q, episode 0, step).  One launch per call: a workgroup serves rows of ONE agent, 4 lanes per row for up to 4 actions,
+ * else 8, times 1 / 4 / 8 rule slices (a full wave per row when n == 1; option "policy_slices"; every shape chooses the same actions).
+ * Rows node >= row_count[e] do not exist: nothing of theirs is read or written -- set their `done` to 1 beforehand.  Agents that are
+ * not named in `agents` cost nothing and keep their row state. */
+typedef struct frirl_hip_policy_batch_rows {
+    int32_t n;                     /* rows per agent; row q belongs to agent q / n                       */
+    int32_t *done, *ep_steps, *success; double *ep_reward;      /* [dev] [E*n]                           */
+    const int32_t *row_count;      /* [dev] [E] rows of agent e that exist (<= n), or NULL = n           */
+    const int32_t *step_cap;       /* [dev] [E] per-agent max_steps, or NULL = agent->max_steps          */
+    const int32_t *agents;         /* [dev] [nagents] agents served by this call, or NULL = 0..E-1       */
+    int32_t nagents;               /* length of agents (ignored when NULL)                               */
+    const uint32_t *exclude_mask;  /* [dev] [E*n] or NULL                                                */
+    const uint8_t *rule_slot;      /* [dev] [E][maxR] or NULL (together with exclude_mask)               */
+    int32_t *rows_live;            /* [dev] [1] incremented by rows not done after the call, or NULL     */
+} frirl_hip_policy_batch_rows;
+int frirl_hip_policy_batch_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                 const frirl_hip_policy_batch_rows *rows, const frirl_hip_agent_io *io, void *stream);
+int frirl_hip_policy_batch_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                   const frirl_hip_policy_batch_rows *rows, const frirl_hip_agent_io *io, void *stream);
+
+/* ---- frirl_hip_reduce_batch with the CALLER'S environment: the reduction of EVERY agent's rule base as a resumable object with the
+ * round protocol of frirl_hip_reducer_*.  Per agent the decisions are exactly those of frirl_hip_reduce_batch (candidate order, cap
+ * min(max_steps, steps_incremental[e] + 1), the acceptance test of :212, in-place compaction of rb, rant, uidx and nrules[e] with the
+ * vacated tail zeroed); the caller places row e * n + node in agent e's start state when it resets its environments.
+ *     r = frirl_hip_batch_reducer_create(t, b, agent, rant, active, strategy, tolerance, depth, stream);
+ *     while (frirl_hip_batch_reducer_next_round(r, &Q, &n, &agents_live) == 0 && Q > 0) {
+ *         reset Q environments, row q to the start state of agent q / n; io.obs = their observations
+ *         frirl_hip_batch_reducer_begin(r, &io);
+ *         do { step the environments with io.action_out; frirl_hip_batch_reducer_observe(r, &io, &live); } while (live > 0);
+ *         frirl_hip_batch_reducer_end_round(r);
+ *     }
+ *     frirl_hip_batch_reducer_result(r, kept, results);  frirl_hip_batch_reducer_destroy(r);
+ * Round 0 is every active agent's baseline replay (n = 1, Q = E); later rounds have n = 2^depth - 1 and Q = E * n, row e * n + node
+ * being node (k, bits) = 2^k - 1 + bits of agent e's accept/reject tree.  The row <-> agent mapping is fixed.  Rows whose `done` is 1
+ * after begin -- agents that are inactive or have finished, nodes beyond 2^d_e - 1 -- need not be stepped (frirl_hip_batch_reducer_row_done,
+ * [dev] [Q]) and cost no workgroup.  Every begin / observe is ONE launch over the rows of the agents still reducing; end_round launches
+ * the tree walk + compaction and the next round's slot tables.  The host reads a 16-byte header (live agents, rows live) and nothing
+ * else before `result`: no slab, no per-row state.  observe with rows_live == NULL does not synchronise.
+ * create returns NULL and sets frirl_hip_last_error on bad arguments (strategy not 1 / 2, depth outside 0..12 with 0 =
+ * frirl_hip_reduce_batch_depth(E, A), nant outside 2..8, nrules[e] outside 1..maxR for an active agent: nothing reduced) or without a
+ * device; t, b and agent are copied, the device arrays they name (and rant [E][nant][maxR], active [E], or NULL) must outlive the
+ * reducer, which owns its device memory from create to destroy.  Calls out of order (begin before next_round or twice, observe outside
+ * a round, end_round while rows are live, next_round or result inside a round) return FRIRL_HIP_EINVAL and change nothing.
+ * kept [host] [E][maxR] or NULL and results [host] [E] as frirl_hip_reduce_batch. */
+typedef struct frirl_hip_batch_reducer frirl_hip_batch_reducer;
+frirl_hip_batch_reducer *frirl_hip_batch_reducer_create(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                                        double *rant, const uint8_t *active, int strategy, double reward_tolerance, int depth,
+                                                        void *stream);
+int frirl_hip_batch_reducer_next_round(frirl_hip_batch_reducer *r, int32_t *Q, int32_t *rows_per_agent, int32_t *agents_live);
+int frirl_hip_batch_reducer_begin(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io);
+int frirl_hip_batch_reducer_observe(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io, int32_t *rows_live);
+int frirl_hip_batch_reducer_end_round(frirl_hip_batch_reducer *r);
+int frirl_hip_batch_reducer_result(frirl_hip_batch_reducer *r, int32_t *kept, frirl_hip_reduce_result *results);
+const int32_t *frirl_hip_batch_reducer_row_done(const frirl_hip_batch_reducer *r);
+void frirl_hip_batch_reducer_destroy(frirl_hip_batch_reducer *r);
+
 /* Lane-group form for MANY agents with SMALL rule bases (the demos' learning regime; the reference's frirl_omp_run model
  * of one agent per core, frirl_agent.c:294-325, at GPU width): G = 4 or 8 consecutive lanes own one environment, each
  * lane evaluates its share of the A + 1 conclusions of a step over ALL rules sequentially -- the reference's summation

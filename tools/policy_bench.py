@@ -6,7 +6,13 @@
       the launch is timed (hip events around N back-to-back calls, rows kept live by a large max_steps).
   (b) wall time of the three demo reductions through reduce_external (frirl_hip_env_step as the caller's environment), through
       frirl_hip_reduce_shared, and of the oracle's sequential loop on one host core; strategy 1.
-python tools/policy_bench.py [--reps 200]"""
+python tools/policy_bench.py [--reps 200]
+With --agents E instead: the reduction of E rule bases learned on the device (start states spread +-10 %, as tools/reduce_bench.py
+--agents) in the caller's environment, strategy 1, frirl_hip_env_step as the environment, mountaincar and acrobot:
+  reduce_external_batch (one launch per step for all agents)  against  a loop of reduce_external over the same rule bases,
+  and Problem.reduce_batch (the environment inside the kernel) as the floor.
+Host clock around calls that end in a synchronise, rule bases restored outside the window, one warm-up, the sides alternating:
+python tools/policy_bench.py --agents 64 [--timed 2] [--loop-sample 64] [--only mountaincar]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np
@@ -68,11 +74,85 @@ def observe_us(prob, agent, Q, shape, reps, dev):
         frirl_amd.set_option("policy_slices", old[1])
 
 
+def agents_leg(env, E, a, dev):
+    d = frirl_amd.demo_describe(env)
+    ns = d["nstates"]
+    rng = np.random.default_rng(11)
+    start = np.zeros((E, ns))
+    for k in range(ns):
+        g = d["grids"][k]
+        start[:, k] = np.clip(d["values_def"][k] + rng.uniform(-0.1, 0.1, E) * (g.max() - g.min()), g.min(), g.max())
+        start[0, k] = d["values_def"][k]
+    ss = torch.from_numpy(np.ascontiguousarray(start)).to(dev)
+    prob, agent, envs = frirl_amd.demo_fresh_batch(env, E, 512, dev, start_states=ss)
+    run = frirl_amd.train_persistent(prob, agent, envs, max_episodes=400)
+    torch.cuda.synchronize()
+    snap = [t.clone() for t in (prob.rb, prob.nrules, prob.uidx, envs.rant)]
+
+    def restore():
+        for t, t0 in zip((prob.rb, prob.nrules, prob.uidx, envs.rant), snap):
+            t.copy_(t0)
+        torch.cuda.synchronize()
+
+    def step_fn(states, action):
+        obs, reward, success, q = frirl_amd.env_step(agent, action, states)
+        return (obs, reward, success, q) if env == "cartpole" else (obs, reward, success)
+
+    sample = list(range(E)) if a.loop_sample >= E else [int(i) for i in np.linspace(0, E - 1, a.loop_sample).astype(int)]
+    views = [frirl_amd.Problem(prob.u, prob.ve, prob.rb[e:e + 1], prob.nrules[e:e + 1], prob.uidx[e:e + 1]) for e in sample]
+    depth = frirl_amd.lib().frirl_hip_reduce_batch_depth(E, d["A"])
+    out = {"what": "reduce_agents", "env": env, "agents": E, "converged": int((run.conv.converged == 1).sum()), "rules_before_sum": int(snap[1].sum()),
+           "depth": depth, "loop_depth": 10, "loop_agents_timed": len(sample), "stepped_batch_s": [], "stepped_loop_s": [], "in_kernel_batch_s": []}
+    for rep in range(a.timed + 1):                                   # rep 0 warms every side up
+        restore()
+        t0 = time.perf_counter()
+        kept, res = frirl_amd.reduce_external_batch(prob, agent, lambda Q, n: ss.repeat_interleave(n, 0), step_fn, 1, 0.0, 0, rant=envs.rant)
+        torch.cuda.synchronize()
+        dt_b = time.perf_counter() - t0
+        after_b = np.array([r.rules_after for r in res])
+        steps_sum = int(sum(r.steps_incremental for r in res))
+        restore()
+        after_l = []
+        t0 = time.perf_counter()
+        for e, view in zip(sample, views):
+            st = ss[e]
+            _, r1 = frirl_amd.reduce_external(view, agent, lambda Q: st.expand(Q, ns).contiguous(), step_fn, 1, 0.0, 0, rant=envs.rant[e])
+            after_l.append(r1.rules_after)
+        torch.cuda.synchronize()
+        dt_l = time.perf_counter() - t0
+        restore()
+        t0 = time.perf_counter()
+        _, res_k = prob.reduce_batch(agent, 1, 0.0, 0, rant=envs.rant, start_states=ss)
+        torch.cuda.synchronize()
+        dt_k = time.perf_counter() - t0
+        assert (after_b[sample] == np.array(after_l)).all(), "batched and single-base stepped reductions disagree"
+        assert (after_b == np.array([r.rules_after for r in res_k])).all(), "stepped and in-kernel batched reductions disagree"
+        if rep:
+            out["stepped_batch_s"].append(round(dt_b, 4))
+            out["stepped_loop_s"].append(round(dt_l, 4))
+            out["in_kernel_batch_s"].append(round(dt_k, 4))
+    scale = E / len(sample)
+    out["stepped_loop_s_all_agents"] = [round(x * scale, 4) for x in out["stepped_loop_s"]]
+    out["loop_extrapolated"] = len(sample) < E
+    out.update(rules_after_sum=int(after_b.sum()), rounds_max=max(r.rounds for r in res), baseline_steps_sum=steps_sum,
+               loop_over_batch_min_over_min=round(min(out["stepped_loop_s_all_agents"]) / min(out["stepped_batch_s"]), 2),
+               batch_over_in_kernel_min_over_min=round(min(out["stepped_batch_s"]) / min(out["in_kernel_batch_s"]), 2))
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--agents", type=int, default=0)
+    ap.add_argument("--timed", type=int, default=2)
+    ap.add_argument("--loop-sample", type=int, default=64)
+    ap.add_argument("--only", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.agents:
+        for env in ([a.only] if a.only else ["mountaincar", "acrobot"]):
+            agents_leg(env, a.agents, a, dev)
+        return
     fr = oracle_trained("acrobot")
     prob = shared_problem(fr, dev)
     agent = frirl_amd.demo_agent(frirl_amd.demo_describe("acrobot"), dev, max_steps=1 << 30)
