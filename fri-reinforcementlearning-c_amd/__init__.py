@@ -79,6 +79,12 @@ class AgentIO(C.Structure):
                 ("action_out", C.c_void_p), ("action_idx", C.c_void_p)]
 
 
+class DemonstrationDesc(C.Structure):
+    """struct frirl_hip_demonstration (include/frirl_hip.h)."""
+    _fields_ = [("T", C.c_int32), ("agent_stride", C.c_int64), ("obs", C.c_void_p), ("q_obs", C.c_void_p), ("action", C.c_void_p),
+                ("reward", C.c_void_p), ("success", C.c_void_p), ("start", C.c_void_p), ("length", C.c_void_p)]
+
+
 class PolicyRowsDesc(C.Structure):
     """struct frirl_hip_policy_rows (include/frirl_hip.h)."""
     _fields_ = [("Q", C.c_int32), ("done", C.c_void_p), ("ep_steps", C.c_void_p), ("success", C.c_void_p), ("ep_reward", C.c_void_p),
@@ -171,6 +177,12 @@ SIGNATURES = {
     "frirl_hip_agent_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]),
     "frirl_hip_agent_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
                                           C.c_void_p]),
+    "frirl_hip_agent_begin_taught": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
+                                               C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_observe_taught": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
+                                                 C.c_void_p, C.c_void_p]),
+    "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
+                                                C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
     "frirl_hip_policy_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO),
                                            C.c_void_p]),
@@ -720,25 +732,77 @@ def _agent_io(problem, obs, q_obs=None, reward=None, success=None, reset=None, E
     return io, action, action_idx
 
 
-def agent_begin(problem, agent, envs, obs, reset=None, stream=None):
+def _teacher(teacher, E):
+    import torch
+    assert teacher.is_cuda and teacher.dtype == torch.int32 and teacher.shape == (E,) and teacher.is_contiguous()
+    return _ptr(teacher)
+
+
+def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None):
     """frirl_hip_agent_begin: start an episode from the caller's observations obs [E, nant-1] (float64, on the device) for the rows
     selected by `reset` ([E] uint8 / bool, None = all).  Returns (action values [E] float64, action indices [E] int32): the first
-    action of every restarted row (the other rows' entries are not written).  Does not synchronise."""
+    action of every restarted row (the other rows' entries are not written).  teacher [E] int32 (frirl_hip_agent_begin_taught): a row
+    whose entry is an action index 0..A-1 takes that action, any other value leaves the row its own pick.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, reset=reset)
-    check(lib().frirl_hip_agent_begin(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
-                                      _stream(stream)), "frirl_hip_agent_begin")
+    if teacher is None:
+        check(lib().frirl_hip_agent_begin(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
+                                          _stream(stream)), "frirl_hip_agent_begin")
+    else:
+        check(lib().frirl_hip_agent_begin_taught(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc),
+                                                 C.byref(io), _teacher(teacher, problem.E), _stream(stream)), "frirl_hip_agent_begin_taught")
     return action, action_idx
 
 
-def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None):
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None):
     """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
     last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
     quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
-    rows that were done are not written.  Does not synchronise."""
+    rows that were done are not written.  teacher [E] int32 (frirl_hip_agent_observe_taught): a row whose entry is an action index
+    takes it as its next action and learns towards Q(s', a_teacher).  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
-                                        _stream(stream)), "frirl_hip_agent_observe")
+    if teacher is None:
+        check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
+                                            _stream(stream)), "frirl_hip_agent_observe")
+    else:
+        check(lib().frirl_hip_agent_observe_taught(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc),
+                                                   C.byref(io), _teacher(teacher, problem.E), _stream(stream)), "frirl_hip_agent_observe_taught")
     return action, action_idx
+
+
+class Demonstration:
+    """Recorded logs for learn_demonstration (struct frirl_hip_demonstration): obs [L, T, nant-1] float64, action [L, T] int32,
+    reward [L, T] float64, success [L, T] int32, optional q_obs (as obs), start [L, T] uint8 / bool and length [E] int32, all on the
+    device and contiguous.  L = E gives every agent its own log, L = 1 makes every agent replay the one log (agent_stride = 0)."""
+
+    def __init__(self, obs, action, reward, success, q_obs=None, start=None, length=None):
+        import torch
+        L, T, ns = obs.shape
+        assert obs.is_cuda and obs.dtype == torch.float64 and obs.is_contiguous() and T >= 1
+        assert action.dtype == torch.int32 and action.shape == (L, T) and action.is_contiguous()
+        assert reward.dtype == torch.float64 and reward.shape == (L, T) and reward.is_contiguous()
+        assert success.dtype == torch.int32 and success.shape == (L, T) and success.is_contiguous()
+        assert q_obs is None or (q_obs.dtype == torch.float64 and q_obs.shape == obs.shape and q_obs.is_contiguous())
+        assert start is None or (start.dtype in (torch.uint8, torch.bool) and start.shape == (L, T) and start.is_contiguous())
+        assert length is None or (length.dtype == torch.int32 and length.dim() == 1 and length.is_contiguous())
+        self.obs, self.action, self.reward, self.success, self.q_obs, self.start, self.length = obs, action, reward, success, q_obs, start, length
+        self.L, self.T, self.ns = L, T, ns
+        self.desc = DemonstrationDesc(T, T if L > 1 else 0, obs.data_ptr(), q_obs.data_ptr() if q_obs is not None else None, action.data_ptr(),
+                                      reward.data_ptr(), success.data_ptr(), start.data_ptr() if start is not None else None,
+                                      length.data_ptr() if length is not None else None)
+
+
+def learn_demonstration(problem, agent, envs, demo, passes=1, stream=None):
+    """frirl_hip_learn_demonstration: every agent replays its recorded log `demo` (Demonstration) `passes` times in one launch, as the
+    chain of agent_begin / agent_observe calls with teacher = the logged action would.  Returns (replayed [E] int32: records
+    consumed, refused [E] uint8: an append was refused at a full rule base).  Does not synchronise."""
+    import torch
+    assert demo.ns == problem.nant - 1 and demo.L in (1, problem.E) and (demo.length is None or demo.length.shape == (problem.E,))
+    replayed = torch.empty((problem.E,), dtype=torch.int32, device=demo.obs.device)
+    refused = torch.empty((problem.E,), dtype=torch.uint8, device=demo.obs.device)
+    check(lib().frirl_hip_learn_demonstration(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc),
+                                              C.byref(demo.desc), passes, _ptr(replayed), _ptr(refused), _stream(stream)),
+          "frirl_hip_learn_demonstration")
+    return replayed, refused
 
 
 class PolicyRows:

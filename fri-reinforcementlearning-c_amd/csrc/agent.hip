@@ -1,4 +1,5 @@
-// agent.hip -- frirl_episode with the caller's environment: frirl_hip_agent_begin / frirl_hip_agent_observe (include/frirl_hip.h).
+// agent.hip -- frirl_episode with the caller's environment: frirl_hip_agent_begin / frirl_hip_agent_observe and their taught forms
+// (include/frirl_hip.h).
 // The kernels are the fused episode kernels of sarsa.hip with EXT = true (episode_kernel.h), instantiated per antecedent count in
 // agent_i<N>.hip.
 #include "device_common.h"
@@ -7,12 +8,12 @@ using namespace frirl_host;
 
 #define FRIRL_AGENT_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
 #define M(N) void frirl_agent_launch_##N(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
-                                         const frirl_hip_envs *ev, const frirl_hip_agent_io &io, hipStream_t s);
+                                         const frirl_hip_envs *ev, const frirl_hip_agent_io &io, const int32_t *teacher, hipStream_t s);
 FRIRL_AGENT_NANT_CASES(M)
 #undef M
 
-static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const frirl_hip_envs *ev,
-                            const frirl_hip_agent_io *io, bool begin, const char *who)
+// everything of an agent call's arguments but the caller's step data and the device (also frirl_hip_learn_demonstration, teach.hip)
+int frirl_host::check_agent_shape(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const frirl_hip_envs *ev, const char *who)
 {
     if (!t || t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t ? t->nant : 0); return FRIRL_HIP_EINVAL; }
     int rc = check_rulebases(t, b);
@@ -23,18 +24,26 @@ static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases
         if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
     if (a->grid_len[t->nant - 1] != a->A) { set_error("%s: the action grid has %d values, A=%d", who, a->grid_len[t->nant - 1], a->A); return FRIRL_HIP_EINVAL; }
     if (!ev || !ev->states || !ev->q_ant || !ev->fus || !ev->done || !ev->ep_steps || !ev->ep_reward) { set_error("%s: NULL env state", who); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const frirl_hip_envs *ev,
+                            const frirl_hip_agent_io *io, bool begin, const char *who)
+{
+    const int rc = check_agent_shape(t, b, a, ev, who);
+    if (rc) return rc;
     if (!io || !io->obs || !io->action_out) { set_error("%s: NULL io / io->obs / io->action_out", who); return FRIRL_HIP_EINVAL; }
     if (!begin && (!io->reward || !io->success)) { set_error("%s: NULL io->reward / io->success", who); return FRIRL_HIP_EINVAL; }
     return check_device();
 }
 
 static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
-                      const frirl_hip_agent_io *io, void *stream, bool begin, const char *who)
+                      const frirl_hip_agent_io *io, const int32_t *teacher, void *stream, bool begin, const char *who)
 {
     int rc = check_agent_call(t, b, agent, envs, io, begin, who);
     if (rc) return rc;
     switch (t->nant) {
-#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, as_stream(stream)); break;
+#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, teacher, as_stream(stream)); break;
         FRIRL_AGENT_NANT_CASES(M)
 #undef M
     }
@@ -44,11 +53,24 @@ static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, c
 extern "C" int frirl_hip_agent_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                                      const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream)
 {
-    return agent_call(t, b, agent, envs, io, stream, true, "frirl_hip_agent_begin");
+    return agent_call(t, b, agent, envs, io, nullptr, stream, true, "frirl_hip_agent_begin");
 }
 
 extern "C" int frirl_hip_agent_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                                        const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream)
 {
-    return agent_call(t, b, agent, envs, io, stream, false, "frirl_hip_agent_observe");
+    return agent_call(t, b, agent, envs, io, nullptr, stream, false, "frirl_hip_agent_observe");
+}
+
+// imitation (frirl_episode.c:58-79,127-151): teacher[e] in 0..A-1 replaces row e's epsilon-greedy action; NULL = the untaught call
+extern "C" int frirl_hip_agent_begin_taught(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                            const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream)
+{
+    return agent_call(t, b, agent, envs, io, teacher, stream, true, "frirl_hip_agent_begin_taught");
+}
+
+extern "C" int frirl_hip_agent_observe_taught(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                              const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream)
+{
+    return agent_call(t, b, agent, envs, io, teacher, stream, false, "frirl_hip_agent_observe_taught");
 }

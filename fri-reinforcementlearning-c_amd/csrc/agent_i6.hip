@@ -2,8 +2,11 @@
 #include "episode_kernel.h"
 
 void frirl_agent_launch_6(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                          const frirl_hip_agent_io &io, hipStream_t s)
+                          const frirl_hip_agent_io &io, const int32_t *teacher, hipStream_t s)
 {
-    if (begin) frirl::launch_episode<6, true, true>(t, b, ag, ev, s, io);
-    else frirl::launch_episode<6, false, true>(t, b, ag, ev, s, io);
+    frirl::ExtIo x;
+    static_cast<frirl_hip_agent_io &>(x) = io;
+    x.teacher = teacher;
+    if (begin) frirl::launch_episode<6, true, true>(t, b, ag, ev, s, x);
+    else frirl::launch_episode<6, false, true>(t, b, ag, ev, s, x);
 }

@@ -146,6 +146,8 @@ int check_launch(const char *what);       // hipGetLastError -> code
 int check_tables(const frirl_hip_tables *t);
 int check_rulebases(const frirl_hip_tables *t, const frirl_hip_rulebases *b);
 int check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who);   // shared.hip: env_kind names a demo with t->nant antecedents
+int check_agent_shape(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
+                      const char *who);   // agent.hip: nant 2..8, rule bases, grids, A 1..32, env state; not the device
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // The library-owned batches switch to their own device; the caller's current device is put back on every exit path.

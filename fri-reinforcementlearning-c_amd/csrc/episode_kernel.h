@@ -15,8 +15,22 @@ namespace frirl {
 
 // the caller's step data (frirl_hip_agent_io) for EXT kernels, nothing for the demo kernels
 struct NoIo {};
+// ... plus the teacher's actions of frirl_hip_agent_begin_taught / _observe_taught: [E] action indices, or NULL (the untaught calls)
+struct ExtIo : frirl_hip_agent_io {
+    const int32_t *teacher;
+};
 template <bool EXT>
-using IoArg = std::conditional_t<EXT, frirl_hip_agent_io, NoIo>;
+using IoArg = std::conditional_t<EXT, ExtIo, NoIo>;
+
+// imitation (reference frirl_episode.c:58-79,127-151: keyaction replaces the epsilon-greedy action; key 32 = the agent chooses): row e
+// takes teacher[e] when it is an action index, and keeps `chosen` for any other value.  The exploration stream is counter-based, so
+// a taught pick consumes nothing of it.
+__device__ __forceinline__ int taught_action(const ExtIo &io, int e, int A, int chosen)
+{
+    if (!io.teacher) return chosen;
+    const int32_t k = io.teacher[e];
+    return (k >= 0 && k < A) ? k : chosen;
+}
 
 struct StepShared {
     double q_ant[FRIRL_HIP_MAX_NANT];      // raw antecedent values of (s, a)
@@ -173,6 +187,7 @@ __global__ __launch_bounds__(BLOCK) void episode_begin_kernel(const double *__re
         const uint32_t epi = ev.episode ? (uint32_t)(ev.episode[e] + 1) : 0u;
         if (ev.episode) ev.episode[e] = (int32_t)epi;
         a0 = e_greedy(ag, a0, (uint32_t)e, epi, 0u);
+        if constexpr (EXT) a0 = taught_action(io, e, ag.A, a0);                                                    // :58-79
         ev.q_ant[(size_t)e * NANT + NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + a0];                 // :82
         if constexpr (EXT) {
             io.action_out[e] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + a0];
@@ -287,7 +302,8 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
     const long long tm1 = wall_clock64();
 #endif
     if (threadIdx.x == 0) {
-        const int chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
+        int chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
+        if constexpr (EXT) chosen = taught_action(io, e, ag.A, chosen);                               // :127-151: Q(s', a_teacher) below
         gs.best = chosen;
         sh.cur_q_ant[NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + chosen];                  // :151
         sh.ve2[NS] = gs.ave[chosen];

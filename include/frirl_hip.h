@@ -461,6 +461,52 @@ int frirl_hip_agent_begin(const frirl_hip_tables *t, const frirl_hip_rulebases *
 int frirl_hip_agent_observe(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                             const frirl_hip_envs *envs, const frirl_hip_agent_io *io, void *stream);
 
+/* ---- imitation: a teacher's action replaces the epsilon-greedy one (reference frirl_episode.c:58-79,127-151: original_learning == 0,
+ * keyaction; key 32 = "let the agent choose").  The calls above with one more array:
+ *   teacher [dev] [E] int32, or NULL = the untaught call, bit for bit.
+ * teacher[e] in 0..A-1: row e takes that action index instead of its epsilon-greedy pick -- io->action_out / io->action_idx carry
+ * it, q_ant (begin) / the new q_ant (observe) get its value, and the SARSA update runs towards Q(s', a_teacher)
+ * (frirl_episode.c:139,151,159).  Any other value: the row chooses for itself exactly as in the untaught call (the exploration
+ * stream is counter-based, so taught picks before it do not move its position).  Reset mask, done rows, agent->evaluate, status
+ * and the argument checks (FRIRL_HIP_EINVAL before FRIRL_HIP_ENODEV) are those of frirl_hip_agent_begin / _observe. */
+int frirl_hip_agent_begin_taught(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                 const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
+int frirl_hip_agent_observe_taught(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                   const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
+
+/* ---- one-launch replay of recorded demonstrations: every agent learns a log of (observation, action, reward, success) records in
+ * ONE launch, one workgroup per agent looping over its records; no environment runs.  nant 2..8, A 1..32, any Shepard power.
+ * Per record r of agent e (its log starts at record e * agent_stride of every array):
+ *   - a START record (record 0 always; record r when start[r] != 0) is frirl_hip_agent_begin_taught on that row alone with
+ *     obs and teacher = action[r];
+ *   - any other record is frirl_hip_agent_observe_taught on that row with obs, q_obs, reward, success and teacher = action[r] --
+ *     including "skipped while done[e] != 0": records after an episode's end, up to the next start, change nothing but
+ *     status (FRIRL_HIP_UPD_INACTIVE) and still count as consumed;
+ *   - a record whose action lies outside 0..A-1 ends that agent's replay before it (all remaining passes included).
+ * Every action is the log's, so a record costs two conclusions per rule, Q(s,a) and Q(s',a'), from one read of the rule base.
+ * Pass k + 1 starts again at record 0.  replayed[e] = records consumed over all passes; refused[e] = 1 iff an append was ever
+ * refused (FRIRL_HIP_UPD_FULL; envs->status only shows the last record).  `envs` is left as the per-record chain leaves it
+ * (episode, ep_steps, ep_reward, done, q_ant, states, fus, rant, spread_*; an agent that consumed nothing keeps what it had);
+ * consequents agree with the chain within the 1e-6 contract (same summation order: ~1e-15 in practice), decisions exactly.
+ * Limits: agent->max_steps must cover the longest logged episode (a longer one is cut there, as _observe would), and the launch
+ * runs passes * T records per agent back to back -- the caller bounds it.
+ * FRIRL_HIP_EINVAL, before the device: NULL demo / obs / action / reward / success, T < 1, passes outside 1..1024, agent_stride
+ * negative or 0 < agent_stride < T, and the argument checks of frirl_hip_agent_begin.  Does not synchronise. */
+typedef struct frirl_hip_demonstration {
+    int32_t T;                /* records per agent (capacity of each row of the arrays below)                                 */
+    int64_t agent_stride;     /* records between the logs of agent e and e+1; 0 = every agent replays ONE log                 */
+    const double  *obs;       /* [dev] [..][T][nant-1] what the environment returned on arriving here; the start observation for a start record */
+    const double  *q_obs;     /* [dev] same shape, the caller's quantised form, or NULL = the generic grid rule               */
+    const int32_t *action;    /* [dev] [..][T] index 0..A-1 of the action taken AT this observation                           */
+    const double  *reward;    /* [dev] [..][T] reward on arriving here (not read for a start record)                          */
+    const int32_t *success;   /* [dev] [..][T] likewise                                                                       */
+    const uint8_t *start;     /* [dev] [..][T] != 0: this record begins an episode; NULL = only record 0; record 0 always is one */
+    const int32_t *length;    /* [dev] [E] records of agent e (clamped to 0..T), or NULL = T                                  */
+} frirl_hip_demonstration;
+int frirl_hip_learn_demonstration(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                  const frirl_hip_envs *envs, const frirl_hip_demonstration *demo, int32_t passes,
+                                  int32_t *replayed /* [dev][E] or NULL */, uint8_t *refused /* [dev][E] or NULL */, void *stream);
+
 /* ---- frirl_test_run's greedy episode with the CALLER'S environment, Q rows on ONE shared rule base (b->E == 1) ----------------
  * frirl_hip_rollout_shared cut at the step boundary: frirl_episode with reduction_state == 1 (frirl_episode.c:28-194 without the
  * update at :155, so the rule base is read-only), the environment's three callbacks (:97,106,112) replaced by the caller's data in
