@@ -847,8 +847,51 @@ class PolicyBatchRows:
                                         _ptr(exclude_mask), _ptr(rule_slot), _ptr(rows_live))
 
 
-class BatchReducer:
+class _ReducerBase:
+    """What Reducer and BatchReducer share: the calls of a round on the handle self.h, named frirl_hip_<_name>_<call>."""
+    _name = None
+
+    def _call(self, call, *args):
+        fn = f"frirl_hip_{self._name}_{call}"
+        check(getattr(lib(), fn)(self.h, *args), fn)
+
+    def __init_subclass__(cls):
+        cls._observe_fn = f"frirl_hip_{cls._name}_observe"       # the per-step call: no name is built per step
+
+    def _begin_out(self, obs):
+        """The action tensors begin hands to the library, or None: fresh ones."""
+        return None
+
+    def begin(self, obs):
+        io, action, action_idx = _agent_io(self.problem, obs, E=self.Q, out=self._begin_out(obs))
+        self._call("begin", C.byref(io))
+        self._out = (action, action_idx)
+        return action, action_idx
+
+    def observe(self, obs, reward, success, q_obs=None, count_live=True):
+        """Returns (action values, action indices, rows still live or None when count_live is False: no synchronisation).  The
+        action tensors are those begin returned, updated in place: rows whose replay has ended keep their last action."""
+        io, action, action_idx = _agent_io(self.problem, obs, q_obs, reward, success, E=self.Q, out=getattr(self, "_out", None))
+        live = C.c_int32()
+        check(getattr(lib(), self._observe_fn)(self.h, C.byref(io), C.byref(live) if count_live else None), self._observe_fn)
+        return action, action_idx, (live.value if count_live else None)
+
+    def end_round(self):
+        self._call("end_round")
+
+    def close(self):
+        if self.h:
+            getattr(lib(), f"frirl_hip_{self._name}_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            self.close()
+
+
+class BatchReducer(_ReducerBase):
     """frirl_hip_batch_reducer: the rule-base reduction of EVERY rule base of `problem` with the caller's environment, round by round."""
+    _name = "batch_reducer"
 
     def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None, stream=None):
         import torch
@@ -867,28 +910,13 @@ class BatchReducer:
         """Rows of the next round: E rows in round 0 (the baseline replays), then E * (2^depth - 1); 0 = finished.  Row q belongs to
         agent q // rows_per_agent."""
         q, n, live = C.c_int32(), C.c_int32(), C.c_int32()
-        check(lib().frirl_hip_batch_reducer_next_round(self.h, C.byref(q), C.byref(n), C.byref(live)), "frirl_hip_batch_reducer_next_round")
+        self._call("next_round", C.byref(q), C.byref(n), C.byref(live))
         self.Q, self.rows_per_agent, self.agents_live = q.value, n.value, live.value
         return q.value
 
-    def begin(self, obs):
+    def _begin_out(self, obs):                  # rows that are never stepped hold action 0.0
         import torch
-        out = (torch.zeros((self.Q,), dtype=torch.float64, device=obs.device), torch.zeros((self.Q,), dtype=torch.int32, device=obs.device))
-        io, action, action_idx = _agent_io(self.problem, obs, E=self.Q, out=out)       # rows that are never stepped hold action 0.0
-        check(lib().frirl_hip_batch_reducer_begin(self.h, C.byref(io)), "frirl_hip_batch_reducer_begin")
-        self._out = (action, action_idx)
-        return action, action_idx
-
-    def observe(self, obs, reward, success, q_obs=None, count_live=True):
-        """Returns (action values, action indices, rows still live or None when count_live is False: no synchronisation).  The
-        action tensors are those begin returned, updated in place: rows whose replay has ended keep their last action."""
-        io, action, action_idx = _agent_io(self.problem, obs, q_obs, reward, success, E=self.Q, out=getattr(self, "_out", None))
-        live = C.c_int32()
-        check(lib().frirl_hip_batch_reducer_observe(self.h, C.byref(io), C.byref(live) if count_live else None), "frirl_hip_batch_reducer_observe")
-        return action, action_idx, (live.value if count_live else None)
-
-    def end_round(self):
-        check(lib().frirl_hip_batch_reducer_end_round(self.h), "frirl_hip_batch_reducer_end_round")
+        return (torch.zeros((self.Q,), dtype=torch.float64, device=obs.device), torch.zeros((self.Q,), dtype=torch.int32, device=obs.device))
 
     def row_done(self):
         """[Q] int32 view of the reducer's own `done` array: 1 = the caller need not step this row."""
@@ -905,21 +933,13 @@ class BatchReducer:
         E = self.problem.E
         kept = np.zeros((E, self.problem.maxR), dtype=np.int32)
         res = (ReduceResult * E)()
-        check(lib().frirl_hip_batch_reducer_result(self.h, kept.ctypes.data_as(C.POINTER(C.c_int32)), res), "frirl_hip_batch_reducer_result")
+        self._call("result", kept.ctypes.data_as(C.POINTER(C.c_int32)), res)
         return [kept[e, : res[e].rules_after].copy() for e in range(E)], list(res)
 
-    def close(self):
-        if self.h:
-            lib().frirl_hip_batch_reducer_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            self.close()
-
-
-class Reducer:
+class Reducer(_ReducerBase):
     """frirl_hip_reducer: the rule-base reduction of ONE rule base (problem.E == 1) with the caller's environment, round by round."""
+    _name = "reducer"
 
     def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, stream=None):
         assert problem.E == 1
@@ -933,87 +953,51 @@ class Reducer:
     def next_round(self):
         """Rows to replay from the start state in the next round (round 0: the baseline replay, 1 row); 0 = finished."""
         q = C.c_int32()
-        check(lib().frirl_hip_reducer_next_round(self.h, C.byref(q)), "frirl_hip_reducer_next_round")
+        self._call("next_round", C.byref(q))
         self.Q = q.value
         return q.value
-
-    def begin(self, obs):
-        io, action, action_idx = _agent_io(self.problem, obs, E=self.Q)
-        check(lib().frirl_hip_reducer_begin(self.h, C.byref(io)), "frirl_hip_reducer_begin")
-        self._out = (action, action_idx)
-        return action, action_idx
-
-    def observe(self, obs, reward, success, q_obs=None, count_live=True):
-        """Returns (action values, action indices, rows still live or None when count_live is False: no synchronisation).  The
-        action tensors are those begin returned, updated in place: rows whose replay has ended keep their last action."""
-        io, action, action_idx = _agent_io(self.problem, obs, q_obs, reward, success, E=self.Q, out=getattr(self, "_out", None))
-        live = C.c_int32()
-        check(lib().frirl_hip_reducer_observe(self.h, C.byref(io), C.byref(live) if count_live else None), "frirl_hip_reducer_observe")
-        return action, action_idx, (live.value if count_live else None)
-
-    def end_round(self):
-        check(lib().frirl_hip_reducer_end_round(self.h), "frirl_hip_reducer_end_round")
 
     def result(self):
         """(kept original indices, ReduceResult) so far."""
         import numpy as np
         kept = np.zeros(self.R0, dtype=np.int32)
         res = ReduceResult()
-        check(lib().frirl_hip_reducer_result(self.h, kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)), "frirl_hip_reducer_result")
+        self._call("result", kept.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res))
         return kept[: res.rules_after], res
 
-    def close(self):
-        if self.h:
-            lib().frirl_hip_reducer_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            self.close()
+def _reduce_rounds(red, reset_fn, step_fn):
+    """The round loop of reduce_external / reduce_external_batch on an open reducer; reset_fn(red) -> obs of the round's rows."""
+    import torch
+    try:
+        while red.next_round() > 0:
+            states = reset_fn(red).contiguous()
+            action, _ = red.begin(states)
+            live = red.Q
+            while live > 0:
+                out = step_fn(states, action)
+                obs, reward, success = out[0].contiguous(), out[1].contiguous(), out[2].to(torch.int32).contiguous()
+                nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
+                states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
+            red.end_round()
+        return red.result()
+    finally:
+        red.close()
 
 
 def reduce_external(problem, agent, reset_fn, step_fn, strategy, reward_tolerance=0.0, depth=0, rant=None):
     """The reduction's round loop with the caller's environment: reset_fn(Q) -> obs [Q, nant-1] (Q environments at the start state),
     step_fn(states, action) -> obs, reward, success or obs, reward, success, q_obs (q_obs: the environment's own quantiser).
     Returns (kept original indices, ReduceResult); compacts problem's rule base in place."""
-    import torch
-    red = Reducer(problem, agent, strategy, reward_tolerance, depth, rant)
-    try:
-        while red.next_round() > 0:
-            states = reset_fn(red.Q).contiguous()
-            action, _ = red.begin(states)
-            live = red.Q
-            while live > 0:
-                out = step_fn(states, action)
-                obs, reward, success = out[0].contiguous(), out[1].contiguous(), out[2].to(torch.int32).contiguous()
-                nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
-                states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
-            red.end_round()
-        return red.result()
-    finally:
-        red.close()
+    return _reduce_rounds(Reducer(problem, agent, strategy, reward_tolerance, depth, rant), lambda red: reset_fn(red.Q), step_fn)
 
 
 def reduce_external_batch(problem, agent, reset_fn, step_fn, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None):
     """The batched reduction's round loop with the caller's environment, every rule base of `problem` at once:
     reset_fn(Q, rows_per_agent) -> obs [Q, nant-1] with agent q // rows_per_agent's start state in row q; step_fn as for
     reduce_external.  Returns (list of kept original indices, list of ReduceResult), as Problem.reduce_batch; compacts in place."""
-    import torch
-    red = BatchReducer(problem, agent, strategy, reward_tolerance, depth, rant, active)
-    try:
-        while red.next_round() > 0:
-            states = reset_fn(red.Q, red.rows_per_agent).contiguous()
-            action, _ = red.begin(states)
-            live = red.Q
-            while live > 0:
-                out = step_fn(states, action)
-                obs, reward, success = out[0].contiguous(), out[1].contiguous(), out[2].to(torch.int32).contiguous()
-                nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
-                states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
-            red.end_round()
-        return red.result()
-    finally:
-        red.close()
+    return _reduce_rounds(BatchReducer(problem, agent, strategy, reward_tolerance, depth, rant, active),
+                          lambda red: reset_fn(red.Q, red.rows_per_agent), step_fn)
 
 
 def dist():

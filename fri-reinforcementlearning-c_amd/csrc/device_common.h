@@ -146,6 +146,12 @@ int check_launch(const char *what);       // hipGetLastError -> code
 int check_tables(const frirl_hip_tables *t);
 int check_rulebases(const frirl_hip_tables *t, const frirl_hip_rulebases *b);
 int check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who);   // shared.hip: env_kind names a demo with t->nant antecedents
+int check_grid_len(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who);    // shared.hip: every grid_len[k] in 1..FRIRL_HIP_MAX_GRID
+// policy.hip, for the caller-stepped roll-outs on one rule base and on many: nant 2..8, rule bases, agent, A 1..32, grids, action grid;
+// the caller's step data
+int check_policy_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const char *who);
+int check_policy_io(const frirl_hip_agent_io *io, bool begin, const char *who);
+#define FRIRL_POLICY_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)      // antecedent counts the policy kernels are instantiated for
 int check_agent_shape(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
                       const char *who);   // agent.hip: nant 2..8, rule bases, grids, A 1..32, env state; not the device
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }

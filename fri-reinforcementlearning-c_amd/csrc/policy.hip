@@ -3,67 +3,59 @@
 // The kernels are policy_kernel.h, instantiated per antecedent count in policy_i<N>.hip; the reduction's host logic is reduce_plan.h,
 // shared with frirl_hip_reduce_shared.
 #include "reduce_plan.h"
+#include "shape_ladder.h"
 #include <new>
 
 using namespace frirl_host;
 
-#define FRIRL_POLICY_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
 #define M(N) void frirl_policy_launch_##N(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
                                           const frirl_hip_policy_rows *rows, const frirl_hip_agent_io *io, int begin, int G, int H, hipStream_t s);
 FRIRL_POLICY_NANT_CASES(M)
 #undef M
 
-// Lanes per row and rule slices per conclusion: the selection rule of frirl_hip_rollout_shared's tiled kernel (shared.hip:
-// rollout_group / rollout_slices).  One lane per row once the rows alone fill the chip, else the actions split over 4 (A <= 4) or 8
-// lanes; rule slices while the launch stays under ~2048 waves.  Kept as they are after measuring every shape on the 367-rule acrobot
-// base (profiles/r07_policy_reduce.md, tools/policy_bench.py): at Q = 1023 the rule chosen here, (4, 8), is the fastest call (12.4 us
-// against 16.5 / 47 / 103 us for (4, 4) / (4, 1) / (1, 1)); at Q = 65 536 it chooses (4, 1), 93 us, level with the best.
-static int policy_group(int Q, int A)
-{
-    { const int g = opts().policy_group; if (g == 1 || (g == 4 && A <= 4) || (g == 8 && A > 4)) return g; }
-    if (A < 2 || Q >= 131072) return 1;
-    return A <= 4 ? 4 : 8;
-}
-
-static int policy_slices(int Q, int G)
-{
-    if (G == 1) return 1;
-    { const int v = opts().policy_slices; if (v == 1 || v == 4 || v == 8) return v; }
-    const long waves1 = ((long)Q * G + 63) / 64;
-    return waves1 * 8 <= 2048 ? 8 : (waves1 * 4 <= 2048 ? 4 : 1);
-}
-
-static int check_policy_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const char *who)
+int frirl_host::check_policy_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const char *who)
 {
     if (!t || t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t ? t->nant : 0); return FRIRL_HIP_EINVAL; }
     int rc = check_rulebases(t, b);
     if (rc) return rc;
-    if (b->E != 1) { set_error("%s: needs ONE shared rule base (E == 1), got E=%d", who, b->E); return FRIRL_HIP_EINVAL; }
     if (!a || !a->grid_values || !a->action_ve) { set_error("%s: NULL agent / grid_values / action_ve", who); return FRIRL_HIP_EINVAL; }
     if (a->A < 1 || a->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, a->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
-    for (int k = 0; k < t->nant; k++)
-        if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_grid_len(t, a, who))) return rc;
     if (a->grid_len[t->nant - 1] != a->A) { set_error("%s: the action grid has %d values, A=%d", who, a->grid_len[t->nant - 1], a->A); return FRIRL_HIP_EINVAL; }
     return FRIRL_HIP_OK;
 }
 
-static int check_policy_io(const frirl_hip_agent_io *io, bool begin, const char *who)
+int frirl_host::check_policy_io(const frirl_hip_agent_io *io, bool begin, const char *who)
 {
     if (!io || !io->obs || !io->action_out) { set_error("%s: NULL io / io->obs / io->action_out", who); return FRIRL_HIP_EINVAL; }
     if (!begin && (!io->reward || !io->success)) { set_error("%s: NULL io->reward / io->success", who); return FRIRL_HIP_EINVAL; }
     return FRIRL_HIP_OK;
 }
 
+// the forms on ONE shared rule base
+static int check_policy_one(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const char *who)
+{
+    const int rc = check_policy_args(t, b, a, who);
+    if (rc) return rc;
+    if (b->E != 1) { set_error("%s: needs ONE shared rule base (E == 1), got E=%d", who, b->E); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+// Lanes per row and rule slices per conclusion follow the selection rule of frirl_hip_rollout_shared's tiled kernel (lane_group /
+// lane_slices, shape_ladder.h), read from the options policy_group / policy_slices.  Kept as they are after measuring every shape on
+// the 367-rule acrobot base (profiles/r07_policy_reduce.md, tools/policy_bench.py): at Q = 1023 the rule chosen there, (4, 8), is
+// the fastest call (12.4 us against 16.5 / 47 / 103 us for (4, 4) / (4, 1) / (1, 1)); at Q = 65 536 it chooses (4, 1), 93 us, level
+// with the best.
 static int policy_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_policy_rows *rows,
                        const frirl_hip_agent_io *io, void *stream, bool begin, const char *who)
 {
-    int rc = check_policy_args(t, b, agent, who);
+    int rc = check_policy_one(t, b, agent, who);
     if (rc) return rc;
     if (!rows || !rows->done || !rows->ep_steps || !rows->success || !rows->ep_reward) { set_error("%s: NULL row state", who); return FRIRL_HIP_EINVAL; }
     if (rows->Q < 1) { set_error("%s: Q=%d < 1", who, rows->Q); return FRIRL_HIP_EINVAL; }
     if ((rows->exclude_mask == nullptr) != (rows->rule_slot == nullptr)) { set_error("%s: exclude_mask and rule_slot go together", who); return FRIRL_HIP_EINVAL; }
     if ((rc = check_policy_io(io, begin, who)) || (rc = check_device())) return rc;
-    const int G = policy_group(rows->Q, agent->A), H = policy_slices(rows->Q, G);
+    const int G = lane_group(opts().policy_group, rows->Q, agent->A), H = lane_slices(opts().policy_slices, rows->Q, G);
     switch (t->nant) {
 #define M(N) case N: frirl_policy_launch_##N(t, b, agent, rows, io, begin ? 1 : 0, G, H, as_stream(stream)); break;
         FRIRL_POLICY_NANT_CASES(M)
@@ -122,10 +114,10 @@ extern "C" frirl_hip_reducer *frirl_hip_reducer_create(const frirl_hip_tables *t
                                                        int strategy, double reward_tolerance, int depth, void *stream)
 {
     const char *who = "frirl_hip_reducer_create";
-    if (check_policy_args(t, b, agent, who)) return nullptr;
+    if (check_policy_one(t, b, agent, who)) return nullptr;
     if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return nullptr; }
     if (depth == 0) depth = 10;
-    if (depth < 1 || depth > 12) { set_error("%s: depth %d outside 1..12", who, depth); return nullptr; }
+    if (depth < 1 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 1..%d", who, depth, frirl::RW_MAX_DEPTH); return nullptr; }
     if (agent->max_steps < 0) { set_error("%s: max_steps=%d < 0", who, agent->max_steps); return nullptr; }
     if (check_device()) return nullptr;
     frirl_hip_reducer *r = new (std::nothrow) frirl_hip_reducer;

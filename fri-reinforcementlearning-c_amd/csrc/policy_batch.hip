@@ -9,7 +9,6 @@
 #include "reduce_batch_kernels.h"
 #include <new>
 
-#define FRIRL_POLICY_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
 #define M(N) void frirl_policy_batch_launch_##N(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
                                                 const frirl::PolicyBatchArgs *pa, const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s);
 FRIRL_POLICY_NANT_CASES(M)
@@ -23,26 +22,6 @@ static int policy_batch_slices(long rows, int n, int A)
     { const int v = opts().policy_slices; if (v == 1 || v == 4 || v == 8) return v; }
     if (n == 1) return FRIRL_WAVE / rb_group(A);
     return rb_slices(rows, A);
-}
-
-static int check_policy_batch_args(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *a, const char *who)
-{
-    if (!t || t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t ? t->nant : 0); return FRIRL_HIP_EINVAL; }
-    int rc = check_rulebases(t, b);
-    if (rc) return rc;
-    if (!a || !a->grid_values || !a->action_ve) { set_error("%s: NULL agent / grid_values / action_ve", who); return FRIRL_HIP_EINVAL; }
-    if (a->A < 1 || a->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, a->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
-    for (int k = 0; k < t->nant; k++)
-        if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
-    if (a->grid_len[t->nant - 1] != a->A) { set_error("%s: the action grid has %d values, A=%d", who, a->grid_len[t->nant - 1], a->A); return FRIRL_HIP_EINVAL; }
-    return FRIRL_HIP_OK;
-}
-
-static int check_policy_batch_io(const frirl_hip_agent_io *io, bool begin, const char *who)
-{
-    if (!io || !io->obs || !io->action_out) { set_error("%s: NULL io / io->obs / io->action_out", who); return FRIRL_HIP_EINVAL; }
-    if (!begin && (!io->reward || !io->success)) { set_error("%s: NULL io->reward / io->success", who); return FRIRL_HIP_EINVAL; }
-    return FRIRL_HIP_OK;
 }
 
 static void policy_batch_launch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl::PolicyBatchArgs *pa,
@@ -59,13 +38,13 @@ static void policy_batch_launch(const frirl_hip_tables *t, const frirl_hip_ruleb
 static int policy_batch_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_policy_batch_rows *rows,
                              const frirl_hip_agent_io *io, void *stream, bool begin, const char *who)
 {
-    int rc = check_policy_batch_args(t, b, agent, who);
+    int rc = check_policy_args(t, b, agent, who);
     if (rc) return rc;
     if (!rows || !rows->done || !rows->ep_steps || !rows->success || !rows->ep_reward) { set_error("%s: NULL row state", who); return FRIRL_HIP_EINVAL; }
     if (rows->n < 1 || (long)rows->n * b->E > 0x7fffffffL) { set_error("%s: n=%d < 1 or E * n beyond 2^31 - 1", who, rows->n); return FRIRL_HIP_EINVAL; }
     if ((rows->exclude_mask == nullptr) != (rows->rule_slot == nullptr)) { set_error("%s: exclude_mask and rule_slot go together", who); return FRIRL_HIP_EINVAL; }
     if (rows->agents && (rows->nagents < 1 || rows->nagents > b->E)) { set_error("%s: nagents=%d outside 1..E=%d", who, rows->nagents, b->E); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_policy_batch_io(io, begin, who)) || (rc = check_device())) return rc;
+    if ((rc = check_policy_io(io, begin, who)) || (rc = check_device())) return rc;
     frirl::PolicyBatchArgs pa = {};
     pa.rows = *rows;
     pa.list = rows->agents;
@@ -160,7 +139,7 @@ extern "C" frirl_hip_batch_reducer *frirl_hip_batch_reducer_create(const frirl_h
                                                                    void *stream)
 {
     const char *who = "frirl_hip_batch_reducer_create";
-    if (check_policy_batch_args(t, b, agent, who)) return nullptr;
+    if (check_policy_args(t, b, agent, who)) return nullptr;
     if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return nullptr; }
     if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return nullptr; }
     if (agent->max_steps < 0) { set_error("%s: max_steps=%d < 0", who, agent->max_steps); return nullptr; }
@@ -237,7 +216,7 @@ extern "C" int frirl_hip_batch_reducer_begin(frirl_hip_batch_reducer *r, const f
     const char *who = "frirl_hip_batch_reducer_begin";
     if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::OPEN) { set_error("%s: no open round (frirl_hip_batch_reducer_next_round first; one begin per round)", who); return FRIRL_HIP_EINVAL; }
-    int rc = check_policy_batch_io(io, true, who);
+    int rc = check_policy_io(io, true, who);
     if (rc) return rc;
     frirl_hip_agent_io all = *io;
     all.reset = nullptr;                                              // every row of the round starts
@@ -251,7 +230,7 @@ extern "C" int frirl_hip_batch_reducer_observe(frirl_hip_batch_reducer *r, const
     const char *who = "frirl_hip_batch_reducer_observe";
     if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::RUNNING) { set_error("%s: no running round (frirl_hip_batch_reducer_begin first)", who); return FRIRL_HIP_EINVAL; }
-    int rc = check_policy_batch_io(io, false, who);
+    int rc = check_policy_io(io, false, who);
     if (rc || (rc = batch_reducer_step(r, io, 0, who)) || !rows_live) return rc;
     if ((rc = batch_reducer_header(r, who))) return rc;
     r->live_known = true;

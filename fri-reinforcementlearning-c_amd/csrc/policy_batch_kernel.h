@@ -4,10 +4,8 @@
 // observation handling, sweep, first maximum, epsilon-greedy, bookkeeping -- is policy_step_kernel's (frirl_episode.c:28-194 with
 // reduction_state == 1).  Instantiated per antecedent count in policy_batch_i<N>.hip.
 #pragma once
-#include "shared_sweep.h"
-#include "envs.h"
+#include "policy_kernel.h"
 #include "reduce_walk.h"
-#include <type_traits>
 
 namespace frirl {
 
@@ -138,29 +136,15 @@ static void launch_policy_batch(const frirl_hip_tables *t, const frirl_hip_ruleb
         hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, false, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa);
 }
 
-// The lane shapes of the batched reduction's roll-out kernel (reduce_batch.hip: launch_rows_n): G = 4 lanes per row with one
-// conclusion each for up to 4 actions, else 8 lanes with chunks of 4; H = 1 / 4 / 8 rule slices, 16 (G = 4) = a full wave per row.
-// H is chosen by policy_batch.hip.
+// the lane shapes of the batched reduction's roll-out kernel (for_batch_shape, shape_ladder.h); H is chosen by policy_batch.hip
 template <int N>
 static void launch_policy_batch_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const PolicyBatchArgs *pa,
                                   const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s)
 {
-    const bool few = ag->A <= 4;
-    if (ag->p > 0 && ag->p != N) {          // run-time Shepard power: the variants without rule slices
-        if (few) launch_policy_batch<N, 1, 4, 1, false>(t, b, ag, pa, io, begin, nlist, s);
-        else launch_policy_batch<N, 4, 8, 1, false>(t, b, ag, pa, io, begin, nlist, s);
-        return;
-    }
-    if (few) {
-        if (H == 16) launch_policy_batch<N, 1, 4, 16>(t, b, ag, pa, io, begin, nlist, s);
-        else if (H == 8) launch_policy_batch<N, 1, 4, 8>(t, b, ag, pa, io, begin, nlist, s);
-        else if (H == 4) launch_policy_batch<N, 1, 4, 4>(t, b, ag, pa, io, begin, nlist, s);
-        else launch_policy_batch<N, 1, 4, 1>(t, b, ag, pa, io, begin, nlist, s);
-    } else {
-        if (H == 8) launch_policy_batch<N, 4, 8, 8>(t, b, ag, pa, io, begin, nlist, s);
-        else if (H == 4) launch_policy_batch<N, 4, 8, 4>(t, b, ag, pa, io, begin, nlist, s);
-        else launch_policy_batch<N, 4, 8, 1>(t, b, ag, pa, io, begin, nlist, s);
-    }
+    for_batch_shape<N>(ag, H, [&](auto sh) {
+        using S = decltype(sh);
+        launch_policy_batch<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, pa, io, begin, nlist, s);
+    });
 }
 
 }  // namespace frirl

@@ -5,6 +5,7 @@
 // lives in the caller's arrays (frirl_hip_policy_rows).  Instantiated per antecedent count in policy_i<N>.hip.
 #pragma once
 #include "shared_sweep.h"
+#include "shape_ladder.h"
 #include "envs.h"
 #include <type_traits>
 
@@ -96,31 +97,15 @@ static void launch_policy(const frirl_hip_tables *t, const frirl_hip_rulebases *
         hipLaunchKernelGGL((policy_step_kernel<N, AMAX, G, H, false, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *rows, *io, begin);
 }
 
-template <int N, int AMAX, int G>
-static void launch_policy_h(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_policy_rows *rows,
-                            const frirl_hip_agent_io *io, int begin, int H, hipStream_t s)
-{
-    if (H == 8) launch_policy<N, AMAX, G, 8>(t, b, ag, rows, io, begin, s);
-    else if (H == 4) launch_policy<N, AMAX, G, 4>(t, b, ag, rows, io, begin, s);
-    else launch_policy<N, AMAX, G, 1>(t, b, ag, rows, io, begin, s);
-}
-
-// G (1, 4 with A <= 4, 8 with A > 4) and H (1 / 4 / 8, 1 when G == 1 or the Shepard power is not the default) are chosen by policy.hip
+// G and H are chosen by policy.hip (lane_group / lane_slices); the compiled variant: for_shared_shape (shape_ladder.h)
 template <int N>
 static void launch_policy_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_policy_rows *rows,
                             const frirl_hip_agent_io *io, int begin, int G, int H, hipStream_t s)
 {
-    if (ag->p > 0 && ag->p != N) {          // run-time Shepard power: the variants without rule slices
-        if (G == 4) launch_policy<N, 1, 4, 1, false>(t, b, ag, rows, io, begin, s);
-        else if (G == 8) launch_policy<N, 4, 8, 1, false>(t, b, ag, rows, io, begin, s);
-        else if (ag->A <= 4) launch_policy<N, 4, 1, 1, false>(t, b, ag, rows, io, begin, s);
-        else launch_policy<N, 8, 1, 1, false>(t, b, ag, rows, io, begin, s);
-        return;
-    }
-    if (G == 4) launch_policy_h<N, 1, 4>(t, b, ag, rows, io, begin, H, s);
-    else if (G == 8) launch_policy_h<N, 4, 8>(t, b, ag, rows, io, begin, H, s);
-    else if (ag->A <= 4) launch_policy<N, 4, 1, 1>(t, b, ag, rows, io, begin, s);
-    else launch_policy<N, 8, 1, 1>(t, b, ag, rows, io, begin, s);
+    for_shared_shape<N>(ag, G, H, [&](auto sh) {
+        using S = decltype(sh);
+        launch_policy<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, rows, io, begin, s);
+    });
 }
 
 }  // namespace frirl

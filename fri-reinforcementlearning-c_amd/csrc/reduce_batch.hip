@@ -9,6 +9,7 @@
 // and the host reads one 16-byte header (the live count) per round.  No slab and no per-row result crosses to the host.
 #include "rollout_episode.h"
 #include "reduce_batch_kernels.h"
+#include "shape_ladder.h"
 
 namespace frirl {
 
@@ -76,28 +77,15 @@ static void launch_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b,
                        b->nrules, b->maxR, *ag, start, cur, wpa, first, ws);
 }
 
-
 template <int N>
 static void launch_rows_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const double *start, int cur, int nlive,
                           int nodes, int first, const ReduceBatchWs &ws, hipStream_t s)
 {
-    const bool few = ag->A <= 4;
-    if (ag->p > 0 && ag->p != N) {          // run-time Shepard power: the variants without rule slices, as frirl_hip_rollout_shared
-        if (few) launch_rows<N, 1, 4, 1, false>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else launch_rows<N, 4, 8, 1, false>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        return;
-    }
-    const int H = first ? (few ? 16 : 8) : rb_slices((long)nlive * nodes, ag->A);
-    if (few) {
-        if (H == 16) launch_rows<N, 1, 4, 16>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else if (H == 8) launch_rows<N, 1, 4, 8>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else if (H == 4) launch_rows<N, 1, 4, 4>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else launch_rows<N, 1, 4, 1>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-    } else {
-        if (H == 8) launch_rows<N, 4, 8, 8>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else if (H == 4) launch_rows<N, 4, 8, 4>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-        else launch_rows<N, 4, 8, 1>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
-    }
+    const int H = first ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)nlive * nodes, ag->A);     // the baseline replay: a full wave per row
+    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+        using S = decltype(sh);
+        launch_rows<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
+    });
 }
 
 extern "C" int frirl_hip_reduce_walk_check(int d, const int32_t *steps, const double *reward, int steps_inc, double prev_reward, double good_above,
@@ -125,8 +113,7 @@ extern "C" int frirl_hip_reduce_batch(const frirl_hip_tables *t, const frirl_hip
     if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return FRIRL_HIP_EINVAL; }
     if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
     if ((rc = check_demo_kind(t, agent, who))) return rc;
-    for (int k = 0; k < t->nant; k++)
-        if (agent->grid_len[k] < 1 || agent->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, agent->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_grid_len(t, agent, who))) return rc;
     if (depth == 0) depth = frirl_hip_reduce_batch_depth(b->E, agent->A);
     const size_t E = (size_t)b->E, M = (size_t)b->maxR;
     const int nodes = frirl::rw_nodes(depth);

@@ -1,9 +1,11 @@
 // reduce_plan.h -- host side of the speculative try-remove reduction (frirl_sequential_run.c:170-350; include/frirl_hip.h):
-// candidate order, the mask table of a round's accept/reject tree, the tree walk and the compaction.  One helper for both forms:
+// the host copies of the rule base, the slot and mask tables of a round's accept/reject tree and the compaction; the order, the
+// masks, the walk and the drop flags themselves are reduce_walk.h's, as in the batched reduction's kernels.  One helper for both forms:
 // frirl_hip_reduce_shared (shared.hip: the replays run the demo dynamics in the kernel) and frirl_hip_reducer_* (policy.hip: the
 // caller steps the environment).  Neither form owns a second copy of this logic.
 #pragma once
 #include "device_common.h"
+#include "reduce_walk.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -26,7 +28,7 @@ struct ReducePlan {
     int R0 = 0, R = 0, j = 0, d = 0, rounds = 0, rollouts = 0, steps_inc = 0;
     double prev_reward = 0.0;
 
-    int lanes_max() const { return (1 << depth) - 1; }
+    int lanes_max() const { return frirl::rw_nodes(depth); }
     bool finished() const { return j >= R0; }
 
 #define FRIRL_PLAN_TRY(expr)                                                                                       \
@@ -50,19 +52,19 @@ struct ReducePlan {
         if (rant) { rants.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(rants.data(), rant, rants.size() * sizeof(double), hipMemcpyDeviceToHost, s)); }
         if (b.uidx) { idx.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(idx.data(), b.uidx, idx.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s)); }
         FRIRL_PLAN_TRY(hipStreamSynchronize(s));
-        // candidate order: the reference rescans for the first minimum (strategy 1, `mvalue > fabs(..)` :268) or the first
-        // maximum (strategy 2, :286) of the not-yet-tested consequents after every episode; the consequents never change and
-        // removals keep the relative rule order, so that is a stable sort, fixed up front
+        // candidate order: the reference rescans for the first minimum (strategy 1) or the first maximum (strategy 2) of the
+        // not-yet-tested consequents after every episode; the consequents never change and removals keep the relative rule order,
+        // so that is the strict total order rw_before, fixed up front
         const double *qcol = slab.data() + (size_t)nant * col;
         order.resize(R0);
         std::iota(order.begin(), order.end(), 0);
-        if (strategy == 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) < std::fabs(qcol[c]); });
-        else std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return std::fabs(qcol[a]) > std::fabs(qcol[c]); });
+        std::sort(order.begin(), order.end(), [&](int a, int c) { return frirl::rw_before(std::fabs(qcol[a]), a, std::fabs(qcol[c]), c, strategy); });
         alive.resize(R0);
         std::iota(alive.begin(), alive.end(), 0);
         where.resize(R0);
         slot.resize(col);
         mask.resize(lanes_max());
+        for (size_t n = 0; n < mask.size(); n++) mask[n] = frirl::rw_node_mask((uint32_t)n);     // the same in every round
         j = d = rounds = 0;
         return FRIRL_HIP_OK;
     }
@@ -79,13 +81,11 @@ struct ReducePlan {
         *lanes = 0;
         if (finished()) return FRIRL_HIP_OK;
         d = std::min(depth, R0 - j);
-        const int n = (1 << d) - 1;
+        const int n = frirl::rw_nodes(d);
         std::fill(where.begin(), where.end(), -1);
         for (int i = 0; i < R; i++) where[alive[i]] = i;
         std::fill(slot.begin(), slot.end(), (uint8_t)255);
         for (int i = 0; i < d; i++) slot[where[order[j + i]]] = (uint8_t)i;
-        for (int k = 0; k < d; k++)                                   // node (k, bits): candidates j..j+k-1 had outcomes `bits`, candidate j+k is on trial
-            for (uint32_t bits = 0; bits < (1u << k); bits++) mask[(1u << k) - 1 + bits] = bits | (1u << k);
         FRIRL_PLAN_TRY(hipMemcpyAsync(d_slot, slot.data(), (size_t)maxR, hipMemcpyHostToDevice, s));
         FRIRL_PLAN_TRY(hipMemcpyAsync(d_mask, mask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
         *lanes = n;
@@ -97,22 +97,12 @@ struct ReducePlan {
     {
         const size_t col = (size_t)maxR;
         rounds++;
-        rollouts += (1 << d) - 1;
-        uint32_t bits = 0;
-        for (int k = 0; k < d; k++) {
-            const uint32_t lane = (1u << k) - 1 + bits;
-            const double diff = prev_reward - reward[lane];
-            if (reward[lane] > reward_good_above && steps[lane] == steps_inc && std::fabs(diff) <= reward_tolerance) {   // :212
-                bits |= 1u << k;
-                prev_reward = reward[lane];                           // :222
-            }
-        }
+        rollouts += frirl::rw_nodes(d);
+        const uint32_t bits = frirl::rw_walk(d, steps, reward, steps_inc, prev_reward, reward_good_above, reward_tolerance);   // :212, :222
         if (bits) {                                                   // five_remove_rule of every accepted candidate: compact all columns
-            std::vector<char> drop(R, 0);
-            for (int i = 0; i < d; i++) if ((bits >> i) & 1u) drop[where[order[j + i]]] = 1;
             int w = 0;
             for (int r = 0; r < R; r++) {
-                if (drop[r]) continue;
+                if (frirl::rw_dropped(slot[r], bits)) continue;
                 if (w != r) {
                     for (int k = 0; k <= nant; k++) slab[(size_t)k * col + w] = slab[(size_t)k * col + r];
                     if (rant) for (int k = 0; k < nant; k++) rants[(size_t)k * col + w] = rants[(size_t)k * col + r];

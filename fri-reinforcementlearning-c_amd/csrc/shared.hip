@@ -8,6 +8,7 @@
 // (lane, rule, action).
 #include "rollout_episode.h"
 #include "reduce_plan.h"
+#include "shape_ladder.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -98,6 +99,13 @@ static int check_shared(const frirl_hip_tables *t, const frirl_hip_rulebases *b,
     return rc ? rc : check_device();
 }
 
+int frirl_host::check_grid_len(const frirl_hip_tables *t, const frirl_hip_agent *a, const char *who)
+{
+    for (int k = 0; k < t->nant; k++)
+        if (a->grid_len[k] < 1 || a->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("%s: grid_len[%d]=%d outside 1..%d", who, k, a->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
 // the roll-outs run the demo dynamics on the device: env_kind must name one of them, with its antecedent count
 int frirl_host::check_demo_kind(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who)
 {
@@ -159,50 +167,16 @@ static void launch_rollout(const frirl_hip_tables *t, const frirl_hip_rulebases 
         hipLaunchKernelGGL((frirl::rollout_shared_kernel<N, AMAX, G, H, false, PN>), grid, dim3(frirl::SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, Q, *ro, run_if);
 }
 
-// lanes per environment: 1 once the environments alone fill the chip, else split the actions over 4 (A <= 4) or 8 lanes
-static int rollout_group(int Q, int A)
-{
-    { const int g = frirl_host::opts().rollout_group; if (g == 1 || (g == 4 && A <= 4) || (g == 8 && A > 4)) return g; }
-    if (A < 2 || Q >= 131072) return 1;
-    return A <= 4 ? 4 : 8;
-}
-
-// rule slices per conclusion (G > 1 only): the replays of the reduction run ~1000 environments, one step is then a
-// latency chain over the rules -- 4 or 8 lanes share it while the launch stays under ~2048 waves
-static int rollout_slices(int Q, int G)
-{
-    if (G == 1) return 1;
-    { const int v = frirl_host::opts().rollout_slices; if (v == 1 || v == 4 || v == 8) return v; }
-    const long waves1 = ((long)Q * G + 63) / 64;
-    return waves1 * 8 <= 2048 ? 8 : (waves1 * 4 <= 2048 ? 4 : 1);
-}
-
-template <int N, int AMAX, int G>
-static void launch_rollout_h(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, int Q, const frirl_hip_rollout *ro,
-                             hipStream_t s, const unsigned *run_if)
-{
-    const int H = rollout_slices(Q, G);
-    if (H == 8) launch_rollout<N, AMAX, G, 8>(t, b, ag, Q, ro, s, run_if);
-    else if (H == 4) launch_rollout<N, AMAX, G, 4>(t, b, ag, Q, ro, s, run_if);
-    else launch_rollout<N, AMAX, G, 1>(t, b, ag, Q, ro, s, run_if);
-}
-
+// lanes per environment and rule slices: lane_group / lane_slices; the compiled variant: for_shared_shape (shape_ladder.h)
 template <int N>
 static void launch_rollout_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, int Q, const frirl_hip_rollout *ro,
                              hipStream_t s, const unsigned *run_if)
 {
-    const int G = rollout_group(Q, ag->A);
-    if (ag->p > 0 && ag->p != N) {          // run-time Shepard power: the variants without rule slices
-        if (G == 4) launch_rollout<N, 1, 4, 1, false>(t, b, ag, Q, ro, s, run_if);
-        else if (G == 8) launch_rollout<N, 4, 8, 1, false>(t, b, ag, Q, ro, s, run_if);
-        else if (ag->A <= 4) launch_rollout<N, 4, 1, 1, false>(t, b, ag, Q, ro, s, run_if);
-        else launch_rollout<N, 8, 1, 1, false>(t, b, ag, Q, ro, s, run_if);
-        return;
-    }
-    if (G == 4) launch_rollout_h<N, 1, 4>(t, b, ag, Q, ro, s, run_if);
-    else if (G == 8) launch_rollout_h<N, 4, 8>(t, b, ag, Q, ro, s, run_if);
-    else if (ag->A <= 4) launch_rollout<N, 4, 1, 1>(t, b, ag, Q, ro, s, run_if);
-    else launch_rollout<N, 8, 1, 1>(t, b, ag, Q, ro, s, run_if);
+    const int G = lane_group(opts().rollout_group, Q, ag->A), H = lane_slices(opts().rollout_slices, Q, G);
+    frirl::for_shared_shape<N>(ag, G, H, [&](auto sh) {
+        using S = decltype(sh);
+        launch_rollout<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, Q, ro, s, run_if);
+    });
 }
 
 int frirl_rollout_resident(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, int Q, const frirl_hip_rollout *ro,
@@ -215,8 +189,7 @@ extern "C" int frirl_hip_rollout_shared(const frirl_hip_tables *t, const frirl_h
     if (rc) return rc;
     if (!agent || !ro || !ro->steps || !ro->reward || !agent->grid_values || !agent->action_ve) { set_error("frirl_hip_rollout_shared: NULL argument"); return FRIRL_HIP_EINVAL; }
     if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("frirl_hip_rollout_shared: A=%d / max_steps=%d out of range", agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    for (int k = 0; k < t->nant; k++)
-        if (agent->grid_len[k] < 1 || agent->grid_len[k] > FRIRL_HIP_MAX_GRID) { set_error("frirl_hip_rollout_shared: grid_len[%d]=%d outside 1..%d", k, agent->grid_len[k], FRIRL_HIP_MAX_GRID); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_grid_len(t, agent, "frirl_hip_rollout_shared"))) return rc;
     if ((ro->exclude_mask == nullptr) != (ro->rule_slot == nullptr)) { set_error("frirl_hip_rollout_shared: exclude_mask and rule_slot go together"); return FRIRL_HIP_EINVAL; }
     if ((rc = check_demo_kind(t, agent, "frirl_hip_rollout_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
@@ -254,7 +227,7 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
     if (!agent || !result) { set_error("frirl_hip_reduce_shared: NULL argument"); return FRIRL_HIP_EINVAL; }
     if (strategy != 1 && strategy != 2) { set_error("frirl_hip_reduce_shared: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", strategy); return FRIRL_HIP_EINVAL; }
     if (depth == 0) depth = 10;
-    if (depth < 1 || depth > 12) { set_error("frirl_hip_reduce_shared: depth %d outside 1..12", depth); return FRIRL_HIP_EINVAL; }
+    if (depth < 1 || depth > frirl::RW_MAX_DEPTH) { set_error("frirl_hip_reduce_shared: depth %d outside 1..%d", depth, frirl::RW_MAX_DEPTH); return FRIRL_HIP_EINVAL; }
     if ((rc = check_demo_kind(t, agent, "frirl_hip_reduce_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
 #define HIP_TRY(expr)                                                                                              \

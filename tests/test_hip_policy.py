@@ -24,7 +24,7 @@ DEV = "cuda"
 
 
 def group_shapes(A):
-    """Every (lanes per row, rule slices) the launcher can choose for A actions (csrc/policy.hip: policy_group / policy_slices)."""
+    """Every (lanes per row, rule slices) the launcher can choose for A actions (csrc/shape_ladder.h: lane_group / lane_slices with the options policy_group / policy_slices)."""
     G = 4 if A <= 4 else 8
     return [(1, 1), (G, 1), (G, 4), (G, 8)]
 

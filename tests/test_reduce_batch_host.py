@@ -1,7 +1,7 @@
 """CPU-side checks of the batched rule-base reduction (frirl_hip_reduce_batch, csrc/reduce_batch.hip): the ABI surface, argument
 validation before the device is looked for, the workspace size and depth rules, and the tree walk the close-round kernel runs
-(csrc/reduce_walk.h through the host-only probe frirl_hip_reduce_walk_check) against a Python restatement of
-ReducePlan::close_round (csrc/reduce_plan.h:101-109)."""
+(csrc/reduce_walk.h through the host-only probe frirl_hip_reduce_walk_check; ReducePlan::close_round, csrc/reduce_plan.h, runs the
+same rw_walk on the host) against a Python restatement of the reference's walk (frirl_sequential_run.c:212,222)."""
 import ctypes as C
 
 import numpy as np
@@ -133,7 +133,8 @@ def test_depth_rule(lib):
 
 
 def walk_restated(d, steps, reward, steps_inc, prev_reward, good_above, tol):
-    """ReducePlan::close_round's walk (csrc/reduce_plan.h:101-109), restated."""
+    """The walk of a round's tree, restated independently of csrc/reduce_walk.h: the acceptance test of frirl_sequential_run.c:212
+    along the outcomes that happened, prev_reward carried from accepted removal to accepted removal (:222)."""
     bits = 0
     for k in range(d):
         lane = (1 << k) - 1 + bits
