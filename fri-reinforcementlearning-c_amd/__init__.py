@@ -61,6 +61,18 @@ class RolloutDesc(C.Structure):
                 ("reward", C.c_void_p), ("success", C.c_void_p), ("final_states", C.c_void_p)]
 
 
+class RolloutBatchDesc(C.Structure):
+    """struct frirl_hip_rollout_batch_rows (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("start_states", C.c_void_p), ("row_count", C.c_void_p), ("step_cap", C.c_void_p), ("active", C.c_void_p),
+                ("steps", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p), ("final_states", C.c_void_p)]
+
+
+class RolloutScore(C.Structure):
+    """struct frirl_hip_rollout_score (include/frirl_hip.h)."""
+    _fields_ = [("rows", C.c_int32), ("successes", C.c_int32), ("steps_sum", C.c_int64), ("reward_sum", C.c_double),
+                ("reward_min", C.c_double), ("reward_max", C.c_double)]
+
+
 class SenderDesc(C.Structure):
     """struct frirl_hip_sender (include/frirl_hip.h)."""
     _fields_ = [("rant", C.c_void_p), ("rule_stride", C.c_int64), ("dim_stride", C.c_int64), ("rconc", C.c_void_p), ("S", C.c_int32),
@@ -143,6 +155,9 @@ SIGNATURES = {
     "frirl_hip_get_best_action_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_rollout_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_int32, C.POINTER(RolloutDesc), C.c_void_p]),
+    "frirl_hip_rollout_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_rollout_batch": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(RolloutBatchDesc), C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_reduce_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_int, C.c_double, C.c_int,
                                           C.POINTER(C.c_int32), C.POINTER(ReduceResult), C.c_void_p]),
     "frirl_hip_reduce_batch_depth": (C.c_int, [C.c_int32, C.c_int32]),
@@ -224,6 +239,7 @@ SIGNATURES = {
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult)]),
     "frirl_hip_batch_reduce_all": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_train_merged": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "frirl_hip_merge_rb": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(SenderDesc), C.c_void_p,
@@ -347,6 +363,7 @@ class Problem:
         # workspaces of five_hip_rule_distance_packed_ws (per-call squared-difference tables), one per stream the scan is called on:
         # calls on different streams may run at the same time and must not share one
         self._rd_ws = {}
+        self._ro_ws = {}          # workspaces of frirl_hip_rollout_batch, per stream as _rd_ws
 
     @property
     def bases(self):
@@ -520,6 +537,45 @@ class Problem:
               "frirl_hip_rollout_shared")
         return steps, reward, success, final
 
+    def _ro_workspace(self, n, A, stream):
+        """The batched roll-out's workspace for `stream` (uint8 tensor, grown when a call needs more)."""
+        import torch
+        key = _stream(stream).value
+        need = lib().frirl_hip_rollout_batch_workspace_bytes(self.nant, self.E, self.maxR, n, A)
+        ws = self._ro_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ro_ws[key] = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.rb.device)
+        return ws, need
+
+    def rollout_batch(self, agent, n, start_states=None, row_count=None, step_cap=None, active=None, scores=False, stream=None, out=None):
+        """frirl_hip_rollout_batch: n greedy roll-outs (frirl_test_run's episode) on EVERY rule base of this problem, row q = e * n + j on
+        the rule base of agent e.  start_states [E * n, nant-1] f64 (None = agent.values_def); row_count / step_cap [E] int32; active [E]
+        uint8 / bool.  Returns (steps [E*n] i32, reward [E*n] f64, success [E*n] i32, final_states [E*n, nant-1][, scores [E, 40] uint8:
+        struct frirl_hip_rollout_score per agent, see rollout_scores]).  out: the caller's (steps, reward, success, final_states) to write
+        into.  Does not synchronise."""
+        import torch
+        dev_ = self.rb.device
+        Q = self.E * n
+        if out is None:
+            out = (torch.empty((Q,), dtype=torch.int32, device=dev_), torch.empty((Q,), dtype=torch.float64, device=dev_),
+                   torch.empty((Q,), dtype=torch.int32, device=dev_), torch.empty((Q, self.nant - 1), dtype=torch.float64, device=dev_))
+        steps, reward, success, final = out
+        ro = RolloutBatchDesc()
+        ro.n = n
+        if start_states is not None:
+            assert start_states.shape == (Q, self.nant - 1) and start_states.dtype == torch.float64 and start_states.is_contiguous()
+            ro.start_states = _ptr(start_states)
+        for x in (row_count, step_cap):
+            assert x is None or (x.shape == (self.E,) and x.dtype == torch.int32 and x.is_contiguous())
+        assert active is None or (active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous())
+        ro.row_count, ro.step_cap, ro.active = _ptr(row_count), _ptr(step_cap), _ptr(active)
+        ro.steps, ro.reward, ro.success, ro.final_states = _ptr(steps), _ptr(reward), _ptr(success), _ptr(final)
+        sc = torch.empty((self.E, C.sizeof(RolloutScore)), dtype=torch.uint8, device=dev_) if scores else None
+        ws, need = self._ro_workspace(n, agent.desc.A, stream)
+        check(lib().frirl_hip_rollout_batch(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(ro), _ptr(sc), _ptr(ws), need,
+                                            _stream(stream)), "frirl_hip_rollout_batch")
+        return (steps, reward, success, final, sc) if scores else (steps, reward, success, final)
+
     def reduce_shared(self, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, stream=None):
         """frirl_hip_reduce_shared: the reference's rule-base reduction as speculative batched try-remove; compacts this
         ONE rule base in place.  Returns (kept original indices, ReduceResult)."""
@@ -664,6 +720,12 @@ class Envs:
                              self.ep_reward.data_ptr(), self.rant.data_ptr() if self.rant is not None else None, self.status.data_ptr(),
                              self.start_states.data_ptr() if self.start_states is not None else None, self.episode.data_ptr(),
                              self.spread_ant.data_ptr(), self.spread_R.data_ptr())
+
+
+def rollout_scores(sc):
+    """The [E, 40] uint8 tensor Problem.rollout_batch(scores=True) returns as a host array of RolloutScore (synchronises)."""
+    raw = sc.cpu().numpy().tobytes()
+    return (RolloutScore * sc.shape[0]).from_buffer_copy(raw)
 
 
 def update_sarsa(problem, agent, envs, q_ant, reward, cur_q_ant, active=None, stream=None):

@@ -338,6 +338,56 @@ extern "C" int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, doub
     return FRIRL_HIP_OK;
 }
 
+extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)
+{
+    static const char *who = "frirl_hip_batch_evaluate";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (n < 1 || (int64_t)b->E * n > INT32_MAX) { set_error("%s: n=%d outside 1..INT32_MAX / E", who, n); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, Q = E * (size_t)n;
+    // every row at the agent's own start: its desc.start_states row n times (agent.values_def where the batch has none: no array at all)
+    std::vector<double> own;
+    if (!start_states && b->d_start) {
+        std::vector<double> one(E * ns);
+        BCHK(hipMemcpy(one.data(), b->d_start, sizeof(double) * E * ns, hipMemcpyDeviceToHost), "start states download");
+        own.resize(Q * ns);
+        for (size_t q = 0; q < Q; q++) memcpy(&own[q * ns], &one[(q / (size_t)n) * ns], sizeof(double) * ns);
+        start_states = own.data();
+    }
+    const size_t ws_bytes = frirl_hip_rollout_batch_workspace_bytes(b->nant, b->E, b->maxR, n, b->agent.A);
+    const size_t off_reward = (sizeof(frirl_hip_rollout_score) * E + 15) / 16 * 16, off_start = off_reward + sizeof(double) * Q;
+    const size_t off_steps = off_start + (start_states ? sizeof(double) * Q * ns : 0), off_ws = (off_steps + sizeof(int32_t) * 2 * Q + 15) / 16 * 16;
+    char *mem = nullptr;
+    BCHK(hipMalloc(reinterpret_cast<void **>(&mem), off_ws + ws_bytes), "evaluation buffers");
+    frirl_hip_rollout_batch_rows ro = {};
+    ro.n = n;
+    ro.reward = reinterpret_cast<double *>(mem + off_reward);
+    ro.steps = reinterpret_cast<int32_t *>(mem + off_steps);
+    ro.success = ro.steps + Q;
+    frirl_hip_agent greedy = b->agent;
+    greedy.no_random = 1;                                             // an evaluation is greedy (frirl_test_run: reduction_state == 1)
+    std::vector<frirl_hip_rollout_score> sc(E);
+    int rc = FRIRL_HIP_OK;
+    hipError_t he = hipSuccess;
+    if (start_states) {
+        ro.start_states = reinterpret_cast<double *>(mem + off_start);
+        he = hipMemcpyAsync(mem + off_start, start_states, sizeof(double) * Q * ns, hipMemcpyHostToDevice, b->s);
+    }
+    if (he == hipSuccess) rc = frirl_hip_rollout_batch(&b->t, &b->rb, &greedy, &ro, reinterpret_cast<frirl_hip_rollout_score *>(mem), mem + off_ws, ws_bytes, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(sc.data(), mem, sizeof(frirl_hip_rollout_score) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `own` and `mem` may be in use by the upload
+    else (void)hipStreamSynchronize(b->s);
+    (void)hipFree(mem);
+    if (rc) return rc;
+    if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
+    int32_t win = 0;                                                  // most successes, then the largest reward_sum, then the lowest index
+    for (int e = 1; e < b->E; e++)
+        if (sc[e].successes > sc[win].successes || (sc[e].successes == sc[win].successes && sc[e].reward_sum > sc[win].reward_sum)) win = e;
+    if (scores) memcpy(scores, sc.data(), sizeof(frirl_hip_rollout_score) * E);
+    if (best) *best = win;
+    return FRIRL_HIP_OK;
+}
+
 // ---- multi-agent rule-base merge: one round of the reference's many-agent loop (frirl_agent.c:426-462) -------------------
 // (1) every agent id >= 1 takes over the master's (agent 0's) rules -- all receivers in ONE launch; (2) the master takes over the
 // rules of agent 1, 2, ... one after the other (sequential by definition: each merge changes the master).  Agents whose rule base

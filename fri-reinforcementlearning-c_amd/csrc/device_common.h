@@ -189,6 +189,9 @@ struct Options {
     int rollout_cap;      // resident roll-out: steps before a long episode is parked for the latency form, 0 = max_steps / 6 (FRIRL_HIP_ROLLOUT_CAP)
     int rollout_pair;     // resident roll-out, one environment per wave: 0 = the one-wave form instead of sweeper + speculative stepper (FRIRL_HIP_ROLLOUT_PAIR)
     int rollout_wps;      // resident roll-out: persistent waves per SIMD, 1 ... 4 (0 = 2, or 4 for queue-fed launches) (FRIRL_HIP_ROLLOUT_WPS)
+    int rollout_batch_resident;       // batched roll-out: -1 = automatic, 0 = never the LDS-resident form, 1 = wherever it fits (FRIRL_HIP_ROLLOUT_BATCH_RESIDENT)
+    int rollout_batch_resident_rules; // batched roll-out: rule count up to which an agent takes the resident form, 0 = the shape's capacity (FRIRL_HIP_ROLLOUT_BATCH_RESIDENT_RULES)
+    int rollout_batch_slices;         // batched roll-out, resident form: lanes per row 1 / 4 / 16 / 64, 0 = by shape (FRIRL_HIP_ROLLOUT_BATCH_SLICES)
     int policy_group;     // caller-stepped shared-base step: lanes per row 1 / 4 / 8, 0 = by shape  (FRIRL_HIP_POLICY_GROUP)
     int policy_slices;    // caller-stepped shared-base step: rule slices 1 / 4 / 8, 0 = by shape    (FRIRL_HIP_POLICY_SLICES)
     int learn_slices;     // persistent learner: lanes per agent 4 / 16 / 64, 0 = by the number of live agents (FRIRL_HIP_LEARN_SLICES)

@@ -21,7 +21,7 @@
 // Sums: each lane adds its rules in index order, the H partials are added in butterfly order; every phase of one call runs a
 // different H, so an environment's Shepard sums change their rounding (not their value, <= 1e-13) when it is parked; WHICH
 // environments are parked depends only on their own trajectory and the static cap: results are deterministic.
-#include "sweeps.h"
+#include "rollout_resident.h"
 #include "envs.h"
 #include <mutex>
 #include <type_traits>
@@ -56,71 +56,7 @@ struct RolloutPhase {
     int ht;                    // slots of the exact-hit hash table (power of two >= 2 rps)
 };
 
-// ---- exact hits by lookup ----------------------------------------------------------------------------------------------
-// The rule base of a roll-out never changes, so "the lowest rule whose antecedents equal the observation's VE point" (an exact hit:
-// distance 0 <=> every antecedent equal, FIVEVagConcl_FRIRL_BestAct.c:89-93) is found through a hash table over the rules' VE
-// tuples, built once per workgroup: one probe per action and step instead of a compare + select per action and RULE in the sweep.
-constexpr uint32_t HT_EMPTY = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t hash_mix(uint32_t hsh, double x)
-{
-    const double c = x + 0.0;                             // -0.0 and +0.0 are the same antecedent
-    const uint32_t lo = (uint32_t)__double2loint(c), hi = (uint32_t)__double2hiint(c);
-    hsh = (hsh ^ lo) * 0x9E3779B1u;
-    hsh = (hsh ^ hi) * 0x85EBCA6Bu;
-    return hsh ^ (hsh >> 15);
-}
-
-// The LDS image of the rule base is rule-major: rule r occupies the NANT + 1 consecutive doubles col[r * (NANT + 1) + k] (antecedent VE
-// values, then the consequent) -- one address per rule and 16-byte reads with immediate offsets in the sweep.
-template <int NANT>
-__device__ __forceinline__ bool rule_equals(const double *col, int, int r, const double (&key)[NANT])
-{
-    bool eq = true;
-#pragma unroll
-    for (int k = 0; k < NANT; k++) eq = eq && (col[r * (NANT + 1) + k] == key[k]);
-    return eq;
-}
-
-template <int NANT>
-__device__ __forceinline__ void hash_insert(uint32_t *tab, int ht, const double *col, int RPS, int r)
-{
-    double key[NANT];
-    uint32_t hsh = 0u;
-#pragma unroll
-    for (int k = 0; k < NANT; k++) { key[k] = col[r * (NANT + 1) + k]; hsh = hash_mix(hsh, key[k]); }
-    for (int i = 0; i < ht; i++) {
-        const uint32_t slot = (hsh + (uint32_t)i) & (uint32_t)(ht - 1);
-        const uint32_t cur = atomicCAS(&tab[slot], HT_EMPTY, (uint32_t)r);
-        if (cur == HT_EMPTY) return;
-        if (rule_equals<NANT>(col, RPS, (int)cur, key)) { atomicMin(&tab[slot], (uint32_t)r); return; }   // duplicates: the lowest index
-    }
-}
-
-// lowest rule with these antecedents, or FRIRL_HIP_NO_HIT; `hsh` = hash of key[0 .. NANT-2], the last antecedent is mixed in here
-template <int NANT>
-__device__ __forceinline__ unsigned hash_lookup(const uint32_t *tab, int ht, const double *col, int RPS, uint32_t hsh, const double (&key)[NANT])
-{
-    hsh = hash_mix(hsh, key[NANT - 1]);
-    for (int i = 0; i < ht; i++) {
-        const uint32_t cur = tab[(hsh + (uint32_t)i) & (uint32_t)(ht - 1)];
-        if (cur == HT_EMPTY) return FRIRL_HIP_NO_HIT;
-        if (rule_equals<NANT>(col, RPS, (int)cur, key)) return cur;
-    }
-    return FRIRL_HIP_NO_HIT;
-}
-
-template <int N>
-__device__ __forceinline__ void group_sum_n(double (&v)[N], int H)
-{
-    for (int off = 1; off < H; off <<= 1) {
-        double t[N];
-#pragma unroll
-        for (int i = 0; i < N; i++) t[i] = __shfl_xor(v[i], off, FRIRL_WAVE);
-#pragma unroll
-        for (int i = 0; i < N; i++) v[i] = v[i] + t[i];
-    }
-}
+// image layout and staging, exact hits by hash lookup (hash_insert / hash_lookup) and group_sum_n: rollout_resident.h
 
 template <int NANT, int NA, int KIND, int H, bool EXCL>
 __global__ __launch_bounds__(RR_BLOCK, 2) void rollout_resident_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
@@ -144,11 +80,7 @@ __global__ __launch_bounds__(RR_BLOCK, 2) void rollout_resident_kernel(const dou
     uint32_t *hash_s = reinterpret_cast<uint32_t *>(tab_s + (LT ? 2 * NANT * U : 0));
     uint8_t *slot_s = reinterpret_cast<uint8_t *>(hash_s + ph.ht);
     const int nj = (R + H - 1) / H;                       // rules per lane; the padding rules of the last round weigh exactly 0
-    for (int i = threadIdx.x; i < (NANT + 1) * RPS; i += RR_BLOCK) {
-        const int k = i / RPS, r = i - k * RPS;          // coalesced reads of the canonical columns, transposed into the rule-major image
-        // padding: first antecedent 1e150 away (squared distance ~1e300, its weight underflows to 0), consequent 0
-        col[r * (NANT + 1) + k] = (r < R) ? rb[(size_t)k * maxR + r] : (k == 0 ? 1.0e150 : 0.0);
-    }
+    resident_stage_image<NANT>(col, RPS, rb, maxR, R, threadIdx.x, RR_BLOCK);
     if (EXCL) for (int r = threadIdx.x; r < RPS; r += RR_BLOCK) slot_s[r] = (r < R) ? ro.rule_slot[r] : (uint8_t)255;
     for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += RR_BLOCK) grid_s[i] = ag.grid_values[i];
     if (LT) for (int i = threadIdx.x; i < NANT * U; i += RR_BLOCK) { tab_s[i] = ve[i]; tab_s[NANT * U + i] = u[i]; }
@@ -411,10 +343,7 @@ __global__ __launch_bounds__(RP_BLOCK, 4) void rollout_pair_kernel(const double 
     uint32_t *hash_s = reinterpret_cast<uint32_t *>(tab_s + (LT ? 2 * NANT * U : 0));
     uint8_t *slot_s = reinterpret_cast<uint8_t *>(hash_s + ph.ht);
     const int nj = (R + H - 1) / H;
-    for (int i = threadIdx.x; i < (NANT + 1) * RPS; i += RP_BLOCK) {
-        const int k = i / RPS, r = i - k * RPS;
-        col[r * (NANT + 1) + k] = (r < R) ? rb[(size_t)k * maxR + r] : (k == 0 ? 1.0e150 : 0.0);
-    }
+    resident_stage_image<NANT>(col, RPS, rb, maxR, R, threadIdx.x, RP_BLOCK);
     if (EXCL) for (int r = threadIdx.x; r < RPS; r += RP_BLOCK) slot_s[r] = (r < R) ? ro.rule_slot[r] : (uint8_t)255;
     for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += RP_BLOCK) grid_s[i] = ag.grid_values[i];
     if (LT) for (int i = threadIdx.x; i < NANT * U; i += RP_BLOCK) { tab_s[i] = ve[i]; tab_s[NANT * U + i] = u[i]; }

@@ -15,6 +15,14 @@
 #include "frirl_types_def.h"
 #include "frirl_app_helpers.h"
 #include "frirl_demo.h"
+#include "demo_rows.h"
+
+static int usage(const char *what)
+{
+    fprintf(stderr, "usage error: %s\n"
+                    "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F]   (K >= 1 rows per agent, 0 <= F <= 1)\n", what);
+    return 2;
+}
 
 int main(int argc, char **argv)
 {
@@ -23,6 +31,8 @@ int main(int argc, char **argv)
     char name[128];
     int i, max_episodes = 0, fargc = 0, reduce = 0, agents = 0, gpus = -1, merge = 0, reduce_all = 0;
     const char *load_bin = NULL, *save_bin = NULL;
+    int evaluate = -1;              /* --evaluate K: greedy roll-outs of every agent from K start states, -1 = not asked for */
+    double spread = 0.15;           /* --spread F: rows 1 .. K-1 start at values_def +- F * span */
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -35,9 +45,24 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--save") && i + 1 < argc) save_bin = argv[++i];             /* batched: all agents' rule bases to one .bin */
         else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) reduce = atoi(argv[++i]);   /* construct, then reduce with strategy 1|2 */
         else if (!strcmp(argv[i], "--reduce-all")) reduce_all = 1;                              /* with --agents and --reduce: every agent's rule base, not agent 0's alone */
+        else if (!strcmp(argv[i], "--evaluate") && i + 1 < argc) { evaluate = atoi(argv[++i]); if (evaluate < 1) return usage("--evaluate needs K >= 1"); }
+        else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
         else if (fargc < 15) fargv[fargc++] = argv[i];
     }
+    if (evaluate > 0 && (agents < 1 || merge || gpus >= 0 || reduce)) return usage("--evaluate goes with --agents N (one device, no --merge / --reduce)");
     frirl_parse_cmdline(&fr, fargc, fargv);
+    if (evaluate > 0) {             /* train (or --load), then every agent rolled out from K start states */
+        int ns = 0, U = 0, A = 0, ms = 0, rc;
+        double *units;
+        if (frirl_demo_describe(env, &ns, &U, &A, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &ms) != 0) return 2;
+        units = malloc(sizeof(double) * (size_t)agents * (size_t)evaluate * (size_t)ns);
+        if (!units) return 1;
+        frirl_demo_row_units(agents, evaluate, ns, units);
+        rc = frirl_demo_batch_run_evaluate(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), load_bin, save_bin, evaluate, spread,
+                                           units, 1);
+        free(units);
+        return rc >= 0 ? 0 : 3;
+    }
     if (agents > 0 && merge && gpus >= 0) {       /* rule-base exchange across devices */
         snprintf(name, sizeof name, "%s.multi.merged.frirlrb.txt", env);
         return frirl_demo_multi_merged_run(env, agents, gpus, max_episodes > 0 ? max_episodes : fr.max_episodes, name, 1) >= 0 ? 0 : 3;

@@ -461,6 +461,69 @@ int frirl_demo_multi_merged_run(const char *env, int agents, int gpus, int max_e
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
                           const char *save_bin, const char *out_txt, int verbose);
 
+int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
+                                  const double *units, int verbose)
+{
+    int nant = 0, ns, episodes = 0, rc, e, j, k;
+    int32_t best = 0;
+    frirl_hip_batch_desc d;
+    struct demo_desc_mem mm;
+    frirl_hip_batch *b;
+    frirl_hip_rollout_score *sc;
+    double *start;
+    long long rows = 0, succ = 0, steps = 0;
+    double rsum = 0.0, rmin = 0.0, rmax = 0.0;
+    if (K < 1 || !units || !(spread >= 0.0) || demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    ns = nant - 1;
+    sc = malloc(sizeof *sc * (size_t)agents);
+    start = malloc(sizeof(double) * (size_t)agents * (size_t)K * (size_t)ns);
+    if (!sc || !start) return -1;
+    for (k = 0; k < ns; k++) {
+        const double *g = mm.grid + (size_t)k * FRIRL_HIP_MAX_GRID;
+        double lo = g[0], hi = g[0];
+        for (j = 0; j < d.agent.grid_len[k]; j++) { if (g[j] < lo) lo = g[j]; if (g[j] > hi) hi = g[j]; }
+        for (e = 0; e < agents; e++)
+            for (j = 0; j < K; j++) {
+                const size_t i = ((size_t)e * K + j) * ns + k;
+                double v = d.agent.values_def[k] + spread * units[i] * (hi - lo);
+                if (j == 0) v = d.agent.values_def[k];              /* the agent's own start state */
+                start[i] = v < lo ? lo : (v > hi ? hi : v);
+            }
+    }
+    b = frirl_hip_batch_create(&d);
+    if (!b) five_dropin_fatal("frirl_demo_batch_run_evaluate(create)", FRIRL_HIP_ENODEV);
+    if (load_bin) {
+        int32_t nrec = 0;
+        rc = frirl_hip_batch_load_rulebases(b, load_bin, &nrec);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(load)", rc);
+        if (verbose) printf("evaluate %s: loaded %d rule base record(s) from %s\n", env, (int)nrec, load_bin);
+    } else {
+        rc = frirl_hip_batch_train(b, max_episodes, &episodes);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(train)", rc);
+    }
+    if (save_bin) {
+        rc = frirl_hip_batch_save_rulebases(b, save_bin);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(save)", rc);
+    }
+    rc = frirl_hip_batch_evaluate(b, K, start, sc, &best);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(evaluate)", rc);
+    for (e = 0; e < agents; e++) {
+        if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_min < rmin)) rmin = sc[e].reward_min;
+        if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_max > rmax)) rmax = sc[e].reward_max;
+        rows += sc[e].rows; succ += sc[e].successes; steps += sc[e].steps_sum; rsum += sc[e].reward_sum;
+    }
+    if (verbose) {
+        printf("evaluate %s: agents %d rows %lld successful %.4f mean-steps %.3f mean-reward %.6f (min %.6f max %.6f) spread %.3f\n", env, agents, rows,
+               rows ? (double)succ / rows : 0.0, rows ? (double)steps / rows : 0.0, rows ? rsum / rows : 0.0, rmin, rmax, spread);
+        printf("evaluate %s: best agent %d: %d of %d rows successful, reward-sum %.6f, steps %lld\n", env, (int)best, (int)sc[best].successes,
+               (int)sc[best].rows, sc[best].reward_sum, (long long)sc[best].steps_sum);
+    }
+    frirl_hip_batch_destroy(b);
+    demo_desc_free(&mm);
+    free(sc); free(start);
+    return (int)best;
+}
+
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                             const char *out_txt, int verbose)
 {

@@ -36,6 +36,13 @@ int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int r
  * alone; prints one summary line: agents reduced, rules before -> after summed over the agents, rounds, replays */
 int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                     const char *out_txt, int verbose);
+/* Population evaluation: the agents learn (or, load_bin != NULL, load their rule bases), then EVERY agent is rolled out greedily on its
+ * own rule base from K start states (frirl_hip_batch_evaluate): row 0 = agent.values_def, row j >= 1 = values_def[k] + spread *
+ * units[e][j][k] * (largest - smallest grid value of dimension k), clipped to the grid; units HOST [agents][K][nstates] in -1..1.
+ * Prints one summary line (agents, rows, share of successful rows, mean steps, mean / min / max reward) and the best agent.
+ * Returns the best agent's index, or -1 on error. */
+int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
+                                  const double *units, int verbose);
 
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */

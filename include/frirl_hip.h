@@ -100,7 +100,7 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
  * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
- * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "rollout_batch_resident", "rollout_batch_resident_rules", "rollout_batch_slices", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -275,6 +275,53 @@ int frirl_hip_rollout_shared(const frirl_hip_tables *t, const frirl_hip_rulebase
  * whole rule base in LDS, H = 4 / 16 / 64 lanes per environment splitting the rules, finished groups refilled from an in-order
  * queue, long episodes parked and finished by whole waves, exact hits by hash lookup); 0 = the tiled kernel serves the shape. */
 int frirl_hip_rollout_resident_rules(int32_t nant, int32_t A, int32_t p, int32_t env_kind);
+
+/* The same greedy roll-outs on EVERY agent's OWN rule base (b->E >= 1) in one call: E * n rows, row q = e * n + j on the slab of agent
+ * e = q / n -- "evaluate my population".  Per row exactly what frirl_hip_rollout_shared does on agent e's slab alone with this row's
+ * start state (un-quantised for the first sweep); the epsilon-greedy stream of row q is (env_id_base + q, episode 0, step), the keys of
+ * frirl_hip_policy_batch_*, so the caller-stepped path is a row-for-row cross-check.  The rule bases are read-only.
+ * A row is NOT rolled out when j >= row_count[e], when its agent is inactive, or when nrules[e] lies outside 1..maxR; it then reads
+ * steps -1, reward 0, success 0 and its final_states are left untouched.  That is decided on the device: the call reads nothing back,
+ * does not synchronise and allocates nothing.
+ * Two kernel forms, chosen per agent on the device; which one served an agent is not visible in steps, success or final_states (their
+ * Shepard sums may round differently, as the two forms of frirl_hip_rollout_shared do):
+ *   resident  agents with nrules[e] <= frirl_hip_rollout_resident_rules (the demos' shapes, default Shepard power): the agent's
+ *             workgroups stage its rule base and exact-hit hash table in LDS once, groups of H = 1 / 4 / 16 / 64 lanes (4 / 16 for
+ *             21 actions) then take the agent's rows one after another from a per-agent counter; no barrier per step.  H follows from
+ *             E, n and maxR so that the chip is filled.  No straggler parking: a never-succeeding episode holds its lanes to the cap
+ *   tiled     every other agent, any Shepard power: a workgroup serves rows of ONE agent, 4 lanes per row for up to 4 actions, else
+ *             8, times 1 / 4 / 8 rule slices by the rows of the whole call (a full wave per row when n == 1)
+ * Options: "rollout_batch_resident" (-1 = automatic, 0 = never, 1 = wherever it fits), "rollout_batch_resident_rules" (0 = the shape's
+ * capacity, else a lower cap), "rollout_batch_slices" (forces H).
+ * scores ([dev] [E], or NULL) is filled by a small kernel behind the roll-outs from the per-row outputs, the sums in row order: the
+ * same bits whatever lane shape ran the rows.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL t / b / agent / ro / ro->steps / ro->reward, n < 1, E * n > INT32_MAX, a
+ * workspace that is NULL, not 16-byte aligned or smaller than frirl_hip_rollout_batch_workspace_bytes(nant, E, maxR, n, A), an
+ * env_kind that is not one of the three demos with its antecedent count (nant 3 / 5), A outside 1..32.
+ * frirl_hip_rollout_batch_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_rollout_batch_rows {
+    int32_t n;                     /* rows per agent; row q = e * n + j runs on the rule base of agent e = q / n          */
+    const double  *start_states;   /* [dev] [E*n][nant-1], or NULL = agent->values_def for every row                       */
+    const int32_t *row_count;      /* [dev] [E] rows of agent e that exist (clamped to 0..n), or NULL = n                  */
+    const int32_t *step_cap;       /* [dev] [E] per-agent cap, clamped to 1..agent->max_steps, or NULL = agent->max_steps  */
+    const uint8_t *active;         /* [dev] [E] 0 = skip this agent, or NULL = all                                         */
+    int32_t *steps;                /* [dev] [E*n] reward.ep_total_steps; -1 for a row that was not rolled out              */
+    double  *reward;               /* [dev] [E*n] reward.ep_total_value (0 for such a row)                                 */
+    int32_t *success;              /* [dev] [E*n] or NULL                                                                  */
+    double  *final_states;         /* [dev] [E*n][nant-1] or NULL (rows not rolled out are left untouched)                 */
+} frirl_hip_rollout_batch_rows;
+
+typedef struct frirl_hip_rollout_score {   /* 40 bytes */
+    int32_t rows, successes;       /* rows rolled out; rows whose episode ended with success == 1 */
+    int64_t steps_sum;
+    double reward_sum;             /* added in row order j = 0, 1, ... */
+    double reward_min, reward_max; /* 0 when rows == 0 */
+} frirl_hip_rollout_score;
+
+size_t frirl_hip_rollout_batch_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t n, int32_t A);
+int frirl_hip_rollout_batch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                            const frirl_hip_rollout_batch_rows *ro, frirl_hip_rollout_score *scores /* [dev][E] or NULL */,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* Rule-base reduction (reference frirl_sequential_run.c:170-350, strategies 1 = smallest |Q| first, 2 = largest |Q|
  * first) as a batched "try-remove" on the GPU.  The reference tests ONE candidate per replayed episode: remove it, replay
@@ -828,6 +875,13 @@ int frirl_hip_batch_reduce(frirl_hip_batch *b, int32_t e, int strategy, double r
  * allocated and freed inside the call.  results: HOST [E] or NULL; *agents_reduced (or NULL): agents that lost at least one rule. */
 int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, frirl_hip_reduce_result *results,
                                int32_t *agents_reduced);
+/* Greedy roll-outs of EVERY agent of the batch on its own rule base from n start states each (frirl_hip_rollout_batch with
+ * agent.no_random = 1): which of the agents is any good away from the start state it trained on.  Row 0 .. n-1 of agent e start at
+ * start_states[e][0 .. n-1]; NULL = every row at the agent's own start (its desc.start_states row, agent.values_def where the batch
+ * has none).  scores[e] (HOST [E], or NULL) as frirl_hip_rollout_batch fills it; *best (or NULL) = the agent with the most successes,
+ * then the largest reward_sum, then the lowest index.  The workspace is allocated and freed inside the call, which synchronises. */
+int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states /* HOST [E][n][nant-1], or NULL */,
+                             frirl_hip_rollout_score *scores /* HOST [E] */, int32_t *best);
 /* One round of the reference's multi-agent rule-base exchange (frirl_omp_run, frirl_agent.c:426-462) inside the batch: every agent
  * id >= 1 takes over the master's (agent 0's) rules -- all of them in one launch of frirl_hip_merge_rb --, then the master takes
  * over the rules of agent 1, 2, ... in turn.  Agents whose rule base is complete do not send (:432,:444).  *full_agents (or NULL):
