@@ -73,6 +73,34 @@ class RolloutScore(C.Structure):
                 ("reward_min", C.c_double), ("reward_max", C.c_double)]
 
 
+class RolloutLogDesc(C.Structure):
+    """struct frirl_hip_rollout_log (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("episodes", C.c_int32), ("T", C.c_int32), ("reserved", C.c_int32), ("start_states", C.c_void_p),
+                ("row_count", C.c_void_p), ("active", C.c_void_p), ("obs", C.c_void_p), ("q_obs", C.c_void_p), ("action", C.c_void_p),
+                ("reward", C.c_void_p), ("success", C.c_void_p), ("start", C.c_void_p), ("length", C.c_void_p), ("ep_steps", C.c_void_p),
+                ("ep_reward", C.c_void_p), ("ep_success", C.c_void_p)]
+
+
+class TeachResult(C.Structure):
+    """struct frirl_hip_teach_result (include/frirl_hip.h)."""
+    _fields_ = [("teacher", C.c_int32), ("episodes_recorded", C.c_int32), ("successes", C.c_int32), ("records", C.c_int32),
+                ("students", C.c_int32), ("refused", C.c_int32), ("records_replayed", C.c_int64)]
+
+
+class BatchDesc(C.Structure):
+    """struct frirl_hip_batch_desc (include/frirl_hip.h)."""
+    _fields_ = [("nant", C.c_int32), ("U", C.c_int32), ("E", C.c_int32), ("maxR", C.c_int32), ("u", C.c_void_p), ("ve", C.c_void_p),
+                ("agent", AgentDesc), ("R0", C.c_int32), ("rant0", C.c_void_p), ("rconc0", C.c_void_p), ("start_states", C.c_void_p),
+                ("device_select", C.c_int32), ("device", C.c_int32)]
+
+
+class BatchStats(C.Structure):
+    """struct frirl_hip_batch_stats_t (include/frirl_hip.h)."""
+    _fields_ = [("reward_sum", C.c_double), ("steps_sum", C.c_double), ("rules_sum", C.c_double), ("reward_min", C.c_double),
+                ("reward_max", C.c_double), ("agents", C.c_int64), ("converged", C.c_int64), ("episodes_max", C.c_int64),
+                ("total_env_steps", C.c_int64), ("full_agents", C.c_int64)]
+
+
 class SenderDesc(C.Structure):
     """struct frirl_hip_sender (include/frirl_hip.h)."""
     _fields_ = [("rant", C.c_void_p), ("rule_stride", C.c_int64), ("dim_stride", C.c_int64), ("rconc", C.c_void_p), ("S", C.c_int32),
@@ -158,6 +186,7 @@ SIGNATURES = {
     "frirl_hip_rollout_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_rollout_batch": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(RolloutBatchDesc), C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_rollout_record": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(RolloutLogDesc), C.c_void_p]),
     "frirl_hip_reduce_shared": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_int, C.c_double, C.c_int,
                                           C.POINTER(C.c_int32), C.POINTER(ReduceResult), C.c_void_p]),
     "frirl_hip_reduce_batch_depth": (C.c_int, [C.c_int32, C.c_int32]),
@@ -240,6 +269,7 @@ SIGNATURES = {
     "frirl_hip_batch_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult)]),
     "frirl_hip_batch_reduce_all": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_teach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(TeachResult)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_train_merged": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "frirl_hip_merge_rb": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(SenderDesc), C.c_void_p,
@@ -576,6 +606,30 @@ class Problem:
                                             _stream(stream)), "frirl_hip_rollout_batch")
         return (steps, reward, success, final, sc) if scores else (steps, reward, success, final)
 
+    def rollout_record(self, agent, n, episodes, T, start_states=None, row_count=None, active=None, stream=None, out=None):
+        """frirl_hip_rollout_record: n logs of `episodes` greedy (or epsilon-greedy) episodes on EVERY rule base of this problem, every
+        step written as a record; log q = e * n + j on the rule base of agent e.  start_states [E * n, episodes, nant-1] f64 (None =
+        agent.values_def); row_count [E] int32; active [E] uint8 / bool.  Returns a RolloutLog (out: the caller's, to write into);
+        its .demonstration() feeds learn_demonstration from the same memory.  Does not synchronise."""
+        import torch
+        Q, ns = self.E * n, self.nant - 1
+        log = out if out is not None else RolloutLog.empty(Q, episodes, T, ns, self.rb.device)
+        assert (log.Q, log.K, log.T, log.ns) == (Q, episodes, T, ns)
+        lg = RolloutLogDesc()
+        lg.n, lg.episodes, lg.T = n, episodes, T
+        if start_states is not None:
+            assert start_states.shape == (Q, episodes, ns) and start_states.dtype == torch.float64 and start_states.is_contiguous()
+            lg.start_states = _ptr(start_states)
+        assert row_count is None or (row_count.shape == (self.E,) and row_count.dtype == torch.int32 and row_count.is_contiguous())
+        assert active is None or (active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous())
+        lg.row_count, lg.active = _ptr(row_count), _ptr(active)
+        for name in RolloutLog.FIELDS:
+            setattr(lg, name, _ptr(getattr(log, name)))
+        log.n = n
+        check(lib().frirl_hip_rollout_record(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(lg), _stream(stream)),
+              "frirl_hip_rollout_record")
+        return log
+
     def reduce_shared(self, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, stream=None):
         """frirl_hip_reduce_shared: the reference's rule-base reduction as speculative batched try-remove; compacts this
         ONE rule base in place.  Returns (kept original indices, ReduceResult)."""
@@ -851,6 +905,94 @@ class Demonstration:
         self.desc = DemonstrationDesc(T, T if L > 1 else 0, obs.data_ptr(), q_obs.data_ptr() if q_obs is not None else None, action.data_ptr(),
                                       reward.data_ptr(), success.data_ptr(), start.data_ptr() if start is not None else None,
                                       length.data_ptr() if length is not None else None)
+
+
+class RolloutLog:
+    """The logs Problem.rollout_record writes (struct frirl_hip_rollout_log): obs / q_obs [Q, T, nant-1] float64, action / success
+    [Q, T] int32, reward [Q, T] float64, start [Q, T] uint8, length [Q] int32 and per episode ep_steps / ep_success [Q, K] int32,
+    ep_reward [Q, K] float64; Q = E * n logs of K episodes and capacity T."""
+    FIELDS = ("obs", "q_obs", "action", "reward", "success", "start", "length", "ep_steps", "ep_reward", "ep_success")
+
+    def __init__(self, obs, q_obs, action, reward, success, start, length, ep_steps, ep_reward, ep_success):
+        import torch
+        Q, T, ns = obs.shape
+        K = ep_steps.shape[1]
+        for x, shape, dt in ((obs, (Q, T, ns), torch.float64), (q_obs, (Q, T, ns), torch.float64), (action, (Q, T), torch.int32),
+                             (reward, (Q, T), torch.float64), (success, (Q, T), torch.int32), (start, (Q, T), torch.uint8),
+                             (length, (Q,), torch.int32), (ep_steps, (Q, K), torch.int32), (ep_reward, (Q, K), torch.float64),
+                             (ep_success, (Q, K), torch.int32)):
+            assert x.is_cuda and x.shape == shape and x.dtype == dt and x.is_contiguous()
+        self.obs, self.q_obs, self.action, self.reward, self.success, self.start, self.length = obs, q_obs, action, reward, success, start, length
+        self.ep_steps, self.ep_reward, self.ep_success = ep_steps, ep_reward, ep_success
+        self.Q, self.K, self.T, self.ns, self.n = Q, K, T, ns, None
+
+    @classmethod
+    def empty(cls, Q, K, T, ns, device):
+        import torch
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        return cls(mk((Q, T, ns), torch.float64), mk((Q, T, ns), torch.float64), mk((Q, T), torch.int32), mk((Q, T), torch.float64),
+                   mk((Q, T), torch.int32), mk((Q, T), torch.uint8), mk((Q,), torch.int32), mk((Q, K), torch.int32), mk((Q, K), torch.float64),
+                   mk((Q, K), torch.int32))
+
+    def demonstration(self, log=None, E=None):
+        """A Demonstration over the same memory, no copy.  log=None: one log per agent (needs n == 1).  log=q: that one log for E
+        students, its length expanded to [E] (a device op; nothing is read back)."""
+        if log is None:
+            assert self.n == 1, "one log per agent needs n == 1"
+            return Demonstration(self.obs, self.action, self.reward, self.success, q_obs=self.q_obs, start=self.start, length=self.length)
+        assert E is not None and E >= 1 and 0 <= log < self.Q
+        s = slice(log, log + 1)
+        return Demonstration(self.obs[s], self.action[s], self.reward[s], self.success[s], q_obs=self.q_obs[s], start=self.start[s],
+                             length=self.length[s].repeat(E))
+
+
+def demo_batch_object(env, E, maxR, start_states=None):
+    """frirl_hip_batch_create for a demo: E agents from the reference's initial rule base (the 2^nant corner rules, Q = 0), agent e
+    starting its episodes at start_states[e] (host [E, nant-1], None = values_def).  Returns the handle for the frirl_hip_batch_*
+    calls of lib(); release it with lib().frirl_hip_batch_destroy."""
+    import numpy as np
+    d = demo_describe(env)
+    nant = d["nant"]
+    grid = np.zeros((nant, MAX_GRID))
+    for k, g in enumerate(d["grids"]):
+        grid[k, : len(g)] = g
+    ncorner = 2 ** nant
+    rant0 = np.zeros((ncorner, nant))
+    for k in range(nant):
+        div = ncorner >> (k + 1)
+        rant0[:, k] = [d["grids"][k].min() if ((j // div) % 2) == 0 else d["grids"][k].max() for j in range(ncorner)]
+    rconc0 = np.zeros(ncorner)
+    u, ve, ave = np.ascontiguousarray(d["u"]), np.ascontiguousarray(d["ve"]), np.ascontiguousarray(d["action_ve"])
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    assert st is None or st.shape == (E, nant - 1)
+    desc = BatchDesc()
+    desc.nant, desc.U, desc.E, desc.maxR, desc.u, desc.ve = nant, d["U"], E, maxR, u.ctypes.data, ve.ctypes.data
+    desc.R0, desc.rant0, desc.rconc0 = ncorner, rant0.ctypes.data, rconc0.ctypes.data
+    desc.start_states = None if st is None else st.ctypes.data
+    ag = desc.agent
+    ag.alpha, ag.gamma, ag.qdiff_pos_boundary, ag.qdiff_neg_boundary = d["alpha"], d["gamma"], d["qdiff_pos"], d["qdiff_neg"]
+    ag.weight_significant, ag.skip_rules, ag.A, ag.env_kind, ag.max_steps, ag.no_random = d["weight_thr"], d["skip_rules"], d["A"], d["kind"], d["max_steps"], 1
+    ag.reward_good_above, ag.qdiff_final_tolerance = d["reward_good_above"], d["qdiff_final_tolerance"]
+    for k in range(nant):
+        ag.grid_len[k], ag.grid_div[k], ag.values_def[k] = len(d["grids"][k]), d["grid_div"][k], d["values_def"][k]
+    ag.grid_values, ag.action_ve = grid.ctypes.data, ave.ctypes.data
+    b = lib().frirl_hip_batch_create(C.byref(desc))          # copies every host array before it returns
+    if not b:
+        raise FrirlHipError("frirl_hip_batch_create: " + lib().frirl_hip_last_error().decode())
+    return b
+
+
+def batch_teach(batch, teacher, episodes, start_states=None, passes=1, students=None):
+    """frirl_hip_batch_teach on a library-owned batch (the handle frirl_hip_batch_create returned): agent `teacher` records `episodes`
+    greedy episodes, every student (students: [E] array of 0 / 1, None = everybody but the teacher) replays the log `passes` times.
+    start_states: host [episodes, nant-1] float64 or None.  Returns the TeachResult."""
+    import numpy as np
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    mask = None if students is None else np.ascontiguousarray(students, dtype=np.uint8)
+    res = TeachResult()
+    check(lib().frirl_hip_batch_teach(batch, teacher, episodes, None if st is None else st.ctypes.data_as(_DP), passes,
+                                      None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(res)), "frirl_hip_batch_teach")
+    return res
 
 
 def learn_demonstration(problem, agent, envs, demo, passes=1, stream=None):

@@ -79,6 +79,30 @@ __global__ void count_running_kernel(const int32_t *__restrict__ done, int E, in
     __syncthreads();
     if (threadIdx.x == 0) *out = s;
 }
+// frirl_hip_batch_teach: every student replays the whole log, everybody else nothing
+__global__ void teach_lengths_kernel(const uint8_t *__restrict__ student, const int32_t *__restrict__ log_length, int E, int32_t *__restrict__ length)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < E) length[e] = student[e] ? log_length[0] : 0;
+}
+// after the replay: a student's convergence state is cleared as convergence_kernel's init clears it (frirl_init.c:149-150), but its
+// episode counter stays; one workgroup per agent
+__global__ __launch_bounds__(256) void teach_reset_kernel(const uint8_t *__restrict__ student, const double *__restrict__ rb,
+                                                          const int32_t *__restrict__ nrules, int maxR, int nant, const frirl_hip_convergence c)
+{
+    const int e = blockIdx.x;
+    if (!student[e]) return;
+    const double *qcol = rb + ((size_t)e * (nant + 1) + nant) * maxR;
+    double *prev = c.prev_rconc + (size_t)e * maxR;
+    for (int r = threadIdx.x; r < maxR; r += blockDim.x) prev[r] = qcol[r];
+    if (threadIdx.x == 0) {
+        c.prev_nrules[e] = nrules[e];
+        c.prev_steps[e] = -1;
+        c.prev_reward[e] = -1.0;
+        c.converged[e] = 0;
+        if (c.epended) c.epended[e] = 0;
+    }
+}
 }  // namespace frirl
 
 extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
@@ -385,6 +409,111 @@ extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const dou
         if (sc[e].successes > sc[win].successes || (sc[e].successes == sc[win].successes && sc[e].reward_sum > sc[win].reward_sum)) win = e;
     if (scores) memcpy(scores, sc.data(), sizeof(frirl_hip_rollout_score) * E);
     if (best) *best = win;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_t episodes, const double *start_states, int32_t passes,
+                                     const uint8_t *students, frirl_hip_teach_result *result)
+{
+    static const char *who = "frirl_hip_batch_teach";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (teacher < 0 || teacher >= b->E) { set_error("%s: teacher=%d outside 0..%d", who, teacher, b->E - 1); return FRIRL_HIP_EINVAL; }
+    if (episodes < 1 || (int64_t)episodes * ((int64_t)b->agent.max_steps + 1) > INT32_MAX) { set_error("%s: episodes=%d outside 1..INT32_MAX / (max_steps + 1)", who, episodes); return FRIRL_HIP_EINVAL; }
+    if (passes < 1 || passes > 1024) { set_error("%s: passes=%d outside 1..1024", who, passes); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    BCHK(hipStreamSynchronize(b->s), "teach sync");
+    int32_t teacher_rules = 0;
+    BCHK(hipMemcpy(&teacher_rules, b->d_nrules + teacher, sizeof teacher_rules, hipMemcpyDeviceToHost), "nrules download");
+    if (teacher_rules < 1 || teacher_rules > b->maxR) { set_error("%s: teacher %d holds %d rules (capacity %d)", who, teacher, teacher_rules, b->maxR); return FRIRL_HIP_EINVAL; }
+    const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, K = (size_t)episodes;
+    const int64_t T64 = (int64_t)episodes * ((int64_t)b->agent.max_steps + 1);
+    const size_t T = (size_t)(T64 < 2 ? 2 : T64);
+    // episode k at the own start state of agent k % E (agent.values_def where the batch has none: no array at all)
+    std::vector<double> own;
+    if (!start_states && b->d_start) {
+        std::vector<double> one(E * ns);
+        BCHK(hipMemcpy(one.data(), b->d_start, sizeof(double) * E * ns, hipMemcpyDeviceToHost), "start states download");
+        own.resize(K * ns);
+        for (size_t k = 0; k < K; k++) memcpy(&own[k * ns], &one[(k % E) * ns], sizeof(double) * ns);
+        start_states = own.data();
+    }
+    std::vector<uint8_t> mask(E);
+    int32_t nstudents = 0;
+    for (size_t e = 0; e < E; e++) {
+        mask[e] = (e != (size_t)teacher && (!students || students[e])) ? 1 : 0;
+        nstudents += mask[e];
+    }
+    // one allocation: doubles, then int32s, then bytes
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; };
+    const size_t o_obs = take(sizeof(double) * T * ns), o_qobs = take(sizeof(double) * T * ns), o_reward = take(sizeof(double) * T);
+    const size_t o_epr = take(sizeof(double) * K), o_st = take(sizeof(double) * K * ns);
+    const size_t o_action = take(sizeof(int32_t) * T), o_success = take(sizeof(int32_t) * T), o_len = take(sizeof(int32_t));
+    const size_t o_eps = take(sizeof(int32_t) * K), o_epok = take(sizeof(int32_t) * K), o_length = take(sizeof(int32_t) * E), o_replayed = take(sizeof(int32_t) * E);
+    const size_t o_start = take(T), o_mask = take(E), o_refused = take(E);
+    char *mem = nullptr;
+    BCHK(hipMalloc(reinterpret_cast<void **>(&mem), off), "teaching buffers");
+    frirl_hip_rollout_log lg = {};
+    lg.n = 1; lg.episodes = episodes; lg.T = (int32_t)T;
+    lg.obs = reinterpret_cast<double *>(mem + o_obs); lg.q_obs = reinterpret_cast<double *>(mem + o_qobs); lg.reward = reinterpret_cast<double *>(mem + o_reward);
+    lg.action = reinterpret_cast<int32_t *>(mem + o_action); lg.success = reinterpret_cast<int32_t *>(mem + o_success);
+    lg.start = reinterpret_cast<uint8_t *>(mem + o_start); lg.length = reinterpret_cast<int32_t *>(mem + o_len);
+    lg.ep_steps = reinterpret_cast<int32_t *>(mem + o_eps); lg.ep_reward = reinterpret_cast<double *>(mem + o_epr); lg.ep_success = reinterpret_cast<int32_t *>(mem + o_epok);
+    int32_t *d_length = reinterpret_cast<int32_t *>(mem + o_length), *d_replayed = reinterpret_cast<int32_t *>(mem + o_replayed);
+    uint8_t *d_mask = reinterpret_cast<uint8_t *>(mem + o_mask), *d_refused = reinterpret_cast<uint8_t *>(mem + o_refused);
+    frirl_hip_agent greedy = b->agent;
+    greedy.no_random = 1;                                             // the teacher shows its greedy policy, as frirl_hip_batch_evaluate rolls out
+    frirl_hip_rulebases one = b->rb;                                  // the teacher's slab alone: it is log 0 of a one-agent call
+    one.E = 1;
+    one.rb = b->rb.rb + (size_t)teacher * (ns + 2) * (size_t)b->maxR;
+    one.nrules = b->rb.nrules + teacher;
+    if (one.uidx) one.uidx = b->rb.uidx + (size_t)teacher * (ns + 1) * (size_t)b->maxR;
+    std::vector<int32_t> h_eps(2 * K + 1), h_replayed(E);
+    std::vector<uint8_t> h_refused(E);
+    int rc = FRIRL_HIP_OK;
+    hipError_t he = hipMemcpyAsync(d_mask, mask.data(), E, hipMemcpyHostToDevice, b->s);
+    if (he == hipSuccess && start_states) {
+        lg.start_states = reinterpret_cast<double *>(mem + o_st);
+        he = hipMemcpyAsync(mem + o_st, start_states, sizeof(double) * K * ns, hipMemcpyHostToDevice, b->s);
+    }
+    if (he == hipSuccess) rc = frirl_hip_rollout_record(&b->t, &one, &greedy, &lg, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) {
+        hipLaunchKernelGGL(frirl::teach_lengths_kernel, dim3((b->E + 255) / 256), dim3(256), 0, b->s, d_mask, lg.length, b->E, d_length);
+        frirl_hip_demonstration dm = {};
+        dm.T = lg.T; dm.agent_stride = 0;
+        dm.obs = lg.obs; dm.q_obs = lg.q_obs; dm.action = lg.action; dm.reward = lg.reward; dm.success = lg.success; dm.start = lg.start; dm.length = d_length;
+        rc = frirl_hip_learn_demonstration(&b->t, &b->rb, &b->agent, &b->envs, &dm, passes, d_replayed, d_refused, b->s);
+    }
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) {
+        hipLaunchKernelGGL(frirl::teach_reset_kernel, dim3(b->E), dim3(256), 0, b->s, d_mask, b->d_rb, b->d_nrules, b->maxR, b->nant, b->conv);
+        he = hipMemcpyAsync(h_eps.data(), lg.ep_steps, sizeof(int32_t) * K, hipMemcpyDeviceToHost, b->s);
+        if (he == hipSuccess) he = hipMemcpyAsync(h_eps.data() + K, lg.ep_success, sizeof(int32_t) * K, hipMemcpyDeviceToHost, b->s);
+        if (he == hipSuccess) he = hipMemcpyAsync(h_eps.data() + 2 * K, lg.length, sizeof(int32_t), hipMemcpyDeviceToHost, b->s);
+        if (he == hipSuccess) he = hipMemcpyAsync(h_replayed.data(), d_replayed, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
+        if (he == hipSuccess) he = hipMemcpyAsync(h_refused.data(), d_refused, E, hipMemcpyDeviceToHost, b->s);
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of a call: `own`, `mask` and `mem` may be in use
+    else (void)hipStreamSynchronize(b->s);
+    (void)hipFree(mem);
+    if (rc) return rc;
+    if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
+    if ((rc = check_launch(who))) return rc;
+    if (result) {
+        frirl_hip_teach_result out = {};
+        out.teacher = teacher;
+        out.records = h_eps[2 * K];
+        out.students = nstudents;
+        for (size_t k = 0; k < K; k++) {
+            out.episodes_recorded += h_eps[k] >= 0 ? 1 : 0;
+            out.successes += (h_eps[k] >= 0 && h_eps[K + k] == 1) ? 1 : 0;
+        }
+        for (size_t e = 0; e < E; e++) {
+            if (!mask[e]) continue;
+            out.refused += h_refused[e] ? 1 : 0;
+            out.records_replayed += h_replayed[e];
+        }
+        *result = out;
+    }
     return FRIRL_HIP_OK;
 }
 

@@ -20,7 +20,7 @@
 static int usage(const char *what)
 {
     fprintf(stderr, "usage error: %s\n"
-                    "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F]   (K >= 1 rows per agent, 0 <= F <= 1)\n", what);
+                    "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F] [--teach-best M [--teach-passes P]]   (K >= 1 rows per agent, 0 <= F <= 1, M >= 1 episodes, 1 <= P <= 1024)\n", what);
     return 2;
 }
 
@@ -33,6 +33,8 @@ int main(int argc, char **argv)
     const char *load_bin = NULL, *save_bin = NULL;
     int evaluate = -1;              /* --evaluate K: greedy roll-outs of every agent from K start states, -1 = not asked for */
     double spread = 0.15;           /* --spread F: rows 1 .. K-1 start at values_def +- F * span */
+    int teach_best = 0;             /* --teach-best M: after the evaluation the best agent teaches every other agent M greedy episodes, 0 = not asked for */
+    int teach_passes = 1;           /* --teach-passes P: passes over the teacher's log */
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -47,9 +49,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--reduce-all")) reduce_all = 1;                              /* with --agents and --reduce: every agent's rule base, not agent 0's alone */
         else if (!strcmp(argv[i], "--evaluate") && i + 1 < argc) { evaluate = atoi(argv[++i]); if (evaluate < 1) return usage("--evaluate needs K >= 1"); }
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
+        else if (!strcmp(argv[i], "--teach-best") && i + 1 < argc) { teach_best = atoi(argv[++i]); if (teach_best < 1) return usage("--teach-best needs M >= 1"); }
+        else if (!strcmp(argv[i], "--teach-passes") && i + 1 < argc) { teach_passes = atoi(argv[++i]); if (teach_passes < 1 || teach_passes > 1024) return usage("--teach-passes needs 1 <= P <= 1024"); }
         else if (fargc < 15) fargv[fargc++] = argv[i];
     }
     if (evaluate > 0 && (agents < 1 || merge || gpus >= 0 || reduce)) return usage("--evaluate goes with --agents N (one device, no --merge / --reduce)");
+    if (teach_best > 0 && evaluate < 1) return usage("--teach-best goes with --evaluate K");
     frirl_parse_cmdline(&fr, fargc, fargv);
     if (evaluate > 0) {             /* train (or --load), then every agent rolled out from K start states */
         int ns = 0, U = 0, A = 0, ms = 0, rc;
@@ -58,8 +63,12 @@ int main(int argc, char **argv)
         units = malloc(sizeof(double) * (size_t)agents * (size_t)evaluate * (size_t)ns);
         if (!units) return 1;
         frirl_demo_row_units(agents, evaluate, ns, units);
-        rc = frirl_demo_batch_run_evaluate(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), load_bin, save_bin, evaluate, spread,
-                                           units, 1);
+        if (teach_best > 0)
+            rc = frirl_demo_batch_run_evaluate_teach(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), load_bin, save_bin, evaluate,
+                                                     spread, units, teach_best, teach_passes, 1);
+        else
+            rc = frirl_demo_batch_run_evaluate(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), load_bin, save_bin, evaluate, spread,
+                                               units, 1);
         free(units);
         return rc >= 0 ? 0 : 3;
     }

@@ -461,10 +461,10 @@ int frirl_demo_multi_merged_run(const char *env, int agents, int gpus, int max_e
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
                           const char *save_bin, const char *out_txt, int verbose);
 
-int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
-                                  const double *units, int verbose)
+int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
+                                        const double *units, int teach_episodes, int teach_passes, int verbose)
 {
-    int nant = 0, ns, episodes = 0, rc, e, j, k;
+    int nant = 0, ns, episodes = 0, rc, e, j, k, stage;
     int32_t best = 0;
     frirl_hip_batch_desc d;
     struct demo_desc_mem mm;
@@ -473,7 +473,7 @@ int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes,
     double *start;
     long long rows = 0, succ = 0, steps = 0;
     double rsum = 0.0, rmin = 0.0, rmax = 0.0;
-    if (K < 1 || !units || !(spread >= 0.0) || demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    if (K < 1 || !units || !(spread >= 0.0) || teach_episodes < 0 || demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
     ns = nant - 1;
     sc = malloc(sizeof *sc * (size_t)agents);
     start = malloc(sizeof(double) * (size_t)agents * (size_t)K * (size_t)ns);
@@ -505,23 +505,41 @@ int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes,
         rc = frirl_hip_batch_save_rulebases(b, save_bin);
         if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(save)", rc);
     }
-    rc = frirl_hip_batch_evaluate(b, K, start, sc, &best);
-    if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(evaluate)", rc);
-    for (e = 0; e < agents; e++) {
-        if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_min < rmin)) rmin = sc[e].reward_min;
-        if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_max > rmax)) rmax = sc[e].reward_max;
-        rows += sc[e].rows; succ += sc[e].successes; steps += sc[e].steps_sum; rsum += sc[e].reward_sum;
-    }
-    if (verbose) {
-        printf("evaluate %s: agents %d rows %lld successful %.4f mean-steps %.3f mean-reward %.6f (min %.6f max %.6f) spread %.3f\n", env, agents, rows,
-               rows ? (double)succ / rows : 0.0, rows ? (double)steps / rows : 0.0, rows ? rsum / rows : 0.0, rmin, rmax, spread);
-        printf("evaluate %s: best agent %d: %d of %d rows successful, reward-sum %.6f, steps %lld\n", env, (int)best, (int)sc[best].successes,
-               (int)sc[best].rows, sc[best].reward_sum, (long long)sc[best].steps_sum);
+    for (stage = 0; stage < (teach_episodes > 0 ? 2 : 1); stage++) {
+        if (stage == 1) {               /* the best agent shows every other agent teach_episodes greedy episodes */
+            frirl_hip_teach_result tr;
+            rc = frirl_hip_batch_teach(b, best, teach_episodes, NULL, teach_passes, NULL, &tr);
+            if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(teach)", rc);
+            if (verbose)
+                printf("taught: teacher %d episodes_recorded %d successes %d records %d students %d refused %d records_replayed %lld\n", (int)tr.teacher,
+                       (int)tr.episodes_recorded, (int)tr.successes, (int)tr.records, (int)tr.students, (int)tr.refused, (long long)tr.records_replayed);
+            rows = succ = steps = 0;
+            rsum = rmin = rmax = 0.0;
+        }
+        rc = frirl_hip_batch_evaluate(b, K, start, sc, &best);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_evaluate(evaluate)", rc);
+        for (e = 0; e < agents; e++) {
+            if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_min < rmin)) rmin = sc[e].reward_min;
+            if (sc[e].rows > 0 && (rows == 0 || sc[e].reward_max > rmax)) rmax = sc[e].reward_max;
+            rows += sc[e].rows; succ += sc[e].successes; steps += sc[e].steps_sum; rsum += sc[e].reward_sum;
+        }
+        if (verbose) {
+            printf("evaluate %s: agents %d rows %lld successful %.4f mean-steps %.3f mean-reward %.6f (min %.6f max %.6f) spread %.3f\n", env, agents, rows,
+                   rows ? (double)succ / rows : 0.0, rows ? (double)steps / rows : 0.0, rows ? rsum / rows : 0.0, rmin, rmax, spread);
+            printf("evaluate %s: best agent %d: %d of %d rows successful, reward-sum %.6f, steps %lld\n", env, (int)best, (int)sc[best].successes,
+                   (int)sc[best].rows, sc[best].reward_sum, (long long)sc[best].steps_sum);
+        }
     }
     frirl_hip_batch_destroy(b);
     demo_desc_free(&mm);
     free(sc); free(start);
     return (int)best;
+}
+
+int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
+                                  const double *units, int verbose)
+{
+    return frirl_demo_batch_run_evaluate_teach(env, agents, max_episodes, load_bin, save_bin, K, spread, units, 0, 1, verbose);
 }
 
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,

@@ -43,6 +43,11 @@ int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episode
  * Returns the best agent's index, or -1 on error. */
 int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
                                   const double *units, int verbose);
+/* The same, then -- teach_episodes >= 1 -- the best agent teaches every other agent teach_episodes greedy episodes in teach_passes
+ * passes (frirl_hip_batch_teach), one `taught:` line with the fields of frirl_hip_teach_result is printed, and the evaluation runs and
+ * prints again.  teach_episodes == 0 is frirl_demo_batch_run_evaluate.  Returns the best agent of the last evaluation, or -1. */
+int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
+                                        const double *units, int teach_episodes, int teach_passes, int verbose);
 
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */

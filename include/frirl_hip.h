@@ -323,6 +323,50 @@ int frirl_hip_rollout_batch(const frirl_hip_tables *t, const frirl_hip_rulebases
                             const frirl_hip_rollout_batch_rows *ro, frirl_hip_rollout_score *scores /* [dev][E] or NULL */,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same roll-outs with EVERY step written out, in the layout frirl_hip_learn_demonstration reads: E * n logs, log q = e * n + j
+ * recorded on the rule base of agent e = q / n, each holding K = `episodes` episodes back to back.  Episode k of log q is the episode of
+ * frirl_hip_rollout_batch's tiled form (frirl_test_run's episode, the rule bases read-only) with the exploration keys
+ * (env_id_base + q, episode k, step); with K = 1 its steps, success, reward bits and last observation are that call's row q.
+ *   start record   start = 1, obs = x0 (the un-quantised start state), q_obs = reward = success = 0, action = the epsilon-greedy pick
+ *                  (key step 0) on the first maximum of Q at the un-quantised x0
+ *   step s >= 1    start = 0, obs = x_s, q_obs = its quantised form, reward, success, action = the epsilon-greedy pick (key step s) on
+ *                  the greedy action at q_obs -- the terminal record carries its pick too (frirl_hip_agent_observe_taught's target)
+ * An episode ends after the record with success == 1 or s == agent->max_steps, so an episode of s steps is s + 1 records; the next
+ * episode's start record follows immediately.  No write ever goes to a record index >= T: an episode in progress when the log is full is
+ * cut there (ep_steps = the steps recorded), and an episode is not begun when fewer than 2 records are free -- it and every later
+ * episode of the log read ep_steps -1, ep_reward 0, ep_success 0.  T >= K * (max_steps + 1) never truncates.  length[q] = records
+ * written; the records at and beyond it are left untouched.  ep_reward is the sum of the step rewards in step order.
+ * A log is NOT recorded when j >= row_count[e], when its agent is inactive, or when nrules[e] lies outside 1..maxR: length 0, every
+ * ep_steps -1, the log arrays untouched.  That is decided on the device: the call reads nothing back, does not synchronise and
+ * allocates nothing.
+ * Lane shapes: those of frirl_hip_rollout_batch's tiled form (4 lanes per log for up to 4 actions, else 8, times 1 / 4 / 8 rule slices
+ * by the logs of the whole call; a full wave per log when n == 1); option "rollout_record_slices" (0 = automatic) forces the slices.
+ * Any Shepard power (agent->p != nant runs the variants without rule slices).
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL t / b / agent / log / obs / action / reward / success / start / length,
+ * n < 1, episodes < 1, T < 2, E * n > INT32_MAX, E * n * T overflowing int64, A outside 1..32, an env_kind that is not one of the three
+ * demos with its antecedent count, a grid_len outside 1..FRIRL_HIP_MAX_GRID. */
+typedef struct frirl_hip_rollout_log {
+    int32_t n;            /* logs per agent; log q = e * n + j is recorded on the rule base of agent e = q / n (b->E >= 1) */
+    int32_t episodes;     /* K >= 1 episodes per log, stored back to back */
+    int32_t T;            /* record capacity of every log */
+    int32_t reserved;
+    const double  *start_states; /* [dev] [E*n][K][nant-1], or NULL = agent->values_def for every episode */
+    const int32_t *row_count;    /* [dev] [E] logs of agent e that exist (clamped 0..n), or NULL = n   */
+    const uint8_t *active;       /* [dev] [E] 0 = skip this agent, or NULL = all                        */
+    /* the logs: struct frirl_hip_demonstration's arrays with agent_stride = T */
+    double  *obs;      /* [dev] [E*n][T][nant-1] */
+    double  *q_obs;    /* [dev] same shape, or NULL */
+    int32_t *action;   /* [dev] [E*n][T] */
+    double  *reward;   /* [dev] [E*n][T] */
+    int32_t *success;  /* [dev] [E*n][T] */
+    uint8_t *start;    /* [dev] [E*n][T] */
+    int32_t *length;   /* [dev] [E*n] records written */
+    /* per episode, each optional */
+    int32_t *ep_steps; double *ep_reward; int32_t *ep_success;   /* [dev] [E*n][K] */
+} frirl_hip_rollout_log;
+int frirl_hip_rollout_record(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                             const frirl_hip_rollout_log *log, void *stream);
+
 /* Rule-base reduction (reference frirl_sequential_run.c:170-350, strategies 1 = smallest |Q| first, 2 = largest |Q|
  * first) as a batched "try-remove" on the GPU.  The reference tests ONE candidate per replayed episode: remove it, replay
  * greedily, keep the removal iff the episode still succeeds (reward > agent->reward_good_above) in the same number of
@@ -882,6 +926,25 @@ int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_t
  * then the largest reward_sum, then the lowest index.  The workspace is allocated and freed inside the call, which synchronises. */
 int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states /* HOST [E][n][nant-1], or NULL */,
                              frirl_hip_rollout_score *scores /* HOST [E] */, int32_t *best);
+/* "Evaluate -> record the best agent -> every other agent learns the log", on the device.  Agent `teacher` records ONE log of
+ * `episodes` greedy episodes (frirl_hip_rollout_record on its rule base with agent.no_random = 1, T = episodes * (max_steps + 1));
+ * episode k starts at start_states[k], NULL = the own start state of agent k % E (its desc.start_states row, agent.values_def where
+ * the batch has none).  Every student then replays that log `passes` times through frirl_hip_learn_demonstration (agent_stride = 0,
+ * length 0 for everybody else); the log never leaves the device, only `result` is read back.  Afterwards the teacher's rule base,
+ * rule count and convergence state are what they were, bit for bit; every student's convergence state is cleared as
+ * frirl_hip_batch_load_rulebases clears it (not converged, no previous episode to compare with, the snapshot of rule count and
+ * consequents retaken; its episode counter stays), its index mirror is kept by the replay, and frirl_hip_batch_train simply continues.
+ * FRIRL_HIP_EINVAL: a NULL batch, teacher outside 0..E-1, episodes < 1 (or episodes * (max_steps + 1) > INT32_MAX), passes outside
+ * 1..1024, a teacher whose nrules lies outside 1..maxR.  The buffers are allocated and freed inside the call, which synchronises. */
+typedef struct frirl_hip_teach_result {
+    int32_t teacher, episodes_recorded, successes, records;   /* of the teacher's log                      */
+    int32_t students, refused;                                /* agents taught; those with a refused append */
+    int64_t records_replayed;                                 /* summed over students and passes            */
+} frirl_hip_teach_result;
+int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_t episodes,
+                          const double *start_states /* HOST [episodes][nant-1], or NULL */, int32_t passes,
+                          const uint8_t *students /* HOST [E], or NULL = every agent but the teacher */,
+                          frirl_hip_teach_result *result);
 /* One round of the reference's multi-agent rule-base exchange (frirl_omp_run, frirl_agent.c:426-462) inside the batch: every agent
  * id >= 1 takes over the master's (agent 0's) rules -- all of them in one launch of frirl_hip_merge_rb --, then the master takes
  * over the rules of agent 1, 2, ... in turn.  Agents whose rule base is complete do not send (:432,:444).  *full_agents (or NULL):
