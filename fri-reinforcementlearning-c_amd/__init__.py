@@ -113,6 +113,19 @@ class ReduceResult(C.Structure):
                 ("steps_incremental", C.c_int32), ("reserved", C.c_int32), ("reward", C.c_double)]
 
 
+class ReduceStarts(C.Structure):
+    """struct frirl_hip_reduce_starts (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("drop_bad_starts", C.c_int32), ("start_states", C.c_void_p), ("start_count", C.c_void_p)]
+
+
+class ReduceStartResult(C.Structure):
+    """struct frirl_hip_reduce_start_result (include/frirl_hip.h)."""
+    _fields_ = [("used", C.c_int32), ("steps_incremental", C.c_int32), ("baseline_reward", C.c_double), ("reward", C.c_double)]
+
+
+REDUCE_MAX_STARTS = 256
+
+
 class AgentIO(C.Structure):
     """struct frirl_hip_agent_io (include/frirl_hip.h)."""
     _fields_ = [("obs", C.c_void_p), ("q_obs", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p), ("reset", C.c_void_p),
@@ -195,6 +208,13 @@ SIGNATURES = {
                                          C.c_double, C.c_int, C.POINTER(C.c_int32), C.POINTER(ReduceResult), C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_reduce_walk_check": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _DP, C.c_int, C.c_double, C.c_double, C.c_double,
                                               C.POINTER(C.c_uint32), _DP]),
+    "frirl_hip_reduce_batch_starts_depth": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch_starts_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch_starts": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(ReduceStarts),
+                                                C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int32), C.POINTER(ReduceResult),
+                                                C.POINTER(ReduceStartResult), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_reduce_walk_starts_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32), _DP, C.c_double, C.c_double,
+                                                     C.POINTER(C.c_uint32)]),
     "frirl_hip_lanes_preferred": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_lanes_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_episode_run_lanes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32,
@@ -268,6 +288,8 @@ SIGNATURES = {
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult)]),
     "frirl_hip_batch_reduce_all": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_reduce_all_starts": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int32, _DP, C.c_int, C.POINTER(ReduceResult),
+                                                    C.POINTER(ReduceStartResult), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_teach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(TeachResult)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -664,6 +686,36 @@ class Problem:
                                            strategy, reward_tolerance, depth, kept.ctypes.data_as(C.POINTER(C.c_int32)), res, _ptr(ws), nbytes,
                                            _stream(stream)), "frirl_hip_reduce_batch")
         return [kept[e, : res[e].rules_after].copy() for e in range(self.E)], list(res)
+
+    def reduce_batch_starts(self, agent, strategy, reward_tolerance, depth, start_states, start_count=None, drop_bad_starts=False, rant=None,
+                            active=None, stream=None):
+        """frirl_hip_reduce_batch_starts: reduce_batch with every removal validated against the start states start_states[e, :start_count[e]]
+        ([E, n, nant-1] f64; start_count [E] int32, None = n): a removal is accepted iff the replay from EVERY used start accepts it.
+        drop_bad_starts: starts whose baseline episode is not good are left out instead of blocking every removal.  Compacts the rule
+        bases in place.  Returns (list of kept original indices, list of ReduceResult, per-start ReduceStartResult [E][n])."""
+        import numpy as np
+        import torch
+        dev_ = self.rb.device
+        assert start_states.dim() == 3 and start_states.shape[0] == self.E and start_states.shape[2] == self.nant - 1
+        assert start_states.dtype == torch.float64 and start_states.is_contiguous()
+        n = int(start_states.shape[1])
+        if start_count is not None:
+            assert start_count.shape == (self.E,) and start_count.dtype == torch.int32 and start_count.is_contiguous()
+        if active is not None:
+            assert active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous()
+        if rant is not None:
+            assert rant.shape == (self.E, self.nant, self.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
+        st = ReduceStarts(n, 1 if drop_bad_starts else 0, _ptr(start_states), _ptr(start_count))
+        nbytes = lib().frirl_hip_reduce_batch_starts_workspace_bytes(self.nant, self.E, self.maxR, depth, n)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev_)
+        kept = np.zeros((self.E, self.maxR), dtype=np.int32)
+        res = (ReduceResult * self.E)()
+        per = (ReduceStartResult * (self.E * n))()
+        check(lib().frirl_hip_reduce_batch_starts(C.byref(self.tables), C.byref(self.bases), C.byref(agent.desc), _ptr(rant), C.byref(st), _ptr(active),
+                                                  strategy, reward_tolerance, depth, kept.ctypes.data_as(C.POINTER(C.c_int32)), res, per, _ptr(ws),
+                                                  nbytes, _stream(stream)), "frirl_hip_reduce_batch_starts")
+        return ([kept[e, : res[e].rules_after].copy() for e in range(self.E)], list(res),
+                [[per[e * n + k] for k in range(n)] for e in range(self.E)])
 
     def policy_begin(self, agent, rows, obs, reset=None, stream=None):
         """frirl_hip_policy_begin: rows (PolicyRows) selected by `reset` ([Q] uint8 / bool, None = all) start a greedy episode on this ONE

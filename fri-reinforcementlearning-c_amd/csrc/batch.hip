@@ -362,6 +362,37 @@ extern "C" int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, doub
     return FRIRL_HIP_OK;
 }
 
+extern "C" int frirl_hip_batch_reduce_all_starts(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, int32_t n, const double *start_states,
+                                                 int drop_bad_starts, frirl_hip_reduce_result *results, frirl_hip_reduce_start_result *per_start,
+                                                 int32_t *agents_reduced)
+{
+    static const char *who = "frirl_hip_batch_reduce_all_starts";
+    if (!b || !start_states) { set_error("%s: NULL batch or start states", who); return FRIRL_HIP_EINVAL; }
+    if (n < 1 || n > FRIRL_HIP_REDUCE_MAX_STARTS) { set_error("%s: n=%d start states outside 1..%d", who, n, FRIRL_HIP_REDUCE_MAX_STARTS); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    std::vector<frirl_hip_reduce_result> res(b->E);
+    const size_t bytes = frirl_hip_reduce_batch_starts_workspace_bytes(b->nant, b->E, b->maxR, depth, n);      // 0: a bad depth, refused below
+    const size_t sbytes = (sizeof(double) * (size_t)b->E * n * (b->nant - 1) + 15) / 16 * 16;
+    char *mem = nullptr;
+    BCHK(hipMalloc(reinterpret_cast<void **>(&mem), sbytes + bytes), "reduction workspace");
+    hipError_t up = hipMemcpyAsync(mem, start_states, sizeof(double) * (size_t)b->E * n * (b->nant - 1), hipMemcpyHostToDevice, b->s);
+    if (up == hipSuccess) up = hipStreamSynchronize(b->s);             // start_states is the caller's pageable memory
+    if (up != hipSuccess) { (void)hipFree(mem); set_error("%s: start states upload: %s", who, hipGetErrorString(up)); return FRIRL_HIP_ELAUNCH; }
+    frirl_hip_reduce_starts st = {};
+    st.n = n;
+    st.drop_bad_starts = drop_bad_starts;
+    st.start_states = reinterpret_cast<const double *>(mem);
+    const int rc = frirl_hip_reduce_batch_starts(&b->t, &b->rb, &b->agent, b->d_rant, &st, nullptr, strategy, reward_tolerance, depth, nullptr, res.data(),
+                                                 per_start, bytes ? mem + sbytes : nullptr, bytes, b->s);
+    (void)hipFree(mem);
+    if (rc) return rc;
+    int32_t reduced = 0;
+    for (int e = 0; e < b->E; e++) reduced += res[e].rules_after < res[e].rules_before;
+    if (results) memcpy(results, res.data(), sizeof(frirl_hip_reduce_result) * b->E);
+    if (agents_reduced) *agents_reduced = reduced;
+    return FRIRL_HIP_OK;
+}
+
 extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)
 {
     static const char *who = "frirl_hip_batch_evaluate";

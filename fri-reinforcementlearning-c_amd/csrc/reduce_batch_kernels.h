@@ -1,7 +1,8 @@
-// reduce_batch_kernels.h -- what the two batched reductions share: the arrays of a run (ReduceBatchWs), the order, open-round,
-// close-round and result kernels, and the host helpers for lane shapes and the workspace layout.  frirl_hip_reduce_batch
-// (reduce_batch.hip) rolls the replays out inside its own kernel; frirl_hip_batch_reducer_* (policy_batch.hip) steps them in the
-// caller's environment.  Moved out of reduce_batch.hip as shared_sweep.h and rollout_episode.h were; the only change is that the
+// reduce_batch_kernels.h -- what the batched reductions share: the arrays of a run (ReduceBatchWs), the order, open-round,
+// close-round and result kernels, the in-place compaction, and the host helpers for lane shapes and the workspace layout.
+// frirl_hip_reduce_batch (reduce_batch.hip) rolls the replays out inside its own kernel; frirl_hip_batch_reducer_* (policy_batch.hip)
+// steps them in the caller's environment; frirl_hip_reduce_batch_starts (reduce_starts.hip) replays every node from several start
+// states and brings its own roll-out and close kernels.  Moved out of reduce_batch.hip as shared_sweep.h and rollout_episode.h were; the only change is that the
 // kernels that are no templates have internal linkage (`static`), since two translation units now hold them.
 #pragma once
 #include "shared_sweep.h"
@@ -93,66 +94,72 @@ static __global__ __launch_bounds__(256) void reduce_batch_open_kernel(const int
     }
 }
 
+// In-place compaction of ONE agent's columns after a walk that ended with `bits` != 0 (both close kernels): chunks of 256 rules in
+// index order, every chunk read into registers by all threads before any of it is written, and a write never lands above its read;
+// then the vacated tail is zeroed.  Every thread of the 256-thread workgroup calls it with the same arguments; wave_kept: 4 ints of
+// LDS.  Returns the number of rules left.
+template <int NANT>
+__device__ __forceinline__ int reduce_batch_compact(double *cols, double *ra, uint16_t *ui, int32_t *al, const uint8_t *sl, size_t M, int R, uint32_t bits, int *wave_kept)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int r0 = 0; r0 < R; r0 += 256) {
+        const int r = r0 + tid;
+        const bool keep = r < R && !rw_dropped(sl[r], bits);
+        double v[NANT + 1], w[NANT];
+        uint16_t x[NANT];
+        int a = 0;
+        if (keep) {
+#pragma unroll
+            for (int k = 0; k <= NANT; k++) v[k] = cols[k * M + r];
+#pragma unroll
+            for (int k = 0; k < NANT; k++) { w[k] = ra ? ra[k * M + r] : 0.0; x[k] = ui ? ui[k * M + r] : (uint16_t)0; }
+            a = al[r];
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wave_kept[wave] = __popcll(bal);
+        __syncthreads();                                           // the chunk is in registers; the wave counts are visible
+        int pos = base + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+        for (int i = 0; i < 4; i++) { pos += i < wave ? wave_kept[i] : 0; tot += wave_kept[i]; }
+        if (keep && pos != r) {                                    // pos <= r
+#pragma unroll
+            for (int k = 0; k <= NANT; k++) cols[k * M + pos] = v[k];
+#pragma unroll
+            for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + pos] = w[k]; if (ui) ui[k * M + pos] = x[k]; }
+            al[pos] = a;
+        }
+        base += tot;
+        __syncthreads();                                           // wave_kept is rewritten by the next chunk
+    }
+    for (int r = base + tid; r < R; r += 256) {                    // vacated tail: zero like five_remove_rule.c:64-80
+#pragma unroll
+        for (int k = 0; k <= NANT; k++) cols[k * M + r] = 0.0;
+#pragma unroll
+        for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + r] = 0.0; if (ui) ui[k * M + r] = 0; }
+    }
+    return base;
+}
+
 // Close-round kernel: one workgroup per live agent.  first: the baseline replay sets steps_incremental, prev_reward and the
-// agent's step cap.  Otherwise: walk the tree (every thread, same result), compact the rule base in place -- chunks of 256 rules
-// in index order, every chunk read into registers by all threads before any of it is written, and a write never lands above
-// its read -- zero the vacated tail, advance the agent and append it to the next live list while candidates are left.
+// agent's step cap.  Otherwise: walk the tree (every thread, same result), compact the rule base in place
+// (reduce_batch_compact), advance the agent and append it to the next live list while candidates are left.
 template <int NANT>
 __global__ __launch_bounds__(256) void reduce_batch_close_kernel(double *__restrict__ rb, int32_t *__restrict__ nrules, uint16_t *__restrict__ uidx,
                                                                  double *__restrict__ rant, int maxR, int cur, int first, int max_steps,
                                                                  double good_above, double tol, ReduceBatchWs ws)
 {
     __shared__ int wave_kept[4];
-    const int e = ws.live[cur][blockIdx.x], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int e = ws.live[cur][blockIdx.x], tid = threadIdx.x;
     const size_t M = (size_t)maxR;
     const int R = nrules[e], d = first ? 0 : ws.d[e];
     const int steps_inc = first ? ws.steps[(size_t)e * ws.nodes] : ws.steps_inc[e];
     double prev = first ? ws.reward[(size_t)e * ws.nodes] : ws.prev[e];
     const uint32_t bits = rw_walk(d, ws.steps + (size_t)e * ws.nodes, ws.reward + (size_t)e * ws.nodes, steps_inc, prev, good_above, tol);
     int Rn = R;
-    if (bits) {                                                        // uniform: every thread walked the same tree
-        double *cols = rb + (size_t)e * (NANT + 1) * M;
-        double *ra = rant ? rant + (size_t)e * NANT * M : nullptr;
-        uint16_t *ui = uidx ? uidx + (size_t)e * NANT * M : nullptr;
-        int32_t *al = ws.alive + (size_t)e * M;
-        const uint8_t *sl = ws.slot + (size_t)e * M;
-        int base = 0;
-        for (int r0 = 0; r0 < R; r0 += 256) {
-            const int r = r0 + tid;
-            const bool keep = r < R && !rw_dropped(sl[r], bits);
-            double v[NANT + 1], w[NANT];
-            uint16_t x[NANT];
-            int a = 0;
-            if (keep) {
-#pragma unroll
-                for (int k = 0; k <= NANT; k++) v[k] = cols[k * M + r];
-#pragma unroll
-                for (int k = 0; k < NANT; k++) { w[k] = ra ? ra[k * M + r] : 0.0; x[k] = ui ? ui[k * M + r] : (uint16_t)0; }
-                a = al[r];
-            }
-            const unsigned long long bal = __ballot(keep);
-            if (lane == 0) wave_kept[wave] = __popcll(bal);
-            __syncthreads();                                           // the chunk is in registers; the wave counts are visible
-            int pos = base + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
-            for (int i = 0; i < 4; i++) { pos += i < wave ? wave_kept[i] : 0; tot += wave_kept[i]; }
-            if (keep && pos != r) {                                    // pos <= r
-#pragma unroll
-                for (int k = 0; k <= NANT; k++) cols[k * M + pos] = v[k];
-#pragma unroll
-                for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + pos] = w[k]; if (ui) ui[k * M + pos] = x[k]; }
-                al[pos] = a;
-            }
-            base += tot;
-            __syncthreads();                                           // wave_kept is rewritten by the next chunk
-        }
-        Rn = base;
-        for (int r = Rn + tid; r < R; r += 256) {                      // vacated tail: zero like five_remove_rule.c:64-80
-#pragma unroll
-            for (int k = 0; k <= NANT; k++) cols[k * M + r] = 0.0;
-#pragma unroll
-            for (int k = 0; k < NANT; k++) { if (ra) ra[k * M + r] = 0.0; if (ui) ui[k * M + r] = 0; }
-        }
-    }
+    if (bits)                                                          // uniform: every thread walked the same tree
+        Rn = reduce_batch_compact<NANT>(rb + (size_t)e * (NANT + 1) * M, rant ? rant + (size_t)e * NANT * M : nullptr,
+                                        uidx ? uidx + (size_t)e * NANT * M : nullptr, ws.alive + (size_t)e * M, ws.slot + (size_t)e * M, M, R, bits,
+                                        wave_kept);
     __syncthreads();                                                   // every thread has read the agent's state
     if (tid != 0) return;
     if (first) {

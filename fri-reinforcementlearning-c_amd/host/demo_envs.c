@@ -458,13 +458,33 @@ int frirl_demo_multi_merged_run(const char *env, int agents, int gpus, int max_e
     return rounds;
 }
 
+/* start states [agents][K][ns] of K rows per agent: row 0 = agent.values_def, row j >= 1 = values_def[k] + spread * units[e][j][k] *
+ * (largest - smallest grid value of dimension k), clipped to the grid (frirl_demo.h: frirl_demo_batch_run_evaluate) */
+static void demo_row_starts(const frirl_hip_batch_desc *d, const struct demo_desc_mem *mm, int agents, int K, int ns, double spread, const double *units,
+                            double *start)
+{
+    int e, j, k;
+    for (k = 0; k < ns; k++) {
+        const double *g = mm->grid + (size_t)k * FRIRL_HIP_MAX_GRID;
+        double lo = g[0], hi = g[0];
+        for (j = 0; j < d->agent.grid_len[k]; j++) { if (g[j] < lo) lo = g[j]; if (g[j] > hi) hi = g[j]; }
+        for (e = 0; e < agents; e++)
+            for (j = 0; j < K; j++) {
+                const size_t i = ((size_t)e * K + j) * ns + k;
+                double v = d->agent.values_def[k] + spread * units[i] * (hi - lo);
+                if (j == 0) v = d->agent.values_def[k];             /* the agent's own start state */
+                start[i] = v < lo ? lo : (v > hi ? hi : v);
+            }
+    }
+}
+
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
-                          const char *save_bin, const char *out_txt, int verbose);
+                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int verbose);
 
 int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
                                         const double *units, int teach_episodes, int teach_passes, int verbose)
 {
-    int nant = 0, ns, episodes = 0, rc, e, j, k, stage;
+    int nant = 0, ns, episodes = 0, rc, e, stage;
     int32_t best = 0;
     frirl_hip_batch_desc d;
     struct demo_desc_mem mm;
@@ -478,18 +498,7 @@ int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_epi
     sc = malloc(sizeof *sc * (size_t)agents);
     start = malloc(sizeof(double) * (size_t)agents * (size_t)K * (size_t)ns);
     if (!sc || !start) return -1;
-    for (k = 0; k < ns; k++) {
-        const double *g = mm.grid + (size_t)k * FRIRL_HIP_MAX_GRID;
-        double lo = g[0], hi = g[0];
-        for (j = 0; j < d.agent.grid_len[k]; j++) { if (g[j] < lo) lo = g[j]; if (g[j] > hi) hi = g[j]; }
-        for (e = 0; e < agents; e++)
-            for (j = 0; j < K; j++) {
-                const size_t i = ((size_t)e * K + j) * ns + k;
-                double v = d.agent.values_def[k] + spread * units[i] * (hi - lo);
-                if (j == 0) v = d.agent.values_def[k];              /* the agent's own start state */
-                start[i] = v < lo ? lo : (v > hi ? hi : v);
-            }
-    }
+    demo_row_starts(&d, &mm, agents, K, ns, spread, units, start);
     b = frirl_hip_batch_create(&d);
     if (!b) five_dropin_fatal("frirl_demo_batch_run_evaluate(create)", FRIRL_HIP_ENODEV);
     if (load_bin) {
@@ -545,17 +554,25 @@ int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes,
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                             const char *out_txt, int verbose)
 {
-    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 0, load_bin, save_bin, out_txt, verbose);
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 0, load_bin, save_bin, out_txt, 0, 0.0, NULL, verbose);
 }
 
 int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                     const char *out_txt, int verbose)
 {
-    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, verbose);
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, 0, 0.0, NULL, verbose);
 }
 
+int frirl_demo_batch_run_reduce_all_starts(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                           const char *out_txt, int K, double spread, const double *units, int verbose)
+{
+    if (K < 1 || K > FRIRL_HIP_REDUCE_MAX_STARTS || !units || !(spread >= 0.0) || (reduce_strategy != 1 && reduce_strategy != 2)) return -1;
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, K, spread, units, verbose);
+}
+
+/* starts >= 1: the reduction of every agent validates each removal against `starts` start states per agent (demo_row_starts) */
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
-                          const char *save_bin, const char *out_txt, int verbose)
+                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int verbose)
 {
     int nant = 0, episodes = 0, rc;
     frirl_hip_batch_desc d;
@@ -595,13 +612,28 @@ static int demo_batch_run(const char *env, int agents, int max_episodes, int red
         long long before = 0, after = 0, rollouts = 0;
         int32_t reduced = 0, rounds = 0;
         int e;
-        rc = rr ? frirl_hip_batch_reduce_all(b, reduce_strategy, 0.0, 0, rr, &reduced) : FRIRL_HIP_ELAUNCH;
+        long long used = 0;
+        if (rr && starts >= 1) {                  /* starts whose baseline episode is not good are left out (drop_bad_starts = 1) */
+            const size_t rows = (size_t)agents * (size_t)starts;
+            double *start = malloc(sizeof(double) * rows * (size_t)(nant - 1));
+            frirl_hip_reduce_start_result *ps = malloc(sizeof *ps * rows);
+            size_t i;
+            if (!start || !ps) five_dropin_fatal("frirl_demo_batch_run(reduce all)", FRIRL_HIP_ELAUNCH);
+            demo_row_starts(&d, &mm, agents, starts, nant - 1, spread, units, start);
+            rc = frirl_hip_batch_reduce_all_starts(b, reduce_strategy, 0.0, 0, starts, start, 1, rr, ps, &reduced);
+            for (i = 0; rc == 0 && i < rows; i++) used += ps[i].used;
+            free(start); free(ps);
+        } else
+            rc = rr ? frirl_hip_batch_reduce_all(b, reduce_strategy, 0.0, 0, rr, &reduced) : FRIRL_HIP_ELAUNCH;
         if (rc) five_dropin_fatal("frirl_demo_batch_run(reduce all)", rc);
         for (e = 0; e < agents; e++) {
             before += rr[e].rules_before; after += rr[e].rules_after; rollouts += rr[e].rollouts;
             if (rr[e].rounds > rounds) rounds = rr[e].rounds;
         }
-        if (verbose)
+        if (verbose && starts > 1)                /* one start state: the agent's own, the line of the run without start states */
+            printf("batch %s: %d of %d agents reduced, %lld -> %lld rules (strategy %d, %d rounds, %lld replays), starts used %lld of %lld\n", env,
+                   (int)reduced, agents, before, after, reduce_strategy, (int)rounds, rollouts, used, (long long)agents * starts);
+        else if (verbose)
             printf("batch %s: %d of %d agents reduced, %lld -> %lld rules (strategy %d, %d rounds, %lld replays)\n", env, (int)reduced, agents, before,
                    after, reduce_strategy, (int)rounds, rollouts);
         free(rr);

@@ -36,6 +36,11 @@ int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int r
  * alone; prints one summary line: agents reduced, rules before -> after summed over the agents, rounds, replays */
 int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                     const char *out_txt, int verbose);
+/* the same with every removal validated against K start states per agent (frirl_hip_batch_reduce_all_starts, drop_bad_starts = 1): the
+ * rows of frirl_demo_batch_run_evaluate (row 0 = agent.values_def; units HOST [agents][K][nstates]), 1 <= K <= 256.  For K > 1 the
+ * summary line also says how many of the agents * K start states were used; K == 1 prints the line of frirl_demo_batch_run_reduce_all */
+int frirl_demo_batch_run_reduce_all_starts(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                           const char *out_txt, int K, double spread, const double *units, int verbose);
 /* Population evaluation: the agents learn (or, load_bin != NULL, load their rule bases), then EVERY agent is rolled out greedily on its
  * own rule base from K start states (frirl_hip_batch_evaluate): row 0 = agent.values_def, row j >= 1 = values_def[k] + spread *
  * units[e][j][k] * (largest - smallest grid value of dimension k), clipped to the grid; units HOST [agents][K][nstates] in -1..1.

@@ -426,6 +426,52 @@ int frirl_hip_reduce_batch(const frirl_hip_tables *t, const frirl_hip_rulebases 
 int frirl_hip_reduce_walk_check(int d, const int32_t *steps, const double *reward, int steps_inc, double prev_reward, double good_above, double tol,
                                 uint32_t *bits_out, double *prev_out);
 
+/* frirl_hip_reduce_batch with every removal validated against SEVERAL start states per agent (DESIGN.md "Reduction against a set of
+ * start states").  Per agent e, independent of every other agent:
+ *   starts     start k takes part iff k < start_count[e] (clamped to 1..n; NULL = n)
+ *   baseline   the un-reduced rule base is replayed greedily from every participating start: steps_inc[e][k], prev[e][k] and the step
+ *              cap[e][k] = min(max_steps, steps_inc[e][k] + 1) of the replays from that start
+ *   drop_bad_starts == 0: a start whose baseline reward is not > reward_good_above stays in and so blocks every removal (what
+ *              frirl_hip_reduce_batch does with its one start); 1: such starts are left out of the agent's tests (decided on the device
+ *              after the baseline).  The starts that remain are the agent's USED starts; an agent with none keeps every rule, rounds == 0
+ *   trial      candidate order, tree of d_e = min(depth, R0_e - j_e) candidates, masks and compaction are frirl_hip_reduce_batch's; every
+ *              node is replayed from every used start, and the removal on trial at a node is accepted iff the acceptance test (:212)
+ *              holds for ALL used starts; prev[e][k] then moves to that node's reward from start k (:222, per start)
+ * With n == 1 and drop_bad_starts == 0 every output (results, kept, the device state) equals frirl_hip_reduce_batch's for the same inputs.
+ * A round's rows for agent e are nodes x used starts (row = node * K_e + ki); rows of one agent with different caps share a workgroup.
+ *   results    [host] [E]; steps_incremental and reward are those of the agent's first used start (start 0 where none is used);
+ *              rollouts = baseline replays + (2^d - 1) * K_e per round
+ *   per_start  [host] [E][n] or NULL; an inactive agent's entries are {0, -1, 0, 0}
+ *   workspace  [dev] 16-byte aligned, >= frirl_hip_reduce_batch_starts_workspace_bytes(nant, E, maxR, depth, n) bytes
+ * The other arguments are those of frirl_hip_reduce_batch; arguments are checked before the device is looked for.
+ * frirl_hip_reduce_batch_starts_depth: the largest depth in 1..10 with E * n * (2^depth - 1) <= the rows that stay resident (see
+ * frirl_hip_reduce_batch_depth), at least 1.  Results never depend on the depth.
+ * frirl_hip_reduce_batch_starts_workspace_bytes: a multiple of 16, non-decreasing in every argument (depth 0: enough for any action
+ * count); 0 for E < 1, maxR < 1, a depth outside 0..12 or n outside 1..FRIRL_HIP_REDUCE_MAX_STARTS. */
+#define FRIRL_HIP_REDUCE_MAX_STARTS 256
+typedef struct frirl_hip_reduce_starts {
+    int32_t n;                    /* start states per agent, 1..FRIRL_HIP_REDUCE_MAX_STARTS */
+    int32_t drop_bad_starts;      /* 0 / 1, above */
+    const double *start_states;   /* [dev] [E][n][nant-1] */
+    const int32_t *start_count;   /* [dev] [E], clamped 1..n, or NULL = n */
+} frirl_hip_reduce_starts;
+typedef struct frirl_hip_reduce_start_result {   /* 24 bytes */
+    int32_t used;                 /* 1 = took part in the trials */
+    int32_t steps_incremental;    /* steps of the baseline replay from this start; -1 for k >= start_count[e] */
+    double baseline_reward;       /* prev_reward at the baseline */
+    double reward;                /* prev_reward after the last accepted removal */
+} frirl_hip_reduce_start_result;
+int frirl_hip_reduce_batch_starts_depth(int32_t E, int32_t A, int32_t n);
+size_t frirl_hip_reduce_batch_starts_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t depth, int32_t n);
+int frirl_hip_reduce_batch_starts(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                                  const frirl_hip_reduce_starts *starts, const uint8_t *active, int strategy, double reward_tolerance, int depth,
+                                  int32_t *kept, frirl_hip_reduce_result *results, frirl_hip_reduce_start_result *per_start, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+/* Host-only probe of the walk over nodes x starts (csrc/reduce_walk.h: rw_walk_starts): d candidates (0..12), K starts
+ * (1..FRIRL_HIP_REDUCE_MAX_STARTS), steps / reward HOST [2^d - 1][K], steps_inc HOST [K], prev HOST [K] in / out.  Needs no device. */
+int frirl_hip_reduce_walk_starts_check(int d, int K, const int32_t *steps, const double *reward, const int32_t *steps_inc, double *prev,
+                                       double good_above, double tol, uint32_t *bits_out);
+
 /* Per-environment episode state (reference: fields of frirl_desc + frirl_reward_desc that
  * frirl_episode() carries from step to step, src/frirl/frirl_episode.c:28-194). */
 typedef struct frirl_hip_envs {
@@ -919,6 +965,11 @@ int frirl_hip_batch_reduce(frirl_hip_batch *b, int32_t e, int strategy, double r
  * allocated and freed inside the call.  results: HOST [E] or NULL; *agents_reduced (or NULL): agents that lost at least one rule. */
 int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, frirl_hip_reduce_result *results,
                                int32_t *agents_reduced);
+/* The same with every removal validated against n start states per agent (frirl_hip_reduce_batch_starts; every start counts).
+ * start_states: HOST [E][n][nant-1]; per_start: HOST [E][n] or NULL.  Workspace and device copies are allocated and freed inside. */
+int frirl_hip_batch_reduce_all_starts(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, int32_t n, const double *start_states,
+                                      int drop_bad_starts, frirl_hip_reduce_result *results, frirl_hip_reduce_start_result *per_start,
+                                      int32_t *agents_reduced);
 /* Greedy roll-outs of EVERY agent of the batch on its own rule base from n start states each (frirl_hip_rollout_batch with
  * agent.no_random = 1): which of the agents is any good away from the start state it trained on.  Row 0 .. n-1 of agent e start at
  * start_states[e][0 .. n-1]; NULL = every row at the agent's own start (its desc.start_states row, agent.values_def where the batch

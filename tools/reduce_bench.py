@@ -5,7 +5,11 @@
 python tools/reduce_bench.py [--depth 10] [--envs 65536]
 With --agents E (repeatable) instead: the batched reduction of E learned rule bases (frirl_hip_reduce_batch, every agent from its own
 start state) against a loop of frirl_hip_reduce_shared over the same rule bases with values_def set per agent, mountaincar and acrobot:
-python tools/reduce_bench.py --agents 64 --agents 4096 [--depth 0] [--loop-sample 64] [--reps 2]"""
+python tools/reduce_bench.py --agents 64 --agents 4096 [--depth 0] [--loop-sample 64] [--reps 2]
+With --agents E --starts K (both repeatable): the reduction against K start states per agent (frirl_hip_reduce_batch_starts, strategy 1) on
+the same learned rule bases: n = 1 against frirl_hip_reduce_batch (alternating), n = K against n = 1 (time, rounds, rules kept), and how many
+of the independent test starts that the un-reduced rule bases solve are still solved afterwards (Problem.rollout_batch):
+python tools/reduce_bench.py --agents 64 --starts 4 --starts 16 [--reps 3] [--spread 0.1] [--test-starts 32]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
@@ -85,6 +89,90 @@ def batch_leg(env, E, a, dev):
     print(json.dumps(out), flush=True)
 
 
+def starts_leg(env, E, a, dev):
+    """The rule bases of batch_leg (trained from starts at +-0.1 span).  Validation starts: row 0 = the agent's own start, rows 1.. = own
+    +- spread * span (seed 17); test starts: --test-starts per agent, same spread, seed 5.  Host clock around calls that end in a device
+    synchronise; rule bases restored from a snapshot before every timed call; first repetition = warm-up."""
+    d = frirl_amd.demo_describe(env)
+    ns = d["nstates"]
+    lo = np.array([d["grids"][k].min() for k in range(ns)])
+    hi = np.array([d["grids"][k].max() for k in range(ns)])
+    vd = np.array([d["values_def"][k] for k in range(ns)])
+    rng = np.random.default_rng(11)
+    start = np.zeros((E, ns))
+    for k in range(ns):
+        start[:, k] = np.clip(vd[k] + rng.uniform(-0.1, 0.1, E) * (hi[k] - lo[k]), lo[k], hi[k])
+        start[0, k] = vd[k]
+    tens = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    ss = tens(start)
+    prob, agent, envs = frirl_amd.demo_fresh_batch(env, E, 512, dev, start_states=ss)
+    run = frirl_amd.train_persistent(prob, agent, envs, max_episodes=400)
+    torch.cuda.synchronize()
+    snap = [t.clone() for t in (prob.rb, prob.nrules, prob.uidx, envs.rant)]
+
+    def restore():
+        for t, t0 in zip((prob.rb, prob.nrules, prob.uidx, envs.rant), snap):
+            t.copy_(t0)
+        torch.cuda.synchronize()
+
+    def around(n, seed):
+        r = np.random.default_rng(seed)
+        x = np.clip(start[:, None, :] + r.uniform(-a.spread, a.spread, (E, n, ns)) * (hi - lo), lo, hi)
+        return x
+
+    Kmax = max(a.starts)
+    val = around(Kmax, 17)
+    val[:, 0, :] = start
+    test = tens(around(a.test_starts, 5).reshape(E * a.test_starts, ns))
+
+    def solved():
+        _, reward, _, _ = prob.rollout_batch(agent, a.test_starts, start_states=test)
+        torch.cuda.synchronize()
+        return (reward > d["reward_good_above"]).cpu().numpy()
+
+    base = solved()
+    out = {"env": env, "agents": E, "converged": int((run.conv.converged == 1).sum()), "rules_before_sum": int(snap[1].sum()), "strategy": 1,
+           "spread": a.spread, "test_starts": int(base.size), "test_solved_before": int(base.sum())}
+    # 1. n = 1 against frirl_hip_reduce_batch, alternating
+    one = tens(val[:, :1, :])
+    t_b, t_s = [], []
+    for rep in range(max(a.reps, 3) + 1):
+        restore()
+        t0 = time.perf_counter()
+        kept_b, res_b = prob.reduce_batch(agent, 1, 0.0, a.depth, rant=envs.rant, start_states=ss)
+        dt_b = time.perf_counter() - t0
+        restore()
+        t0 = time.perf_counter()
+        kept_s, res_s, _ = prob.reduce_batch_starts(agent, 1, 0.0, a.depth, one, rant=envs.rant)
+        dt_s = time.perf_counter() - t0
+        assert all((x == y).all() for x, y in zip(kept_b, kept_s)) and [r.rollouts for r in res_b] == [r.rollouts for r in res_s]
+        if rep:
+            t_b.append(round(dt_b, 4)); t_s.append(round(dt_s, 4))
+    lost1 = base & ~solved()                                          # the state after the last n = 1 run
+    out.update(reduce_batch_s=t_b, starts_n1_s=t_s, n1_over_reduce_batch_min=round(min(t_s) / min(t_b), 3),
+               n1_over_reduce_batch_median=round(float(np.median(t_s) / np.median(t_b)), 3),
+               n1={"rules_after_sum": int(sum(r.rules_after for r in res_s)), "rounds_max": max(r.rounds for r in res_s),
+                   "depth": a.depth or frirl_amd.lib().frirl_hip_reduce_batch_starts_depth(E, d["A"], 1), "test_lost": int(lost1.sum())})
+    # 2. n = K, start states whose baseline is not good left out
+    for K in a.starts:
+        vk = tens(val[:, :K, :])
+        ts = []
+        for rep in range(max(a.reps, 3) + 1):
+            restore()
+            t0 = time.perf_counter()
+            _, res, per = prob.reduce_batch_starts(agent, 1, 0.0, a.depth, vk, drop_bad_starts=True, rant=envs.rant)
+            dt = time.perf_counter() - t0
+            if rep:
+                ts.append(round(dt, 4))
+        lost = base & ~solved()
+        out[f"n{K}"] = {"s": ts, "over_n1_min": round(min(ts) / min(t_s), 2), "rules_after_sum": int(sum(r.rules_after for r in res)),
+                        "rounds_max": max(r.rounds for r in res), "rollouts_sum": int(sum(r.rollouts for r in res)),
+                        "depth": a.depth or frirl_amd.lib().frirl_hip_reduce_batch_starts_depth(E, d["A"], K),
+                        "starts_used": int(sum(p.used for row in per for p in row)), "starts_given": E * K, "test_lost": int(lost.sum()),
+                        "lost_coverage_recovered": round(1.0 - lost.sum() / lost1.sum(), 3) if lost1.sum() else None}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--depth", type=int, default=0)
@@ -93,12 +181,15 @@ def main():
     ap.add_argument("--loop-sample", type=int, default=64)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--only", default="")
+    ap.add_argument("--starts", type=int, action="append", default=[])
+    ap.add_argument("--spread", type=float, default=0.1)
+    ap.add_argument("--test-starts", type=int, default=32)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.agents:
         for env in ([a.only] if a.only else ["mountaincar", "acrobot"]):
             for E in a.agents:
-                batch_leg(env, E, a, dev)
+                (starts_leg if a.starts else batch_leg)(env, E, a, dev)
         return
     for env in ("mountaincar", "cartpole", "acrobot"):
         prob, agent, envs = learned(env, dev)
