@@ -215,6 +215,8 @@ SIGNATURES = {
                                                 C.POINTER(ReduceStartResult), C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_reduce_walk_starts_check": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32), _DP, C.c_double, C.c_double,
                                                      C.POINTER(C.c_uint32)]),
+    "frirl_hip_reduce_walk_starts_rows_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32),
+                                                          _DP, C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
     "frirl_hip_lanes_preferred": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_lanes_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_episode_run_lanes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32,
@@ -271,6 +273,10 @@ SIGNATURES = {
     "frirl_hip_batch_reducer_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReduceResult)]),
     "frirl_hip_batch_reducer_row_done": (C.c_void_p, [C.c_void_p]),
     "frirl_hip_batch_reducer_destroy": (None, [C.c_void_p]),
+    "frirl_hip_batch_reducer_create_starts": (C.c_void_p, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.c_void_p,
+                                                           C.POINTER(ReduceStarts), C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    "frirl_hip_batch_reducer_result_starts": (C.c_int, [C.c_void_p, C.POINTER(ReduceStartResult)]),
+    "frirl_hip_batch_reducer_starts": (C.c_int, [C.c_void_p]),
     "frirl_hip_episode_run": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_int32, C.c_void_p]),
     "frirl_hip_convergence_init": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(ConvergenceDesc), C.c_void_p]),
     "frirl_hip_convergence_update": (C.c_int, [C.POINTER(RuleBases), C.c_int, C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
@@ -1146,20 +1152,34 @@ class _ReducerBase:
 
 
 class BatchReducer(_ReducerBase):
-    """frirl_hip_batch_reducer: the rule-base reduction of EVERY rule base of `problem` with the caller's environment, round by round."""
+    """frirl_hip_batch_reducer: the rule-base reduction of EVERY rule base of `problem` with the caller's environment, round by round.
+    starts = n (1..REDUCE_MAX_STARTS): every removal is validated against n start states per agent (frirl_hip_batch_reducer_create_starts;
+    start_count [E] int32 or None = n, drop_bad_starts as Problem.reduce_batch_starts).  The rows of a round are then
+    row (e * nodes + node) * n + k = tree node `node` of agent e from its start k (round 0: row e * n + k)."""
     _name = "batch_reducer"
 
-    def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None, stream=None):
+    def __init__(self, problem, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, active=None, stream=None, starts=None, start_count=None,
+                 drop_bad_starts=False):
         import torch
         if rant is not None:
             assert rant.shape == (problem.E, problem.nant, problem.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
         if active is not None:
             assert active.shape == (problem.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous()
-        self.problem, self._keep = problem, (rant, active, agent)
-        self.h = lib().frirl_hip_batch_reducer_create(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _ptr(rant), _ptr(active),
-                                                      strategy, reward_tolerance, depth, _stream(stream))
+        self.problem, self._keep = problem, (rant, active, agent, start_count)
+        args = (C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _ptr(rant), _ptr(active))
+        if starts is None:
+            assert start_count is None and not drop_bad_starts, "start_count and drop_bad_starts go with starts"
+            fn = "frirl_hip_batch_reducer_create"
+            self.h = lib().frirl_hip_batch_reducer_create(*args, strategy, reward_tolerance, depth, _stream(stream))
+        else:
+            if start_count is not None:
+                assert start_count.shape == (problem.E,) and start_count.dtype == torch.int32 and start_count.is_contiguous()
+            fn = "frirl_hip_batch_reducer_create_starts"
+            st = ReduceStarts(int(starts), 1 if drop_bad_starts else 0, None, _ptr(start_count))
+            self.h = lib().frirl_hip_batch_reducer_create_starts(*args, C.byref(st), strategy, reward_tolerance, depth, _stream(stream))
         if not self.h:
-            raise FrirlHipError(f"frirl_hip_batch_reducer_create: {lib().frirl_hip_last_error().decode()}")
+            raise FrirlHipError(f"{fn}: {lib().frirl_hip_last_error().decode()}")
+        self.starts = lib().frirl_hip_batch_reducer_starts(self.h)
         self.Q = self.rows_per_agent = self.agents_live = 0
 
     def next_round(self):
@@ -1192,6 +1212,13 @@ class BatchReducer(_ReducerBase):
         self._call("result", kept.ctypes.data_as(C.POINTER(C.c_int32)), res)
         return [kept[e, : res[e].rules_after].copy() for e in range(E)], list(res)
 
+    def result_starts(self):
+        """Per-start ReduceStartResult [E][n] so far (n = 1 for a reducer made without starts); between rounds only."""
+        E, n = self.problem.E, self.starts
+        per = (ReduceStartResult * (E * n))()
+        self._call("result_starts", per)
+        return [[per[e * n + k] for k in range(n)] for e in range(E)]
+
 
 class Reducer(_ReducerBase):
     """frirl_hip_reducer: the rule-base reduction of ONE rule base (problem.E == 1) with the caller's environment, round by round."""
@@ -1222,7 +1249,7 @@ class Reducer(_ReducerBase):
         return kept[: res.rules_after], res
 
 
-def _reduce_rounds(red, reset_fn, step_fn):
+def _reduce_rounds(red, reset_fn, step_fn, result=None):
     """The round loop of reduce_external / reduce_external_batch on an open reducer; reset_fn(red) -> obs of the round's rows."""
     import torch
     try:
@@ -1236,7 +1263,7 @@ def _reduce_rounds(red, reset_fn, step_fn):
                 nxt, _, live = red.observe(obs, reward, success, q_obs=out[3].contiguous() if len(out) > 3 else None)
                 states, action = obs, nxt          # rows that are done keep their last action; what they return is no longer read
             red.end_round()
-        return red.result()
+        return red.result() if result is None else result(red)
     finally:
         red.close()
 
@@ -1254,6 +1281,15 @@ def reduce_external_batch(problem, agent, reset_fn, step_fn, strategy, reward_to
     reduce_external.  Returns (list of kept original indices, list of ReduceResult), as Problem.reduce_batch; compacts in place."""
     return _reduce_rounds(BatchReducer(problem, agent, strategy, reward_tolerance, depth, rant, active),
                           lambda red: reset_fn(red.Q, red.rows_per_agent), step_fn)
+
+
+def reduce_external_batch_starts(problem, agent, reset_fn, step_fn, strategy, n, reward_tolerance=0.0, depth=0, rant=None, active=None,
+                                 start_count=None, drop_bad_starts=False):
+    """reduce_external_batch with every removal validated against n start states per agent (BatchReducer(starts=n)):
+    reset_fn(Q, rows_per_agent, n) -> obs [Q, nant-1] with start q % n of agent q // rows_per_agent in row q; step_fn as for
+    reduce_external.  Returns (kept, results, per_start) as Problem.reduce_batch_starts; compacts in place."""
+    red = BatchReducer(problem, agent, strategy, reward_tolerance, depth, rant, active, starts=n, start_count=start_count, drop_bad_starts=drop_bad_starts)
+    return _reduce_rounds(red, lambda r: reset_fn(r.Q, r.rows_per_agent, n), step_fn, result=lambda r: r.result() + (r.result_starts(),))
 
 
 def dist():

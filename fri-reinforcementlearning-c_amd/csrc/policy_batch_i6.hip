@@ -2,7 +2,7 @@
 #include "policy_batch_kernel.h"
 
 void frirl_policy_batch_launch_6(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl::PolicyBatchArgs *pa,
-                                 const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s)
+                                 const frirl_hip_agent_io *io, int begin, int nlist, int H, const frirl::PolicyStartsArgs *st, hipStream_t s)
 {
-    frirl::launch_policy_batch_n<6>(t, b, ag, pa, io, begin, nlist, H, s);
+    frirl::launch_policy_batch_n<6>(t, b, ag, pa, io, begin, nlist, H, st, s);
 }

@@ -24,12 +24,26 @@ struct PolicyBatchArgs {
 // everything in front of a barrier depends on the agent and on the workgroup's first row alone.  Rows node >= n_e do not exist:
 // nothing of theirs is read or written.  After the step the rows of the workgroup that are not done are counted into
 // *rows.rows_live: one integer atomic per workgroup.
-template <int NANT, int AMAX, int G, int H, bool EXCL, bool PN = true>
+//
+// The try-remove rounds of the reducer against a set of start states (frirl_hip_batch_reducer_create_starts) pass ONE more kernel
+// argument, a PolicyStartsArgs (ST...; without it the kernel and its arguments are what they were): an agent then has ns rows per
+// node, row = node * ns + k being node `node` replayed from start k.  The mask is the node's (row / ns), the cap is start k's, and
+// a row exists iff its node does (row < (2^d_e - 1) * ns) and start k is used; the holes in between are rows like those beyond n_e.
+struct PolicyStartsArgs {
+    const frirl_hip_reduce_start_result *res;      // [dev] [E][ns] res[e * ns + k].used != 0: start k of agent e is used
+    const int32_t *cap;                            // [dev] [E][ns] step cap of the replays from start k
+    int32_t ns;                                    // starts per agent
+};
+__device__ __forceinline__ const PolicyStartsArgs &only(const PolicyStartsArgs &st) { return st; }
+
+template <int NANT, int AMAX, int G, int H, bool EXCL, bool PN = true, typename... ST>
 __global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const double *__restrict__ u, const double *__restrict__ ve, int U,
                                                                       const double *__restrict__ rb_all, const int32_t *__restrict__ nrules, int maxR,
                                                                       const frirl_hip_agent ag, const PolicyBatchArgs pa,
-                                                                      const frirl_hip_agent_io io, int begin, int wpa)
+                                                                      const frirl_hip_agent_io io, int begin, int wpa, const ST... starts)
 {
+    constexpr bool STARTS = sizeof...(ST) == 1;
+    static_assert(sizeof...(ST) == 0 || (STARTS && EXCL), "at most one extra argument, a PolicyStartsArgs, and only with exclusions");
     constexpr int NS = NANT - 1, GH = G * H, EPB = SH_BLOCK / GH;
     __shared__ SharedTile<NANT> tl;
     const frirl_hip_policy_batch_rows &rows = pa.rows;
@@ -39,11 +53,20 @@ __global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const doubl
     const int row0 = (blockIdx.x % wpa) * EPB;
     const int n = rows.n;
     int ne = pa.depth_of ? rw_nodes(pa.depth_of[e]) : (rows.row_count ? rows.row_count[e] : n);
+    if constexpr (STARTS) ne *= only(starts...).ns;
     ne = ne < 0 ? 0 : (ne > n ? n : ne);
     if (row0 >= ne) return;                                          // the whole workgroup, before the first barrier
     const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
     const int node = row0 + threadIdx.x / GH;
-    const bool exists = node < ne;
+    bool exists = node < ne;
+    int mask_ix = node;
+    size_t start_ix = 0;                                             // STARTS: (agent, start) of the row
+    if constexpr (STARTS) {
+        const PolicyStartsArgs &st = only(starts...);
+        mask_ix = node / st.ns;
+        start_ix = (size_t)e * st.ns + (node - mask_ix * st.ns);
+        exists = exists && st.res[start_ix].used != 0;
+    }
     const size_t qi = (size_t)e * n + node, si = (size_t)e * pa.state_stride + node;
     const bool live = exists && (begin ? (!io.reset || io.reset[qi] != 0) : rows.done[qi] == 0);
     if (__syncthreads_count(live ? 1 : 0) == 0) {                    // no row of the workgroup takes this step: nothing is staged
@@ -61,7 +84,7 @@ __global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const doubl
     const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
     const int nchunks = (apl + AMAX - 1) / AMAX;
     if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
-    const uint32_t mask = (EXCL && exists) ? rows.exclude_mask[pa.mask_by_node ? (size_t)node : qi] : 0u;
+    const uint32_t mask = (EXCL && exists) ? rows.exclude_mask[pa.mask_by_node ? (size_t)mask_ix : qi] : 0u;
     double q[NS];
     if (live) {
         double s[NS], qs[NS];
@@ -107,7 +130,9 @@ __global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const doubl
                 rows.done[qi] = 0;
                 running = 1;
             } else {
-                const int cap = rows.step_cap ? rows.step_cap[e] : ag.max_steps;
+                int cap;
+                if constexpr (STARTS) cap = only(starts...).cap[start_ix];
+                else cap = rows.step_cap ? rows.step_cap[e] : ag.max_steps;
                 const int success = io.success[qi];                                                      // :106
                 const int done = (success == 1 || steps >= cap) ? 1 : 0;                                 // :183, :86
                 rows.ep_steps[si] = steps;
@@ -125,12 +150,14 @@ __global__ __launch_bounds__(SH_BLOCK) void policy_batch_step_kernel(const doubl
 
 template <int N, int AMAX, int G, int H, bool PN = true>
 static void launch_policy_batch(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const PolicyBatchArgs *pa,
-                                const frirl_hip_agent_io *io, int begin, int nlist, hipStream_t s)
+                                const frirl_hip_agent_io *io, int begin, int nlist, const PolicyStartsArgs *st, hipStream_t s)
 {
     constexpr int EPB = SH_BLOCK / (G * H);
     const int wpa = (pa->rows.n + EPB - 1) / EPB;
     const dim3 grid((unsigned)nlist * wpa);
-    if (pa->rows.exclude_mask && pa->rows.rule_slot)
+    if (st)
+        hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, true, PN, PolicyStartsArgs>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa, *st);
+    else if (pa->rows.exclude_mask && pa->rows.rule_slot)
         hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, true, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa);
     else
         hipLaunchKernelGGL((policy_batch_step_kernel<N, AMAX, G, H, false, PN>), grid, dim3(SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb, b->nrules, b->maxR, *ag, *pa, *io, begin, wpa);
@@ -139,11 +166,11 @@ static void launch_policy_batch(const frirl_hip_tables *t, const frirl_hip_ruleb
 // the lane shapes of the batched reduction's roll-out kernel (for_batch_shape, shape_ladder.h); H is chosen by policy_batch.hip
 template <int N>
 static void launch_policy_batch_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const PolicyBatchArgs *pa,
-                                  const frirl_hip_agent_io *io, int begin, int nlist, int H, hipStream_t s)
+                                  const frirl_hip_agent_io *io, int begin, int nlist, int H, const PolicyStartsArgs *st, hipStream_t s)
 {
     for_batch_shape<N>(ag, H, [&](auto sh) {
         using S = decltype(sh);
-        launch_policy_batch<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, pa, io, begin, nlist, s);
+        launch_policy_batch<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, pa, io, begin, nlist, st, s);
     });
 }
 

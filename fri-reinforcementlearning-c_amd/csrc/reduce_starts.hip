@@ -3,48 +3,18 @@
 //
 // The order, open-round and result kernels, the masks, the slot tables, the live lists and the compaction are those of the batched
 // reduction (reduce_batch_kernels.h).  New here: a row space of nodes x used starts per agent (row = node * K_e + ki), per-start
-// baselines and step caps, and a close kernel that accepts a removal only if every used start accepts it (rw_walk_starts).
+// baselines and step caps, and a close kernel that accepts a removal only if every used start accepts it (rw_walk_starts).  The
+// per-start arrays, the init, close and result kernels and the layout are reduce_starts_kernels.h (shared with the caller-stepped form).
 //   roll   a workgroup serves 256 / (G * H) rows of ONE agent; rows with different caps share it, so the step loop is written here:
 //          its bound is the agent's largest cap, a row goes inactive after its own cap, the workgroup leaves through
 //          __syncthreads_count.  Per row the result is rollout_episode's (rollout_episode.h) with max_steps = the row's cap.
 //   close  first: per-start baselines, caps and the compact list of used starts; otherwise walk, compaction, next live list.
 #include "shared_sweep.h"
 #include "envs.h"
-#include "reduce_batch_kernels.h"
+#include "reduce_starts_kernels.h"
 #include "shape_ladder.h"
 
 namespace frirl {
-
-// the arrays of one call: those of the batched reduction (b.steps / b.reward hold nodes * n entries per agent) and the per-start ones
-struct ReduceStartsWs {
-    ReduceBatchWs b;
-    int32_t *cnt;                 // [E] participating starts: start_count[e] clamped to 1..n
-    int32_t *K;                   // [E] used starts (after the baseline)
-    int32_t *capmax;              // [E] largest cap of a used start: the roll-out kernel's loop bound
-    int32_t *used;                // [E][n] the used starts in ascending order (first K[e] entries)
-    int32_t *steps_inc;           // [E][n] per start: steps of the baseline replay, -1 = takes no part
-    int32_t *cap;                 // [E][n] per start: min(max_steps, steps_inc + 1)
-    double *prev;                 // [E][n] per start: prev_reward
-    frirl_hip_reduce_start_result *res;      // [E][n]
-    int n;                        // starts per agent
-};
-
-// Init kernel: one workgroup per agent; the per-start state of an agent that never takes part stays as written here.
-static __global__ __launch_bounds__(256) void reduce_starts_init_kernel(const int32_t *__restrict__ start_count, ReduceStartsWs ws)
-{
-    const int e = blockIdx.x, tid = threadIdx.x, n = ws.n;
-    if (tid == 0) {
-        int c = start_count ? start_count[e] : n;
-        ws.cnt[e] = c < 1 ? 1 : (c > n ? n : c);
-        ws.K[e] = 0;
-        ws.capmax[e] = 0;
-    }
-    for (int k = tid; k < n; k += 256) {
-        const size_t i = (size_t)e * n + k;
-        ws.used[i] = 0; ws.steps_inc[i] = -1; ws.cap[i] = 0; ws.prev[i] = 0.0;
-        ws.res[i].used = 0; ws.res[i].steps_incremental = -1; ws.res[i].baseline_reward = 0.0; ws.res[i].reward = 0.0;
-    }
-}
 
 // Roll-out kernel: `wpa` workgroups per live agent, each serving 256 / (G * H) rows of that agent.  first: the baseline replays, row k
 // = start k, no exclusions, cap max_steps.  Otherwise row r = node * K_e + ki: the node's mask, the ki-th used start and that start's
@@ -136,79 +106,7 @@ __global__ __launch_bounds__(SH_BLOCK) void reduce_starts_rollout_kernel(const d
     ws.b.reward[out] = total;
 }
 
-// Close-round kernel: one workgroup per live agent.  first: thread 0 takes every participating start's baseline (steps_inc, prev,
-// cap), decides which starts are used and lists them; an agent with no used start is not appended to the live list.  Otherwise:
-// thread 0 walks the tree over nodes x starts (it alone reads and writes the agent's prev array), the workgroup compacts.
-template <int NANT>
-__global__ __launch_bounds__(256) void reduce_starts_close_kernel(double *__restrict__ rb, int32_t *__restrict__ nrules, uint16_t *__restrict__ uidx,
-                                                                  double *__restrict__ rant, int maxR, int cur, int first, int max_steps,
-                                                                  double good_above, double tol, int drop_bad, ReduceStartsWs ws)
-{
-    __shared__ int wave_kept[4];
-    __shared__ uint32_t bits_s;
-    const int e = ws.b.live[cur][blockIdx.x], tid = threadIdx.x, n = ws.n;
-    const size_t M = (size_t)maxR, en = (size_t)e * n, rows0 = (size_t)e * ws.b.nodes * n;
-    if (first) {                                                       // uniform
-        if (tid != 0) return;
-        const int cnt = ws.cnt[e];
-        int K = 0, capmax = 0;
-        for (int k = 0; k < cnt; k++) {
-            const int st = ws.b.steps[rows0 + k];
-            const double rw = ws.b.reward[rows0 + k];
-            const int cap = max_steps > st + 1 ? st + 1 : max_steps;   // a longer replay is rejected anyway (:212)
-            const bool use = !drop_bad || rw > good_above;
-            ws.steps_inc[en + k] = st;
-            ws.prev[en + k] = rw;
-            ws.cap[en + k] = cap;
-            ws.res[en + k].used = use ? 1 : 0;
-            ws.res[en + k].steps_incremental = st;
-            ws.res[en + k].baseline_reward = rw;
-            if (use) {
-                ws.used[en + K++] = k;
-                capmax = cap > capmax ? cap : capmax;
-            }
-        }
-        const int k0 = K ? ws.used[en] : 0;
-        ws.K[e] = K;
-        ws.capmax[e] = capmax;
-        ws.b.steps_inc[e] = ws.steps_inc[en + k0];
-        ws.b.prev[e] = ws.prev[en + k0];
-        ws.b.rollouts[e] = cnt;
-        if (K > 0 && ws.b.R0[e] > 0) ws.b.live[cur ^ 1][atomicAdd(&ws.b.hdr[cur ^ 1], 1)] = e;
-        return;
-    }
-    const int R = nrules[e], d = ws.b.d[e], K = ws.K[e];
-    if (tid == 0)
-        bits_s = rw_walk_starts(d, K, ws.b.steps + rows0, ws.b.reward + rows0, ws.used + en, ws.steps_inc + en, ws.prev + en, good_above, tol);
-    __syncthreads();
-    const uint32_t bits = bits_s;
-    int Rn = R;
-    if (bits)                                                          // uniform
-        Rn = reduce_batch_compact<NANT>(rb + (size_t)e * (NANT + 1) * M, rant ? rant + (size_t)e * NANT * M : nullptr,
-                                        uidx ? uidx + (size_t)e * NANT * M : nullptr, ws.b.alive + (size_t)e * M, ws.b.slot + (size_t)e * M, M, R, bits,
-                                        wave_kept);
-    __syncthreads();                                                   // every thread has read the agent's state
-    if (tid != 0) return;
-    ws.b.rounds[e] += 1;
-    ws.b.rollouts[e] += rw_nodes(d) * K;
-    nrules[e] = Rn;
-    ws.b.prev[e] = ws.prev[en + ws.used[en]];
-    const int j = ws.b.j[e] + d;
-    ws.b.j[e] = j;
-    if (j < ws.b.R0[e]) ws.b.live[cur ^ 1][atomicAdd(&ws.b.hdr[cur ^ 1], 1)] = e;
-}
-
-// prev_reward of every start that took a baseline replay, after the last accepted removal
-static __global__ void reduce_starts_result_kernel(int total, ReduceStartsWs ws)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (ws.steps_inc[i] >= 0) ws.res[i].reward = ws.prev[i];
-}
-
 }  // namespace frirl
-
-using frirl::ReduceStartsWs;
 
 extern "C" int frirl_hip_reduce_batch_starts_depth(int32_t E, int32_t A, int32_t n)
 {
@@ -218,23 +116,6 @@ extern "C" int frirl_hip_reduce_batch_starts_depth(int32_t E, int32_t A, int32_t
     int d = 1;
     while (d < 10 && (long)E * n * frirl::rw_nodes(d + 1) <= rows) d++;
     return d;
-}
-
-// carves the arrays of a call out of `base` (NULL: sizes only); `rows` = entries of steps / reward
-static size_t reduce_starts_layout(char *base, size_t E, size_t maxR, int depth, size_t rows, int n, ReduceStartsWs *ws)
-{
-    ReduceStartsWs w;
-    size_t off = reduce_batch_layout(base, E, maxR, depth, rows, &w.b);
-    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += up16(bytes); return p; };
-    w.n = n;
-    int32_t **per_agent[] = {&w.cnt, &w.K, &w.capmax};
-    for (int32_t **p : per_agent) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
-    int32_t **per_start[] = {&w.used, &w.steps_inc, &w.cap};
-    for (int32_t **p : per_start) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * n));
-    w.prev = reinterpret_cast<double *>(take(sizeof(double) * E * n));
-    w.res = reinterpret_cast<frirl_hip_reduce_start_result *>(take(sizeof(frirl_hip_reduce_start_result) * E * n));
-    if (ws) *ws = w;
-    return off;
 }
 
 extern "C" size_t frirl_hip_reduce_batch_starts_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t depth, int32_t n)
@@ -277,7 +158,22 @@ extern "C" int frirl_hip_reduce_walk_starts_check(int d, int K, const int32_t *s
                   FRIRL_HIP_REDUCE_MAX_STARTS);
         return FRIRL_HIP_EINVAL;
     }
-    *bits_out = frirl::rw_walk_starts(d, K, steps, reward, nullptr, steps_inc, prev, good_above, tol);
+    *bits_out = frirl::rw_walk_starts(d, K, K, false, steps, reward, nullptr, steps_inc, prev, good_above, tol);
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_reduce_walk_starts_rows_check(int d, int K, int n, const int32_t *used, const int32_t *steps, const double *reward,
+                                                       const int32_t *steps_inc, double *prev, double good_above, double tol, uint32_t *bits_out)
+{
+    bool ok = d >= 0 && d <= frirl::RW_MAX_DEPTH && n >= 1 && n <= FRIRL_HIP_REDUCE_MAX_STARTS && K >= 1 && K <= n && used && (d == 0 || (steps && reward)) &&
+              steps_inc && prev && bits_out;
+    for (int ki = 0; ok && ki < K; ki++) ok = used[ki] >= 0 && used[ki] < n;
+    if (!ok) {
+        set_error("frirl_hip_reduce_walk_starts_rows_check: d=%d outside 0..%d, n=%d outside 1..%d, K=%d outside 1..n, used[] outside 0..n-1 or NULL argument", d,
+                  frirl::RW_MAX_DEPTH, n, FRIRL_HIP_REDUCE_MAX_STARTS, K);
+        return FRIRL_HIP_EINVAL;
+    }
+    *bits_out = frirl::rw_walk_starts(d, K, n, true, steps, reward, used, steps_inc, prev, good_above, tol);
     return FRIRL_HIP_OK;
 }
 

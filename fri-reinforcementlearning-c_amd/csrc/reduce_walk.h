@@ -56,24 +56,29 @@ __host__ __device__ inline uint32_t rw_walk(int d, const int32_t *steps, const d
     return bits;
 }
 
-// The same walk with K replays per node (steps / reward: [node * K + ki], the node's replay from the ki-th used start state): a
-// removal is accepted iff rw_accept holds for EVERY start, and then every start's prev_reward moves to its own replay's reward (:222,
-// per start).  steps_inc / prev_reward are indexed by the start's number used[ki] (used == NULL: by ki itself).  K == 1 is rw_walk.
+// The same walk with K replays per node, the node's replay from the ki-th used start state: a removal is accepted iff rw_accept holds
+// for EVERY start, and then every start's prev_reward moves to its own replay's reward (:222, per start).  steps_inc / prev_reward
+// are indexed by the start's number used[ki] (used == NULL: by ki itself).  A node's replays sit `stride` entries apart from the next
+// node's, the ki-th at column ki (by_start == false; the compact form is stride == K) or at column used[ki] (by_start: the
+// caller-stepped form, one column per start whether used or not, stride == n).  K == 1 is rw_walk.
 // All K tests of a node are evaluated (no early exit): their loads do not depend on each other.
-__host__ __device__ inline uint32_t rw_walk_starts(int d, int K, const int32_t *steps, const double *reward, const int32_t *used,
-                                                   const int32_t *steps_inc, double *prev_reward, double good_above, double tol)
+__host__ __device__ inline uint32_t rw_walk_starts(int d, int K, int stride, bool by_start, const int32_t *steps, const double *reward,
+                                                   const int32_t *used, const int32_t *steps_inc, double *prev_reward, double good_above, double tol)
 {
     uint32_t bits = 0;
     for (int k = 0; k < d; k++) {
-        const size_t row = (size_t)rw_node(k, bits) * K;
+        const size_t row = (size_t)rw_node(k, bits) * stride;
         bool all = true;
         for (int ki = 0; ki < K; ki++) {
-            const int s = used ? used[ki] : ki;
-            all = rw_accept(steps[row + ki], reward[row + ki], steps_inc[s], prev_reward[s], good_above, tol) && all;
+            const int s = used ? used[ki] : ki, c = by_start ? s : ki;
+            all = rw_accept(steps[row + c], reward[row + c], steps_inc[s], prev_reward[s], good_above, tol) && all;
         }
         if (!all) continue;
         bits |= 1u << k;
-        for (int ki = 0; ki < K; ki++) prev_reward[used ? used[ki] : ki] = reward[row + ki];
+        for (int ki = 0; ki < K; ki++) {
+            const int s = used ? used[ki] : ki;
+            prev_reward[s] = reward[row + (by_start ? s : ki)];
+        }
     }
     return bits;
 }

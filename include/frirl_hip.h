@@ -471,6 +471,11 @@ int frirl_hip_reduce_batch_starts(const frirl_hip_tables *t, const frirl_hip_rul
  * (1..FRIRL_HIP_REDUCE_MAX_STARTS), steps / reward HOST [2^d - 1][K], steps_inc HOST [K], prev HOST [K] in / out.  Needs no device. */
 int frirl_hip_reduce_walk_starts_check(int d, int K, const int32_t *steps, const double *reward, const int32_t *steps_inc, double *prev,
                                        double good_above, double tol, uint32_t *bits_out);
+/* The same walk over the rows of the caller-stepped form (frirl_hip_batch_reducer_create_starts): one column per start whether it is
+ * used or not.  n starts (1..FRIRL_HIP_REDUCE_MAX_STARTS), used HOST [K] the used starts ascending (1 <= K <= n), steps / reward HOST
+ * [2^d - 1][n] (columns of starts that are not used are never read), steps_inc HOST [n], prev HOST [n] in / out.  Needs no device. */
+int frirl_hip_reduce_walk_starts_rows_check(int d, int K, int n, const int32_t *used, const int32_t *steps, const double *reward,
+                                            const int32_t *steps_inc, double *prev, double good_above, double tol, uint32_t *bits_out);
 
 /* Per-environment episode state (reference: fields of frirl_desc + frirl_reward_desc that
  * frirl_episode() carries from step to step, src/frirl/frirl_episode.c:28-194). */
@@ -763,6 +768,31 @@ int frirl_hip_batch_reducer_end_round(frirl_hip_batch_reducer *r);
 int frirl_hip_batch_reducer_result(frirl_hip_batch_reducer *r, int32_t *kept, frirl_hip_reduce_result *results);
 const int32_t *frirl_hip_batch_reducer_row_done(const frirl_hip_batch_reducer *r);
 void frirl_hip_batch_reducer_destroy(frirl_hip_batch_reducer *r);
+
+/* The same object with every removal validated against SEVERAL start states per agent: frirl_hip_reduce_batch_starts with the
+ * CALLER'S environment.  Per agent the semantics are those of frirl_hip_reduce_batch_starts item for item (participating starts
+ * k < clamp(start_count[e], 1, n); per-start baselines steps_inc[e][k], prev[e][k], cap[e][k]; the used starts; a removal accepted iff
+ * the acceptance test holds for ALL used starts; results, rollouts and per_start as documented there).  Of `starts`, n,
+ * drop_bad_starts and start_count are read; start_states is not and may be NULL: the caller places the rows.  depth 0 =
+ * frirl_hip_reduce_batch_starts_depth(E, A, n); nant 2..8, A 1..32, env_kind is not read; E * n * (2^depth - 1) <= INT32_MAX / 2.
+ * The round protocol is that of frirl_hip_batch_reducer_* above, with a FIXED row layout the caller computes by arithmetic:
+ *     round 0       rows_per_agent = n                     row e * n + k                       = agent e from its start k
+ *     later rounds  rows_per_agent = (2^depth - 1) * n     row (e * nodes + node) * n + k      = tree node `node` of agent e from start k
+ * so for row q: e = q / rows_per_agent, k = q % n.  Rows that are `done` after begin need not be stepped: starts that take no part
+ * (round 0) or are not used (later), nodes beyond 2^d_e - 1, agents that are inactive or finished (frirl_hip_batch_reducer_row_done).
+ * A workgroup all of whose rows are such holes stages nothing; a hole inside a served workgroup idles its lanes.  A row ends
+ * at success or at ITS START'S cap.  With n == 1 and drop_bad_starts == 0 every output and the device state equal those of a reducer
+ * made by frirl_hip_batch_reducer_create.  Bad arguments (those of _create, NULL starts, n outside 1..FRIRL_HIP_REDUCE_MAX_STARTS, too
+ * many rows) return NULL with frirl_hip_last_error set, before the device is looked for.
+ * frirl_hip_batch_reducer_result_starts: per_start [host] [E][n] as frirl_hip_reduce_batch_starts; between rounds only, as _result.  On
+ * a reducer made by _create it reports the n = 1 view ([E]: used = 1, the agent's steps_incremental, baseline reward and reward;
+ * {0, -1, 0, 0} for an agent that is inactive or whose baseline has not run).
+ * frirl_hip_batch_reducer_starts: n; 1 for a reducer made by _create; 0 for NULL. */
+frirl_hip_batch_reducer *frirl_hip_batch_reducer_create_starts(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                                               double *rant, const uint8_t *active, const frirl_hip_reduce_starts *starts,
+                                                               int strategy, double reward_tolerance, int depth, void *stream);
+int frirl_hip_batch_reducer_result_starts(frirl_hip_batch_reducer *r, frirl_hip_reduce_start_result *per_start /* [host][E][n] */);
+int frirl_hip_batch_reducer_starts(const frirl_hip_batch_reducer *r);
 
 /* Lane-group form for MANY agents with SMALL rule bases (the demos' learning regime; the reference's frirl_omp_run model
  * of one agent per core, frirl_agent.c:294-325, at GPU width): G = 4 or 8 consecutive lanes own one environment, each

@@ -9,7 +9,11 @@ python tools/reduce_bench.py --agents 64 --agents 4096 [--depth 0] [--loop-sampl
 With --agents E --starts K (both repeatable): the reduction against K start states per agent (frirl_hip_reduce_batch_starts, strategy 1) on
 the same learned rule bases: n = 1 against frirl_hip_reduce_batch (alternating), n = K against n = 1 (time, rounds, rules kept), and how many
 of the independent test starts that the un-reduced rule bases solve are still solved afterwards (Problem.rollout_batch):
-python tools/reduce_bench.py --agents 64 --starts 4 --starts 16 [--reps 3] [--spread 0.1] [--test-starts 32]"""
+python tools/reduce_bench.py --agents 64 --starts 4 --starts 16 [--reps 3] [--spread 0.1] [--test-starts 32]
+With --stepped in addition: the same inputs through the caller-stepped reducers, the demo dynamics stepped from torch (frirl_hip_env_step):
+n = 1 made with start states against the reducer made without (reduce_external_batch, alternating), n = K stepped against the in-kernel
+frirl_hip_reduce_batch_starts, and the share of the staged workgroups' rows that are holes with drop_bad_starts = 1:
+python tools/reduce_bench.py --agents 64 --starts 16 --stepped [--reps 3]"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
@@ -89,10 +93,10 @@ def batch_leg(env, E, a, dev):
     print(json.dumps(out), flush=True)
 
 
-def starts_leg(env, E, a, dev):
-    """The rule bases of batch_leg (trained from starts at +-0.1 span).  Validation starts: row 0 = the agent's own start, rows 1.. = own
-    +- spread * span (seed 17); test starts: --test-starts per agent, same spread, seed 5.  Host clock around calls that end in a device
-    synchronise; rule bases restored from a snapshot before every timed call; first repetition = warm-up."""
+def starts_inputs(env, E, a, dev):
+    """What starts_leg and stepped_leg share: the rule bases of batch_leg (trained from starts at +-0.1 span), restore() to put them
+    back, the validation starts val [E, max K, ns] (row 0 = the agent's own start, rows 1.. = own +- spread * span, seed 17) and
+    around(n, seed) for further draws."""
     d = frirl_amd.demo_describe(env)
     ns = d["nstates"]
     lo = np.array([d["grids"][k].min() for k in range(ns)])
@@ -123,6 +127,14 @@ def starts_leg(env, E, a, dev):
     Kmax = max(a.starts)
     val = around(Kmax, 17)
     val[:, 0, :] = start
+    return d, prob, agent, envs, run, snap, restore, tens, ss, val, around
+
+
+def starts_leg(env, E, a, dev):
+    """Test starts: --test-starts per agent, spread as the validation starts, seed 5.  Host clock around calls that end in a device
+    synchronise; rule bases restored from a snapshot before every timed call; first repetition = warm-up."""
+    d, prob, agent, envs, run, snap, restore, tens, ss, val, around = starts_inputs(env, E, a, dev)
+    ns = d["nstates"]
     test = tens(around(a.test_starts, 5).reshape(E * a.test_starts, ns))
 
     def solved():
@@ -173,6 +185,90 @@ def starts_leg(env, E, a, dev):
     print(json.dumps(out), flush=True)
 
 
+def stepped_leg(env, E, a, dev):
+    """The inputs of starts_leg through the caller-stepped reducers; every environment step is one frirl_hip_env_step over all rows of
+    the round and one observe.  Clock and repetitions as starts_leg.  Rows per workgroup for the hole share: 256 / (G * 8), the shape
+    the depth rule keeps resident (G = 4 lanes per row for up to 4 actions, else 8)."""
+    d, prob, agent, envs, run, snap, restore, tens, ss, val, around = starts_inputs(env, E, a, dev)
+
+    def step_fn(states, action):
+        obs, reward, success, q = frirl_amd.env_step(agent, action, states)
+        return (obs, reward, success, q) if env == "cartpole" else (obs, reward, success)
+
+    def rows_of(S):
+        def reset_fn(Q, rpa, n):
+            q = torch.arange(Q, device=dev)
+            return S[q // rpa, q % n].contiguous()
+        return reset_fn
+
+    def timed(fn):
+        restore()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    out = {"env": env, "agents": E, "converged": int((run.conv.converged == 1).sum()), "rules_before_sum": int(snap[1].sum()), "strategy": 1,
+           "spread": a.spread, "stepped": True}
+    # (a) n = 1: the reducer made with start states against the one made without, alternating
+    one = tens(val[:, :1, :])
+    t_p, t_s = [], []
+    for rep in range(max(a.reps, 3) + 1):
+        dt_p, (kept_p, res_p) = timed(lambda: frirl_amd.reduce_external_batch(prob, agent, lambda Q, n: ss.repeat_interleave(n, 0), step_fn, 1, 0.0, a.depth,
+                                                                             rant=envs.rant))
+        dt_s, (kept_s, res_s, _) = timed(lambda: frirl_amd.reduce_external_batch_starts(prob, agent, rows_of(one), step_fn, 1, 1, 0.0, a.depth, rant=envs.rant))
+        assert all((x == y).all() for x, y in zip(kept_p, kept_s)) and [r.rollouts for r in res_p] == [r.rollouts for r in res_s]
+        if rep:
+            t_p.append(round(dt_p, 4)); t_s.append(round(dt_s, 4))
+    out.update(plain_reducer_s=t_p, starts_reducer_n1_s=t_s, n1_over_plain_min=round(min(t_s) / min(t_p), 3),
+               n1_over_plain_median=round(float(np.median(t_s) / np.median(t_p)), 3), rules_after_sum_n1=int(sum(r.rules_after for r in res_s)))
+    # (b) n = K with drop_bad_starts = 1: stepped against in-kernel; (c) the holes of the stepped rows
+    for K in a.starts:
+        vk = tens(val[:, :K, :])
+        t_k, t_x = [], []
+        for rep in range(max(a.reps, 3) + 1):
+            dt_k, (kept_k, res_k, _) = timed(lambda: prob.reduce_batch_starts(agent, 1, 0.0, a.depth, vk, drop_bad_starts=True, rant=envs.rant))
+            dt_x, (kept_x, res_x, per_x) = timed(lambda: frirl_amd.reduce_external_batch_starts(prob, agent, rows_of(vk), step_fn, 1, K, 0.0, a.depth,
+                                                                                                 rant=envs.rant, drop_bad_starts=True))
+            same = sum(len(x) == len(y) and (x == y).all() for x, y in zip(kept_k, kept_x))
+            if rep:
+                t_k.append(round(dt_k, 4)); t_x.append(round(dt_x, 4))
+        # one more run, not timed: rows that exist after every begin, in workgroups of `epb` rows of one agent
+        restore()
+        epb = 256 // ((4 if d["A"] <= 4 else 8) * 8)
+        lanes = rows = steps = 0
+        red = frirl_amd.BatchReducer(prob, agent, 1, 0.0, a.depth, envs.rant, starts=K, drop_bad_starts=True)
+        try:
+            rnd = 0
+            while red.next_round() > 0:
+                states = rows_of(vk)(red.Q, red.rows_per_agent, K)
+                action, _ = red.begin(states)
+                if rnd:
+                    ex = (red.row_done() == 0).view(E, red.rows_per_agent)
+                    pad = (-red.rows_per_agent) % epb
+                    wg = torch.nn.functional.pad(ex, (0, pad)).view(E, -1, epb)
+                    lanes += int(wg.any(2).sum()) * epb
+                    rows += int(ex.sum())
+                live = red.Q
+                while live > 0:
+                    o = step_fn(states, action)
+                    action, _, live = red.observe(o[0].contiguous(), o[1].contiguous(), o[2].to(torch.int32).contiguous(),
+                                                  q_obs=o[3].contiguous() if len(o) > 3 else None)
+                    states = o[0]
+                    steps += 1
+                red.end_round()
+                rnd += 1
+        finally:
+            red.close()
+        out[f"n{K}"] = {"in_kernel_s": t_k, "stepped_s": t_x, "stepped_over_in_kernel_min": round(min(t_x) / min(t_k), 2),
+                        "agents_with_equal_kept": int(same), "rules_after_sum": int(sum(r.rules_after for r in res_x)),
+                        "rounds_max": max(r.rounds for r in res_x), "rollouts_sum": int(sum(r.rollouts for r in res_x)),
+                        "depth": a.depth or frirl_amd.lib().frirl_hip_reduce_batch_starts_depth(E, d["A"], K), "observe_calls": steps,
+                        "starts_used": int(sum(p.used for row in per_x for p in row)), "starts_given": E * K, "rows_per_workgroup": epb,
+                        "rows_in_staged_workgroups": lanes, "rows_that_exist": rows, "share_lost_to_holes": round(1.0 - rows / lanes, 4) if lanes else None}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--depth", type=int, default=0)
@@ -184,12 +280,13 @@ def main():
     ap.add_argument("--starts", type=int, action="append", default=[])
     ap.add_argument("--spread", type=float, default=0.1)
     ap.add_argument("--test-starts", type=int, default=32)
+    ap.add_argument("--stepped", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.agents:
         for env in ([a.only] if a.only else ["mountaincar", "acrobot"]):
             for E in a.agents:
-                (starts_leg if a.starts else batch_leg)(env, E, a, dev)
+                (stepped_leg if a.stepped and a.starts else starts_leg if a.starts else batch_leg)(env, E, a, dev)
         return
     for env in ("mountaincar", "cartpole", "acrobot"):
         prob, agent, envs = learned(env, dev)
