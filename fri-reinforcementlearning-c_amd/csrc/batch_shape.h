@@ -1,5 +1,5 @@
 // batch_shape.h -- host side: the lane shapes of the kernels whose workgroups each serve rows of ONE agent of a batch (the batched
-// reductions, reduce_batch_kernels.h, and the batched roll-outs, rollout_batch.hip).  Moved out of reduce_batch_kernels.h unchanged.
+// reductions, which see it through reduce_ws.h, and the batched roll-outs, rollout_batch.hip).
 #pragma once
 #include "shared_sweep.h"
 

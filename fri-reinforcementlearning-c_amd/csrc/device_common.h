@@ -156,6 +156,13 @@ int check_agent_shape(const frirl_hip_tables *t, const frirl_hip_rulebases *b, c
                       const char *who);   // agent.hip: nant 2..8, rule bases, grids, A 1..32, env state; not the device
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// a HIP call that must succeed: otherwise the error text becomes "who: expression: hipGetErrorString" and `on_fail` runs
+#define FRIRL_HIP_TRY(expr, who, on_fail)                                                                          \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess) { frirl_host::set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); on_fail; } \
+    } while (0)
+
 // The library-owned batches switch to their own device; the caller's current device is put back on every exit path.
 struct DeviceGuard {
     int prev = -1;

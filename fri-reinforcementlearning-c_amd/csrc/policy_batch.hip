@@ -1,13 +1,13 @@
 // policy_batch.hip -- EVERY agent's own rule base in the caller's environment: frirl_hip_policy_batch_begin / _observe (one greedy step
 // of E * n caller-stepped rows, row q on the rule base of agent q / n) and the resumable batched reduction frirl_hip_batch_reducer_* on
 // top of them (include/frirl_hip.h).  The step kernels are policy_batch_kernel.h, instantiated per antecedent count in
-// policy_batch_i<N>.hip; the order, open, close and result kernels and the workspace are those of frirl_hip_reduce_batch
-// (reduce_batch_kernels.h), for a reducer made with a set of start states those of frirl_hip_reduce_batch_starts
-// (reduce_starts_kernels.h).  A round of the reducer is: the caller's begin / observe loop, every step ONE launch over the rows of the
-// agents still reducing, then close (tree walk + compaction) and the next round's open kernel.  The host reads the 16-byte header
-// only: live agents of the next round, rows still live.
+// policy_batch_i<N>.hip; the round protocol of the reduction (checks, workspace, order, open, close and result kernels, with or
+// without a set of start states) is ReduceRun's (reduce_run.h), the one frirl_hip_reduce_batch and _starts run.  The reducer owns what
+// is its own: the IDLE / OPEN / RUNNING state machine, the row flags, and the n = 1 view of _result_starts.  A round is: the caller's
+// begin / observe loop, every step ONE launch over the rows of the agents still reducing, then ReduceRun::close (tree walk +
+// compaction, the next round's open kernel).  The host reads the 16-byte header only: live agents of the next round, rows still live.
 #include "policy_batch_kernel.h"
-#include "reduce_starts_kernels.h"
+#include "reduce_run.h"
 #include <new>
 
 #define M(N) void frirl_policy_batch_launch_##N(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
@@ -94,32 +94,20 @@ __global__ void policy_batch_one_start_kernel(int E, ReduceBatchWs ws, const dou
 
 struct frirl_hip_batch_reducer {
     enum State { IDLE, OPEN, RUNNING };       // between rounds; next_round called; begin called
-    frirl_hip_tables t;
-    frirl_hip_rulebases b;
-    frirl_hip_agent agent;                    // greedy copy (no_random = 1)
-    double *rant = nullptr;
-    double reward_good_above = 0.0, reward_tolerance = 0.0;
-    int depth = 0, nodes = 0;
-    hipStream_t s = nullptr;
+    ReduceRun run;                            // checks, workspace view, header, round number and every protocol kernel
     void *d_ws = nullptr, *d_done = nullptr, *d_success = nullptr, *d_base = nullptr, *d_view = nullptr;
-    ReduceBatchWs ws;                         // == sw.b for a reducer made with start states
-    ReduceStartsWs sw = {};
-    int ns = 0, drop_bad = 0;                 // start states per agent (0: made by _create, one row per node) and drop_bad_starts
-    int32_t hdr[4] = {0, 0, 0, 0};            // host copy of ws.hdr: live agents of even / odd rounds, bad agent + 1, rows live
-    int round = 0;                            // round 0 = the baseline replays
     State state = IDLE;
     int n = 0, Q = 0;                         // rows per agent (with start states: rows of a node x ns) and rows of the open round
-    bool live_known = false;                  // hdr[3] holds the rows still live after the last launch
+    bool live_known = false;                  // run.hdr[3] holds the rows still live after the last launch
 
     ~frirl_hip_batch_reducer()
     {
         for (void *p : {d_ws, d_done, d_success, d_base, d_view}) if (p) (void)hipFree(p);
     }
-    int cur() const { return round & 1; }
-    int per_node() const { return ns ? ns : 1; }
-    bool starts_round() const { return ns && round > 0; }            // the rows are nodes x starts: PolicyStartsArgs
+    bool starts_round() const { return run.ns && !run.first(); }     // the rows are nodes x starts: PolicyStartsArgs
     frirl::PolicyBatchArgs args() const
     {
+        const ReduceBatchWs &ws = run.ws;
         frirl::PolicyBatchArgs pa = {};
         pa.rows.n = n;
         pa.rows.done = static_cast<int32_t *>(d_done);
@@ -128,41 +116,27 @@ struct frirl_hip_batch_reducer {
         pa.rows.ep_reward = ws.reward;
         pa.rows.step_cap = ws.cap;
         pa.rows.rows_live = ws.hdr + 3;
-        if (ns && round == 0) pa.rows.row_count = sw.cnt;             // the baseline replays: row k = participating start k
-        if (round > 0) {
+        if (run.ns && run.first()) pa.rows.row_count = run.sw.cnt;    // the baseline replays: row k = participating start k
+        if (!run.first()) {
             pa.rows.exclude_mask = ws.mask;
             pa.rows.rule_slot = ws.slot;
             pa.depth_of = ws.d;
             pa.mask_by_node = 1;
         }
-        pa.list = ws.live[cur()];
-        pa.E = b.E;
-        pa.state_stride = ws.nodes * per_node();
+        pa.list = ws.live[run.cur()];
+        pa.E = run.b.E;
+        pa.state_stride = ws.nodes * run.per_node();
         return pa;
     }
     frirl::PolicyStartsArgs starts_args() const
     {
         frirl::PolicyStartsArgs st = {};
-        st.res = sw.res;
-        st.cap = sw.cap;
-        st.ns = ns;
+        st.res = run.sw.res;
+        st.cap = run.sw.cap;
+        st.ns = run.ns;
         return st;
     }
 };
-
-#define BR_TRY(expr, fail)                                                                                         \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); fail; }                \
-    } while (0)
-
-// the 16-byte header to the host; synchronises
-static int batch_reducer_header(frirl_hip_batch_reducer *r, const char *who)
-{
-    BR_TRY(hipMemcpyAsync(r->hdr, r->ws.hdr, sizeof r->hdr, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
-    BR_TRY(hipStreamSynchronize(r->s), return FRIRL_HIP_ELAUNCH);
-    return FRIRL_HIP_OK;
-}
 
 // frirl_hip_batch_reducer_create (starts == NULL) and _create_starts
 static frirl_hip_batch_reducer *batch_reducer_create(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
@@ -170,57 +144,20 @@ static frirl_hip_batch_reducer *batch_reducer_create(const frirl_hip_tables *t, 
                                                      int depth, void *stream, const char *who)
 {
     if (check_policy_args(t, b, agent, who)) return nullptr;
-    const int ns = starts ? starts->n : 0, per_node = starts ? ns : 1;
-    if (starts && (ns < 1 || ns > FRIRL_HIP_REDUCE_MAX_STARTS)) { set_error("%s: n=%d start states outside 1..%d", who, ns, FRIRL_HIP_REDUCE_MAX_STARTS); return nullptr; }
-    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return nullptr; }
-    if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return nullptr; }
-    if (agent->max_steps < 0) { set_error("%s: max_steps=%d < 0", who, agent->max_steps); return nullptr; }
-    if (depth == 0) depth = starts ? frirl_hip_reduce_batch_starts_depth(b->E, agent->A, ns) : frirl_hip_reduce_batch_depth(b->E, agent->A);
-    const size_t E = (size_t)b->E, M = (size_t)b->maxR;
-    const int nodes = frirl::rw_nodes(depth);
-    const size_t rows = E * per_node * nodes;
-    if (!starts && rows > 0x7fffffffu) { set_error("%s: E=%d agents x %d rows per round beyond 2^31 - 1", who, b->E, nodes); return nullptr; }
-    if (starts && rows > (size_t)INT32_MAX / 2) { set_error("%s: E=%d x n=%d x %d nodes: too many rows per round", who, b->E, ns, nodes); return nullptr; }
-    if (check_device()) return nullptr;
     frirl_hip_batch_reducer *r = new (std::nothrow) frirl_hip_batch_reducer;
     if (!r) { set_error("%s: out of memory", who); return nullptr; }
-    r->t = *t; r->b = *b; r->agent = *agent;
-    r->agent.no_random = 1;                                           // the replays are greedy (reduction_state == 1)
-    r->rant = rant;
-    r->reward_good_above = agent->reward_good_above;
-    r->reward_tolerance = reward_tolerance;
-    r->depth = depth;
-    r->nodes = nodes;
-    r->ns = ns;
-    r->drop_bad = starts && starts->drop_bad_starts != 0;
-    r->s = as_stream(stream);
-    const size_t need = starts ? reduce_starts_layout(nullptr, E, M, depth, rows, ns, nullptr) : reduce_batch_layout(nullptr, E, M, depth, rows, nullptr);
-    bool ok = hipMalloc(&r->d_ws, need) == hipSuccess && hipMalloc(&r->d_done, sizeof(int32_t) * rows) == hipSuccess &&
+    ReduceRun &run = r->run;
+    if (run.init(who, t, b, agent, rant, starts, strategy, reward_tolerance, depth, true, stream) || check_device()) { delete r; return nullptr; }
+    const size_t E = (size_t)b->E, rows = E * run.per_node() * run.nodes;
+    bool ok = hipMalloc(&r->d_ws, run.need) == hipSuccess && hipMalloc(&r->d_done, sizeof(int32_t) * rows) == hipSuccess &&
               hipMalloc(&r->d_success, sizeof(int32_t) * rows) == hipSuccess;
     if (ok && !starts)                                               // for the n = 1 view of _result_starts
         ok = hipMalloc(&r->d_base, sizeof(double) * E) == hipSuccess && hipMalloc(&r->d_view, sizeof(frirl_hip_reduce_start_result) * E) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         set_error("%s: hipMalloc failed", who);
-        delete r;
-        return nullptr;
     }
-    if (starts) {
-        reduce_starts_layout(static_cast<char *>(r->d_ws), E, M, depth, rows, ns, &r->sw);
-        r->ws = r->sw.b;
-    } else {
-        reduce_batch_layout(static_cast<char *>(r->d_ws), E, M, depth, rows, &r->ws);
-    }
-    BR_TRY(hipMemsetAsync(r->ws.hdr, 0, sizeof r->hdr, r->s), { delete r; return nullptr; });
-    hipLaunchKernelGGL(frirl::reduce_batch_order_kernel, dim3((unsigned)E), dim3(256), 0, r->s, b->rb, b->nrules, t->nant, b->maxR, active, strategy,
-                       r->agent.max_steps, r->ws);
-    if (starts) hipLaunchKernelGGL(frirl::reduce_starts_init_kernel, dim3((unsigned)E), dim3(256), 0, r->s, starts->start_count, r->sw);
-    if (batch_reducer_header(r, who) || check_launch(who)) { delete r; return nullptr; }
-    if (r->hdr[2]) {
-        set_error("%s: agent %d: nrules outside 1..maxR=%d", who, r->hdr[2] - 1, b->maxR);
-        delete r;
-        return nullptr;
-    }
+    if (!ok || run.start(who, r->d_ws, active, starts ? starts->start_count : nullptr)) { delete r; return nullptr; }
     return r;
 }
 
@@ -240,7 +177,7 @@ extern "C" frirl_hip_batch_reducer *frirl_hip_batch_reducer_create_starts(const 
     return batch_reducer_create(t, b, agent, rant, active, starts, strategy, reward_tolerance, depth, stream, who);
 }
 
-extern "C" int frirl_hip_batch_reducer_starts(const frirl_hip_batch_reducer *r) { return r ? r->per_node() : 0; }
+extern "C" int frirl_hip_batch_reducer_starts(const frirl_hip_batch_reducer *r) { return r ? r->run.per_node() : 0; }
 
 extern "C" void frirl_hip_batch_reducer_destroy(frirl_hip_batch_reducer *r) { delete r; }
 
@@ -249,17 +186,17 @@ extern "C" int frirl_hip_batch_reducer_next_round(frirl_hip_batch_reducer *r, in
     const char *who = "frirl_hip_batch_reducer_next_round";
     if (!r || !Q) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::IDLE) { set_error("%s: the previous round has not been closed (frirl_hip_batch_reducer_end_round)", who); return FRIRL_HIP_EINVAL; }
-    const int nlive = r->hdr[r->cur()];
-    const int n = nlive == 0 ? 0 : (r->round == 0 ? 1 : r->nodes) * r->per_node();
+    const int nlive = r->run.nlive();
+    const int n = nlive == 0 ? 0 : r->run.rows_per_agent();
     if (nlive > 0) {                                                  // rows of agents that sit out, and nodes that do not exist, stay done
-        const int q = r->b.E * n;
-        hipLaunchKernelGGL(frirl::policy_batch_fill_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, r->s, static_cast<int32_t *>(r->d_done), q, 1);
+        const int q = r->run.b.E * n;
+        hipLaunchKernelGGL(frirl::policy_batch_fill_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, r->run.s, static_cast<int32_t *>(r->d_done), q, 1);
         const int rc = check_launch(who);
         if (rc) return rc;
         r->state = frirl_hip_batch_reducer::OPEN;
     }
     r->n = n;
-    *Q = r->Q = r->b.E * n;
+    *Q = r->Q = r->run.b.E * n;
     if (rows_per_agent) *rows_per_agent = n;
     if (agents_live) *agents_live = nlive;
     return FRIRL_HIP_OK;
@@ -267,10 +204,11 @@ extern "C" int frirl_hip_batch_reducer_next_round(frirl_hip_batch_reducer *r, in
 
 static int batch_reducer_step(frirl_hip_batch_reducer *r, const frirl_hip_agent_io *io, int begin, const char *who)
 {
-    BR_TRY(hipMemsetAsync(r->ws.hdr + 3, 0, sizeof(int32_t), r->s), return FRIRL_HIP_ELAUNCH);
+    const ReduceRun &run = r->run;
+    FRIRL_HIP_TRY(hipMemsetAsync(run.ws.hdr + 3, 0, sizeof(int32_t), run.s), who, return FRIRL_HIP_ELAUNCH);
     const frirl::PolicyBatchArgs pa = r->args();
     const frirl::PolicyStartsArgs st = r->starts_args();
-    policy_batch_launch(&r->t, &r->b, &r->agent, &pa, io, begin, r->hdr[r->cur()], r->s, r->starts_round() ? &st : nullptr);
+    policy_batch_launch(&run.t, &run.b, &run.agent, &pa, io, begin, run.nlive(), run.s, r->starts_round() ? &st : nullptr);
     r->live_known = false;
     return check_launch(who);
 }
@@ -296,9 +234,9 @@ extern "C" int frirl_hip_batch_reducer_observe(frirl_hip_batch_reducer *r, const
     if (r->state != frirl_hip_batch_reducer::RUNNING) { set_error("%s: no running round (frirl_hip_batch_reducer_begin first)", who); return FRIRL_HIP_EINVAL; }
     int rc = check_policy_io(io, false, who);
     if (rc || (rc = batch_reducer_step(r, io, 0, who)) || !rows_live) return rc;
-    if ((rc = batch_reducer_header(r, who))) return rc;
+    if ((rc = r->run.header(who))) return rc;
     r->live_known = true;
-    *rows_live = r->hdr[3];
+    *rows_live = r->run.hdr[3];
     return FRIRL_HIP_OK;
 }
 
@@ -307,33 +245,18 @@ extern "C" int frirl_hip_batch_reducer_end_round(frirl_hip_batch_reducer *r)
     const char *who = "frirl_hip_batch_reducer_end_round";
     if (!r) { set_error("%s: NULL reducer", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::RUNNING) { set_error("%s: no running round", who); return FRIRL_HIP_EINVAL; }
+    ReduceRun &run = r->run;
     int rc;
     if (!r->live_known) {
-        if ((rc = batch_reducer_header(r, who))) return rc;
+        if ((rc = run.header(who))) return rc;
         r->live_known = true;
     }
-    if (r->hdr[3] > 0) { set_error("%s: %d of %d replays have not ended", who, r->hdr[3], r->Q); return FRIRL_HIP_EINVAL; }
-    const int cur = r->cur(), first = r->round == 0, nlive = r->hdr[cur];
-    switch (r->t.nant) {
-#define M(N) case N:                                                                                                                                   \
-        if (r->ns)                                                                                                                                     \
-            hipLaunchKernelGGL((frirl::reduce_starts_close_kernel<N, true>), dim3(nlive), dim3(256), 0, r->s, r->b.rb, r->b.nrules, r->b.uidx, r->rant, \
-                               r->b.maxR, cur, first, r->agent.max_steps, r->reward_good_above, r->reward_tolerance, r->drop_bad, r->sw);               \
-        else                                                                                                                                           \
-            hipLaunchKernelGGL(frirl::reduce_batch_close_kernel<N>, dim3(nlive), dim3(256), 0, r->s, r->b.rb, r->b.nrules, r->b.uidx, r->rant,         \
-                               r->b.maxR, cur, first, r->agent.max_steps, r->reward_good_above, r->reward_tolerance, r->ws);                           \
-        break;
-        FRIRL_POLICY_NANT_CASES(M)
-#undef M
-    }
-    if (first && !r->ns)                                              // the baseline rewards, for the n = 1 view of _result_starts
-        BR_TRY(hipMemcpyAsync(r->d_base, r->ws.prev, sizeof(double) * r->b.E, hipMemcpyDeviceToDevice, r->s), return FRIRL_HIP_ELAUNCH);
-    if ((rc = batch_reducer_header(r, who))) return rc;               // the next round's live count
-    r->round += 1;
+    if (run.hdr[3] > 0) { set_error("%s: %d of %d replays have not ended", who, run.hdr[3], r->Q); return FRIRL_HIP_EINVAL; }
+    const bool base = run.first() && !run.ns;                         // keep the baseline rewards for the n = 1 view of _result_starts:
+    if ((rc = run.close(who))) return rc;                             // ws.prev holds them until the next round's close kernel
     r->state = frirl_hip_batch_reducer::IDLE;
-    const int next = r->hdr[r->cur()];
-    if (next > 0) hipLaunchKernelGGL(frirl::reduce_batch_open_kernel, dim3(next), dim3(256), 0, r->s, r->b.nrules, r->b.maxR, r->depth, r->cur(), r->ws);
-    return check_launch(who);
+    if (base) FRIRL_HIP_TRY(hipMemcpyAsync(r->d_base, run.ws.prev, sizeof(double) * run.b.E, hipMemcpyDeviceToDevice, run.s), who, return FRIRL_HIP_ELAUNCH);
+    return FRIRL_HIP_OK;
 }
 
 extern "C" int frirl_hip_batch_reducer_result(frirl_hip_batch_reducer *r, int32_t *kept, frirl_hip_reduce_result *results)
@@ -341,12 +264,7 @@ extern "C" int frirl_hip_batch_reducer_result(frirl_hip_batch_reducer *r, int32_
     const char *who = "frirl_hip_batch_reducer_result";
     if (!r || !results) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::IDLE) { set_error("%s: a round is open (frirl_hip_batch_reducer_end_round first)", who); return FRIRL_HIP_EINVAL; }
-    const size_t E = (size_t)r->b.E, M = (size_t)r->b.maxR;
-    hipLaunchKernelGGL(frirl::reduce_batch_result_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, r->s, r->b.nrules, (int)E, r->ws);
-    BR_TRY(hipMemcpyAsync(results, r->ws.res, sizeof(frirl_hip_reduce_result) * E, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
-    if (kept) BR_TRY(hipMemcpyAsync(kept, r->ws.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
-    BR_TRY(hipStreamSynchronize(r->s), return FRIRL_HIP_ELAUNCH);
-    return check_launch(who);
+    return r->run.results(who, kept, results, nullptr);
 }
 
 extern "C" int frirl_hip_batch_reducer_result_starts(frirl_hip_batch_reducer *r, frirl_hip_reduce_start_result *per_start)
@@ -354,17 +272,14 @@ extern "C" int frirl_hip_batch_reducer_result_starts(frirl_hip_batch_reducer *r,
     const char *who = "frirl_hip_batch_reducer_result_starts";
     if (!r || !per_start) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
     if (r->state != frirl_hip_batch_reducer::IDLE) { set_error("%s: a round is open (frirl_hip_batch_reducer_end_round first)", who); return FRIRL_HIP_EINVAL; }
-    const size_t total = (size_t)r->b.E * r->per_node();
-    const dim3 grid((unsigned)((total + 255) / 256));
-    frirl_hip_reduce_start_result *d_res = r->sw.res;
-    if (r->ns) {
-        hipLaunchKernelGGL(frirl::reduce_starts_result_kernel, grid, dim3(256), 0, r->s, (int)total, r->sw);
-    } else {                                                          // no per-start arrays: the view is built from the per-agent ones
-        d_res = reinterpret_cast<frirl_hip_reduce_start_result *>(r->d_view);
-        hipLaunchKernelGGL(frirl::policy_batch_one_start_kernel, grid, dim3(256), 0, r->s, (int)total, r->ws, static_cast<const double *>(r->d_base), d_res);
-    }
-    BR_TRY(hipMemcpyAsync(per_start, d_res, sizeof(frirl_hip_reduce_start_result) * total, hipMemcpyDeviceToHost, r->s), return FRIRL_HIP_ELAUNCH);
-    BR_TRY(hipStreamSynchronize(r->s), return FRIRL_HIP_ELAUNCH);
+    ReduceRun &run = r->run;
+    if (run.ns) return run.results(who, nullptr, nullptr, per_start);
+    // no per-start arrays: the n = 1 view is built from the per-agent ones
+    const int E = run.b.E;
+    frirl_hip_reduce_start_result *d_res = static_cast<frirl_hip_reduce_start_result *>(r->d_view);
+    hipLaunchKernelGGL(frirl::policy_batch_one_start_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, run.s, E, run.ws, static_cast<const double *>(r->d_base), d_res);
+    FRIRL_HIP_TRY(hipMemcpyAsync(per_start, d_res, sizeof(frirl_hip_reduce_start_result) * E, hipMemcpyDeviceToHost, run.s), who, return FRIRL_HIP_ELAUNCH);
+    FRIRL_HIP_TRY(hipStreamSynchronize(run.s), who, return FRIRL_HIP_ELAUNCH);
     return check_launch(who);
 }
 

@@ -7,9 +7,11 @@
 //          rollout_episode / shared_sweep (the code of frirl_hip_rollout_shared) at that agent's slab, start state and step cap
 //   close  tree walk (reduce_walk.h), in-place compaction of the agent's columns, next live list
 // and the host reads one 16-byte header (the live count) per round.  No slab and no per-row result crosses to the host.
+// This file holds `roll` and the entry point; the protocol around it (checks, order, open, close, results) is ReduceRun's (reduce_run.h).
 #include "rollout_episode.h"
-#include "reduce_batch_kernels.h"
+#include "reduce_run.h"
 #include "shape_ladder.h"
+#include <type_traits>
 
 namespace frirl {
 
@@ -47,14 +49,7 @@ __global__ __launch_bounds__(SH_BLOCK) void reduce_batch_rollout_kernel(const do
 
 }  // namespace frirl
 
-extern "C" int frirl_hip_reduce_batch_depth(int32_t E, int32_t A)
-{
-    if (E < 1) E = 1;
-    const long rows = rb_resident_rows(A);
-    int d = 1;
-    while (d < 10 && (long)E * frirl::rw_nodes(d + 1) <= rows) d++;
-    return d;
-}
+extern "C" int frirl_hip_reduce_batch_depth(int32_t E, int32_t A) { return frirl_hip_reduce_batch_starts_depth(E, A, 1); }
 
 extern "C" size_t frirl_hip_reduce_batch_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t depth)
 {
@@ -67,24 +62,18 @@ extern "C" size_t frirl_hip_reduce_batch_workspace_bytes(int32_t nant, int32_t E
     return reduce_batch_layout(nullptr, E, maxR, 10, (size_t)((long)E > cap ? (long)E : cap), nullptr);
 }
 
-template <int N, int AMAX, int G, int H, bool PN = true>
-static void launch_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const double *start, int cur, int nlive,
-                        int nodes, int first, const ReduceBatchWs &ws, hipStream_t s)
-{
-    constexpr int EPB = frirl::SH_BLOCK / (G * H);
-    const int wpa = (nodes + EPB - 1) / EPB;
-    hipLaunchKernelGGL((frirl::reduce_batch_rollout_kernel<N, AMAX, G, H, PN>), dim3((unsigned)nlive * wpa), dim3(frirl::SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb,
-                       b->nrules, b->maxR, *ag, start, cur, wpa, first, ws);
-}
-
+// the replays of the run's current round: one row per node of every live agent
 template <int N>
-static void launch_rows_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const double *start, int cur, int nlive,
-                          int nodes, int first, const ReduceBatchWs &ws, hipStream_t s)
+static void launch_rows(const ReduceRun &r, const double *start)
 {
-    const int H = first ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)nlive * nodes, ag->A);     // the baseline replay: a full wave per row
-    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+    const int nlive = r.nlive(), nodes = r.rows_per_agent(), first = r.first();
+    const int H = first ? FRIRL_WAVE / rb_group(r.agent.A) : rb_slices((long)nlive * nodes, r.agent.A);     // the baseline replay: a full wave per row
+    frirl::for_batch_shape<N>(&r.agent, H, [&](auto sh) {
         using S = decltype(sh);
-        launch_rows<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, start, cur, nlive, nodes, first, ws, s);
+        constexpr int EPB = frirl::SH_BLOCK / (S::G * S::H);
+        const int wpa = (nodes + EPB - 1) / EPB;
+        hipLaunchKernelGGL((frirl::reduce_batch_rollout_kernel<N, S::AMAX, S::G, S::H, S::PN>), dim3((unsigned)nlive * wpa), dim3(frirl::SH_BLOCK), 0, r.s, r.t.u,
+                           r.t.ve, r.t.U, r.b.rb, r.b.nrules, r.b.maxR, r.agent, start, r.cur(), wpa, first, r.ws);
     });
 }
 
@@ -109,59 +98,17 @@ extern "C" int frirl_hip_reduce_batch(const frirl_hip_tables *t, const frirl_hip
     int rc = check_rulebases(t, b);
     if (rc) return rc;
     if (!agent || !results || !agent->grid_values || !agent->action_ve) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
-    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
-    if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return FRIRL_HIP_EINVAL; }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_demo_kind(t, agent, who))) return rc;
-    if ((rc = check_grid_len(t, agent, who))) return rc;
-    if (depth == 0) depth = frirl_hip_reduce_batch_depth(b->E, agent->A);
-    const size_t E = (size_t)b->E, M = (size_t)b->maxR;
-    const int nodes = frirl::rw_nodes(depth);
-    const size_t need = reduce_batch_layout(nullptr, E, M, depth, E * nodes, nullptr);
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need) {
-        set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (frirl_hip_reduce_batch_workspace_bytes)", who, workspace, workspace_bytes, need);
-        return FRIRL_HIP_EINVAL;
-    }
-    if ((rc = check_device())) return rc;
-    hipStream_t s = as_stream(stream);
-#define RB_TRY(expr)                                                                                               \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
-    } while (0)
-    ReduceBatchWs ws;
-    reduce_batch_layout(static_cast<char *>(workspace), E, M, depth, E * nodes, &ws);
-    frirl_hip_agent greedy = *agent;
-    greedy.no_random = 1;                                             // the replays are greedy (reduction_state == 1 keeps epsilon at 0 in every demo)
-    int32_t hdr[4] = {0, 0, 0, 0};
-    RB_TRY(hipMemsetAsync(ws.hdr, 0, sizeof hdr, s));
-    hipLaunchKernelGGL(frirl::reduce_batch_order_kernel, dim3((unsigned)E), dim3(256), 0, s, b->rb, b->nrules, t->nant, b->maxR, active, strategy,
-                       greedy.max_steps, ws);
-    RB_TRY(hipMemcpyAsync(hdr, ws.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    RB_TRY(hipStreamSynchronize(s));
-    if (hdr[2]) { set_error("%s: agent %d: nrules outside 1..maxR=%d", who, hdr[2] - 1, b->maxR); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_demo_kind(t, agent, who)) || (rc = check_grid_len(t, agent, who))) return rc;
+    ReduceRun run;
+    if ((rc = run.init(who, t, b, agent, rant, nullptr, strategy, reward_tolerance, depth, false, stream)) ||
+        (rc = run.check_workspace(who, workspace, workspace_bytes)) || (rc = check_device()) || (rc = run.start(who, workspace, active, nullptr)))
+        return rc;
     // round 0 = the baseline replay of every active agent (:196-198 and the first loop iteration, :204-206); then rounds until no
-    // agent has a candidate left.  Per round the host reads the 16-byte header: the next round's live count.
-    for (int round = 0;; round++) {
-        const int cur = round & 1, first = round == 0;
-        const int nlive = hdr[cur];
-        if (nlive == 0) break;
-        if (!first) hipLaunchKernelGGL(frirl::reduce_batch_open_kernel, dim3(nlive), dim3(256), 0, s, b->nrules, b->maxR, depth, cur, ws);
-        if (t->nant == 3) launch_rows_n<3>(t, b, &greedy, start_states, cur, nlive, first ? 1 : nodes, first, ws, s);
-        else launch_rows_n<5>(t, b, &greedy, start_states, cur, nlive, first ? 1 : nodes, first, ws, s);
-        if (t->nant == 3)
-            hipLaunchKernelGGL(frirl::reduce_batch_close_kernel<3>, dim3(nlive), dim3(256), 0, s, b->rb, b->nrules, b->uidx, rant, b->maxR, cur, first,
-                               greedy.max_steps, agent->reward_good_above, reward_tolerance, ws);
-        else
-            hipLaunchKernelGGL(frirl::reduce_batch_close_kernel<5>, dim3(nlive), dim3(256), 0, s, b->rb, b->nrules, b->uidx, rant, b->maxR, cur, first,
-                               greedy.max_steps, agent->reward_good_above, reward_tolerance, ws);
-        RB_TRY(hipMemcpyAsync(hdr, ws.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-        RB_TRY(hipStreamSynchronize(s));
+    // agent has a candidate left
+    while (run.nlive() > 0) {
+        if (t->nant == 3) launch_rows<3>(run, start_states);
+        else launch_rows<5>(run, start_states);
+        if ((rc = run.close(who))) return rc;
     }
-    hipLaunchKernelGGL(frirl::reduce_batch_result_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, b->nrules, (int)E, ws);
-    RB_TRY(hipMemcpyAsync(results, ws.res, sizeof(frirl_hip_reduce_result) * E, hipMemcpyDeviceToHost, s));
-    if (kept) RB_TRY(hipMemcpyAsync(kept, ws.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, s));
-    RB_TRY(hipStreamSynchronize(s));
-#undef RB_TRY
-    return check_launch(who);
+    return run.results(who, kept, results, nullptr);
 }

@@ -1,39 +1,17 @@
-// reduce_batch_kernels.h -- what the batched reductions share: the arrays of a run (ReduceBatchWs), the order, open-round,
-// close-round and result kernels, the in-place compaction, and the host helpers for lane shapes and the workspace layout.
-// frirl_hip_reduce_batch (reduce_batch.hip) rolls the replays out inside its own kernel; frirl_hip_batch_reducer_* (policy_batch.hip)
-// steps them in the caller's environment; frirl_hip_reduce_batch_starts (reduce_starts.hip) replays every node from several start
-// states and brings its own roll-out and close kernels.  Moved out of reduce_batch.hip as shared_sweep.h and rollout_episode.h were; the only change is that the
-// kernels that are no templates have internal linkage (`static`), since two translation units now hold them.
+// reduce_batch_kernels.h -- the protocol kernels of the batched reductions: order, open-round, close-round and result kernels and the
+// in-place compaction, over the arrays of reduce_ws.h.  Included by reduce_run.hip ONLY: the library is built without relocatable
+// device code, so a kernel is launched from the translation unit that defines it, and every launch of these sits behind ReduceRun
+// (reduce_run.h).  Who runs the replays between open and close -- a roll-out kernel or the caller -- is not their business.
 #pragma once
-#include "shared_sweep.h"
-#include "reduce_walk.h"
-#include "batch_shape.h"
-#include <cstring>
-#include <type_traits>
+#include "reduce_ws.h"
 
 namespace frirl {
 
 constexpr int RB_ORDER_TILE = 1024;      // |Q| values staged in LDS per pass of the rank count
 
-// the arrays of one call, carved out of the caller's workspace (reduce_batch_layout)
-struct ReduceBatchWs {
-    int32_t *hdr;                 // [4] live count of even rounds, of odd rounds, first agent with a bad rule count + 1, pad
-    uint32_t *mask;               // [nodes] exclude mask of every tree node: the same for every agent
-    int32_t *live[2];             // [E] agents still reducing, this round's list and the next one's
-    int32_t *order;               // [E][maxR] candidates in trial order (original rule indices)
-    int32_t *alive;               // [E][maxR] original index of the rule in each current slot
-    uint8_t *slot;                // [E][maxR] candidate slot of every current rule in this round, 255 = none
-    int32_t *steps;               // [E][nodes] replay results of this round
-    double *reward;               // [E][nodes]
-    int32_t *j, *d, *R0, *rounds, *rollouts, *steps_inc, *cap;      // [E]
-    double *prev;                 // [E] prev_reward
-    frirl_hip_reduce_result *res; // [E]
-    int nodes;                    // 2^depth - 1
-};
-
 // Order kernel: one workgroup per agent.  Per-agent state, and the stable rank of every |Q| by counting (rw_before) with the
 // consequents staged in LDS; workgroup 0 also builds the mask table.  Active agents join the first live list.
-static __global__ __launch_bounds__(256) void reduce_batch_order_kernel(const double *__restrict__ rb, const int32_t *__restrict__ nrules, int nant, int maxR,
+__global__ __launch_bounds__(256) void reduce_batch_order_kernel(const double *__restrict__ rb, const int32_t *__restrict__ nrules, int nant, int maxR,
                                                                  const uint8_t *__restrict__ active, int strategy, int max_steps, ReduceBatchWs ws)
 {
     __shared__ double aq[RB_ORDER_TILE];
@@ -72,7 +50,7 @@ static __global__ __launch_bounds__(256) void reduce_batch_order_kernel(const do
 }
 
 // Open-round kernel: one workgroup per live agent; d_e and the slot table of its next candidates.
-static __global__ __launch_bounds__(256) void reduce_batch_open_kernel(const int32_t *__restrict__ nrules, int maxR, int depth, int cur, ReduceBatchWs ws)
+__global__ __launch_bounds__(256) void reduce_batch_open_kernel(const int32_t *__restrict__ nrules, int maxR, int depth, int cur, ReduceBatchWs ws)
 {
     __shared__ int cand[RW_MAX_DEPTH];
     const int e = ws.live[cur][blockIdx.x], tid = threadIdx.x;
@@ -177,7 +155,7 @@ __global__ __launch_bounds__(256) void reduce_batch_close_kernel(double *__restr
     if (j < ws.R0[e]) ws.live[cur ^ 1][atomicAdd(&ws.hdr[cur ^ 1], 1)] = e;
 }
 
-static __global__ void reduce_batch_result_kernel(const int32_t *__restrict__ nrules, int E, ReduceBatchWs ws)
+__global__ void reduce_batch_result_kernel(const int32_t *__restrict__ nrules, int E, ReduceBatchWs ws)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
@@ -193,33 +171,3 @@ static __global__ void reduce_batch_result_kernel(const int32_t *__restrict__ nr
 }
 
 }  // namespace frirl
-
-using namespace frirl_host;
-using frirl::ReduceBatchWs;
-
-// ---- shapes ----------------------------------------------------------------------------------------------------------------
-// rb_group, rb_resident_rows, rb_slices, up16: batch_shape.h (shared with the batched roll-outs, rollout_batch.hip)
-
-// carves the arrays of a call out of `base` (NULL: sizes only); `rows` = entries of steps / reward
-static size_t reduce_batch_layout(char *base, size_t E, size_t maxR, int depth, size_t rows, ReduceBatchWs *ws)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += up16(bytes); return p; };
-    ReduceBatchWs w;
-    w.nodes = frirl::rw_nodes(depth);
-    w.hdr = reinterpret_cast<int32_t *>(take(4 * sizeof(int32_t)));
-    w.mask = reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * w.nodes));
-    w.live[0] = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
-    w.live[1] = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
-    w.order = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * maxR));
-    w.alive = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * maxR));
-    w.slot = reinterpret_cast<uint8_t *>(take(E * maxR));
-    w.steps = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * rows));
-    w.reward = reinterpret_cast<double *>(take(sizeof(double) * rows));
-    int32_t **per_agent[] = {&w.j, &w.d, &w.R0, &w.rounds, &w.rollouts, &w.steps_inc, &w.cap};
-    for (int32_t **p : per_agent) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
-    w.prev = reinterpret_cast<double *>(take(sizeof(double) * E));
-    w.res = reinterpret_cast<frirl_hip_reduce_result *>(take(sizeof(frirl_hip_reduce_result) * E));
-    if (ws) *ws = w;
-    return off;
-}

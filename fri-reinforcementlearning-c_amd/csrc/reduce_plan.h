@@ -31,27 +31,21 @@ struct ReducePlan {
     int lanes_max() const { return frirl::rw_nodes(depth); }
     bool finished() const { return j >= R0; }
 
-#define FRIRL_PLAN_TRY(expr)                                                                                       \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
-    } while (0)
-
     // host copies of the rule base and the candidate order; synchronises `s`
     int load(const char *who_, const frirl_hip_tables *t, const frirl_hip_rulebases *b_, double *rant_, int strategy, int depth_, hipStream_t s)
     {
         who = who_; nant = t->nant; maxR = b_->maxR; depth = depth_; b = *b_; rant = rant_;
         const size_t col = (size_t)maxR;
         int32_t r0 = 0;
-        FRIRL_PLAN_TRY(hipMemcpyAsync(&r0, b.nrules, sizeof r0, hipMemcpyDeviceToHost, s));
-        FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+        FRIRL_HIP_TRY(hipMemcpyAsync(&r0, b.nrules, sizeof r0, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+        FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
         if (r0 < 1 || r0 > maxR) { set_error("%s: nrules=%d outside 1..maxR=%d", who, r0, maxR); return FRIRL_HIP_EINVAL; }
         R0 = R = r0;
         slab.resize((size_t)(nant + 1) * col);
-        FRIRL_PLAN_TRY(hipMemcpyAsync(slab.data(), b.rb, slab.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (rant) { rants.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(rants.data(), rant, rants.size() * sizeof(double), hipMemcpyDeviceToHost, s)); }
-        if (b.uidx) { idx.resize((size_t)nant * col); FRIRL_PLAN_TRY(hipMemcpyAsync(idx.data(), b.uidx, idx.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s)); }
-        FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+        FRIRL_HIP_TRY(hipMemcpyAsync(slab.data(), b.rb, slab.size() * sizeof(double), hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+        if (rant) { rants.resize((size_t)nant * col); FRIRL_HIP_TRY(hipMemcpyAsync(rants.data(), rant, rants.size() * sizeof(double), hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH); }
+        if (b.uidx) { idx.resize((size_t)nant * col); FRIRL_HIP_TRY(hipMemcpyAsync(idx.data(), b.uidx, idx.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH); }
+        FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
         // candidate order: the reference rescans for the first minimum (strategy 1) or the first maximum (strategy 2) of the
         // not-yet-tested consequents after every episode; the consequents never change and removals keep the relative rule order,
         // so that is the strict total order rw_before, fixed up front
@@ -86,8 +80,8 @@ struct ReducePlan {
         for (int i = 0; i < R; i++) where[alive[i]] = i;
         std::fill(slot.begin(), slot.end(), (uint8_t)255);
         for (int i = 0; i < d; i++) slot[where[order[j + i]]] = (uint8_t)i;
-        FRIRL_PLAN_TRY(hipMemcpyAsync(d_slot, slot.data(), (size_t)maxR, hipMemcpyHostToDevice, s));
-        FRIRL_PLAN_TRY(hipMemcpyAsync(d_mask, mask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        FRIRL_HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), (size_t)maxR, hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
+        FRIRL_HIP_TRY(hipMemcpyAsync(d_mask, mask.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
         *lanes = n;
         return FRIRL_HIP_OK;
     }
@@ -119,16 +113,15 @@ struct ReducePlan {
             R = w;
             alive.resize(R);
             const int32_t Rn = R;
-            FRIRL_PLAN_TRY(hipMemcpyAsync(b.rb, slab.data(), slab.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            if (rant) FRIRL_PLAN_TRY(hipMemcpyAsync(rant, rants.data(), rants.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            if (b.uidx) FRIRL_PLAN_TRY(hipMemcpyAsync(b.uidx, idx.data(), idx.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            FRIRL_PLAN_TRY(hipMemcpyAsync(b.nrules, &Rn, sizeof Rn, hipMemcpyHostToDevice, s));
-            FRIRL_PLAN_TRY(hipStreamSynchronize(s));
+            FRIRL_HIP_TRY(hipMemcpyAsync(b.rb, slab.data(), slab.size() * sizeof(double), hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
+            if (rant) FRIRL_HIP_TRY(hipMemcpyAsync(rant, rants.data(), rants.size() * sizeof(double), hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
+            if (b.uidx) FRIRL_HIP_TRY(hipMemcpyAsync(b.uidx, idx.data(), idx.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
+            FRIRL_HIP_TRY(hipMemcpyAsync(b.nrules, &Rn, sizeof Rn, hipMemcpyHostToDevice, s), who, return FRIRL_HIP_ELAUNCH);
+            FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
         }
         j += d;
         return FRIRL_HIP_OK;
     }
-#undef FRIRL_PLAN_TRY
 
     void result(int32_t *kept, frirl_hip_reduce_result *res) const
     {

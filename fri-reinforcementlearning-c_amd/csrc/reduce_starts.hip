@@ -1,18 +1,17 @@
 // reduce_starts.hip -- frirl_hip_reduce_batch (reduce_batch.hip) with every removal validated against SEVERAL start states per agent
 // (frirl_hip_reduce_batch_starts; include/frirl_hip.h, DESIGN.md "Reduction against a set of start states").
 //
-// The order, open-round and result kernels, the masks, the slot tables, the live lists and the compaction are those of the batched
-// reduction (reduce_batch_kernels.h).  New here: a row space of nodes x used starts per agent (row = node * K_e + ki), per-start
-// baselines and step caps, and a close kernel that accepts a removal only if every used start accepts it (rw_walk_starts).  The
-// per-start arrays, the init, close and result kernels and the layout are reduce_starts_kernels.h (shared with the caller-stepped form).
-//   roll   a workgroup serves 256 / (G * H) rows of ONE agent; rows with different caps share it, so the step loop is written here:
-//          its bound is the agent's largest cap, a row goes inactive after its own cap, the workgroup leaves through
+// The round protocol is ReduceRun's (reduce_run.h), as for frirl_hip_reduce_batch; with start states it adds the init kernel and a
+// close kernel that accepts a removal only if every used start accepts it (rw_walk_starts).  This file holds the entry point and
+//   roll   a row space of nodes x used starts per agent (row = node * K_e + ki) with per-start baselines and step caps (ReduceStartsWs,
+//          reduce_ws.h).  A workgroup serves 256 / (G * H) rows of ONE agent; rows with different caps share it, so the step loop is
+//          written here: its bound is the agent's largest cap, a row goes inactive after its own cap, the workgroup leaves through
 //          __syncthreads_count.  Per row the result is rollout_episode's (rollout_episode.h) with max_steps = the row's cap.
-//   close  first: per-start baselines, caps and the compact list of used starts; otherwise walk, compaction, next live list.
 #include "shared_sweep.h"
 #include "envs.h"
-#include "reduce_starts_kernels.h"
+#include "reduce_run.h"
 #include "shape_ladder.h"
+#include <type_traits>
 
 namespace frirl {
 
@@ -128,25 +127,18 @@ extern "C" size_t frirl_hip_reduce_batch_starts_workspace_bytes(int32_t nant, in
     return reduce_starts_layout(nullptr, E, maxR, 10, (size_t)(en > cap ? en : cap), n, nullptr);
 }
 
-template <int N, int AMAX, int G, int H, bool PN = true>
-static void launch_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const double *start, int cur, int nlive,
-                        int rows, int first, const ReduceStartsWs &ws, hipStream_t s)
-{
-    constexpr int EPB = frirl::SH_BLOCK / (G * H);
-    const int wpa = (rows + EPB - 1) / EPB;
-    hipLaunchKernelGGL((frirl::reduce_starts_rollout_kernel<N, AMAX, G, H, PN>), dim3((unsigned)nlive * wpa), dim3(frirl::SH_BLOCK), 0, s, t->u, t->ve, t->U, b->rb,
-                       b->nrules, b->maxR, *ag, start, cur, wpa, first, ws);
-}
-
-// rows: the most rows an agent can have this round (n baseline replays, or nodes * n)
+// the replays of the run's current round; rows: the most rows an agent can have this round (n baseline replays, or nodes * n)
 template <int N>
-static void launch_rows_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const double *start, int cur, int nlive,
-                          int rows, int first, const ReduceStartsWs &ws, hipStream_t s)
+static void launch_rows(const ReduceRun &r, const double *start)
 {
-    const int H = (first && ws.n == 1) ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)nlive * rows, ag->A);   // one baseline replay per agent: a full wave per row
-    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+    const int nlive = r.nlive(), rows = r.rows_per_agent(), first = r.first();
+    const int H = (first && r.ns == 1) ? FRIRL_WAVE / rb_group(r.agent.A) : rb_slices((long)nlive * rows, r.agent.A);   // one baseline replay per agent: a full wave per row
+    frirl::for_batch_shape<N>(&r.agent, H, [&](auto sh) {
         using S = decltype(sh);
-        launch_rows<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, start, cur, nlive, rows, first, ws, s);
+        constexpr int EPB = frirl::SH_BLOCK / (S::G * S::H);
+        const int wpa = (rows + EPB - 1) / EPB;
+        hipLaunchKernelGGL((frirl::reduce_starts_rollout_kernel<N, S::AMAX, S::G, S::H, S::PN>), dim3((unsigned)nlive * wpa), dim3(frirl::SH_BLOCK), 0, r.s, r.t.u,
+                           r.t.ve, r.t.U, r.b.rb, r.b.nrules, r.b.maxR, r.agent, start, r.cur(), wpa, first, r.sw);
     });
 }
 
@@ -186,67 +178,17 @@ extern "C" int frirl_hip_reduce_batch_starts(const frirl_hip_tables *t, const fr
     int rc = check_rulebases(t, b);
     if (rc) return rc;
     if (!agent || !results || !starts || !starts->start_states || !agent->grid_values || !agent->action_ve) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
-    if (starts->n < 1 || starts->n > FRIRL_HIP_REDUCE_MAX_STARTS) { set_error("%s: n=%d start states outside 1..%d", who, starts->n, FRIRL_HIP_REDUCE_MAX_STARTS); return FRIRL_HIP_EINVAL; }
-    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
-    if (depth < 0 || depth > frirl::RW_MAX_DEPTH) { set_error("%s: depth %d outside 0..%d", who, depth, frirl::RW_MAX_DEPTH); return FRIRL_HIP_EINVAL; }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_demo_kind(t, agent, who))) return rc;
-    if ((rc = check_grid_len(t, agent, who))) return rc;
-    const int n = starts->n, drop_bad = starts->drop_bad_starts != 0;
-    if (depth == 0) depth = frirl_hip_reduce_batch_starts_depth(b->E, agent->A, n);
-    const size_t E = (size_t)b->E, M = (size_t)b->maxR;
-    const int nodes = frirl::rw_nodes(depth);
-    if (E * n * nodes > (size_t)INT32_MAX / 2) { set_error("%s: E=%zu x n=%d x %d nodes: too many rows per round", who, E, n, nodes); return FRIRL_HIP_EINVAL; }
-    const size_t need = reduce_starts_layout(nullptr, E, M, depth, E * n * nodes, n, nullptr);
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need) {
-        set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (frirl_hip_reduce_batch_starts_workspace_bytes)", who, workspace, workspace_bytes, need);
-        return FRIRL_HIP_EINVAL;
+    if ((rc = check_demo_kind(t, agent, who)) || (rc = check_grid_len(t, agent, who))) return rc;
+    ReduceRun run;
+    if ((rc = run.init(who, t, b, agent, rant, starts, strategy, reward_tolerance, depth, false, stream)) ||
+        (rc = run.check_workspace(who, workspace, workspace_bytes)) || (rc = check_device()) ||
+        (rc = run.start(who, workspace, active, starts->start_count)))
+        return rc;
+    // round 0 = the baseline replays of every active agent; then rounds until no agent has a candidate left
+    while (run.nlive() > 0) {
+        if (t->nant == 3) launch_rows<3>(run, starts->start_states);
+        else launch_rows<5>(run, starts->start_states);
+        if ((rc = run.close(who))) return rc;
     }
-    if ((rc = check_device())) return rc;
-    hipStream_t s = as_stream(stream);
-#define RS_TRY(expr)                                                                                               \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { set_error("%s: %s: %s", who, #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
-    } while (0)
-    ReduceStartsWs ws;
-    reduce_starts_layout(static_cast<char *>(workspace), E, M, depth, E * n * nodes, n, &ws);
-    frirl_hip_agent greedy = *agent;
-    greedy.no_random = 1;                                             // the replays are greedy, as frirl_hip_reduce_batch forces it
-    int32_t hdr[4] = {0, 0, 0, 0};
-    RS_TRY(hipMemsetAsync(ws.b.hdr, 0, sizeof hdr, s));
-    hipLaunchKernelGGL(frirl::reduce_batch_order_kernel, dim3((unsigned)E), dim3(256), 0, s, b->rb, b->nrules, t->nant, b->maxR, active, strategy,
-                       greedy.max_steps, ws.b);
-    hipLaunchKernelGGL(frirl::reduce_starts_init_kernel, dim3((unsigned)E), dim3(256), 0, s, starts->start_count, ws);
-    RS_TRY(hipMemcpyAsync(hdr, ws.b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-    RS_TRY(hipStreamSynchronize(s));
-    if (hdr[2]) { set_error("%s: agent %d: nrules outside 1..maxR=%d", who, hdr[2] - 1, b->maxR); return FRIRL_HIP_EINVAL; }
-    // round 0 = the baseline replays of every active agent; then rounds until no agent has a candidate left.  Per round the host reads
-    // the 16-byte header: the next round's live count.
-    for (int round = 0;; round++) {
-        const int cur = round & 1, first = round == 0;
-        const int nlive = hdr[cur];
-        if (nlive == 0) break;
-        // round 0 appends to list 1 without an open kernel before it: the header was zeroed above; later rounds zero the other count here
-        if (!first) hipLaunchKernelGGL(frirl::reduce_batch_open_kernel, dim3(nlive), dim3(256), 0, s, b->nrules, b->maxR, depth, cur, ws.b);
-        const int rows = first ? n : nodes * n;
-        if (t->nant == 3) launch_rows_n<3>(t, b, &greedy, starts->start_states, cur, nlive, rows, first, ws, s);
-        else launch_rows_n<5>(t, b, &greedy, starts->start_states, cur, nlive, rows, first, ws, s);
-        if (t->nant == 3)
-            hipLaunchKernelGGL(frirl::reduce_starts_close_kernel<3>, dim3(nlive), dim3(256), 0, s, b->rb, b->nrules, b->uidx, rant, b->maxR, cur, first,
-                               greedy.max_steps, agent->reward_good_above, reward_tolerance, drop_bad, ws);
-        else
-            hipLaunchKernelGGL(frirl::reduce_starts_close_kernel<5>, dim3(nlive), dim3(256), 0, s, b->rb, b->nrules, b->uidx, rant, b->maxR, cur, first,
-                               greedy.max_steps, agent->reward_good_above, reward_tolerance, drop_bad, ws);
-        RS_TRY(hipMemcpyAsync(hdr, ws.b.hdr, sizeof hdr, hipMemcpyDeviceToHost, s));
-        RS_TRY(hipStreamSynchronize(s));
-    }
-    hipLaunchKernelGGL(frirl::reduce_batch_result_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, b->nrules, (int)E, ws.b);
-    hipLaunchKernelGGL(frirl::reduce_starts_result_kernel, dim3((unsigned)((E * n + 255) / 256)), dim3(256), 0, s, (int)(E * n), ws);
-    RS_TRY(hipMemcpyAsync(results, ws.b.res, sizeof(frirl_hip_reduce_result) * E, hipMemcpyDeviceToHost, s));
-    if (per_start) RS_TRY(hipMemcpyAsync(per_start, ws.res, sizeof(frirl_hip_reduce_start_result) * E * n, hipMemcpyDeviceToHost, s));
-    if (kept) RS_TRY(hipMemcpyAsync(kept, ws.b.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, s));
-    RS_TRY(hipStreamSynchronize(s));
-#undef RS_TRY
-    return check_launch(who);
+    return run.results(who, kept, results, per_start);
 }

@@ -1,30 +1,14 @@
-// reduce_starts_kernels.h -- what the reductions against a set of start states share: the per-start arrays of a run
-// (ReduceStartsWs), the init, close-round and result kernels and the workspace layout.  frirl_hip_reduce_batch_starts
-// (reduce_starts.hip) rolls the replays out inside its own kernel over a compact row space (row = node * K_e + ki); the
-// caller-stepped frirl_hip_batch_reducer_create_starts (policy_batch.hip) steps them in the caller's environment over the fixed row
-// space (row = node * n + k).  Moved out of reduce_starts.hip; the only change to the close kernel is the STEPPED flag, which selects
-// the row layout its walk reads.
+// reduce_starts_kernels.h -- the protocol kernels of a reduction against a set of start states, next to those of
+// reduce_batch_kernels.h: init, close-round and result kernel over the per-start arrays (ReduceStartsWs, reduce_ws.h).  Included by
+// reduce_run.hip only, like reduce_batch_kernels.h.  The close kernel's STEPPED flag selects the row layout its walk reads: compact
+// (row = node * K_e + ki, the in-kernel roll-outs of reduce_starts.hip) or fixed (row = node * n + k, the caller-stepped reducer).
 #pragma once
 #include "reduce_batch_kernels.h"
 
 namespace frirl {
 
-// the arrays of one call: those of the batched reduction (b.steps / b.reward hold nodes * n entries per agent) and the per-start ones
-struct ReduceStartsWs {
-    ReduceBatchWs b;
-    int32_t *cnt;                 // [E] participating starts: start_count[e] clamped to 1..n
-    int32_t *K;                   // [E] used starts (after the baseline)
-    int32_t *capmax;              // [E] largest cap of a used start: the roll-out kernel's loop bound
-    int32_t *used;                // [E][n] the used starts in ascending order (first K[e] entries)
-    int32_t *steps_inc;           // [E][n] per start: steps of the baseline replay, -1 = takes no part
-    int32_t *cap;                 // [E][n] per start: min(max_steps, steps_inc + 1)
-    double *prev;                 // [E][n] per start: prev_reward
-    frirl_hip_reduce_start_result *res;      // [E][n]
-    int n;                        // starts per agent
-};
-
 // Init kernel: one workgroup per agent; the per-start state of an agent that never takes part stays as written here.
-static __global__ __launch_bounds__(256) void reduce_starts_init_kernel(const int32_t *__restrict__ start_count, ReduceStartsWs ws)
+__global__ __launch_bounds__(256) void reduce_starts_init_kernel(const int32_t *__restrict__ start_count, ReduceStartsWs ws)
 {
     const int e = blockIdx.x, tid = threadIdx.x, n = ws.n;
     if (tid == 0) {
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256) void reduce_starts_close_kernel(double *__rest
 }
 
 // prev_reward of every start that took a baseline replay, after the last accepted removal
-static __global__ void reduce_starts_result_kernel(int total, ReduceStartsWs ws)
+__global__ void reduce_starts_result_kernel(int total, ReduceStartsWs ws)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
@@ -114,22 +98,3 @@ static __global__ void reduce_starts_result_kernel(int total, ReduceStartsWs ws)
 }
 
 }  // namespace frirl
-
-using frirl::ReduceStartsWs;
-
-// carves the arrays of a call out of `base` (NULL: sizes only); `rows` = entries of steps / reward
-static size_t reduce_starts_layout(char *base, size_t E, size_t maxR, int depth, size_t rows, int n, ReduceStartsWs *ws)
-{
-    ReduceStartsWs w;
-    size_t off = reduce_batch_layout(base, E, maxR, depth, rows, &w.b);
-    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += up16(bytes); return p; };
-    w.n = n;
-    int32_t **per_agent[] = {&w.cnt, &w.K, &w.capmax};
-    for (int32_t **p : per_agent) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E));
-    int32_t **per_start[] = {&w.used, &w.steps_inc, &w.cap};
-    for (int32_t **p : per_start) *p = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * E * n));
-    w.prev = reinterpret_cast<double *>(take(sizeof(double) * E * n));
-    w.res = reinterpret_cast<frirl_hip_reduce_start_result *>(take(sizeof(frirl_hip_reduce_start_result) * E * n));
-    if (ws) *ws = w;
-    return off;
-}

@@ -230,12 +230,6 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
     if (depth < 1 || depth > frirl::RW_MAX_DEPTH) { set_error("frirl_hip_reduce_shared: depth %d outside 1..%d", depth, frirl::RW_MAX_DEPTH); return FRIRL_HIP_EINVAL; }
     if ((rc = check_demo_kind(t, agent, "frirl_hip_reduce_shared")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
-#define HIP_TRY(expr)                                                                                              \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) { set_error("frirl_hip_reduce_shared: %s: %s", #expr, hipGetErrorString(e_)); return FRIRL_HIP_ELAUNCH; } \
-    } while (0)
-
     // candidate order, mask tables, tree walk and compaction: reduce_plan.h (shared with the caller-stepped form, policy.hip)
     ReducePlan plan;
     if ((rc = plan.load("frirl_hip_reduce_shared", t, b, rant, strategy, depth, s))) return rc;
@@ -254,9 +248,9 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
     greedy.no_random = 1;                                             // the replays are greedy (reduction_state == 1 keeps epsilon at 0 in every demo)
     rc = frirl_hip_rollout_shared(t, b, &greedy, 1, &ro, stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    FRIRL_HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t), hipMemcpyDeviceToHost, s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
+    FRIRL_HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double), hipMemcpyDeviceToHost, s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
+    FRIRL_HIP_TRY(hipStreamSynchronize(s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
     plan.set_baseline(steps[0], reward[0]);
     frirl_hip_agent capped = greedy;
     capped.max_steps = plan.capped_steps(capped.max_steps);
@@ -269,12 +263,11 @@ extern "C" int frirl_hip_reduce_shared(const frirl_hip_tables *t, const frirl_hi
         if (lanes == 0) break;
         rc = frirl_hip_rollout_shared(t, b, &capped, lanes, &ro, stream);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t) * lanes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double) * lanes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        FRIRL_HIP_TRY(hipMemcpyAsync(steps.data(), d_steps.p, sizeof(int32_t) * lanes, hipMemcpyDeviceToHost, s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
+        FRIRL_HIP_TRY(hipMemcpyAsync(reward.data(), d_reward.p, sizeof(double) * lanes, hipMemcpyDeviceToHost, s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
+        FRIRL_HIP_TRY(hipStreamSynchronize(s), "frirl_hip_reduce_shared", return FRIRL_HIP_ELAUNCH);
         if ((rc = plan.close_round(steps.data(), reward.data(), agent->reward_good_above, reward_tolerance, s))) return rc;
     }
-#undef HIP_TRY
     plan.result(kept, result);
     return FRIRL_HIP_OK;
 }
