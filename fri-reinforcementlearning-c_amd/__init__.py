@@ -126,6 +126,23 @@ class ReduceStartResult(C.Structure):
 REDUCE_MAX_STARTS = 256
 
 
+class MapPoints(C.Structure):
+    """struct frirl_hip_map_points (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("points", C.c_void_p), ("point_count", C.c_void_p), ("active", C.c_void_p)]
+
+
+class ReduceMapResult(C.Structure):
+    """struct frirl_hip_reduce_map_result (include/frirl_hip.h)."""
+    _fields_ = [("rules_before", C.c_int32), ("rules_after", C.c_int32), ("points", C.c_int32), ("tries", C.c_int32)]
+
+
+class LogPointsDesc(C.Structure):
+    """struct frirl_hip_log_points_desc (include/frirl_hip.h)."""
+    _fields_ = [("E", C.c_int32), ("n_logs", C.c_int32), ("T", C.c_int32), ("ns", C.c_int32), ("cap", C.c_int32), ("only_successful", C.c_int32),
+                ("obs", C.c_void_p), ("q_obs", C.c_void_p), ("success", C.c_void_p), ("start", C.c_void_p), ("length", C.c_void_p),
+                ("points", C.c_void_p), ("point_count", C.c_void_p), ("overflow", C.c_void_p)]
+
+
 class AgentIO(C.Structure):
     """struct frirl_hip_agent_io (include/frirl_hip.h)."""
     _fields_ = [("obs", C.c_void_p), ("q_obs", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p), ("reset", C.c_void_p),
@@ -217,6 +234,14 @@ SIGNATURES = {
                                                      C.POINTER(C.c_uint32)]),
     "frirl_hip_reduce_walk_starts_rows_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32),
                                                           _DP, C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
+    "frirl_hip_policy_map_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_policy_map": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(MapPoints), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_reduce_batch_map_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch_map": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(MapPoints), C.c_int,
+                                             C.POINTER(C.c_int32), C.POINTER(ReduceMapResult), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_log_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_log_points": (C.c_int, [C.POINTER(LogPointsDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_lanes_preferred": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_lanes_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_episode_run_lanes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32,
@@ -382,6 +407,16 @@ def _stream(stream=None):
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+def _scratch(nbytes, device, stream):
+    """A workspace for ONE asynchronous call that is dropped when the wrapper returns: allocated on the current stream and, where the
+    call runs on another one, recorded on it, so that the caching allocator does not hand the block out again while the kernel uses it."""
+    import torch
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=device)
+    if stream is not None:
+        ws.record_stream(stream)
+    return ws
 
 
 class Problem:
@@ -723,6 +758,52 @@ class Problem:
         return ([kept[e, : res[e].rules_after].copy() for e in range(self.E)], list(res),
                 [[per[e * n + k] for k in range(n)] for e in range(self.E)])
 
+    def _map_points(self, points, point_count, active):
+        import torch
+        assert points.is_cuda and points.dtype == torch.float64 and points.dim() == 3 and points.is_contiguous()
+        assert points.shape[0] == self.E and points.shape[2] == self.nant - 1 and points.shape[1] >= 1
+        assert point_count is None or (point_count.shape == (self.E,) and point_count.dtype == torch.int32 and point_count.is_contiguous())
+        assert active is None or (active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous())
+        return MapPoints(int(points.shape[1]), 0, _ptr(points), _ptr(point_count), _ptr(active))
+
+    def policy_map(self, agent, points, point_count=None, active=None, actconc=True, stream=None, out=None):
+        """frirl_hip_policy_map: the greedy action of EVERY rule base of this problem at its own points, points [E, n, nant-1] f64 used as
+        given; point_count [E] int32 (None = n); active [E] uint8 / bool.  Returns (best [E, n] int32, actconc [E, n, A] f64 or None):
+        best is -1 and actconc untouched for a point that does not exist, an inactive agent or nrules outside 1..maxR.  out: the caller's
+        (best, actconc) to write into.  Does not synchronise."""
+        import torch
+        mp = self._map_points(points, point_count, active)
+        n, A = mp.n, agent.desc.A
+        if out is None:
+            out = (torch.empty((self.E, n), dtype=torch.int32, device=points.device),
+                   torch.empty((self.E, n, A), dtype=torch.float64, device=points.device) if actconc else None)
+        best, conc = out
+        assert best.shape == (self.E, n) and best.dtype == torch.int32 and best.is_contiguous()
+        assert conc is None or (conc.shape == (self.E, n, A) and conc.dtype == torch.float64 and conc.is_contiguous())
+        nbytes = lib().frirl_hip_policy_map_workspace_bytes(self.nant, self.E, n)
+        ws = _scratch(nbytes, points.device, stream)
+        check(lib().frirl_hip_policy_map(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(mp), _ptr(best), _ptr(conc), _ptr(ws),
+                                         nbytes, _stream(stream)), "frirl_hip_policy_map")
+        return best, conc
+
+    def reduce_batch_map(self, agent, points, point_count=None, active=None, strategy=1, rant=None, stream=None):
+        """frirl_hip_reduce_batch_map: try-remove of EVERY rule base of this problem, a removal kept iff the greedy action stays the same at
+        every one of the agent's points (points / point_count / active as policy_map); rant: [E, nant, maxR] compacted alongside.
+        Compacts the rule bases in place.  Returns (list of ReduceMapResult, list of kept original indices)."""
+        import numpy as np
+        import torch
+        mp = self._map_points(points, point_count, active)
+        if rant is not None:
+            assert rant.shape == (self.E, self.nant, self.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
+        nbytes = lib().frirl_hip_reduce_batch_map_workspace_bytes(self.nant, self.E, self.maxR, mp.n)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=points.device)
+        kept = np.zeros((self.E, self.maxR), dtype=np.int32)
+        res = (ReduceMapResult * self.E)()
+        check(lib().frirl_hip_reduce_batch_map(C.byref(self.tables), C.byref(self.bases), C.byref(agent.desc), _ptr(rant), C.byref(mp), strategy,
+                                               kept.ctypes.data_as(C.POINTER(C.c_int32)), res, _ptr(ws), nbytes, _stream(stream)),
+              "frirl_hip_reduce_batch_map")
+        return list(res), [kept[e, : res[e].rules_after].copy() for e in range(self.E)]
+
     def policy_begin(self, agent, rows, obs, reset=None, stream=None):
         """frirl_hip_policy_begin: rows (PolicyRows) selected by `reset` ([Q] uint8 / bool, None = all) start a greedy episode on this ONE
         rule base from the caller's observations obs [Q, nant-1].  Returns (action values [Q], action indices [Q]); rows that were not
@@ -992,6 +1073,12 @@ class RolloutLog:
                    mk((Q, T), torch.int32), mk((Q, T), torch.uint8), mk((Q,), torch.int32), mk((Q, K), torch.int32), mk((Q, K), torch.float64),
                    mk((Q, K), torch.int32))
 
+    def points(self, cap, only_successful=False, stream=None):
+        """log_points over these logs (needs the n of the rollout_record call that wrote them): (points [E, cap, ns], point_count [E],
+        overflow [E]), ready for Problem.policy_map / reduce_batch_map."""
+        assert self.n is not None and self.Q % self.n == 0
+        return log_points(self.obs, self.q_obs, self.success, self.start, self.length, self.Q // self.n, cap, only_successful, stream)
+
     def demonstration(self, log=None, E=None):
         """A Demonstration over the same memory, no copy.  log=None: one log per agent (needs n == 1).  log=q: that one log for E
         students, its length expanded to [E] (a device op; nothing is read back)."""
@@ -1002,6 +1089,38 @@ class RolloutLog:
         s = slice(log, log + 1)
         return Demonstration(self.obs[s], self.action[s], self.reward[s], self.success[s], q_obs=self.q_obs[s], start=self.start[s],
                              length=self.length[s].repeat(E))
+
+
+def log_points(obs, q_obs, success, start, length, E, cap, only_successful=False, stream=None):
+    """frirl_hip_log_points: per agent the de-duplicated points of its logs (obs / q_obs [E * n_logs, T, ns] f64, success [E * n_logs, T]
+    int32, start [E * n_logs, T] uint8, length [E * n_logs] int32; logs e * n_logs + j belong to agent e): a start record's obs, every
+    other record's q_obs, first occurrence first.  Returns (points [E, cap, ns] f64 -- rows at and beyond point_count[e] are zero --,
+    point_count [E] int32, overflow [E] int32).  Does not synchronise."""
+    import torch
+    Q, T, ns = obs.shape
+    assert Q % E == 0 and Q >= E >= 1
+    for x, shape, dt in ((obs, (Q, T, ns), torch.float64), (q_obs, (Q, T, ns), torch.float64), (success, (Q, T), torch.int32),
+                         (start, (Q, T), torch.uint8), (length, (Q,), torch.int32)):
+        assert x.is_cuda and x.shape == shape and x.dtype == dt and x.is_contiguous()
+    dev_ = obs.device
+    points = torch.zeros((E, cap, ns), dtype=torch.float64, device=dev_)
+    count = torch.empty((E,), dtype=torch.int32, device=dev_)
+    overflow = torch.empty((E,), dtype=torch.int32, device=dev_)
+    lp = LogPointsDesc(E, Q // E, T, ns, cap, 1 if only_successful else 0, _ptr(obs), _ptr(q_obs), _ptr(success), _ptr(start), _ptr(length),
+                       _ptr(points), _ptr(count), _ptr(overflow))
+    nbytes = lib().frirl_hip_log_points_workspace_bytes(E, Q // E, T)
+    ws = _scratch(nbytes, dev_, stream)
+    check(lib().frirl_hip_log_points(C.byref(lp), _ptr(ws), nbytes, _stream(stream)), "frirl_hip_log_points")
+    return points, count, overflow
+
+
+def grid_points(desc, device=None):
+    """The Cartesian product of the state grids of a problem description (demo_describe / describe): [cells, nant-1] float64, the
+    last state varying fastest (torch.cartesian_prod order).  With Problem.policy_map before and after a reduction, "how many
+    cells of the grid changed their greedy action" is (best_before != best_after).sum()."""
+    import torch
+    axes = [torch.as_tensor(list(g), dtype=torch.float64, device=device) for g in desc["grids"][:-1]]
+    return torch.cartesian_prod(*axes).reshape(-1, len(axes)).contiguous()
 
 
 def demo_batch_object(env, E, maxR, start_states=None):

@@ -199,6 +199,7 @@ struct Options {
     int rollout_batch_resident;       // batched roll-out: -1 = automatic, 0 = never the LDS-resident form, 1 = wherever it fits (FRIRL_HIP_ROLLOUT_BATCH_RESIDENT)
     int rollout_batch_resident_rules; // batched roll-out: rule count up to which an agent takes the resident form, 0 = the shape's capacity (FRIRL_HIP_ROLLOUT_BATCH_RESIDENT_RULES)
     int rollout_batch_slices;         // batched roll-out, resident form: lanes per row 1 / 4 / 16 / 64, 0 = by shape (FRIRL_HIP_ROLLOUT_BATCH_SLICES)
+    int reduce_map_resident;          // policy map / map-validated reduction: -1 / 1 = rules in LDS wherever they fit, 0 = never (FRIRL_HIP_REDUCE_MAP_RESIDENT)
     int rollout_record_slices;        // recorded roll-out: rule slices 1 / 4 / 8 (16 for up to 4 actions), 0 = by shape (FRIRL_HIP_ROLLOUT_RECORD_SLICES)
     int policy_group;     // caller-stepped shared-base step: lanes per row 1 / 4 / 8, 0 = by shape  (FRIRL_HIP_POLICY_GROUP)
     int policy_slices;    // caller-stepped shared-base step: rule slices 1 / 4 / 8, 0 = by shape    (FRIRL_HIP_POLICY_SLICES)

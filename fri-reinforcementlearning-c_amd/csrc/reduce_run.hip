@@ -4,6 +4,7 @@
 // the replays between two calls of close().  Per round the host reads one 16-byte header: the next round's live count.
 #include "reduce_run.h"
 #include "reduce_starts_kernels.h"
+#include "reduce_map_kernels.h"
 
 int ReduceRun::init(const char *who, const frirl_hip_tables *t_, const frirl_hip_rulebases *b_, const frirl_hip_agent *agent_, double *rant_,
                     const frirl_hip_reduce_starts *starts, int strategy_, double reward_tolerance_, int depth_, bool stepped_, void *stream)
@@ -108,4 +109,36 @@ int ReduceRun::results(const char *who, int32_t *kept, frirl_hip_reduce_result *
     if (kept) FRIRL_HIP_TRY(hipMemcpyAsync(kept, ws.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
     FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
     return check_launch(who);
+}
+
+// ---- the map-validated reduction (frirl_hip_reduce_batch_map, policy_map.hip): its launches of the order kernel and of the kernel that
+// reuses the compaction sit in this translation unit (reduce_map_ws.h) ----
+int reduce_map_launch_order(const char *who, const frirl_hip_tables &t, const frirl_hip_rulebases &b, const uint8_t *active, int strategy,
+                            const ReduceMapWs &ws, hipStream_t s)
+{
+    FRIRL_HIP_TRY(hipMemsetAsync(ws.b.hdr, 0, 4 * sizeof(int32_t), s), who, return FRIRL_HIP_ELAUNCH);
+    hipLaunchKernelGGL(frirl::reduce_batch_order_kernel, dim3((unsigned)b.E), dim3(256), 0, s, b.rb, b.nrules, t.nant, b.maxR, active, strategy, 0, ws.b);
+    return check_launch(who);
+}
+
+template <int N>
+static void launch_reduce_map(const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident, const ReduceMapWs &ws, hipStream_t s)
+{
+    const int rcap = resident ? frirl::map_resident_rules(N, b.maxR) : 0;
+    const size_t lds = (size_t)rcap * frirl::map_rule_bytes(N);
+    // one action per lane while every (point, action) pair of an agent fits one pass of its workgroup, else blocks of 4
+    if ((long)m.n * m.A <= frirl::PM_BLOCK)
+        hipLaunchKernelGGL((frirl::reduce_map_kernel<N, 1>), dim3((unsigned)b.E), dim3(frirl::PM_BLOCK), lds, s, b.rb, b.nrules, b.uidx, rant, b.maxR, m, rcap, ws);
+    else
+        hipLaunchKernelGGL((frirl::reduce_map_kernel<N, 4>), dim3((unsigned)b.E), dim3(frirl::PM_BLOCK), lds, s, b.rb, b.nrules, b.uidx, rant, b.maxR, m, rcap, ws);
+}
+
+void reduce_map_launch_run(const frirl_hip_tables &t, const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident,
+                           const ReduceMapWs &ws, hipStream_t s)
+{
+    switch (t.nant) {
+#define M(N) case N: launch_reduce_map<N>(b, rant, m, resident, ws, s); break;
+        FRIRL_POLICY_NANT_CASES(M)
+#undef M
+    }
 }

@@ -100,7 +100,7 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
  * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
- * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "rollout_batch_resident", "rollout_batch_resident_rules", "rollout_batch_slices", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "rollout_batch_resident", "rollout_batch_resident_rules", "rollout_batch_slices", "reduce_map_resident", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -476,6 +476,98 @@ int frirl_hip_reduce_walk_starts_check(int d, int K, const int32_t *steps, const
  * [2^d - 1][n] (columns of starts that are not used are never read), steps_inc HOST [n], prev HOST [n] in / out.  Needs no device. */
 int frirl_hip_reduce_walk_starts_rows_check(int d, int K, int n, const int32_t *used, const int32_t *steps, const double *reward,
                                             const int32_t *steps_inc, double *prev, double good_above, double tol, uint32_t *bits_out);
+
+/* ---- the policy map: what a rule base does at a set of points, and a reduction that preserves it ----------------
+ * frirl_hip_policy_map: the greedy action of EVERY agent's own rule base (b->E >= 1) at n points per agent.  Per point exactly what
+ * frirl_hip_get_best_action computes on agent e's slab alone for states = the point: the point is snapped to the universes as `states`
+ * are -- nothing else is quantised -- and Q of an action is the consequent of the first exact-hit rule, else the Shepard interpolation.
+ *   best     [dev] [E][n] int32: index of the first maximum; -1 for a point that does not exist (j >= point_count[e]), for an inactive
+ *            agent and for nrules[e] outside 1..maxR
+ *   actconc  [dev] [E][n][A] the conclusions, or NULL; left untouched where best reads -1
+ * Of `agent` only A (1..32), action_ve and p are read (p <= 0 = nant; every power runs the run-time-power form of the Shepard weight, so
+ * the bits do not depend on whether p is the default): env_kind is not read, the caller's environments (nant 2..8) are served.
+ * Summation order: every conclusion is accumulated by ONE lane over the rules in ascending index order (the order of
+ * five_hip_vag_concl_shared), so the bits of a conclusion depend on the rule base, the point and the action only -- not on n, E, the
+ * other points or the launch shape.  Lanes are spread over (point, block of actions); a rule base that fits 56 KiB of LDS is staged there
+ * (option "reduce_map_resident": -1 = wherever it fits, 0 = never, 1 = wherever it fits -- today the same as -1; read from global memory
+ * otherwise, the same bits).  The rule bases are read-only.  Asynchronous on `stream`; nothing is read back or allocated.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL t / b / agent / agent->action_ve / pts / pts->points / best, n < 1, E * n >
+ * INT32_MAX, nant outside 2..8, A outside 1..32, a workspace that is NULL, not 16-byte aligned or smaller than
+ * frirl_hip_policy_map_workspace_bytes(nant, E, n) (it holds the snapped points).
+ * frirl_hip_policy_map_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_map_points {
+    int32_t n;                    /* points per agent */
+    int32_t reserved;
+    const double  *points;        /* [dev] [E][n][nant-1], used as given */
+    const int32_t *point_count;   /* [dev] [E] points of agent e that exist (clamped to 0..n), or NULL = n */
+    const uint8_t *active;        /* [dev] [E] 0 = skip this agent, or NULL = all */
+} frirl_hip_map_points;
+size_t frirl_hip_policy_map_workspace_bytes(int32_t nant, int32_t E, int32_t n);
+int frirl_hip_policy_map(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_map_points *pts,
+                         int32_t *best, double *actconc, void *workspace, size_t workspace_bytes, void *stream);
+
+/* frirl_hip_reduce_batch_map: try-remove of every agent's rule base, a removal validated on the policy map instead of by a replay.
+ * Per agent e, independent of every other agent:
+ *   order      the candidate order of frirl_hip_reduce_batch: stable by |Q|, strategy 1 ascending, 2 descending
+ *   baseline   best0 = the map (frirl_hip_policy_map's best) of the un-reduced rule base at the agent's existing points
+ *   trial      for each candidate in order: it is removed iff the map over the rules still present minus the candidate equals best0 at
+ *              EVERY existing point; the last remaining rule is never tried.  A trial is evaluated with frirl_hip_policy_map's arithmetic
+ *              and order on the rule base with the absent rules SKIPPED, which is bit-identical to frirl_hip_policy_map on the
+ *              compacted rule base: the additions that remain are the same, in the same order
+ *   compaction as frirl_hip_reduce_batch: rb columns, rant, uidx if present, nrules[e]; the vacated tail zeroed
+ * By construction frirl_hip_policy_map of the reduced rule base equals best0 at every one of the agent's points, so every greedy
+ * trajectory whose observations are among them is reproduced exactly.  No environment is stepped: env_kind is not read (nant 2..8).
+ * An agent that is inactive, has point_count[e] == 0 or nrules[e] == 1 is left untouched (rules_after == rules_before, tries 0).
+ * nrules[e] outside 1..maxR for an active agent: FRIRL_HIP_EINVAL, nothing reduced.
+ * One launch reduces every agent (one workgroup each, the loop over its candidates inside the kernel, its rules and their "removed"
+ * bytes in LDS while they fit 56 KiB, else read from global memory; option "reduce_map_resident" as above; both forms make the same
+ * decisions).  The call synchronises `stream` twice: after the order kernel (the rule-count check) and for the results.
+ *   kept       [host] [E][maxR] original index of each surviving rule of agent e (first results[e].rules_after entries), or NULL
+ *   results    [host] [E]
+ *   workspace  [dev] 16-byte aligned, >= frirl_hip_reduce_batch_map_workspace_bytes(nant, E, maxR, n) bytes; no other allocation
+ * FRIRL_HIP_EINVAL, before the device is looked for: the cases of frirl_hip_policy_map (best is not an argument), NULL results, a
+ * strategy outside 1..2.
+ * frirl_hip_reduce_batch_map_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_reduce_map_result {   /* 16 bytes */
+    int32_t rules_before, rules_after;
+    int32_t points;               /* existing points the removals were validated at (0 for an inactive agent) */
+    int32_t tries;                /* candidates tried */
+} frirl_hip_reduce_map_result;
+size_t frirl_hip_reduce_batch_map_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t n);
+int frirl_hip_reduce_batch_map(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                               const frirl_hip_map_points *pts, int strategy, int32_t *kept, frirl_hip_reduce_map_result *results,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* frirl_hip_log_points: every agent's de-duplicated list of the points its recorded roll-outs visited, from logs in the layout of
+ * frirl_hip_rollout_log / frirl_hip_demonstration (agent_stride = T); logs q = e * n_logs + j belong to agent e.
+ * A start record (start != 0) contributes obs, the un-quantised start; every other record contributes q_obs: the observations the
+ * greedy policy was asked at.  Only records below length[q] (clamped to 0..T) count.  Points are compared bit-wise; the output order
+ * is first occurrence over (log j ascending, record ascending).  only_successful != 0: an episode (a start record up to the record
+ * before the next start record or the end of the log) whose last record has success != 1 contributes nothing -- the map counterpart
+ * of drop_bad_starts.
+ *   points       [dev] [E][cap][ns] the first min(distinct, cap) points of agent e; the rows behind them are left untouched
+ *   point_count  [dev] [E] rows written;  overflow [dev] [E] 1 = more than cap distinct points exist (the first cap are kept), else 0
+ * Cost: one workgroup per agent compares every contributing record with the agent's list so far, 256 records at a time:
+ * O(records x distinct points / 256) steps per agent, serial within the workgroup -- meant for caps of hundreds to a few thousand
+ * points; with tens of thousands of distinct points per agent de-duplicate elsewhere.
+ * Asynchronous on `stream`; nothing is read back or allocated.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL lp / obs / q_obs / start / length / points / point_count / overflow, NULL
+ * success with only_successful, E, n_logs, T or cap < 1, ns outside 1..7, E * n_logs * T > INT32_MAX, E * cap > INT32_MAX, a workspace that is NULL, not 16-byte aligned or smaller than
+ * frirl_hip_log_points_workspace_bytes(E, n_logs, T) (one byte per record: whether it contributes).
+ * frirl_hip_log_points_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_log_points_desc {
+    int32_t E, n_logs, T, ns;     /* agents, logs per agent, record capacity of every log, state dimensions (nant - 1) */
+    int32_t cap, only_successful;
+    const double  *obs, *q_obs;   /* [dev] [E*n_logs][T][ns] */
+    const int32_t *success;       /* [dev] [E*n_logs][T], or NULL without only_successful */
+    const uint8_t *start;         /* [dev] [E*n_logs][T] */
+    const int32_t *length;        /* [dev] [E*n_logs] records written */
+    double  *points;              /* [dev] [E][cap][ns] */
+    int32_t *point_count;         /* [dev] [E] */
+    int32_t *overflow;            /* [dev] [E] */
+} frirl_hip_log_points_desc;
+size_t frirl_hip_log_points_workspace_bytes(int32_t E, int32_t n_logs, int32_t T);
+int frirl_hip_log_points(const frirl_hip_log_points_desc *lp, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Per-environment episode state (reference: fields of frirl_desc + frirl_reward_desc that
  * frirl_episode() carries from step to step, src/frirl/frirl_episode.c:28-194). */
