@@ -143,6 +143,22 @@ class LogPointsDesc(C.Structure):
                 ("points", C.c_void_p), ("point_count", C.c_void_p), ("overflow", C.c_void_p)]
 
 
+class RolloutPointsDesc(C.Structure):
+    """struct frirl_hip_rollout_points_desc (include/frirl_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("cap", C.c_int32), ("only_successful", C.c_int32), ("reserved", C.c_int32), ("start_states", C.c_void_p),
+                ("row_count", C.c_void_p), ("active", C.c_void_p), ("points", C.c_void_p), ("point_count", C.c_void_p), ("overflow", C.c_void_p),
+                ("steps", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p)]
+
+
+class ReduceMapTotals(C.Structure):
+    """struct frirl_hip_reduce_map_totals (include/frirl_hip.h)."""
+    _fields_ = [("agents_reduced", C.c_int32), ("agents_overflow", C.c_int32), ("agents_without_points", C.c_int32), ("reserved", C.c_int32),
+                ("rules_before", C.c_int64), ("rules_after", C.c_int64), ("points", C.c_int64)]
+
+
+POINTS_MAX_CAP = 512
+
+
 class AgentIO(C.Structure):
     """struct frirl_hip_agent_io (include/frirl_hip.h)."""
     _fields_ = [("obs", C.c_void_p), ("q_obs", C.c_void_p), ("reward", C.c_void_p), ("success", C.c_void_p), ("reset", C.c_void_p),
@@ -242,6 +258,9 @@ SIGNATURES = {
                                              C.POINTER(C.c_int32), C.POINTER(ReduceMapResult), C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_log_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_log_points": (C.c_int, [C.POINTER(LogPointsDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_rollout_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_rollout_points": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(RolloutPointsDesc), C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
     "frirl_hip_lanes_preferred": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_lanes_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_episode_run_lanes": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32,
@@ -321,6 +340,8 @@ SIGNATURES = {
     "frirl_hip_batch_reduce_all": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(ReduceResult), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_reduce_all_starts": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int32, _DP, C.c_int, C.POINTER(ReduceResult),
                                                     C.POINTER(ReduceStartResult), C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_reduce_all_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, _DP, C.c_int, C.c_int32, C.POINTER(ReduceMapResult),
+                                                 C.POINTER(ReduceMapTotals)]),
     "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_teach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(TeachResult)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -692,6 +713,45 @@ class Problem:
         check(lib().frirl_hip_rollout_record(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(lg), _stream(stream)),
               "frirl_hip_rollout_record")
         return log
+
+    def rollout_points(self, agent, n, cap=POINTS_MAX_CAP, only_successful=False, start_states=None, row_count=None, active=None, stream=None,
+                       out=None, rows_out=None):
+        """frirl_hip_rollout_points: n roll-outs (one episode each) on EVERY rule base of this problem, row q = e * n + j on the rule base
+        of agent e, keeping per agent the de-duplicated set of the points the policy was asked at -- the sets rollout_record(episodes=1,
+        T=max_steps + 1) followed by RolloutLog.points gives, without the logs.  start_states [E * n, nant-1] f64 (None =
+        agent.values_def); row_count [E] int32; active [E] uint8 / bool.  Returns (points [E, cap, ns] f64, point_count [E] int32,
+        overflow [E] int32, steps [E*n] i32, reward [E*n] f64, success [E*n] i32); the order of a list is unspecified.  out: the caller's
+        (points, point_count, overflow) to write into, else points comes zeroed; rows_out: the caller's (steps, reward, success).  Does
+        not synchronise."""
+        import torch
+        dev_ = self.rb.device
+        Q, ns = self.E * n, self.nant - 1
+        if out is None:
+            out = (torch.zeros((self.E, cap, ns), dtype=torch.float64, device=dev_), torch.empty((self.E,), dtype=torch.int32, device=dev_),
+                   torch.empty((self.E,), dtype=torch.int32, device=dev_))
+        if rows_out is None:
+            rows_out = (torch.empty((Q,), dtype=torch.int32, device=dev_), torch.empty((Q,), dtype=torch.float64, device=dev_),
+                        torch.empty((Q,), dtype=torch.int32, device=dev_))
+        points, count, overflow = out
+        steps, reward, success = rows_out
+        assert points.shape == (self.E, cap, ns) and points.dtype == torch.float64 and points.is_contiguous()
+        for x in (count, overflow):
+            assert x.shape == (self.E,) and x.dtype == torch.int32 and x.is_contiguous()
+        rp = RolloutPointsDesc()
+        rp.n, rp.cap, rp.only_successful = n, cap, 1 if only_successful else 0
+        if start_states is not None:
+            assert start_states.shape == (Q, ns) and start_states.dtype == torch.float64 and start_states.is_contiguous()
+            rp.start_states = _ptr(start_states)
+        assert row_count is None or (row_count.shape == (self.E,) and row_count.dtype == torch.int32 and row_count.is_contiguous())
+        assert active is None or (active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous())
+        rp.row_count, rp.active = _ptr(row_count), _ptr(active)
+        rp.points, rp.point_count, rp.overflow = _ptr(points), _ptr(count), _ptr(overflow)
+        rp.steps, rp.reward, rp.success = _ptr(steps), _ptr(reward), _ptr(success)
+        nbytes = lib().frirl_hip_rollout_points_workspace_bytes(self.nant, self.E, self.maxR, n, cap, agent.desc.A)
+        ws = _scratch(nbytes, dev_, stream)
+        check(lib().frirl_hip_rollout_points(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(rp), _ptr(ws), nbytes,
+                                             _stream(stream)), "frirl_hip_rollout_points")
+        return points, count, overflow, steps, reward, success
 
     def reduce_shared(self, agent, strategy, reward_tolerance=0.0, depth=0, rant=None, stream=None):
         """frirl_hip_reduce_shared: the reference's rule-base reduction as speculative batched try-remove; compacts this
@@ -1170,6 +1230,24 @@ def batch_teach(batch, teacher, episodes, start_states=None, passes=1, students=
     check(lib().frirl_hip_batch_teach(batch, teacher, episodes, None if st is None else st.ctypes.data_as(_DP), passes,
                                       None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(res)), "frirl_hip_batch_teach")
     return res
+
+
+def batch_reduce_all_map(batch, strategy, n, start_states=None, only_successful=True, cap=0):
+    """frirl_hip_batch_reduce_all_map on a library-owned batch (the handle frirl_hip_batch_create returned): every agent's rule base
+    reduced with the removals validated on the policy map at the points its greedy policy visits from n start states (start_states:
+    host [E, n, nant-1] float64; None: n must be 1, every agent's own start).  cap: points per agent at most, 0 = 512; an agent with
+    more is left untouched.  Returns (list of ReduceMapResult, ReduceMapTotals)."""
+    import numpy as np
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    stats = BatchStats()
+    check(lib().frirl_hip_batch_stats(batch, C.byref(stats)), "frirl_hip_batch_stats")
+    E = int(stats.agents)
+    assert st is None or (st.ndim == 3 and st.shape[:2] == (E, n))
+    res = (ReduceMapResult * E)()
+    tot = ReduceMapTotals()
+    check(lib().frirl_hip_batch_reduce_all_map(batch, strategy, n, None if st is None else st.ctypes.data_as(_DP), 1 if only_successful else 0, cap, res,
+                                               C.byref(tot)), "frirl_hip_batch_reduce_all_map")
+    return list(res), tot
 
 
 def learn_demonstration(problem, agent, envs, demo, passes=1, stream=None):

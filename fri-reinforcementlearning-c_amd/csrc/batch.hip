@@ -393,6 +393,75 @@ extern "C" int frirl_hip_batch_reduce_all_starts(frirl_hip_batch *b, int strateg
     return FRIRL_HIP_OK;
 }
 
+extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, int32_t n, const double *start_states, int only_successful, int32_t cap,
+                                              frirl_hip_reduce_map_result *results, frirl_hip_reduce_map_totals *totals)
+{
+    static const char *who = "frirl_hip_batch_reduce_all_map";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (n < 1 || n > FRIRL_HIP_REDUCE_MAX_STARTS) { set_error("%s: n=%d start states outside 1..%d", who, n, FRIRL_HIP_REDUCE_MAX_STARTS); return FRIRL_HIP_EINVAL; }
+    if (!start_states && n != 1) { set_error("%s: NULL start states with n=%d (every agent's own start: n = 1)", who, n); return FRIRL_HIP_EINVAL; }
+    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
+    if (cap < 0 || cap > FRIRL_HIP_POINTS_MAX_CAP) { set_error("%s: cap=%d outside 0..%d", who, cap, FRIRL_HIP_POINTS_MAX_CAP); return FRIRL_HIP_EINVAL; }
+    if (cap == 0) cap = FRIRL_HIP_POINTS_MAX_CAP;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, Q = E * (size_t)n;
+    const size_t ws_points = frirl_hip_rollout_points_workspace_bytes(b->nant, b->E, b->maxR, n, cap, b->agent.A);
+    const size_t ws_map = frirl_hip_reduce_batch_map_workspace_bytes(b->nant, b->E, b->maxR, cap);
+    const size_t ws_bytes = ws_points > ws_map ? ws_points : ws_map;   // the two calls follow each other on one stream
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; };
+    const size_t o_ws = take(ws_bytes), o_points = take(sizeof(double) * E * (size_t)cap * ns), o_start = take(start_states ? sizeof(double) * Q * ns : 0);
+    const size_t o_count = take(sizeof(int32_t) * E), o_over = take(sizeof(int32_t) * E), o_active = take(E);
+    char *mem = nullptr;
+    BCHK(hipMalloc(reinterpret_cast<void **>(&mem), off), "map reduction buffers");
+    frirl_hip_rollout_points_desc rp = {};
+    rp.n = n; rp.cap = cap; rp.only_successful = only_successful ? 1 : 0;
+    rp.start_states = start_states ? reinterpret_cast<const double *>(mem + o_start) : b->d_start;   // n == 1: the batch's own [E][nant-1], or values_def
+    rp.points = reinterpret_cast<double *>(mem + o_points);
+    rp.point_count = reinterpret_cast<int32_t *>(mem + o_count);
+    rp.overflow = reinterpret_cast<int32_t *>(mem + o_over);
+    frirl_hip_agent greedy = b->agent;
+    greedy.no_random = 1;                                             // the points of the GREEDY policy (frirl_test_run: reduction_state == 1)
+    std::vector<int32_t> count(E), over(E);
+    std::vector<uint8_t> active(E);
+    std::vector<frirl_hip_reduce_map_result> res(E);
+    int rc = FRIRL_HIP_OK;
+    hipError_t he = hipSuccess;
+    if (start_states) he = hipMemcpyAsync(mem + o_start, start_states, sizeof(double) * Q * ns, hipMemcpyHostToDevice, b->s);
+    if (he == hipSuccess) rc = frirl_hip_rollout_points(&b->t, &b->rb, &greedy, &rp, mem + o_ws, ws_bytes, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(count.data(), rp.point_count, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(over.data(), rp.overflow, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `start_states` may be in use by the upload
+    else (void)hipStreamSynchronize(b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) {
+        for (size_t e = 0; e < E; e++) active[e] = over[e] ? 0 : 1;
+        he = hipMemcpy(mem + o_active, active.data(), E, hipMemcpyHostToDevice);
+    }
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) {
+        frirl_hip_map_points mp = {};
+        mp.n = cap;
+        mp.points = rp.points;
+        mp.point_count = rp.point_count;
+        mp.active = reinterpret_cast<const uint8_t *>(mem + o_active);
+        rc = frirl_hip_reduce_batch_map(&b->t, &b->rb, &greedy, b->d_rant, &mp, strategy, nullptr, res.data(), mem + o_ws, ws_bytes, b->s);
+    }
+    (void)hipFree(mem);
+    if (rc) return rc;
+    if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
+    frirl_hip_reduce_map_totals tot = {};
+    for (size_t e = 0; e < E; e++) {
+        tot.agents_reduced += res[e].rules_after < res[e].rules_before;
+        tot.agents_overflow += over[e] != 0;
+        tot.agents_without_points += !over[e] && count[e] == 0;
+        tot.rules_before += res[e].rules_before;
+        tot.rules_after += res[e].rules_after;
+        tot.points += over[e] ? 0 : count[e];
+    }
+    if (results) memcpy(results, res.data(), sizeof(frirl_hip_reduce_map_result) * E);
+    if (totals) *totals = tot;
+    return FRIRL_HIP_OK;
+}
+
 extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)
 {
     static const char *who = "frirl_hip_batch_evaluate";

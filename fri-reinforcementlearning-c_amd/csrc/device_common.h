@@ -201,6 +201,7 @@ struct Options {
     int rollout_batch_slices;         // batched roll-out, resident form: lanes per row 1 / 4 / 16 / 64, 0 = by shape (FRIRL_HIP_ROLLOUT_BATCH_SLICES)
     int reduce_map_resident;          // policy map / map-validated reduction: -1 / 1 = rules in LDS wherever they fit, 0 = never (FRIRL_HIP_REDUCE_MAP_RESIDENT)
     int rollout_record_slices;        // recorded roll-out: rule slices 1 / 4 / 8 (16 for up to 4 actions), 0 = by shape (FRIRL_HIP_ROLLOUT_RECORD_SLICES)
+    int rollout_points_slices;        // point-keeping roll-out: rule slices 1 / 4 / 8 (16 for up to 4 actions), 0 = by shape (FRIRL_HIP_ROLLOUT_POINTS_SLICES)
     int policy_group;     // caller-stepped shared-base step: lanes per row 1 / 4 / 8, 0 = by shape  (FRIRL_HIP_POLICY_GROUP)
     int policy_slices;    // caller-stepped shared-base step: rule slices 1 / 4 / 8, 0 = by shape    (FRIRL_HIP_POLICY_SLICES)
     int learn_slices;     // persistent learner: lanes per agent 4 / 16 / 64, 0 = by the number of live agents (FRIRL_HIP_LEARN_SLICES)

@@ -50,6 +50,7 @@ static const OptName k_opts[] = {
     {"rollout_batch_slices", "FRIRL_HIP_ROLLOUT_BATCH_SLICES", &Options::rollout_batch_slices, 0},
     {"reduce_map_resident", "FRIRL_HIP_REDUCE_MAP_RESIDENT", &Options::reduce_map_resident, -1},
     {"rollout_record_slices", "FRIRL_HIP_ROLLOUT_RECORD_SLICES", &Options::rollout_record_slices, 0},
+    {"rollout_points_slices", "FRIRL_HIP_ROLLOUT_POINTS_SLICES", &Options::rollout_points_slices, 0},
     {"policy_group", "FRIRL_HIP_POLICY_GROUP", &Options::policy_group, 0},
     {"policy_slices", "FRIRL_HIP_POLICY_SLICES", &Options::policy_slices, 0},
     {"learn_slices", "FRIRL_HIP_LEARN_SLICES", &Options::learn_slices, 0},

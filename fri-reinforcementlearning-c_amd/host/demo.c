@@ -21,7 +21,8 @@ static int usage(const char *what)
 {
     fprintf(stderr, "usage error: %s\n"
                     "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F] [--teach-best M [--teach-passes P]]   (K >= 1 rows per agent, 0 <= F <= 1, M >= 1 episodes, 1 <= P <= 1024)\n"
-                    "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-starts K [--spread F]   (S = 1 | 2, 1 <= K <= 256 start states per agent, 0 <= F <= 1)\n", what);
+                    "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-starts K [--spread F]   (S = 1 | 2, 1 <= K <= 256 start states per agent, 0 <= F <= 1)\n"
+                    "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-map K [--spread F] [--reduce-map-all]   (removals validated on the policy map at the points visited from K start states; --reduce-map-all: of every start, not the successful ones alone)\n", what);
     return 2;
 }
 
@@ -37,6 +38,8 @@ int main(int argc, char **argv)
     int teach_best = 0;             /* --teach-best M: after the evaluation the best agent teaches every other agent M greedy episodes, 0 = not asked for */
     int teach_passes = 1;           /* --teach-passes P: passes over the teacher's log */
     int reduce_starts = 0;          /* --reduce-starts K: with --reduce-all, every removal is validated against K start states per agent, 0 = not asked for */
+    int reduce_map = 0;             /* --reduce-map K: with --reduce-all, every removal is validated on the policy map at the points visited from K start states, 0 = not asked for */
+    int reduce_map_all = 0;         /* --reduce-map-all: the points of every start, not of the successful ones alone */
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -51,6 +54,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--reduce-all")) reduce_all = 1;                              /* with --agents and --reduce: every agent's rule base, not agent 0's alone */
         else if (!strcmp(argv[i], "--evaluate") && i + 1 < argc) { evaluate = atoi(argv[++i]); if (evaluate < 1) return usage("--evaluate needs K >= 1"); }
         else if (!strcmp(argv[i], "--reduce-starts") && i + 1 < argc) { reduce_starts = atoi(argv[++i]); if (reduce_starts < 1 || reduce_starts > 256) return usage("--reduce-starts needs 1 <= K <= 256"); }
+        else if (!strcmp(argv[i], "--reduce-map") && i + 1 < argc) { reduce_map = atoi(argv[++i]); if (reduce_map < 1 || reduce_map > 256) return usage("--reduce-map needs 1 <= K <= 256"); }
+        else if (!strcmp(argv[i], "--reduce-map-all")) reduce_map_all = 1;
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
         else if (!strcmp(argv[i], "--teach-best") && i + 1 < argc) { teach_best = atoi(argv[++i]); if (teach_best < 1) return usage("--teach-best needs M >= 1"); }
         else if (!strcmp(argv[i], "--teach-passes") && i + 1 < argc) { teach_passes = atoi(argv[++i]); if (teach_passes < 1 || teach_passes > 1024) return usage("--teach-passes needs 1 <= P <= 1024"); }
@@ -60,6 +65,10 @@ int main(int argc, char **argv)
     if (teach_best > 0 && evaluate < 1) return usage("--teach-best goes with --evaluate K");
     if (reduce_starts > 0 && (agents < 1 || !reduce_all || (reduce != 1 && reduce != 2) || merge || gpus >= 0))
         return usage("--reduce-starts goes with --agents N --reduce S --reduce-all (one device, no --merge)");
+    if (reduce_map > 0 && reduce_starts > 0) return usage("--reduce-map and --reduce-starts exclude each other");
+    if (reduce_map > 0 && (agents < 1 || !reduce_all || (reduce != 1 && reduce != 2) || merge || gpus >= 0))
+        return usage("--reduce-map goes with --agents N --reduce S --reduce-all (one device, no --merge)");
+    if (reduce_map_all && reduce_map < 1) return usage("--reduce-map-all goes with --reduce-map K");
     frirl_parse_cmdline(&fr, fargc, fargv);
     if (evaluate > 0) {             /* train (or --load), then every agent rolled out from K start states */
         int ns = 0, U = 0, A = 0, ms = 0, rc;
@@ -92,6 +101,19 @@ int main(int argc, char **argv)
     if (agents > 0) {
         snprintf(name, sizeof name, "%s.batch.frirlrb.txt", env);
         if (reduce == 1 || reduce == 2) snprintf(name, sizeof name, "%s.batch.reduced%d.frirlrb.txt", env, reduce);
+        if (reduce_map > 0) {       /* the rows --reduce-starts K would use */
+            int ns = 0, U = 0, A = 0, ms = 0, rc;
+            double *units;
+            if (frirl_demo_describe(env, &ns, &U, &A, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &ms) != 0) return 2;
+            units = malloc(sizeof(double) * (size_t)agents * (size_t)reduce_map * (size_t)ns);
+            if (!units) return 1;
+            frirl_demo_row_units(agents, reduce_map, ns, units);
+            snprintf(name, sizeof name, "%s.batch.reducedmap%d.frirlrb.txt", env, reduce);
+            rc = frirl_demo_batch_run_reduce_all_map(env, agents, load_bin ? 2 : (max_episodes > 0 ? max_episodes : fr.max_episodes), reduce, load_bin,
+                                                     save_bin, name, reduce_map, spread, units, !reduce_map_all, 1);
+            free(units);
+            return rc >= 0 ? 0 : 3;
+        }
         if (reduce_starts > 0) {    /* rows as --evaluate K --spread F maps them; row 0 = the agent's own start state */
             int ns = 0, U = 0, A = 0, ms = 0, rc;
             double *units;

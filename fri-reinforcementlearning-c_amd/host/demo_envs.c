@@ -479,7 +479,7 @@ static void demo_row_starts(const frirl_hip_batch_desc *d, const struct demo_des
 }
 
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
-                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int verbose);
+                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int map, int verbose);
 
 int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
                                         const double *units, int teach_episodes, int teach_passes, int verbose)
@@ -554,25 +554,33 @@ int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes,
 int frirl_demo_batch_run_ex(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                             const char *out_txt, int verbose)
 {
-    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 0, load_bin, save_bin, out_txt, 0, 0.0, NULL, verbose);
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 0, load_bin, save_bin, out_txt, 0, 0.0, NULL, 0, verbose);
 }
 
 int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                     const char *out_txt, int verbose)
 {
-    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, 0, 0.0, NULL, verbose);
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, 0, 0.0, NULL, 0, verbose);
 }
 
 int frirl_demo_batch_run_reduce_all_starts(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                            const char *out_txt, int K, double spread, const double *units, int verbose)
 {
     if (K < 1 || K > FRIRL_HIP_REDUCE_MAX_STARTS || !units || !(spread >= 0.0) || (reduce_strategy != 1 && reduce_strategy != 2)) return -1;
-    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, K, spread, units, verbose);
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, K, spread, units, 0, verbose);
 }
 
-/* starts >= 1: the reduction of every agent validates each removal against `starts` start states per agent (demo_row_starts) */
+int frirl_demo_batch_run_reduce_all_map(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                        const char *out_txt, int K, double spread, const double *units, int only_successful, int verbose)
+{
+    if (K < 1 || K > FRIRL_HIP_REDUCE_MAX_STARTS || !units || !(spread >= 0.0) || (reduce_strategy != 1 && reduce_strategy != 2)) return -1;
+    return demo_batch_run(env, agents, max_episodes, reduce_strategy, 1, load_bin, save_bin, out_txt, K, spread, units, only_successful ? 1 : 2, verbose);
+}
+
+/* starts >= 1: the reduction of every agent validates each removal against `starts` start states per agent (demo_row_starts);
+ * map != 0: on the policy map at the points the greedy policy visits from them instead (1 = of the successful starts, 2 = of all) */
 static int demo_batch_run(const char *env, int agents, int max_episodes, int reduce_strategy, int reduce_all, const char *load_bin,
-                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int verbose)
+                          const char *save_bin, const char *out_txt, int starts, double spread, const double *units, int map, int verbose)
 {
     int nant = 0, episodes = 0, rc;
     frirl_hip_batch_desc d;
@@ -607,7 +615,20 @@ static int demo_batch_run(const char *env, int agents, int max_episodes, int red
         rc = frirl_hip_batch_save_rulebases(b, save_bin);
         if (rc) five_dropin_fatal("frirl_demo_batch_run(save)", rc);
     }
-    if ((reduce_strategy == 1 || reduce_strategy == 2) && reduce_all) {      /* every agent's rule base in one batched run */
+    if ((reduce_strategy == 1 || reduce_strategy == 2) && reduce_all && map && starts >= 1) {      /* validated on the policy map */
+        const size_t rows = (size_t)agents * (size_t)starts;
+        double *start = malloc(sizeof(double) * rows * (size_t)(nant - 1));
+        frirl_hip_reduce_map_totals tot;
+        if (!start) five_dropin_fatal("frirl_demo_batch_run(reduce all map)", FRIRL_HIP_ELAUNCH);
+        demo_row_starts(&d, &mm, agents, starts, nant - 1, spread, units, start);
+        rc = frirl_hip_batch_reduce_all_map(b, reduce_strategy, starts, start, map == 1, 0, NULL, &tot);
+        free(start);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run(reduce all map)", rc);
+        if (verbose)
+            printf("reduced-map: batch %s: %d of %d agents reduced, %lld -> %lld rules (strategy %d, %d starts, %s), points %lld, overflow %d, without points %d\n",
+                   env, (int)tot.agents_reduced, agents, (long long)tot.rules_before, (long long)tot.rules_after, reduce_strategy, starts,
+                   map == 1 ? "successful starts" : "all starts", (long long)tot.points, (int)tot.agents_overflow, (int)tot.agents_without_points);
+    } else if ((reduce_strategy == 1 || reduce_strategy == 2) && reduce_all) {      /* every agent's rule base in one batched run */
         frirl_hip_reduce_result *rr = malloc(sizeof *rr * (size_t)agents);
         long long before = 0, after = 0, rollouts = 0;
         int32_t reduced = 0, rounds = 0;

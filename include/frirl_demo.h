@@ -41,6 +41,11 @@ int frirl_demo_batch_run_reduce_all(const char *env, int agents, int max_episode
  * summary line also says how many of the agents * K start states were used; K == 1 prints the line of frirl_demo_batch_run_reduce_all */
 int frirl_demo_batch_run_reduce_all_starts(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
                                            const char *out_txt, int K, double spread, const double *units, int verbose);
+/* the same rows, but every removal validated on the POLICY MAP at the points the agent's greedy policy visits from them
+ * (frirl_hip_batch_reduce_all_map, cap 512): only_successful != 0 = the points of the starts whose episode succeeds.  Prints one
+ * "reduced-map:" line with the totals */
+int frirl_demo_batch_run_reduce_all_map(const char *env, int agents, int max_episodes, int reduce_strategy, const char *load_bin, const char *save_bin,
+                                        const char *out_txt, int K, double spread, const double *units, int only_successful, int verbose);
 /* Population evaluation: the agents learn (or, load_bin != NULL, load their rule bases), then EVERY agent is rolled out greedily on its
  * own rule base from K start states (frirl_hip_batch_evaluate): row 0 = agent.values_def, row j >= 1 = values_def[k] + spread *
  * units[e][j][k] * (largest - smallest grid value of dimension k), clipped to the grid; units HOST [agents][K][nstates] in -1..1.

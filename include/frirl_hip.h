@@ -100,7 +100,7 @@ int frirl_hip_device_info(int device, char *name, int name_len, int32_t *cus, in
 /* Experiment / test switches by name: "no_uidx" (1 = ignore the 16-bit index mirror), "rd_unroll", "rd_chunk", "rd_nt",
  * "rd_persist", "rd_order", "rd_packed" (0 = five_hip_rule_distance_packed streams the 16-bit mirror), "rd_sqdiff" (0 = the packed
  * scan without its squared-difference tables), "rd_qpass" (1 = the packed scan snaps the observations in a pre-pass; only with rd_prepass = 0, which supersedes it), "rd_prepass" (0 =
- * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "rollout_batch_resident", "rollout_batch_resident_rules", "rollout_batch_slices", "reduce_map_resident", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
+ * five_hip_rule_distance_packed_ws builds its squared-difference tables in every workgroup instead of once per call), "rd_coded" (0 = five_hip_rule_distance_coded_ws streams the 4-byte packed words), "step_wave", "step_track", "lanes_slices", "lanes_wpe", "rollout_group", "rollout_slices", "rollout_resident", "rollout_cap", "rollout_pair", "rollout_wps", "rollout_batch_resident", "rollout_batch_resident_rules", "rollout_batch_slices", "rollout_record_slices", "rollout_points_slices", "reduce_map_resident", "policy_group", "policy_slices", "learn_slices", "learn_alone", "learn_persistent", "multi_loopback", "no_many", "mirror_sync".  Their defaults
  * (the shipped configuration) are read ONCE from the matching FRIRL_HIP_<NAME> environment variable, never per launch;
  * results do not depend on any of them (only the kernel variant / launch shape does). */
 int frirl_hip_set_option(const char *name, int value);
@@ -568,6 +568,53 @@ typedef struct frirl_hip_log_points_desc {
 } frirl_hip_log_points_desc;
 size_t frirl_hip_log_points_workspace_bytes(int32_t E, int32_t n_logs, int32_t T);
 int frirl_hip_log_points(const frirl_hip_log_points_desc *lp, void *workspace, size_t workspace_bytes, void *stream);
+
+/* frirl_hip_rollout_points: the same point sets WITHOUT logs -- frirl_hip_rollout_batch's tiled roll-out, one episode per row
+ * (row q = e * n + j on the slab of agent e; exploration keys (env_id_base + q, episode 0, step)), that keeps per agent the
+ * de-duplicated set of the points the policy was asked at while it rolls out.  Memory is bounded by the state grid, not by the episode
+ * length: the scalable source of points for frirl_hip_policy_map / frirl_hip_reduce_batch_map; the log path above remains for callers
+ * who have logs.
+ * For agent e the SET of rows points[e][0 .. point_count[e]) is exactly the set that frirl_hip_rollout_record (episodes = 1,
+ * T = max_steps + 1, the same n, start_states, row_count, active and agent) followed by frirl_hip_log_points (n_logs = n, the same
+ * only_successful, an unbounded cap) gives: the start record contributes the un-quantised start, every later step its q_obs, the
+ * terminal one included; comparison is bit-wise; with only_successful a row whose episode does not end with success == 1 contributes
+ * nothing.
+ *   steps / reward / success   bit for bit row q of frirl_hip_rollout_batch (-1 / 0 / 0 for a row that is not rolled out)
+ *   points       [dev] [E][cap][nant-1]; the rows at and beyond point_count[e] are never written
+ *   point_count  [dev] [E];  overflow [dev] [E] 1 = the set has more than cap members: point_count[e] = cap, WHICH members are kept is
+ *                unspecified, treat the agent as "no list".  Overflow is also raised, whatever cap is, once ONE workgroup's rows
+ *                visit more distinct points than its LDS table takes (contributing or not): 128 / 384 / 640 for cap <= 128 / 384 / 512
+ * A row is not rolled out when j >= row_count[e], when its agent is inactive, or when nrules[e] lies outside 1..maxR; an agent whose
+ * rows are all skipped reads point_count 0, overflow 0 and its points rows are untouched.
+ * The ORDER of a list is unspecified; it is a function of the inputs, the options and the launch shape only: two identical calls return
+ * identical arrays.  (frirl_hip_reduce_batch_map accepts a removal iff the map is unchanged at every point: no order enters.)
+ * Lane shapes: those of frirl_hip_rollout_record; option "rollout_points_slices" (0 = automatic) forces the rule slices 1 / 4 / 8 (16
+ * for up to 4 actions).  Any Shepard power.  A workgroup serves rows of one agent and keeps their points in a hash table in LDS (256 / 512 / 768
+ * slots, every entry with the mask of the rows that visited it); it writes the entries of contributing rows to its own segment of the
+ * workspace, and a second launch merges every agent's segments.  Asynchronous on `stream`; nothing is read back or allocated.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL t / b / agent / rp / points / point_count / overflow, n outside
+ * 1..FRIRL_HIP_REDUCE_MAX_STARTS, cap outside 1..FRIRL_HIP_POINTS_MAX_CAP, only_successful other than 0 / 1, E * n or E * cap >
+ * INT32_MAX, A outside 1..32, an env_kind that is not one of the three demos with its antecedent count, a grid_len outside
+ * 1..FRIRL_HIP_MAX_GRID, a workspace that is NULL, not 16-byte aligned or smaller than
+ * frirl_hip_rollout_points_workspace_bytes(nant, E, maxR, n, cap, A) (one segment of cap points per 4 rows of every agent).
+ * frirl_hip_rollout_points_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+#define FRIRL_HIP_POINTS_MAX_CAP 512
+typedef struct frirl_hip_rollout_points_desc {
+    int32_t n;                  /* rows (start states) per agent, 1..FRIRL_HIP_REDUCE_MAX_STARTS; row q = e*n + j on agent e's slab */
+    int32_t cap;                /* capacity of every agent's point list, 1..FRIRL_HIP_POINTS_MAX_CAP */
+    int32_t only_successful;    /* 0 / 1 */
+    int32_t reserved;
+    const double  *start_states;/* [dev] [E*n][nant-1], or NULL = agent->values_def */
+    const int32_t *row_count;   /* [dev] [E] or NULL = n   (as frirl_hip_rollout_batch_rows) */
+    const uint8_t *active;      /* [dev] [E] or NULL */
+    double  *points;            /* [dev] [E][cap][nant-1] */
+    int32_t *point_count;       /* [dev] [E] */
+    int32_t *overflow;          /* [dev] [E] */
+    int32_t *steps; double *reward; int32_t *success;   /* [dev] [E*n], each optional: the row outputs of frirl_hip_rollout_batch */
+} frirl_hip_rollout_points_desc;
+size_t frirl_hip_rollout_points_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t n, int32_t cap, int32_t A);
+int frirl_hip_rollout_points(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                             const frirl_hip_rollout_points_desc *rp, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Per-environment episode state (reference: fields of frirl_desc + frirl_reward_desc that
  * frirl_episode() carries from step to step, src/frirl/frirl_episode.c:28-194). */
@@ -1092,6 +1139,22 @@ int frirl_hip_batch_reduce_all(frirl_hip_batch *b, int strategy, double reward_t
 int frirl_hip_batch_reduce_all_starts(frirl_hip_batch *b, int strategy, double reward_tolerance, int depth, int32_t n, const double *start_states,
                                       int drop_bad_starts, frirl_hip_reduce_result *results, frirl_hip_reduce_start_result *per_start,
                                       int32_t *agents_reduced);
+/* The reduction validated on the policy map (frirl_hip_reduce_batch_map) for EVERY agent, at the points its greedy policy visits from n
+ * start states: frirl_hip_rollout_points with agent.no_random = 1 (start_states HOST [E][n][nant-1]; NULL: n must be 1, every agent at
+ * its own start -- its desc.start_states row, agent.values_def where the batch has none), then frirl_hip_reduce_batch_map with active =
+ * the agents without overflow.  An agent whose point set overflows `cap` (0 = FRIRL_HIP_POINTS_MAX_CAP) is left untouched and counted
+ * in agents_overflow; one without a point (with only_successful: no successful start) keeps every rule.  The convergence state and the
+ * index mirror are left exactly as frirl_hip_batch_reduce_all leaves them.  results: HOST [E] or NULL (an overflowing agent reads
+ * rules_after == rules_before, points 0, tries 0); totals or NULL: points = the points summed over the agents that took part.
+ * FRIRL_HIP_EINVAL: the cases of frirl_hip_batch_reduce_all_starts (NULL start_states only with n != 1), a strategy outside 1..2, cap
+ * outside 0..512.  Buffers are allocated and freed inside the call, which synchronises. */
+typedef struct frirl_hip_reduce_map_totals {
+    int32_t agents_reduced, agents_overflow, agents_without_points, reserved;
+    int64_t rules_before, rules_after, points;
+} frirl_hip_reduce_map_totals;
+int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, int32_t n, const double *start_states /* HOST [E][n][nant-1]; NULL: n must be 1, every agent's own start */,
+                                   int only_successful, int32_t cap /* 0 = 512 */, frirl_hip_reduce_map_result *results /* HOST [E] or NULL */,
+                                   frirl_hip_reduce_map_totals *totals /* or NULL */);
 /* Greedy roll-outs of EVERY agent of the batch on its own rule base from n start states each (frirl_hip_rollout_batch with
  * agent.no_random = 1): which of the agents is any good away from the start state it trained on.  Row 0 .. n-1 of agent e start at
  * start_states[e][0 .. n-1]; NULL = every row at the agent's own start (its desc.start_states row, agent.values_def where the batch
