@@ -136,6 +136,20 @@ class ReduceMapResult(C.Structure):
     _fields_ = [("rules_before", C.c_int32), ("rules_after", C.c_int32), ("points", C.c_int32), ("tries", C.c_int32)]
 
 
+class RuleUsageOut(C.Structure):
+    """struct frirl_hip_rule_usage_out (include/frirl_hip.h)."""
+    _fields_ = [("sum", C.c_void_p), ("peak", C.c_void_p), ("best", C.c_void_p)]
+
+
+class ReduceOrdersResult(C.Structure):
+    """struct frirl_hip_reduce_orders_result (include/frirl_hip.h)."""
+    _fields_ = [("rules_before", C.c_int32), ("rules_after", C.c_int32), ("points", C.c_int32), ("chosen", C.c_int32), ("tries", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+REDUCE_MAX_ORDERS = 16
+
+
 class LogPointsDesc(C.Structure):
     """struct frirl_hip_log_points_desc (include/frirl_hip.h)."""
     _fields_ = [("E", C.c_int32), ("n_logs", C.c_int32), ("T", C.c_int32), ("ns", C.c_int32), ("cap", C.c_int32), ("only_successful", C.c_int32),
@@ -256,6 +270,14 @@ SIGNATURES = {
     "frirl_hip_reduce_batch_map_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_reduce_batch_map": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(MapPoints), C.c_int,
                                              C.POINTER(C.c_int32), C.POINTER(ReduceMapResult), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_rule_usage_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_rule_usage": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(MapPoints), C.POINTER(RuleUsageOut),
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_rule_order": (C.c_int, [C.POINTER(RuleBases), C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frirl_hip_reduce_batch_map_orders_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "frirl_hip_reduce_batch_map_orders": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(MapPoints), C.c_int32,
+                                                    C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ReduceOrdersResult), C.POINTER(C.c_int32), C.c_void_p,
+                                                    C.c_size_t, C.c_void_p]),
     "frirl_hip_log_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_log_points": (C.c_int, [C.POINTER(LogPointsDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "frirl_hip_rollout_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -342,6 +364,8 @@ SIGNATURES = {
                                                     C.POINTER(ReduceStartResult), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_reduce_all_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, _DP, C.c_int, C.c_int32, C.POINTER(ReduceMapResult),
                                                  C.POINTER(ReduceMapTotals)]),
+    "frirl_hip_batch_reduce_all_map_orders": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, _DP, C.c_int, C.c_int32, C.POINTER(ReduceOrdersResult),
+                                                        C.POINTER(C.c_int32), C.POINTER(ReduceMapTotals)]),
     "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_teach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(TeachResult)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -864,6 +888,62 @@ class Problem:
               "frirl_hip_reduce_batch_map")
         return list(res), [kept[e, : res[e].rules_after].copy() for e in range(self.E)]
 
+    def rule_usage(self, agent, points, point_count=None, active=None, peak=False, stream=None):
+        """frirl_hip_rule_usage: how much the greedy policy of EVERY rule base leans on each of its rules at its points (points /
+        point_count / active as policy_map): per point the normalised Shepard weights of the rules in the greedy action's conclusion
+        (one-hot on an exact hit), summed over the points.  Returns (sum [E, maxR] f64, peak [E, maxR] f64 or None, best [E, n] int32);
+        the sum / peak rows of an inactive agent or one with nrules outside 1..maxR are zeros here (the call leaves them untouched).
+        Does not synchronise."""
+        import torch
+        mp = self._map_points(points, point_count, active)
+        total = torch.zeros((self.E, self.maxR), dtype=torch.float64, device=points.device)
+        top = torch.zeros((self.E, self.maxR), dtype=torch.float64, device=points.device) if peak else None
+        best = torch.empty((self.E, mp.n), dtype=torch.int32, device=points.device)
+        out = RuleUsageOut(total.data_ptr(), top.data_ptr() if peak else None, best.data_ptr())
+        nbytes = lib().frirl_hip_rule_usage_workspace_bytes(self.nant, self.E, mp.n)
+        ws = _scratch(nbytes, points.device, stream)
+        check(lib().frirl_hip_rule_usage(C.byref(self.tables), C.byref(self._bases), C.byref(agent.desc), C.byref(mp), C.byref(out), _ptr(ws), nbytes,
+                                         _stream(stream)), "frirl_hip_rule_usage")
+        return total, top, best
+
+    def rule_order(self, keys=None, descending=False, active=None, stream=None, out=None):
+        """frirl_hip_rule_order: every rule base's rules in the stable order of keys [E, maxR] f64 (None: |Q|, i.e. the candidate order of
+        strategy 1, or 2 with descending); NaN keys last.  Returns order [E, maxR] int32: the first nrules[e] entries of row e (the rest,
+        and the rows of skipped agents, are -1 here; the call leaves them untouched).  Does not synchronise."""
+        import torch
+        if keys is not None:
+            assert keys.is_cuda and keys.shape == (self.E, self.maxR) and keys.dtype == torch.float64 and keys.is_contiguous()
+        assert active is None or (active.shape == (self.E,) and active.dtype in (torch.uint8, torch.bool) and active.is_contiguous())
+        if out is None:
+            out = torch.full((self.E, self.maxR), -1, dtype=torch.int32, device=self.rb.device)
+        assert out.shape == (self.E, self.maxR) and out.dtype == torch.int32 and out.is_contiguous()
+        check(lib().frirl_hip_rule_order(C.byref(self._bases), self.nant, _ptr(keys), 1 if descending else 0, _ptr(active), _ptr(out), _stream(stream)),
+              "frirl_hip_rule_order")
+        return out
+
+    def reduce_batch_map_orders(self, agent, points, orders, point_count=None, active=None, rant=None, stream=None):
+        """frirl_hip_reduce_batch_map_orders: reduce_batch_map with the caller's candidate orders, orders [E, K, maxR] int32 (K in 1..16,
+        e.g. torch.stack of rule_order results along dim 1): every order is tried on its own and the one that leaves the fewest rules is
+        applied (ties: the lowest k).  Compacts the rule bases in place.  Returns (list of ReduceOrdersResult, list of kept original
+        indices, after_per_order [E, K] numpy int32)."""
+        import numpy as np
+        import torch
+        mp = self._map_points(points, point_count, active)
+        assert orders.is_cuda and orders.dim() == 3 and orders.shape[0] == self.E and orders.shape[2] == self.maxR
+        assert orders.dtype == torch.int32 and orders.is_contiguous()
+        K = int(orders.shape[1])
+        if rant is not None:
+            assert rant.shape == (self.E, self.nant, self.maxR) and rant.dtype == torch.float64 and rant.is_contiguous()
+        nbytes = lib().frirl_hip_reduce_batch_map_orders_workspace_bytes(self.nant, self.E, self.maxR, mp.n, K)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=points.device)
+        kept = np.zeros((self.E, self.maxR), dtype=np.int32)
+        after = np.zeros((self.E, max(K, 1)), dtype=np.int32)
+        res = (ReduceOrdersResult * self.E)()
+        check(lib().frirl_hip_reduce_batch_map_orders(C.byref(self.tables), C.byref(self.bases), C.byref(agent.desc), _ptr(rant), C.byref(mp), K, _ptr(orders),
+                                                      kept.ctypes.data_as(C.POINTER(C.c_int32)), res, after.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ws),
+                                                      nbytes, _stream(stream)), "frirl_hip_reduce_batch_map_orders")
+        return list(res), [kept[e, : res[e].rules_after].copy() for e in range(self.E)], after
+
     def policy_begin(self, agent, rows, obs, reset=None, stream=None):
         """frirl_hip_policy_begin: rows (PolicyRows) selected by `reset` ([Q] uint8 / bool, None = all) start a greedy episode on this ONE
         rule base from the caller's observations obs [Q, nant-1].  Returns (action values [Q], action indices [Q]); rows that were not
@@ -1248,6 +1328,26 @@ def batch_reduce_all_map(batch, strategy, n, start_states=None, only_successful=
     check(lib().frirl_hip_batch_reduce_all_map(batch, strategy, n, None if st is None else st.ctypes.data_as(_DP), 1 if only_successful else 0, cap, res,
                                                C.byref(tot)), "frirl_hip_batch_reduce_all_map")
     return list(res), tot
+
+
+def batch_reduce_all_map_orders(batch, order_set, n, start_states=None, only_successful=True, cap=0):
+    """frirl_hip_batch_reduce_all_map_orders on a library-owned batch: batch_reduce_all_map with the reduction run over several candidate
+    orders per agent, the smallest result kept.  order_set: bits 1 = |Q| ascending, 2 = |Q| descending, 4 = least-used first, 8 =
+    most-used first (usage: Problem.rule_usage's sum at the agents' points).  Returns (list of ReduceOrdersResult, after_per_order
+    [E, popcount(order_set)] numpy int32, ReduceMapTotals)."""
+    import numpy as np
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    stats = BatchStats()
+    check(lib().frirl_hip_batch_stats(batch, C.byref(stats)), "frirl_hip_batch_stats")
+    E = int(stats.agents)
+    assert st is None or (st.ndim == 3 and st.shape[:2] == (E, n))
+    res = (ReduceOrdersResult * E)()
+    after = np.zeros((E, max(bin(order_set & 15).count("1"), 1)), dtype=np.int32)
+    tot = ReduceMapTotals()
+    check(lib().frirl_hip_batch_reduce_all_map_orders(batch, order_set, n, None if st is None else st.ctypes.data_as(_DP), 1 if only_successful else 0, cap,
+                                                      res, after.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(tot)),
+          "frirl_hip_batch_reduce_all_map_orders")
+    return list(res), after, tot
 
 
 def learn_demonstration(problem, agent, envs, demo, passes=1, stream=None):

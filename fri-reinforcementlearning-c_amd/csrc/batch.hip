@@ -393,25 +393,33 @@ extern "C" int frirl_hip_batch_reduce_all_starts(frirl_hip_batch *b, int strateg
     return FRIRL_HIP_OK;
 }
 
-extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, int32_t n, const double *start_states, int only_successful, int32_t cap,
-                                              frirl_hip_reduce_map_result *results, frirl_hip_reduce_map_totals *totals)
+// frirl_hip_batch_reduce_all_map (order_set == 0: `strategy`, results in `results`) and frirl_hip_batch_reduce_all_map_orders (order_set
+// != 0: results in `ores` / `after_per_order`): the roll-out of the points, the bookkeeping and the totals are one piece of code
+static int batch_reduce_all_map_run(const char *who, frirl_hip_batch *b, int strategy, int order_set, int32_t n, const double *start_states, int only_successful,
+                                    int32_t cap, frirl_hip_reduce_map_result *results, frirl_hip_reduce_orders_result *ores, int32_t *after_per_order,
+                                    frirl_hip_reduce_map_totals *totals)
 {
-    static const char *who = "frirl_hip_batch_reduce_all_map";
     if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
     if (n < 1 || n > FRIRL_HIP_REDUCE_MAX_STARTS) { set_error("%s: n=%d start states outside 1..%d", who, n, FRIRL_HIP_REDUCE_MAX_STARTS); return FRIRL_HIP_EINVAL; }
     if (!start_states && n != 1) { set_error("%s: NULL start states with n=%d (every agent's own start: n = 1)", who, n); return FRIRL_HIP_EINVAL; }
-    if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
+    if (!order_set && strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
     if (cap < 0 || cap > FRIRL_HIP_POINTS_MAX_CAP) { set_error("%s: cap=%d outside 0..%d", who, cap, FRIRL_HIP_POINTS_MAX_CAP); return FRIRL_HIP_EINVAL; }
     if (cap == 0) cap = FRIRL_HIP_POINTS_MAX_CAP;
     DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
-    const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, Q = E * (size_t)n;
+    const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, Q = E * (size_t)n, M = (size_t)b->maxR;
+    const int K = __builtin_popcount((unsigned)order_set);
+    const bool usage = (order_set & 12) != 0;
     const size_t ws_points = frirl_hip_rollout_points_workspace_bytes(b->nant, b->E, b->maxR, n, cap, b->agent.A);
-    const size_t ws_map = frirl_hip_reduce_batch_map_workspace_bytes(b->nant, b->E, b->maxR, cap);
-    const size_t ws_bytes = ws_points > ws_map ? ws_points : ws_map;   // the two calls follow each other on one stream
+    const size_t ws_map = order_set ? frirl_hip_reduce_batch_map_orders_workspace_bytes(b->nant, b->E, b->maxR, cap, K)
+                                    : frirl_hip_reduce_batch_map_workspace_bytes(b->nant, b->E, b->maxR, cap);
+    const size_t ws_usage = usage ? frirl_hip_rule_usage_workspace_bytes(b->nant, b->E, cap) : 0;
+    const size_t ws_bytes = std::max(ws_points, std::max(ws_map, ws_usage));   // the calls follow each other on one stream
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; };
     const size_t o_ws = take(ws_bytes), o_points = take(sizeof(double) * E * (size_t)cap * ns), o_start = take(start_states ? sizeof(double) * Q * ns : 0);
     const size_t o_count = take(sizeof(int32_t) * E), o_over = take(sizeof(int32_t) * E), o_active = take(E);
+    const size_t o_sum = take(usage ? sizeof(double) * E * M : 0), o_one = take(order_set ? sizeof(int32_t) * E * M : 0);
+    const size_t o_orders = take(sizeof(int32_t) * E * M * (size_t)K);
     char *mem = nullptr;
     BCHK(hipMalloc(reinterpret_cast<void **>(&mem), off), "map reduction buffers");
     frirl_hip_rollout_points_desc rp = {};
@@ -425,6 +433,7 @@ extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, 
     std::vector<int32_t> count(E), over(E);
     std::vector<uint8_t> active(E);
     std::vector<frirl_hip_reduce_map_result> res(E);
+    std::vector<frirl_hip_reduce_orders_result> resk(order_set ? E : 0);
     int rc = FRIRL_HIP_OK;
     hipError_t he = hipSuccess;
     if (start_states) he = hipMemcpyAsync(mem + o_start, start_states, sizeof(double) * Q * ns, hipMemcpyHostToDevice, b->s);
@@ -443,7 +452,26 @@ extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, 
         mp.points = rp.points;
         mp.point_count = rp.point_count;
         mp.active = reinterpret_cast<const uint8_t *>(mem + o_active);
-        rc = frirl_hip_reduce_batch_map(&b->t, &b->rb, &greedy, b->d_rant, &mp, strategy, nullptr, res.data(), mem + o_ws, ws_bytes, b->s);
+        if (!order_set) rc = frirl_hip_reduce_batch_map(&b->t, &b->rb, &greedy, b->d_rant, &mp, strategy, nullptr, res.data(), mem + o_ws, ws_bytes, b->s);
+        double *sum = reinterpret_cast<double *>(mem + o_sum);
+        int32_t *one = reinterpret_cast<int32_t *>(mem + o_one), *orders = reinterpret_cast<int32_t *>(mem + o_orders);
+        if (usage) {
+            const frirl_hip_rule_usage_out uo = {sum, nullptr, nullptr};
+            rc = frirl_hip_rule_usage(&b->t, &b->rb, &greedy, &mp, &uo, mem + o_ws, ws_bytes, b->s);
+        }
+        // order k = the k-th set bit from the lowest: ranked into one [E][maxR] array, then interleaved into [E][K][maxR]
+        for (int bit = 0, k = 0; bit < 4 && rc == FRIRL_HIP_OK && he == hipSuccess; bit++) {
+            if (!(order_set >> bit & 1)) continue;
+            rc = frirl_hip_rule_order(&b->rb, b->nant, bit < 2 ? nullptr : sum, bit & 1, mp.active, one, b->s);
+            if (rc == FRIRL_HIP_OK)
+                he = hipMemcpy2DAsync(orders + (size_t)k * M, sizeof(int32_t) * M * K, one, sizeof(int32_t) * M, sizeof(int32_t) * M, E, hipMemcpyDeviceToDevice, b->s);
+            k += 1;
+        }
+        if (order_set && rc == FRIRL_HIP_OK && he == hipSuccess)
+            rc = frirl_hip_reduce_batch_map_orders(&b->t, &b->rb, &greedy, b->d_rant, &mp, K, orders, nullptr, resk.data(), after_per_order, mem + o_ws, ws_bytes,
+                                                   b->s);
+        else if (order_set) (void)hipStreamSynchronize(b->s);
+        for (size_t e = 0; order_set && e < E; e++) res[e] = {resk[e].rules_before, resk[e].rules_after, resk[e].points, resk[e].tries};
     }
     (void)hipFree(mem);
     if (rc) return rc;
@@ -458,8 +486,26 @@ extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, 
         tot.points += over[e] ? 0 : count[e];
     }
     if (results) memcpy(results, res.data(), sizeof(frirl_hip_reduce_map_result) * E);
+    if (ores) memcpy(ores, resk.data(), sizeof(frirl_hip_reduce_orders_result) * E);
     if (totals) *totals = tot;
     return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, int32_t n, const double *start_states, int only_successful, int32_t cap,
+                                              frirl_hip_reduce_map_result *results, frirl_hip_reduce_map_totals *totals)
+{
+    return batch_reduce_all_map_run("frirl_hip_batch_reduce_all_map", b, strategy, 0, n, start_states, only_successful, cap, results, nullptr, nullptr, totals);
+}
+
+extern "C" int frirl_hip_batch_reduce_all_map_orders(frirl_hip_batch *b, int order_set, int32_t n, const double *start_states, int only_successful, int32_t cap,
+                                                     frirl_hip_reduce_orders_result *results, int32_t *after_per_order, frirl_hip_reduce_map_totals *totals)
+{
+    static const char *who = "frirl_hip_batch_reduce_all_map_orders";
+    if (order_set < 1 || order_set > 15) {
+        set_error("%s: order_set=%d outside 1..15 (1 = |Q| ascending, 2 = |Q| descending, 4 = usage ascending, 8 = usage descending)", who, order_set);
+        return FRIRL_HIP_EINVAL;
+    }
+    return batch_reduce_all_map_run(who, b, 0, order_set, n, start_states, only_successful, cap, nullptr, results, after_per_order, totals);
 }
 
 extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)

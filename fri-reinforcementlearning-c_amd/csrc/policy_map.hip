@@ -1,7 +1,8 @@
 // policy_map.hip -- what a rule base does at a set of points (include/frirl_hip.h): the map kernel and entry point
 // (frirl_hip_policy_map), the entry point of the reduction validated on the map (frirl_hip_reduce_batch_map; its kernel sits behind
-// reduce_map_ws.h, beside the order kernel and the compaction it reuses) and the points of recorded roll-outs (frirl_hip_log_points).
-#include "reduce_map_ws.h"
+// reduce_map_ws.h, beside the order kernel and the compaction it reuses), of the same reduction over several caller orders
+// (frirl_hip_reduce_batch_map_orders; kernels behind reduce_orders_ws.h) and the points of recorded roll-outs (frirl_hip_log_points).
+#include "reduce_orders_ws.h"
 
 namespace frirl {
 
@@ -141,33 +142,16 @@ extern "C" size_t frirl_hip_reduce_batch_map_workspace_bytes(int32_t nant, int32
     return reduce_map_layout(nullptr, (size_t)E, (size_t)maxR, (size_t)n, nant, nullptr);
 }
 
+extern "C" size_t frirl_hip_reduce_batch_map_orders_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t n, int32_t K)
+{
+    if (nant < 2 || E < 1 || maxR < 1 || n < 1 || K < 1) return 0;
+    return reduce_orders_layout(nullptr, (size_t)E, (size_t)maxR, (size_t)n, nant, (size_t)K, nullptr);
+}
+
 extern "C" size_t frirl_hip_log_points_workspace_bytes(int32_t E, int32_t n_logs, int32_t T)
 {
     if (E < 1 || n_logs < 1 || T < 1) return 0;
     return up16((size_t)E * (size_t)n_logs * (size_t)T);
-}
-
-static int check_workspace(const char *who, const void *workspace, size_t bytes, size_t need, const char *query)
-{
-    if (workspace && !(reinterpret_cast<uintptr_t>(workspace) & 15) && bytes >= need) return FRIRL_HIP_OK;
-    set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (%s)", who, workspace, bytes, need, query);
-    return FRIRL_HIP_EINVAL;
-}
-
-// the checks the map and the map-validated reduction share; fills `m` (no device is looked at)
-static int check_map_args(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
-                          const frirl_hip_map_points *pts, frirl::MapArgs *m)
-{
-    int rc = check_rulebases(t, b);
-    if (rc) return rc;
-    if (!agent || !agent->action_ve || !pts || !pts->points) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
-    if (t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t->nant); return FRIRL_HIP_EINVAL; }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, agent->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
-    if (pts->n < 1 || (long long)b->E * pts->n > INT32_MAX) { set_error("%s: n=%d points per agent (E=%d): n < 1 or E * n > 2^31 - 1", who, pts->n, b->E); return FRIRL_HIP_EINVAL; }
-    m->u = t->u; m->ve = t->ve; m->U = t->U;
-    m->A = agent->A; m->p = agent->p > 0 ? agent->p : t->nant; m->n = pts->n;
-    m->action_ve = agent->action_ve; m->points = pts->points; m->point_count = pts->point_count; m->active = pts->active;
-    return FRIRL_HIP_OK;
 }
 
 template <int N>
@@ -191,7 +175,7 @@ extern "C" int frirl_hip_policy_map(const frirl_hip_tables *t, const frirl_hip_r
     int rc = check_map_args(who, t, b, agent, pts, &m);
     if (rc) return rc;
     if (!best) { set_error("%s: NULL best", who); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_workspace(who, workspace, workspace_bytes, frirl_hip_policy_map_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_policy_map_workspace_bytes")) ||
+    if ((rc = check_map_workspace(who, workspace, workspace_bytes, frirl_hip_policy_map_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_policy_map_workspace_bytes")) ||
         (rc = check_device()))
         return rc;
     const int resident = opts().reduce_map_resident != 0;
@@ -214,7 +198,7 @@ extern "C" int frirl_hip_reduce_batch_map(const frirl_hip_tables *t, const frirl
     if (!results) { set_error("%s: NULL results", who); return FRIRL_HIP_EINVAL; }
     if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
     const size_t need = frirl_hip_reduce_batch_map_workspace_bytes(t->nant, b->E, b->maxR, pts->n);
-    if ((rc = check_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_workspace_bytes")) || (rc = check_device())) return rc;
+    if ((rc = check_map_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_workspace_bytes")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     const size_t E = (size_t)b->E, M = (size_t)b->maxR;
     ReduceMapWs ws;
@@ -232,6 +216,43 @@ extern "C" int frirl_hip_reduce_batch_map(const frirl_hip_tables *t, const frirl
     return check_launch(who);
 }
 
+extern "C" int frirl_hip_reduce_batch_map_orders(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                                                 const frirl_hip_map_points *pts, int32_t K, const int32_t *orders, int32_t *kept,
+                                                 frirl_hip_reduce_orders_result *results, int32_t *after_per_order, void *workspace, size_t workspace_bytes,
+                                                 void *stream)
+{
+    static const char *who = "frirl_hip_reduce_batch_map_orders";
+    frirl::MapArgs m;
+    int rc = check_map_args(who, t, b, agent, pts, &m);
+    if (rc) return rc;
+    if (!results || !orders) { set_error("%s: NULL %s", who, results ? "orders" : "results"); return FRIRL_HIP_EINVAL; }
+    if (K < 1 || K > FRIRL_HIP_REDUCE_MAX_ORDERS) { set_error("%s: K=%d orders outside 1..%d", who, K, FRIRL_HIP_REDUCE_MAX_ORDERS); return FRIRL_HIP_EINVAL; }
+    if ((long long)b->E * K * pts->n > INT32_MAX) { set_error("%s: E=%d x K=%d x n=%d beyond 2^31 - 1", who, b->E, K, pts->n); return FRIRL_HIP_EINVAL; }
+    const size_t need = frirl_hip_reduce_batch_map_orders_workspace_bytes(t->nant, b->E, b->maxR, pts->n, K);
+    if ((rc = check_map_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_orders_workspace_bytes")) || (rc = check_device())) return rc;
+    hipStream_t s = as_stream(stream);
+    const size_t E = (size_t)b->E, M = (size_t)b->maxR;
+    ReduceOrdersWs ws;
+    reduce_orders_layout(static_cast<char *>(workspace), E, M, (size_t)pts->n, t->nant, (size_t)K, &ws);
+    if ((rc = reduce_orders_launch_check(who, *b, m, t->nant, orders, ws, s))) return rc;
+    int32_t hdr[4];
+    FRIRL_HIP_TRY(hipMemcpyAsync(hdr, ws.hdr, sizeof hdr, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+    FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
+    if ((rc = check_launch(who))) return rc;
+    if (hdr[0]) { set_error("%s: agent %d: nrules outside 1..maxR=%d", who, INT32_MAX - hdr[0], b->maxR); return FRIRL_HIP_EINVAL; }
+    if (hdr[1]) {
+        const int ek = INT32_MAX - hdr[1];
+        set_error("%s: agent %d, order k=%d: its first nrules entries are not a permutation of 0..nrules-1", who, ek / K, ek % K);
+        return FRIRL_HIP_EINVAL;
+    }
+    reduce_orders_launch_run(*t, *b, rant, m, opts().reduce_map_resident != 0, orders, ws, s);
+    FRIRL_HIP_TRY(hipMemcpyAsync(results, ws.res, sizeof(frirl_hip_reduce_orders_result) * E, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+    if (kept) FRIRL_HIP_TRY(hipMemcpyAsync(kept, ws.alive, sizeof(int32_t) * E * M, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+    if (after_per_order) FRIRL_HIP_TRY(hipMemcpyAsync(after_per_order, ws.after, sizeof(int32_t) * E * (size_t)K, hipMemcpyDeviceToHost, s), who, return FRIRL_HIP_ELAUNCH);
+    FRIRL_HIP_TRY(hipStreamSynchronize(s), who, return FRIRL_HIP_ELAUNCH);
+    return check_launch(who);
+}
+
 extern "C" int frirl_hip_log_points(const frirl_hip_log_points_desc *lp, void *workspace, size_t workspace_bytes, void *stream)
 {
     static const char *who = "frirl_hip_log_points";
@@ -245,7 +266,7 @@ extern "C" int frirl_hip_log_points(const frirl_hip_log_points_desc *lp, void *w
         set_error("%s: E * n_logs * T or E * cap beyond 2^31 - 1", who);
         return FRIRL_HIP_EINVAL;
     }
-    int rc = check_workspace(who, workspace, workspace_bytes, frirl_hip_log_points_workspace_bytes(lp->E, lp->n_logs, lp->T), "frirl_hip_log_points_workspace_bytes");
+    int rc = check_map_workspace(who, workspace, workspace_bytes, frirl_hip_log_points_workspace_bytes(lp->E, lp->n_logs, lp->T), "frirl_hip_log_points_workspace_bytes");
     if (rc || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     uint8_t *take = static_cast<uint8_t *>(workspace);

@@ -74,6 +74,33 @@ __device__ __forceinline__ void map_conclusions(const double *cols, size_t strid
     }
 }
 
+// The squared VE distance of rule r to (q, av) in map_conclusions' operations and FMA chain: the same bits as its d2.
+template <int NANT>
+__device__ __forceinline__ double map_rule_d2(const double *cols, size_t stride, int r, const double (&q)[NANT - 1], double av)
+{
+    const double d0 = q[0] - cols[r];
+    double s = d0 * d0;
+#pragma unroll
+    for (int k = 1; k < NANT - 1; k++) { const double d = q[k] - cols[k * stride + r]; s = __fma_rn(d, d, s); }
+    const double e = av - cols[(NANT - 1) * stride + r];
+    return __fma_rn(e, e, s);
+}
+
+// One more walk for a SINGLE action (rule usage, rule_usage.hip): the Shepard weight sum of the action VE point `av` at q over all R
+// rules in ascending order -- the bits of map_conclusions' sw for that action -- and the first exact hit (FRIRL_HIP_NO_HIT = none).
+template <int NANT>
+__device__ __forceinline__ void map_weight_sum(const double *cols, size_t stride, int R, PowU p, const double (&q)[NANT - 1], double av, double &S,
+                                               unsigned &hit)
+{
+    S = 0.0;
+    hit = FRIRL_HIP_NO_HIT;
+    for (int r = 0; r < R; r++) {
+        const double d2 = map_rule_d2<NANT>(cols, stride, r, q, av);
+        S = S + shepard_w(d2, p);
+        hit = (d2 == 0.0 && hit == FRIRL_HIP_NO_HIT) ? (unsigned)r : hit;
+    }
+}
+
 // LDS of one pass: the first maximum of every lane, combined per point in block order
 struct MapPassLds {
     double bv[PM_BLOCK];

@@ -45,3 +45,27 @@ int reduce_map_launch_order(const char *who, const frirl_hip_tables &t, const fr
                             const ReduceMapWs &ws, hipStream_t s);      // 0 or FRIRL_HIP_ELAUNCH
 void reduce_map_launch_run(const frirl_hip_tables &t, const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident,
                            const ReduceMapWs &ws, hipStream_t s);
+
+// ---- argument checks shared by policy_map.hip and rule_usage.hip (no device is looked at) ----
+static int check_map_workspace(const char *who, const void *workspace, size_t bytes, size_t need, const char *query)
+{
+    if (workspace && !(reinterpret_cast<uintptr_t>(workspace) & 15) && bytes >= need) return FRIRL_HIP_OK;
+    set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (%s)", who, workspace, bytes, need, query);
+    return FRIRL_HIP_EINVAL;
+}
+
+// the checks the map and the map-validated reduction share; fills `m` (no device is looked at)
+static int check_map_args(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                          const frirl_hip_map_points *pts, frirl::MapArgs *m)
+{
+    int rc = check_rulebases(t, b);
+    if (rc) return rc;
+    if (!agent || !agent->action_ve || !pts || !pts->points) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if (t->nant < 2 || t->nant > 8) { set_error("%s: nant=%d outside 2..8", who, t->nant); return FRIRL_HIP_EINVAL; }
+    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS) { set_error("%s: A=%d outside 1..%d", who, agent->A, FRIRL_HIP_MAX_ACTIONS); return FRIRL_HIP_EINVAL; }
+    if (pts->n < 1 || (long long)b->E * pts->n > INT32_MAX) { set_error("%s: n=%d points per agent (E=%d): n < 1 or E * n > 2^31 - 1", who, pts->n, b->E); return FRIRL_HIP_EINVAL; }
+    m->u = t->u; m->ve = t->ve; m->U = t->U;
+    m->A = agent->A; m->p = agent->p > 0 ? agent->p : t->nant; m->n = pts->n;
+    m->action_ve = agent->action_ve; m->points = pts->points; m->point_count = pts->point_count; m->active = pts->active;
+    return FRIRL_HIP_OK;
+}

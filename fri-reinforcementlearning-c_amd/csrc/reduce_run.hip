@@ -5,6 +5,7 @@
 #include "reduce_run.h"
 #include "reduce_starts_kernels.h"
 #include "reduce_map_kernels.h"
+#include "reduce_orders_kernels.h"
 
 int ReduceRun::init(const char *who, const frirl_hip_tables *t_, const frirl_hip_rulebases *b_, const frirl_hip_agent *agent_, double *rant_,
                     const frirl_hip_reduce_starts *starts, int strategy_, double reward_tolerance_, int depth_, bool stepped_, void *stream)
@@ -138,6 +139,41 @@ void reduce_map_launch_run(const frirl_hip_tables &t, const frirl_hip_rulebases 
 {
     switch (t.nant) {
 #define M(N) case N: launch_reduce_map<N>(b, rant, m, resident, ws, s); break;
+        FRIRL_POLICY_NANT_CASES(M)
+#undef M
+    }
+}
+
+// ---- the map-validated reduction over several orders (frirl_hip_reduce_batch_map_orders, policy_map.hip): its kernels reuse the
+// compaction, so their launches sit in this translation unit too (reduce_orders_ws.h) ----
+int reduce_orders_launch_check(const char *who, const frirl_hip_rulebases &b, const frirl::MapArgs &m, int nant, const int32_t *orders,
+                               const ReduceOrdersWs &ws, hipStream_t s)
+{
+    FRIRL_HIP_TRY(hipMemsetAsync(ws.hdr, 0, 4 * sizeof(int32_t), s), who, return FRIRL_HIP_ELAUNCH);
+    hipLaunchKernelGGL(frirl::reduce_orders_check_kernel, dim3((unsigned)b.E * (unsigned)ws.K), dim3(256), 0, s, b.nrules, b.maxR, m, nant - 1, orders, ws);
+    return check_launch(who);
+}
+
+template <int N>
+static void launch_reduce_orders(const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident, const int32_t *orders,
+                                 const ReduceOrdersWs &ws, hipStream_t s)
+{
+    const int rcap = resident ? frirl::map_resident_rules(N, b.maxR) : 0;
+    const size_t lds = (size_t)rcap * frirl::map_rule_bytes(N);
+    const dim3 grid((unsigned)b.E * (unsigned)ws.K), block(frirl::PM_BLOCK);
+    // reduce_map_kernel's lane shapes: one action per lane while an agent's (point, action) pairs fit one pass, else blocks of 4
+    if ((long)m.n * m.A <= frirl::PM_BLOCK)
+        hipLaunchKernelGGL((frirl::reduce_orders_trial_kernel<N, 1>), grid, block, lds, s, b.rb, b.nrules, b.maxR, m, rcap, orders, ws);
+    else
+        hipLaunchKernelGGL((frirl::reduce_orders_trial_kernel<N, 4>), grid, block, lds, s, b.rb, b.nrules, b.maxR, m, rcap, orders, ws);
+    hipLaunchKernelGGL(frirl::reduce_orders_apply_kernel<N>, dim3((unsigned)b.E), dim3(256), 0, s, b.rb, b.nrules, b.uidx, rant, b.maxR, m, ws);
+}
+
+void reduce_orders_launch_run(const frirl_hip_tables &t, const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident,
+                              const int32_t *orders, const ReduceOrdersWs &ws, hipStream_t s)
+{
+    switch (t.nant) {
+#define M(N) case N: launch_reduce_orders<N>(b, rant, m, resident, orders, ws, s); break;
         FRIRL_POLICY_NANT_CASES(M)
 #undef M
     }

@@ -538,6 +538,85 @@ int frirl_hip_reduce_batch_map(const frirl_hip_tables *t, const frirl_hip_ruleba
                                const frirl_hip_map_points *pts, int strategy, int32_t *kept, frirl_hip_reduce_map_result *results,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- rule usage on the policy map; the map-validated reduction over several candidate orders -------------------
+ * frirl_hip_rule_usage: how much the greedy policy of EVERY agent's rule base leans on each of its rules at the agent's points: batched
+ * FIVE_vag_concl_weight (FIVEVagConclWeight.c) at (point, greedy action).  For agent e with R = nrules[e] and existing point j (`pts`
+ * as in frirl_hip_policy_map: snapped the same way, the same `active` / `point_count` rules):
+ *   a*      the map's greedy action; best[e][j] equals frirl_hip_policy_map's value bit for bit, -1 for a point that does not exist
+ *   d2_r    the squared VE distance of rule r to (point, a*), in the operations and FMA chain of the map
+ *   w_r(j)  some d2_r == 0: 1 for the FIRST such rule (the one whose consequent the map returns), 0 for every other rule; otherwise
+ *           s_r / S with s_r the Shepard weight of d2_r (power agent->p, <= 0 = nant) and S = the sum of s_r accumulated by ONE lane in
+ *           ascending r -- the bits of the map's own weight sum -- then a division
+ *   sum     [dev] [E][maxR]: sum[e][r] = the sum over j of w_r(j), ONE lane, plain adds in ascending j;  peak [dev] [E][maxR] or NULL:
+ *           the maximum over j.  Entries r in [R, maxR) are written as 0; an agent with no existing point reads zeros
+ *   best    [dev] [E][n] or NULL
+ * An agent that is inactive or whose nrules lies outside 1..maxR has its sum / peak rows left untouched and its best row reads -1.
+ * A value depends on the rule base, the agent's point LIST (in its order) and p only -- not on E, n, the other agents or the launch
+ * shape.  Two launches: lane = (point, block of actions) for a*, S and the first hit; lane = rule (workgroups of 256 rules per agent)
+ * for the sums, the points walked from LDS tiles.  Option "reduce_map_resident" as for the map.  Asynchronous on `stream`; nothing is
+ * read back or allocated.
+ * FRIRL_HIP_EINVAL, before the device is looked for: the cases of frirl_hip_policy_map (best is not an argument), NULL out or out->sum,
+ * a workspace that is NULL, not 16-byte aligned or smaller than frirl_hip_rule_usage_workspace_bytes(nant, E, n).
+ * frirl_hip_rule_usage_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_rule_usage_out {   /* 24 bytes */
+    double  *sum;                 /* [dev] [E][maxR] */
+    double  *peak;                /* [dev] [E][maxR], or NULL */
+    int32_t *best;                /* [dev] [E][n], or NULL */
+} frirl_hip_rule_usage_out;
+size_t frirl_hip_rule_usage_workspace_bytes(int32_t nant, int32_t E, int32_t n);
+int frirl_hip_rule_usage(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_map_points *pts,
+                         const frirl_hip_rule_usage_out *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* frirl_hip_rule_order: every agent's rules in the STABLE order of their keys: rank(r) = #{q : key_q before key_r} + #{q < r : key_q ==
+ * key_r} over r, q < nrules[e], "before" = `<` (descending 0) or `>` (descending 1); NaN keys rank after every number and are stable
+ * among themselves.  order[e][rank] = r; the entries at and beyond nrules[e] are untouched, and so is the row of an agent that is
+ * inactive (active[e] == 0) or whose nrules lies outside 1..maxR.
+ *   keys    [dev] [E][maxR], or NULL = |Q| of the rule base (column nant): descending 0 / 1 is then the candidate order of strategy 1 / 2
+ *   order   [dev] [E][maxR] int32
+ * Of `b` E, maxR, rb and nrules are read.  One workgroup per agent, ranks by counting.  Asynchronous on `stream`.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL b / b->rb / b->nrules / order, E or maxR < 1, nant outside 2..8, descending
+ * other than 0 / 1. */
+int frirl_hip_rule_order(const frirl_hip_rulebases *b, int32_t nant, const double *keys /* [dev][E][maxR], NULL = |Q| of the rule base */,
+                         int descending, const uint8_t *active, int32_t *order /* [dev][E][maxR] */, void *stream);
+
+/* frirl_hip_reduce_batch_map_orders: frirl_hip_reduce_batch_map with the CALLER's candidate orders, K of them per agent at once; the
+ * order that leaves the fewest rules is applied (ties: the lowest k).  A removal order cannot be wrong -- any order preserves the map at
+ * every point -- but how many rules survive depends on it strongly, and no single order wins.
+ * Per agent e and per order k, independent of every other (agent, order):
+ *   trial      exactly frirl_hip_reduce_batch_map's: best0 = the map of the un-reduced rule base; candidate orders[e][k][j], j ascending,
+ *              is removed iff the map over the rules still present minus the candidate equals best0 at every existing point; the last
+ *              remaining rule is never tried; absent rules are SKIPPED.  The loop works on a private copy of the "removed" bytes in the
+ *              workspace: no rule base is written while the orders run.  One workgroup per (agent, order)
+ *   apply      one workgroup per agent: the best order's removals are compacted as frirl_hip_reduce_batch_map does: rb columns, rant,
+ *              uidx if present, nrules[e]; the vacated tail zeroed
+ * With K = 1 and orders = frirl_hip_rule_order(keys = NULL, descending = 0 / 1) everything the call leaves behind is bit-identical to
+ * frirl_hip_reduce_batch_map with strategy 1 / 2.
+ * Untouched agents: those of frirl_hip_reduce_batch_map (inactive, point_count[e] == 0, nrules[e] == 1): chosen -1, tries 0; their orders
+ * are not read.  An active agent with nrules outside 1..maxR, or an order of an active agent with points whose first nrules[e] entries are
+ * not a permutation of 0..nrules[e]-1: FRIRL_HIP_EINVAL naming the agent (and k), found on the device BEFORE any rule base is modified.
+ *   orders           [dev] [E][K][maxR] int32
+ *   kept             [host] [E][maxR] original index of each surviving rule (first results[e].rules_after entries), or NULL
+ *   results          [host] [E]
+ *   after_per_order  [host] [E][K] the rules order k alone leaves (rules_before for an untouched agent), or NULL
+ *   workspace        [dev] 16-byte aligned, >= frirl_hip_reduce_batch_map_orders_workspace_bytes(nant, E, maxR, n, K) bytes
+ * The call synchronises `stream` twice: after the check launch and for the results.  Option "reduce_map_resident" as above.
+ * FRIRL_HIP_EINVAL, before the device is looked for: the cases of frirl_hip_reduce_batch_map (no strategy), K outside
+ * 1..FRIRL_HIP_REDUCE_MAX_ORDERS, NULL orders, NULL results, E * K * n > INT32_MAX.
+ * frirl_hip_reduce_batch_map_orders_workspace_bytes: a multiple of 16, non-decreasing in every argument, 0 for a non-positive argument. */
+typedef struct frirl_hip_reduce_orders_result {   /* 24 bytes */
+    int32_t rules_before, rules_after;
+    int32_t points;               /* existing points the removals were validated at (0 for an inactive agent) */
+    int32_t chosen;               /* index k of the order that was applied; -1 for an untouched agent */
+    int32_t tries;                /* candidates tried by the chosen order */
+    int32_t reserved;
+} frirl_hip_reduce_orders_result;
+#define FRIRL_HIP_REDUCE_MAX_ORDERS 16
+size_t frirl_hip_reduce_batch_map_orders_workspace_bytes(int32_t nant, int32_t E, int32_t maxR, int32_t n, int32_t K);
+int frirl_hip_reduce_batch_map_orders(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, double *rant,
+                                      const frirl_hip_map_points *pts, int32_t K, const int32_t *orders /* [dev][E][K][maxR] */,
+                                      int32_t *kept /* HOST [E][maxR] or NULL */, frirl_hip_reduce_orders_result *results /* HOST [E] */,
+                                      int32_t *after_per_order /* HOST [E][K] or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 /* frirl_hip_log_points: every agent's de-duplicated list of the points its recorded roll-outs visited, from logs in the layout of
  * frirl_hip_rollout_log / frirl_hip_demonstration (agent_stride = T); logs q = e * n_logs + j belong to agent e.
  * A start record (start != 0) contributes obs, the un-quantised start; every other record contributes q_obs: the observations the
@@ -1155,6 +1234,17 @@ typedef struct frirl_hip_reduce_map_totals {
 int frirl_hip_batch_reduce_all_map(frirl_hip_batch *b, int strategy, int32_t n, const double *start_states /* HOST [E][n][nant-1]; NULL: n must be 1, every agent's own start */,
                                    int only_successful, int32_t cap /* 0 = 512 */, frirl_hip_reduce_map_result *results /* HOST [E] or NULL */,
                                    frirl_hip_reduce_map_totals *totals /* or NULL */);
+/* frirl_hip_batch_reduce_all_map with the reduction over several candidate orders (frirl_hip_reduce_batch_map_orders): order_set is a
+ * non-empty subset of 1 = |Q| ascending, 2 = |Q| descending, 4 = usage sum ascending (least-used first), 8 = usage sum descending; order
+ * k is the k-th set bit from the lowest.  After the roll-out of the points: frirl_hip_rule_usage (only with bit 4 or 8) at the agents'
+ * points, frirl_hip_rule_order per set bit, frirl_hip_reduce_batch_map_orders.  Overflowing agents, agents without points, the
+ * convergence state, the index mirror, allocation and synchronisation: as frirl_hip_batch_reduce_all_map.  With order_set == 1 the batch
+ * afterwards equals that of frirl_hip_batch_reduce_all_map(strategy 1) bit for bit.  results: HOST [E] or NULL (an overflowing agent
+ * reads rules_after == rules_before, points 0, chosen -1, tries 0); after_per_order: HOST [E][popcount(order_set)] or NULL.
+ * FRIRL_HIP_EINVAL: the cases of frirl_hip_batch_reduce_all_map (no strategy), order_set outside 1..15. */
+int frirl_hip_batch_reduce_all_map_orders(frirl_hip_batch *b, int order_set, int32_t n, const double *start_states, int only_successful, int32_t cap,
+                                          frirl_hip_reduce_orders_result *results /* HOST [E] or NULL */,
+                                          int32_t *after_per_order /* HOST [E][popcount] or NULL */, frirl_hip_reduce_map_totals *totals /* or NULL */);
 /* Greedy roll-outs of EVERY agent of the batch on its own rule base from n start states each (frirl_hip_rollout_batch with
  * agent.no_random = 1): which of the agents is any good away from the start state it trained on.  Row 0 .. n-1 of agent e start at
  * start_states[e][0 .. n-1]; NULL = every row at the agent's own start (its desc.start_states row, agent.values_def where the batch
