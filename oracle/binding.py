@@ -24,7 +24,9 @@ class OrcFive(C.Structure):
     _fields_ = [("nant", C.c_int), ("U", C.c_int), ("p", C.c_int), ("R", C.c_int), ("maxR", C.c_int),
                 ("u", c_double_p), ("ve", c_double_p), ("udivs", C.c_double * MAX_NANT),
                 ("rant", c_double_p), ("veval", c_double_p), ("uidx", c_u32_p), ("rconc", c_double_p),
-                ("ruledists", c_double_p), ("weights", c_double_p), ("wi", c_double_p)]
+                ("ruledists", c_double_p), ("weights", c_double_p), ("wi", c_double_p),
+                ("spreads", C.c_long), ("spread_moved_max", C.c_int), ("spread_moved_min", C.c_int), ("spread_lane_max", C.c_int),
+                ("spread_rules", C.c_long), ("outside_rules", C.c_long)]
 
 
 class OrcDim(C.Structure):
@@ -92,6 +94,7 @@ def lib():
         "orc_frirl_ep_steps": (i, [vp]),
         "orc_frirl_ep_reward": (d, [vp]),
         "orc_frirl_hparams": (None, [vp, c_double_p]),
+        "orc_frirl_set_hparams": (None, [vp, c_double_p]),
         "orc_frirl_set_trace": (None, [vp, vp]),
         "orc_frirl_set_exploration": (None, [vp, d, i, u64, u64, C.c_uint]),
         "orc_frirl_rng_episode": (C.c_uint, [vp]),
@@ -219,6 +222,15 @@ class Five:
     @property
     def maxR(self):
         return self.c.maxR
+
+    @property
+    def spread_stats(self):
+        """update_rules' spreads on this rule base so far: how many, the most and the fewest rules one of them wrote, and the most it
+        wrote in one lane's stride of a 64-lane sweep (rules r with r % 128 in {2l, 2l + 1}); the rule count summed over the spreads, and
+        over the updates whose qdiff lay outside the insertion bounds."""
+        c = self.c
+        return dict(spreads=c.spreads, moved_max=c.spread_moved_max, moved_min=c.spread_moved_min, lane_max=c.spread_lane_max,
+                    spread_rules=c.spread_rules, outside_rules=c.outside_rules)
 
     def remove_rule(self, r):
         return lib().orc_remove_rule(self.h, int(r))
@@ -365,6 +377,17 @@ class Frirl:
         lib().orc_frirl_hparams(self.h, dp(out))
         return dict(alpha=out[0], gamma=out[1], qdiff_pos=out[2], qdiff_neg=out[3], weight_thr=out[4],
                     skip_rules=int(out[5]), reward_good_above=out[6], qdiff_final_tolerance=out[7])
+
+    HPARAM_KEYS = ("alpha", "gamma", "qdiff_pos", "qdiff_neg", "weight_thr", "skip_rules", "reward_good_above", "qdiff_final_tolerance")
+
+    def set_hparams(self, **kw):
+        """Override any of the fields of `hparams` from the next update on; the others keep their values."""
+        hp = self.hparams
+        unknown = set(kw) - set(self.HPARAM_KEYS)
+        assert not unknown, f"unknown hyper-parameters {sorted(unknown)}"
+        hp.update(kw)
+        v = np.array([float(hp[k]) for k in self.HPARAM_KEYS])
+        lib().orc_frirl_set_hparams(self.h, dp(v))
 
     def agent(self):
         hp = self.hparams

@@ -804,12 +804,18 @@ static void orc_update_rules(orc_five *f, const orc_agent *ag, double *fus, cons
     double save = 0;
     if (ag->skip_rules == 0) *fus = 0;                                            /* :70-73 */
     else save = f->rconc[f->R - 1];                                               /* :76 */
+    int moved = 0, lane[64] = { 0 }, lane_max = 0;
     for (int r = 0; r < f->R; r++)                                                /* K7, :89-120 */
         if (f->weights[r] > ag->weight_significant) {
             double t = qdiff * f->weights[r];
             f->rconc[r] = qnow + t;
+            if (!(*fus && r == f->R - 1)) { moved++; if (++lane[(r % 128) / 2] > lane_max) lane_max = lane[(r % 128) / 2]; }
         }
     if (*fus) f->rconc[f->R - 1] = save;                                          /* :124-126 */
+    if (f->spreads++ == 0 || moved < f->spread_moved_min) f->spread_moved_min = moved;
+    if (moved > f->spread_moved_max) f->spread_moved_max = moved;
+    if (lane_max > f->spread_lane_max) f->spread_lane_max = lane_max;
+    f->spread_rules += f->R;
 }
 
 /* src/frirl/frirl_update_sarsa.c:348-385 (check_possible_states :146-170, CHECK_STATES = 1).
@@ -823,6 +829,7 @@ void orc_five_update_sarsa(orc_five *f, const orc_agent *ag, double *fus, const 
     double qdiff = ag->alpha * (reward + ag->gamma * qp - qnow);
     if (qdiff > ag->qdiff_pos_boundary || qdiff < ag->qdiff_neg_boundary) {
         double rant[ORC_MAX_NANT], rconc = qnow;
+        f->outside_rules += f->R;
         for (int i = 0; i < n; i++) rant[i] = orc_check_possible_states(q_ant[i], ag->grid[i], ag->grid_len[i]);
         rule_i = orc_vag_concl(f, rant, &rconc);
         if (rule_i == ~0u) {
@@ -1101,6 +1108,13 @@ void orc_frirl_hparams(orc_frirl *fr, double *out8)
 {
     out8[0] = fr->alpha; out8[1] = fr->gamma; out8[2] = fr->qdiff_pos_boundary; out8[3] = fr->qdiff_neg_boundary;
     out8[4] = fr->weight_significant; out8[5] = (double)fr->skip_rules; out8[6] = fr->reward_good_above; out8[7] = fr->qdiff_final_tolerance;
+}
+
+/* same layout as orc_frirl_hparams; takes effect from the next update (the agent description is rebuilt per call) */
+void orc_frirl_set_hparams(orc_frirl *fr, const double in8[8])
+{
+    fr->alpha = in8[0]; fr->gamma = in8[1]; fr->qdiff_pos_boundary = in8[2]; fr->qdiff_neg_boundary = in8[3];
+    fr->weight_significant = in8[4]; fr->skip_rules = (int)in8[5]; fr->reward_good_above = in8[6]; fr->qdiff_final_tolerance = in8[7];
 }
 
 /* whole construct-mode demo: returns 1 when the rule base converged */

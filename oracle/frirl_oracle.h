@@ -47,6 +47,12 @@ typedef struct orc_five {
     double *ruledists;     /* [maxR] */
     double *weights;       /* [maxR] */
     double *wi;            /* [maxR] */
+    /* counters of update_rules' spread (checker bookkeeping, not the reference's): spreads so far, the most and the fewest rules one
+     * of them wrote, and the most it wrote among the rules r with r % 128 in {2l, 2l + 1} for one l (one lane of a 64-lane sweep) */
+    long spreads;
+    int spread_moved_max, spread_moved_min, spread_lane_max;
+    long spread_rules;     /* sum of the rule count over the spreads */
+    long outside_rules;    /* sum of the rule count over the updates whose qdiff lay outside the insertion bounds */
 } orc_five;
 
 /* ---- init-time tables ----------------------------------------------------- */
@@ -193,6 +199,7 @@ unsigned orc_frirl_episode_num(orc_frirl *fr);
 int orc_frirl_ep_steps(orc_frirl *fr);
 double orc_frirl_ep_reward(orc_frirl *fr);
 void orc_frirl_hparams(orc_frirl *fr, double *out8);
+void orc_frirl_set_hparams(orc_frirl *fr, const double in8[8]);      /* same layout; the callers' to choose, as frirl_desc's fields are */
 void orc_frirl_set_exploration(orc_frirl *fr, double epsilon, int no_random, uint64_t seed, uint64_t env_id, unsigned episode);
 unsigned orc_frirl_rng_episode(orc_frirl *fr);
 int orc_frirl_success(orc_frirl *fr);                       /* reward.success of the last step */

@@ -18,6 +18,9 @@ reference's exported C API and each example's own main().  What is committed is 
   tests/golden/merge_<env>.jsonl      multi-agent rule-base merge (frirl_agent.c merge_rb / gen_def_states / omp_init, compiled with
                                       BUILD_OPENMP by oracle/_ref/ref_merge_harness): master and agent rule bases before and
                                       after merging in both directions
+  tests/golden/hparams/<env>_<set>.trace.jsonl, .frirlrb.txt   a few episodes of the reference with its SARSA hyper-parameters
+                                      overridden (ref_harness demo_hp; the sets and cases are tests/hparams_cases.py REF_CASES):
+                                      per-episode records with the running step hash, and the rule base reached
   tests/golden/synth_*.jsonl          hashes for large synthetic rule bases (inputs are re-created
                                       in the tests by oracle orc_synth_*; nant <= 8 only, the
                                       reference's cap is FIVE_MAX_NUM_OF_UNIVERSES = 8); synth_*_p<p>.jsonl: the same
@@ -54,10 +57,27 @@ def run(*cmd, **kw):
     subprocess.run(cmd, check=True, **kw)
 
 
+def hparams_fixtures(tmp):
+    """The reference's runs off the demos' hyper-parameters.  The values go to the harness as C hex-floats, so both sides hold the same bits."""
+    sys.path.insert(0, ROOT)
+    from tests import hparams_cases as hc
+    out = os.path.join(GOLD, "hparams")
+    os.makedirs(out, exist_ok=True)
+    for env, name, nep in hc.REF_CASES:
+        a, g, qp, qn, w, skip = hc.ref_case_values(env, name)
+        with open(os.path.join(tmp, f"{env}.hstdout"), "w") as so:
+            run(HARNESS, "demo_hp", env, tmp, str(nep), float(a).hex(), float(g).hex(), float(qp).hex(), float(qn).hex(), float(w).hex(), str(int(skip)), stdout=so)
+        shutil.copyfile(os.path.join(tmp, f"{env}.frirlrb.txt"), os.path.join(out, f"{env}_{name}.frirlrb.txt"))
+        shutil.copyfile(os.path.join(tmp, f"{env}.hp.trace.jsonl"), os.path.join(out, f"{env}_{name}.trace.jsonl"))
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("reference tree not found: golden vectors can only be regenerated in the build container")
     run("make", "-C", HERE)
+    if "--hparams-only" in sys.argv:
+        os.makedirs("/tmp/frirl_golden", exist_ok=True)
+        return hparams_fixtures("/tmp/frirl_golden")
     os.makedirs(os.path.join(GOLD, "orig"), exist_ok=True)
     for e in ENVS:
         shutil.copyfile(os.path.join(REF, "tests", "orig", f"frirl_example_{e}.frirlrb.txt"),
@@ -92,6 +112,7 @@ def main():
             f.write(json.dumps({"k": "stdout_counts", "episode_lines": txt.count("Episode:"), "pended_lines": txt.count("pended")}) + "\n")
     if "--merge-only" in sys.argv:
         return
+    hparams_fixtures(tmp)
     for (nant, U, R, A, seed, nq) in SYNTH:
         run(HARNESS, "synth", str(nant), str(U), str(R), str(A), str(seed), str(nq),
             os.path.join(GOLD, f"synth_n{nant}_u{U}_r{R}.jsonl"))

@@ -17,6 +17,9 @@
  *   synth   <nant> <U> <R> <A> <seed> <nq> <outfile> [p]   large synthetic bases (inputs from orc_synth_*); p = Shepard power of
  *                                     the queries (omitted or 0: the reference's default p = nant, header without a "p" field)
  *   bench   <nant> <U> <R> <nq>       times five_rule_distance / FIVE_vag_concl (cpu_baseline "reference")
+ *   demo_hp <env> <outdir> <nep> <alpha> <gamma> <qpos> <qneg> <wthr> <skip>
+ *                                     as demo, with the SARSA hyper-parameters of the reference-built frirl_desc overridden and at
+ *                                     most <nep> episodes; no step records, files <env>.hp.trace.jsonl and <env>.frirlrb.txt
  *   reduce  <env> <outdir> <strategy> construct run, then the reference's rule-base reduction
  *                                     (frirl_sequential_run.c:170-350) on the result; <env>.reduced<strategy>.frirlrb.txt
  */
@@ -49,6 +52,8 @@ static int g_nstates;
 #ifndef TRACE_STEPS
 #define TRACE_STEPS 400
 #endif
+static long g_trace_steps = TRACE_STEPS;
+static double g_hp[6];          /* demo_hp: alpha, gamma, qdiff_pos, qdiff_neg, weight threshold, skip_rules */
 
 static void (*o_do_action)(struct frirl_desc *, fri_float, fri_float *, int, fri_float *);
 static void (*o_get_reward)(struct frirl_desc *, fri_float *, int, struct frirl_reward_desc *);
@@ -78,7 +83,7 @@ static void w_do_action(struct frirl_desc *fr, fri_float a, fri_float *s, int n,
     o_do_action(fr, a, s, n, ns);
     g_hash = orc_hash_doubles(g_hash, &a, 1);
     g_hash = orc_hash_doubles(g_hash, ns, n);
-    if (g_step < TRACE_STEPS) { fprintf(g_fp, "{\"k\":\"step\",\"t\":%ld,\"ep\":%d,\"a\":", g_step, g_ep); jd(g_fp, a); fputc(',', g_fp); jarr(g_fp, "s", ns, n); }
+    if (g_step < g_trace_steps) { fprintf(g_fp, "{\"k\":\"step\",\"t\":%ld,\"ep\":%d,\"a\":", g_step, g_ep); jd(g_fp, a); fputc(',', g_fp); jarr(g_fp, "s", ns, n); }
 }
 
 static void w_get_reward(struct frirl_desc *fr, fri_float *s, int n, struct frirl_reward_desc *rw)
@@ -87,7 +92,7 @@ static void w_get_reward(struct frirl_desc *fr, fri_float *s, int n, struct frir
     double rs[2] = { rw->value, (double)rw->success };
     g_hash = orc_hash_doubles(g_hash, rs, 2);
     g_ep_reward += rw->value;
-    if (g_step < TRACE_STEPS) { fprintf(g_fp, ",\"r\":"); jd(g_fp, rw->value); fprintf(g_fp, ",\"f\":%d", rw->success); }
+    if (g_step < g_trace_steps) { fprintf(g_fp, ",\"r\":"); jd(g_fp, rw->value); fprintf(g_fp, ",\"f\":%d", rw->success); }
 }
 
 static void w_quant(struct frirl_desc *fr, fri_float *s, int n, fri_float *ns)
@@ -96,7 +101,7 @@ static void w_quant(struct frirl_desc *fr, fri_float *s, int n, fri_float *ns)
     double nr = (double)fr->fiverb->numofrules;
     g_hash = orc_hash_doubles(g_hash, ns, n);
     g_hash = orc_hash_doubles(g_hash, &nr, 1);
-    if (g_step < TRACE_STEPS) { fputc(',', g_fp); jarr(g_fp, "q", ns, n); fprintf(g_fp, ",\"R\":%d}\n", fr->fiverb->numofrules); }
+    if (g_step < g_trace_steps) { fputc(',', g_fp); jarr(g_fp, "q", ns, n); fprintf(g_fp, ",\"R\":%d}\n", fr->fiverb->numofrules); }
     g_step++; g_ep_steps++;
 }
 
@@ -299,7 +304,12 @@ void harness_run(struct frirl_desc *fr, int verbose)
         fr->reduce_rb = 0;
         return;
     }
-    if (!strcmp(g_mode, "demo")) {
+    if (!strcmp(g_mode, "demo_hp")) {
+        fr->alpha = g_hp[0]; fr->gamma = g_hp[1]; fr->qdiff_pos_boundary = g_hp[2]; fr->qdiff_neg_boundary = g_hp[3];
+        fr->rule_weight_considered_significant_for_update = g_hp[4]; fr->skip_rules = (unsigned char)g_hp[5];
+        fr->max_episodes = g_nep + 1;             /* at most max_episodes-1 episodes run */
+    }
+    if (!strcmp(g_mode, "demo") || !strcmp(g_mode, "demo_hp")) {
         fr->do_action_func = w_do_action; fr->get_reward_func = w_get_reward; fr->quant_obs_func = w_quant;
         fprintf(g_fp, "{\"k\":\"hdr\",\"env\":\"%s\",\"nstates\":%d,\"A\":%d,\"U\":%d}\n", g_env, fr->statedims_len,
                 fr->actiondim.values_len, fr->statedims[0].universe_len);
@@ -411,6 +421,13 @@ int main(int argc, char **argv)
     if (!strcmp(g_mode, "demo")) {
         if (chdir(g_out) != 0) { perror("chdir"); return 1; }
         char p[256]; snprintf(p, sizeof p, "%s.trace.jsonl", g_env);
+        g_fp = fopen(p, "w");
+    } else if (!strcmp(g_mode, "demo_hp")) {
+        if (argc < 11) return 2;
+        g_nep = atoi(argv[4]); g_trace_steps = 0;
+        for (int i = 0; i < 6; i++) g_hp[i] = strtod(argv[5 + i], NULL);      /* strtod reads C hex-floats too */
+        if (chdir(g_out) != 0) { perror("chdir"); return 1; }
+        char p[256]; snprintf(p, sizeof p, "%s.hp.trace.jsonl", g_env);
         g_fp = fopen(p, "w");
     } else if (!strcmp(g_mode, "reduce")) {
         if (argc < 5) return 2;

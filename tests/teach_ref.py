@@ -14,6 +14,7 @@ import numpy as np
 
 import frirl_amd
 from oracle import binding as ob
+from tests import hparams_cases
 from tests.test_hip_external import Mirror, PointEnv, generic_quantize, point_desc
 
 INACTIVE, EXACT, SPREAD, INSERTED, SKIPPED, FULL = (frirl_amd.UPD_INACTIVE, frirl_amd.UPD_EXACT, frirl_amd.UPD_SPREAD, frirl_amd.UPD_INSERTED,
@@ -47,25 +48,9 @@ class TaughtMirror(Mirror):
         """One frirl_update_sarsa with the capacity rule of the device: an append at a full rule base is refused and changes nothing
         (FRIRL_HIP_UPD_FULL).  Returns the status the device reports; the update itself is the oracle's."""
         f, oa = self.five, self.oa
-        _, qp = f.vag_concl(cur_q_ant)
-        hit, qnow = f.vag_concl(q_ant)
-        qdiff = oa.alpha * (reward + oa.gamma * qp - qnow)
-        fus = self.fus
-        if qdiff > oa.qdiff_pos or qdiff < oa.qdiff_neg:
-            snapped = [ob.lib().orc_check_possible_states(float(q_ant[i]), ob.dp(oa.grids[i]), len(oa.grids[i])) for i in range(len(q_ant))]
-            if f.vag_concl(snapped)[0] < 0:
-                if f.R >= f.maxR:
-                    return FULL
-                self.fus = f.update_sarsa(oa, self.fus, q_ant, reward, cur_q_ant)
-                return INSERTED
-            fus = 0
-        rules = f.R - (1 if fus else 0)
-        if hit >= 0 and (oa.skip_rules == 0 or hit < rules):
-            status = EXACT
-        elif oa.skip_rules == 1 and hit >= 0 and hit == rules:
-            status = SKIPPED
-        else:
-            status = SPREAD
+        status = hparams_cases.classify(f, oa, self.fus, q_ant, reward, cur_q_ant)
+        if status == INSERTED and f.R >= f.maxR:
+            return FULL
         self.fus = f.update_sarsa(oa, self.fus, q_ant, reward, cur_q_ant)
         return status
 
@@ -159,10 +144,12 @@ POINT_MAX_STEPS = 60
 
 
 @functools.lru_cache(maxsize=None)
-def point_case(nant, A, E=8, maxR=512, seed=0):
+def point_case(nant, A, E=8, maxR=512, seed=0, hparams="default"):
     """PointEnv logs of a proportional controller with seeded deviations: (description, logs).  The controller takes the action that
-    brings the next state closest to the origin; one pick in seven is a seeded random action instead."""
-    d = dict(point_desc(nant, A), max_steps=POINT_MAX_STEPS)
+    brings the next state closest to the origin; one pick in seven is a seeded random action instead.  hparams: a set of
+    tests/hparams_cases.py applied to the description (the logs are the scripted teacher's and do not depend on it)."""
+    base = point_desc(nant, A)
+    d = dict(base, max_steps=POINT_MAX_STEPS, **hparams_cases.overrides(hparams, base, point=True))
     env, av, ns = PointEnv(nant - 1), point_desc(nant, A)["grids"][-1], nant - 1
     gain = np.array(env.gain)
     writers = []

@@ -227,9 +227,10 @@ class Mirror:
 EXPLORE = dict(epsilon=0.2, seed=4321, env_id_base=2 ** 32 - 5)      # the batch's global ids cross 2^32
 
 
-def new_shape_case(nant, A, p=0, explore=None):
-    """Description, environment, start states and the oracle mirrors of one new-shape case (no GPU needed)."""
-    d = point_desc(nant, A)
+def new_shape_case(nant, A, p=0, explore=None, override=None):
+    """Description, environment, start states and the oracle mirrors of one new-shape case (no GPU needed).  override: fields of the
+    description to replace (hyper-parameters: alpha, gamma, qdiff_pos, qdiff_neg, weight_thr, skip_rules)."""
+    d = dict(point_desc(nant, A), **(override or {}))
     E, maxR = 16, 1024
     starts = np.ascontiguousarray(np.random.default_rng(nant * 100 + A).uniform(-0.9, 0.9, (E, nant - 1)))
     base = explore["env_id_base"] if explore else 0
@@ -270,9 +271,9 @@ def test_new_shapes_explore_and_follow_the_oracle(nant, A):
     assert sum(m.changed for m in mirrors) >= 10
 
 
-def follow_the_oracle(nant, A, p, explore=None):
+def follow_the_oracle(nant, A, p, explore=None, override=None, tol=1e-6):
     import torch
-    d, env, starts, mirrors = new_shape_case(nant, A, p, explore=explore)
+    d, env, starts, mirrors = new_shape_case(nant, A, p, explore=explore, override=override)
     E, maxR, episodes = 16, 1024, 4
     kw = dict(epsilon=explore["epsilon"], no_random=0, seed=explore["seed"], env_id_base=explore["env_id_base"]) if explore else {}
     prob, agent, envs = frirl_amd.fresh_batch(d, E, maxR, DEV, p=p, **kw)
@@ -308,7 +309,7 @@ def follow_the_oracle(nant, A, p, explore=None):
             assert int(nrules[e]) == R, (nant, A, ep, e)
             assert (rant[e, :, :R] == np.array(m.five.rant[:R]).T).all()
             q, ref = rb[e, nant, :R], np.array(m.five.rconc[:R])
-            assert (np.abs(q - ref) <= 1e-6 * np.maximum(np.abs(ref), 1e-9)).all()
+            assert (np.abs(q - ref) <= tol * np.maximum(np.abs(ref), 1e-9)).all()
             assert int(envs.fus[e]) == int(m.fus)
             assert int(conv.converged[e]) == int(m.converged), (nant, A, ep, e)
     return mirrors

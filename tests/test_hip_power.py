@@ -480,7 +480,7 @@ def test_update_sarsa_rounds(env, episodes, p):
 
 
 # ---- frirl_hip_weights_from_spread and frirl_hip_merge_rb ------------------------------------------------------------------------
-def merge_case(nant, p):
+def merge_case(nant, p, weight_thr=0.05):
     """Two synthetic receivers of about 100 rules (one odd count), a rule grid of every 4th universe point, S = 12 sender rules: ten from
     another synthetic base, two copies of receiver 0's rules (exact hits leave the weights array as it is).  No GPU needed."""
     U, R, S = 41, 100, 12
@@ -492,7 +492,7 @@ def merge_case(nant, p):
     srconc = np.ascontiguousarray(snd.rb[0, nant, :S])
     for j, r in ((3, 7), (9, R - 2)):
         srant[j] = b.u[np.arange(nant), b.uidx[0, :, r]]
-    hp = dict(alpha=0.5, gamma=1.0, qdiff_pos=800.0, qdiff_neg=-800.0, weight_thr=0.05, skip_rules=1)
+    hp = dict(alpha=0.5, gamma=1.0, qdiff_pos=800.0, qdiff_neg=-800.0, weight_thr=weight_thr, skip_rules=1)
     oag = ob.Agent(hp["alpha"], hp["gamma"], hp["qdiff_pos"], hp["qdiff_neg"], hp["weight_thr"], hp["skip_rules"], grids)
     rng = np.random.default_rng(nant)
     spread = np.ascontiguousarray(np.array([[rng.uniform(b.u[k, 0], b.u[k, -2]) for k in range(nant)] for _ in range(2)]))

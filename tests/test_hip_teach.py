@@ -23,8 +23,8 @@ DEV = "cuda"
 CONTRACT = 1e-6       # |q - ref| <= 1e-6 * max(|ref|, 1e-9): the project's contract for interpolated values (test_hip_external.py)
 
 
-def within_contract(q, ref):
-    return np.abs(q - ref) <= CONTRACT * np.maximum(np.abs(ref), 1e-9)
+def within_contract(q, ref, tol=CONTRACT):
+    return np.abs(q - ref) <= tol * np.maximum(np.abs(ref), 1e-9)
 
 
 # ---- 1, 2: the taught entry points without a teacher's say --------------------------------------------------------------------
@@ -194,7 +194,7 @@ def replay_and_chain(d, log, maxR, where, p=0, passes=1, q_obs=True, start=True,
 
 
 # ---- 3: forced actions against the oracle -------------------------------------------------------------------------------------
-def assert_matches_mirrors(d, prob, envs, mirrors, where, statuses=True):
+def assert_matches_mirrors(d, prob, envs, mirrors, where, statuses=True, tol=CONTRACT):
     nant = d["nant"]
     rant, rb, nrules = envs.rant.cpu().numpy(), prob.rb.cpu().numpy(), prob.nrules.cpu().numpy()
     steps, reward, status, fus, done, episode = (x.cpu().numpy() for x in (envs.ep_steps, envs.ep_reward, envs.status, envs.fus, envs.done, envs.episode))
@@ -205,7 +205,7 @@ def assert_matches_mirrors(d, prob, envs, mirrors, where, statuses=True):
         assert int(steps[e]) == m.steps and float(reward[e]) == m.total and int(done[e]) == m.done and int(episode[e]) == m.episode_no, (where, e)
         assert int(fus[e]) == int(m.fus) and (not statuses or int(status[e]) == m.status), (where, e)
         q, ref = rb[e, nant, :R], np.array(m.five.rconc[:R])
-        assert within_contract(q, ref).all(), (where, e)
+        assert within_contract(q, ref, tol).all(), (where, e)
 
 
 FORCED = [(2, 3, 0), (2, 11, 0), (4, 3, 0), (4, 11, 0), (6, 3, 0), (6, 11, 0), (8, 3, 0), (8, 11, 0), (3, 32, 0), (4, 11, 2)]
