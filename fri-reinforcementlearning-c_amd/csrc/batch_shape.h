@@ -33,3 +33,41 @@ static int rb_slices(long rows, int A)
     const long rows8 = rb_resident_rows(A);
     return rows <= rows8 ? 8 : (rows <= 2 * rows8 ? 4 : 1);
 }
+
+// rule slices of a tiled batched roll-out of n rows on each of E agents (rollout_batch.hip's tiled form, the recorded and the
+// point-keeping roll-out): rb_slices on the rows of the whole call; one row per agent: a full wave per row.  `forced` (an option's
+// value, 0 = none) overrides it with 1 / 4 / 8, or 16 for up to 4 actions.
+static int rb_rollout_slices(int E, int n, int A, int forced)
+{
+    if (forced == 1 || forced == 4 || forced == 8 || (forced == 16 && A <= 4)) return forced;
+    return n == 1 ? FRIRL_WAVE / rb_group(A) : rb_slices((long)E * n, A);
+}
+
+// ---- argument checks of the entry points (no device is looked at) ----
+// a caller's workspace: refused when NULL, not 16-byte aligned or smaller than `need`; query = the function that tells the size
+static int check_workspace(const char *who, const void *workspace, size_t bytes, size_t need, const char *query)
+{
+    if (workspace && !(reinterpret_cast<uintptr_t>(workspace) & 15) && bytes >= need) return FRIRL_HIP_OK;
+    frirl_host::set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (%s)", who, workspace, bytes, need, query);
+    return FRIRL_HIP_EINVAL;
+}
+
+// The agent of a roll-out in one of the demo environments (frirl_hip_rollout_batch, _record, _points), in the two places the entry
+// points refuse it: first that it, its grids and the call's descriptor (desc: with the arrays it must name) are there, and, behind
+// the descriptor's own refusals, its ranges, environment kind and grid lengths.
+static int check_rollout_agent_null(const frirl_hip_agent *agent, bool desc, const char *who)
+{
+    if (agent && desc && agent->grid_values && agent->action_ve) return FRIRL_HIP_OK;
+    frirl_host::set_error("%s: NULL argument", who);
+    return FRIRL_HIP_EINVAL;
+}
+
+static int check_rollout_agent(const frirl_hip_tables *t, const frirl_hip_agent *agent, const char *who)
+{
+    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) {
+        frirl_host::set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps);
+        return FRIRL_HIP_EINVAL;
+    }
+    const int rc = frirl_host::check_demo_kind(t, agent, who);
+    return rc ? rc : frirl_host::check_grid_len(t, agent, who);
+}

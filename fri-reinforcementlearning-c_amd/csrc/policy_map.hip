@@ -76,7 +76,7 @@ __global__ __launch_bounds__(LP_BLOCK) void log_points_dedup_kernel(const frirl_
     __shared__ uint64_t cand[LP_BLOCK][NS];
     __shared__ uint8_t ctake[LP_BLOCK];
     __shared__ int wave_new[LP_BLOCK / FRIRL_WAVE];
-    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & (FRIRL_WAVE - 1), wave = tid / FRIRL_WAVE;
+    const int e = blockIdx.x, tid = threadIdx.x;
     const long N = (long)lp.n_logs * lp.T;
     const size_t q0 = (size_t)e * lp.n_logs;
     uint64_t *list = reinterpret_cast<uint64_t *>(lp.points) + (size_t)e * lp.cap * NS;
@@ -112,18 +112,12 @@ __global__ __launch_bounds__(LP_BLOCK) void log_points_dedup_kernel(const frirl_
             for (int k = 0; k < NS; k++) same = same && cand[i][k] == x[k];
             fresh = !same;
         }
-        const unsigned long long bal = __ballot(fresh);
-        if (lane == 0) wave_new[wave] = __popcll(bal);
-        __syncthreads();
-        int pos = count + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
-        for (int i = 0; i < LP_BLOCK / FRIRL_WAVE; i++) { pos += i < wave ? wave_new[i] : 0; tot += wave_new[i]; }
+        const int pos = block_append<LP_BLOCK>(fresh, wave_new, lp.cap, count, over);
         if (fresh && pos < lp.cap) {
 #pragma unroll
             for (int k = 0; k < NS; k++) list[(size_t)pos * NS + k] = x[k];
         }
-        over |= count + tot > lp.cap ? 1 : 0;
-        count = count + tot > lp.cap ? lp.cap : count + tot;
-        __syncthreads();                                               // cand / ctake / wave_new are rewritten by the next chunk
+        __syncthreads();                                              // cand / ctake / wave_new are rewritten by the next chunk
     }
     if (tid == 0) { lp.point_count[e] = count; lp.overflow[e] = over; }
 }
@@ -175,7 +169,7 @@ extern "C" int frirl_hip_policy_map(const frirl_hip_tables *t, const frirl_hip_r
     int rc = check_map_args(who, t, b, agent, pts, &m);
     if (rc) return rc;
     if (!best) { set_error("%s: NULL best", who); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_map_workspace(who, workspace, workspace_bytes, frirl_hip_policy_map_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_policy_map_workspace_bytes")) ||
+    if ((rc = check_workspace(who, workspace, workspace_bytes, frirl_hip_policy_map_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_policy_map_workspace_bytes")) ||
         (rc = check_device()))
         return rc;
     const int resident = opts().reduce_map_resident != 0;
@@ -198,7 +192,7 @@ extern "C" int frirl_hip_reduce_batch_map(const frirl_hip_tables *t, const frirl
     if (!results) { set_error("%s: NULL results", who); return FRIRL_HIP_EINVAL; }
     if (strategy != 1 && strategy != 2) { set_error("%s: strategy %d (1 = smallest |Q| first, 2 = largest |Q| first)", who, strategy); return FRIRL_HIP_EINVAL; }
     const size_t need = frirl_hip_reduce_batch_map_workspace_bytes(t->nant, b->E, b->maxR, pts->n);
-    if ((rc = check_map_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_workspace_bytes")) || (rc = check_device())) return rc;
+    if ((rc = check_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_workspace_bytes")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     const size_t E = (size_t)b->E, M = (size_t)b->maxR;
     ReduceMapWs ws;
@@ -229,7 +223,7 @@ extern "C" int frirl_hip_reduce_batch_map_orders(const frirl_hip_tables *t, cons
     if (K < 1 || K > FRIRL_HIP_REDUCE_MAX_ORDERS) { set_error("%s: K=%d orders outside 1..%d", who, K, FRIRL_HIP_REDUCE_MAX_ORDERS); return FRIRL_HIP_EINVAL; }
     if ((long long)b->E * K * pts->n > INT32_MAX) { set_error("%s: E=%d x K=%d x n=%d beyond 2^31 - 1", who, b->E, K, pts->n); return FRIRL_HIP_EINVAL; }
     const size_t need = frirl_hip_reduce_batch_map_orders_workspace_bytes(t->nant, b->E, b->maxR, pts->n, K);
-    if ((rc = check_map_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_orders_workspace_bytes")) || (rc = check_device())) return rc;
+    if ((rc = check_workspace(who, workspace, workspace_bytes, need, "frirl_hip_reduce_batch_map_orders_workspace_bytes")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     const size_t E = (size_t)b->E, M = (size_t)b->maxR;
     ReduceOrdersWs ws;
@@ -266,7 +260,7 @@ extern "C" int frirl_hip_log_points(const frirl_hip_log_points_desc *lp, void *w
         set_error("%s: E * n_logs * T or E * cap beyond 2^31 - 1", who);
         return FRIRL_HIP_EINVAL;
     }
-    int rc = check_map_workspace(who, workspace, workspace_bytes, frirl_hip_log_points_workspace_bytes(lp->E, lp->n_logs, lp->T), "frirl_hip_log_points_workspace_bytes");
+    int rc = check_workspace(who, workspace, workspace_bytes, frirl_hip_log_points_workspace_bytes(lp->E, lp->n_logs, lp->T), "frirl_hip_log_points_workspace_bytes");
     if (rc || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     uint8_t *take = static_cast<uint8_t *>(workspace);

@@ -34,14 +34,11 @@ __global__ __launch_bounds__(SH_BLOCK) void reduce_batch_rollout_kernel(const do
     const int node = row0 + threadIdx.x / GH;
     const bool exists = node < n;                                      // nodes with k >= d_e do not exist
     const uint32_t mask = (exists && !first) ? ws.mask[node] : 0u;
-    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
-    POW p;
-    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
     double states[NS], total;
     int steps, success;
-    rollout_episode<NANT, AMAX, G, H, true, POW>(tl, grid_s, u, ve, U, rb + (size_t)e * (NANT + 1) * maxR, ws.slot + (size_t)e * maxR, nrules[e], maxR, ag, p,
-                                                  exists, (uint32_t)node, mask, start_states ? start_states + (size_t)e * NS : nullptr, ws.cap[e], steps,
-                                                  total, success, states);
+    rollout_episode<NANT, AMAX, G, H, true, KernelPow<NANT, PN>>(tl, grid_s, u, ve, U, rb + (size_t)e * (NANT + 1) * maxR, ws.slot + (size_t)e * maxR, nrules[e], maxR,
+                                                                  ag, kernel_pow<NANT, PN>(ag), exists, (uint32_t)node, mask,
+                                                                  start_states ? start_states + (size_t)e * NS : nullptr, ws.cap[e], steps, total, success, states);
     if (!exists || threadIdx.x % GH != 0) return;
     ws.steps[(size_t)e * ws.nodes + node] = steps;
     ws.reward[(size_t)e * ws.nodes + node] = total;

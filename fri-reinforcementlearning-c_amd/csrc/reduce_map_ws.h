@@ -46,15 +46,8 @@ int reduce_map_launch_order(const char *who, const frirl_hip_tables &t, const fr
 void reduce_map_launch_run(const frirl_hip_tables &t, const frirl_hip_rulebases &b, double *rant, const frirl::MapArgs &m, int resident,
                            const ReduceMapWs &ws, hipStream_t s);
 
-// ---- argument checks shared by policy_map.hip and rule_usage.hip (no device is looked at) ----
-static int check_map_workspace(const char *who, const void *workspace, size_t bytes, size_t need, const char *query)
-{
-    if (workspace && !(reinterpret_cast<uintptr_t>(workspace) & 15) && bytes >= need) return FRIRL_HIP_OK;
-    set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (%s)", who, workspace, bytes, need, query);
-    return FRIRL_HIP_EINVAL;
-}
-
-// the checks the map and the map-validated reduction share; fills `m` (no device is looked at)
+// ---- argument checks shared by policy_map.hip and rule_usage.hip (no device is looked at; the workspace: check_workspace, batch_shape.h) ----
+// the checks the map and the map-validated reduction share; fills `m`
 static int check_map_args(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                           const frirl_hip_map_points *pts, frirl::MapArgs *m)
 {

@@ -48,18 +48,14 @@ __global__ __launch_bounds__(SH_BLOCK) void reduce_starts_rollout_kernel(const d
     const double *rb = rb_all + (size_t)e * (NANT + 1) * maxR;
     const uint8_t *slot_g = ws.b.slot + (size_t)e * maxR;
     const int R = nrules[e];
-    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
-    POW p;
-    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
+    using POW = KernelPow<NANT, PN>;
+    const POW p = kernel_pow<NANT, PN>(ag);
 
-    // ---- rollout_episode's body with the row's own cap inside a loop whose bound is uniform ----
-    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;        // group lane = (rule slice h, action slot sub)
-    const int apl = (ag.A + G - 1) / G;                                // actions per lane
-    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
-    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
-    const int nchunks = (apl + AMAX - 1) / AMAX;
-    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
-    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+    // ---- rollout_episode's body with the row's own cap inside a loop whose bound is uniform (why it is not a call of
+    // rollout_episode: profiles/r24_rollout_loop.md, "tried and put aside") ----
+    const GroupLane l = group_lane<G, H, AMAX>(ag.A);
+    const int abeg = l.abeg, aend = l.aend, nchunks = l.nchunks, h = l.h;
+    stage_agent<NANT>(tl, grid_s, ag);
     double states[NS], cs[NS], qs[NS], q[NS];
 #pragma unroll
     for (int i = 0; i < NS; i++) {
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(SH_BLOCK) void reduce_starts_rollout_kernel(const d
             if (success == 1 || steps >= cap) active = false;                                            // :183; :86 with the row's cap
         }
     }
-    if (!exists || gl != 0) return;
+    if (!exists || !l.leader) return;
     const size_t out = (size_t)e * ws.b.nodes * ws.n + r;
     ws.b.steps[out] = steps;
     ws.b.reward[out] = total;

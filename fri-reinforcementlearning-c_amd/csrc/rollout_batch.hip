@@ -33,10 +33,7 @@ __global__ __launch_bounds__(256) void rollout_batch_prep_kernel(const int32_t *
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q >= (long)E * ro.n) return;
     const int e = (int)(q / ro.n), j = (int)(q - (long)e * ro.n);
-    int rows = ro.row_count ? ro.row_count[e] : ro.n;
-    rows = rows < 0 ? 0 : (rows > ro.n ? ro.n : rows);
-    const int R = nrules[e];
-    if ((ro.active && ro.active[e] == 0) || R < 1 || R > maxR) rows = 0;
+    const int rows = agent_rows(ro.row_count, ro.active, ro.n, nrules, maxR, e);
     if (j == 0) {
         int cap = ro.step_cap ? ro.step_cap[e] : max_steps;
         cap = cap < 1 ? 1 : cap;
@@ -70,13 +67,11 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_batch_tiled_kernel(const dou
     const int j = row0 + threadIdx.x / GH;
     const bool exists = j < rows;
     const size_t q = (size_t)e * ro.n + (exists ? j : 0);
-    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
-    POW p;
-    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
     double states[NS], total;
     int steps, success;
-    rollout_episode<NANT, AMAX, G, H, false, POW>(tl, grid_s, u, ve, U, rb + (size_t)e * (NANT + 1) * maxR, nullptr, R, maxR, ag, p, exists, (uint32_t)q, 0u,
-                                                   ro.start_states ? ro.start_states + q * NS : nullptr, ws.cap[e], steps, total, success, states);
+    rollout_episode<NANT, AMAX, G, H, false, KernelPow<NANT, PN>>(tl, grid_s, u, ve, U, rb + (size_t)e * (NANT + 1) * maxR, nullptr, R, maxR, ag,
+                                                                   kernel_pow<NANT, PN>(ag), exists, (uint32_t)q, 0u,
+                                                                   ro.start_states ? ro.start_states + q * NS : nullptr, ws.cap[e], steps, total, success, states);
     if (!exists || threadIdx.x % GH != 0) return;
     ro.steps[q] = steps;
     ro.reward[q] = total;
@@ -357,13 +352,11 @@ void launch_tiled(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const
                        b->rb, b->nrules, b->maxR, *ag, wpa, resident_rules, *ro, ws);
 }
 
-// rule slices: the rule of the batched reduction's rounds (rb_slices) on the rows of the whole call; one row per agent: a full wave per row
 template <int N>
 void launch_tiled_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_rollout_batch_rows *ro, int resident_rules,
                     const frirl::RolloutBatchWs &ws, hipStream_t s)
 {
-    const int H = ro->n == 1 ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)b->E * ro->n, ag->A);
-    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+    frirl::for_batch_shape<N>(ag, rb_rollout_slices(b->E, ro->n, ag->A, 0), [&](auto sh) {
         using S = decltype(sh);
         launch_tiled<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, ro, resident_rules, ws, s);
     });
@@ -395,19 +388,14 @@ extern "C" int frirl_hip_rollout_batch(const frirl_hip_tables *t, const frirl_hi
     static const char *who = "frirl_hip_rollout_batch";
     int rc = check_rulebases(t, b);
     if (rc) return rc;
-    if (!agent || !ro || !ro->steps || !ro->reward || !agent->grid_values || !agent->action_ve) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_rollout_agent_null(agent, ro && ro->steps && ro->reward, who))) return rc;
     if (ro->n < 1) { set_error("%s: n=%d < 1", who, ro->n); return FRIRL_HIP_EINVAL; }
     if ((int64_t)b->E * ro->n > INT32_MAX) { set_error("%s: E * n = %lld rows exceed INT32_MAX", who, (long long)b->E * ro->n); return FRIRL_HIP_EINVAL; }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_demo_kind(t, agent, who))) return rc;
-    if ((rc = check_grid_len(t, agent, who))) return rc;
+    if ((rc = check_rollout_agent(t, agent, who))) return rc;
     const size_t E = (size_t)b->E, n = (size_t)ro->n;
-    const size_t need = rollout_batch_layout(nullptr, E, n, nullptr, nullptr);
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need) {
-        set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (frirl_hip_rollout_batch_workspace_bytes)", who, workspace, workspace_bytes, need);
-        return FRIRL_HIP_EINVAL;
-    }
-    if ((rc = check_device())) return rc;
+    if ((rc = check_workspace(who, workspace, workspace_bytes, rollout_batch_layout(nullptr, E, n, nullptr, nullptr), "frirl_hip_rollout_batch_workspace_bytes")) ||
+        (rc = check_device()))
+        return rc;
     hipStream_t s = as_stream(stream);
     frirl::RolloutBatchWs ws;
     int32_t *ws_success = nullptr;

@@ -1,6 +1,9 @@
 // rollout_episode.h -- ONE greedy episode of frirl_test_run (src/frirl/frirl_test_run.c:66-70 -> frirl_episode.c:28-194 without the
-// update at :155) by a group of G * H lanes against a read-only rule base: the body of rollout_shared_kernel (shared.hip), shared with
-// the batched reduction's roll-out kernel (reduce_batch.hip), whose workgroups each point it at another agent's slab.
+// update at :155) by a group of G * H lanes against a read-only rule base.  Instantiated by rollout_shared_kernel (shared.hip), by the
+// batched reduction's roll-out kernel (reduce_batch.hip), whose workgroups each point it at another agent's slab, and by the tiled form
+// of the batched roll-out (rollout_batch.hip).  reduce_starts.hip keeps a copy of this loop with a per-row step cap: through a call it
+// compiled to other code and ran 1 - 2 % slower (profiles/r24_rollout_loop.md, "tried and put aside").  The restartable form of the
+// loop is rollout_record_episodes.h.
 #pragma once
 #include "shared_sweep.h"
 #include "envs.h"
@@ -17,14 +20,9 @@ __device__ __forceinline__ void rollout_episode(SharedTile<NANT> &tl, double *gr
                                                 const double *__restrict__ start, int max_steps, int &steps, double &total, int &success,
                                                 double (&states)[NANT - 1])
 {
-    constexpr int NS = NANT - 1, GH = G * H;
-    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
-    const int apl = (ag.A + G - 1) / G;                              // actions per lane
-    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
-    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
-    const int nchunks = (apl + AMAX - 1) / AMAX;
-    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
-    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+    constexpr int NS = NANT - 1;
+    const GroupLane l = group_lane<G, H, AMAX>(ag.A);
+    stage_agent<NANT>(tl, grid_s, ag);
     double cur[NS], qs[NS], q[NS];
 #pragma unroll
     for (int k = 0; k < NS; k++) {
@@ -34,7 +32,7 @@ __device__ __forceinline__ void rollout_episode(SharedTile<NANT> &tl, double *gr
     unsigned h0;
     int a;
     double bv;
-    shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, slot_g, R, maxR, p, abeg, aend, nchunks, q, exists, mask, nullptr, h0, a, bv, h);   // :78 (un-quantised start state)
+    shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, slot_g, R, maxR, p, l.abeg, l.aend, l.nchunks, q, exists, mask, nullptr, h0, a, bv, l.h);   // :78 (un-quantised start state)
     group_first_max<G>(bv, a);
     a = e_greedy(ag, a, row, 0u, 0u);
     double action = grid_s[NS * FRIRL_HIP_MAX_GRID + a];                                                 // :82
@@ -54,7 +52,7 @@ __device__ __forceinline__ void rollout_episode(SharedTile<NANT> &tl, double *gr
             for (int k = 0; k < NS; k++) q[k] = observe_ve(u, ve, U, k, qs[k]);
         }
         int pa;
-        shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, slot_g, R, maxR, p, abeg, aend, nchunks, q, active, mask, nullptr, h0, pa, bv, h);   // :148
+        shared_sweep<NANT, AMAX, true, EXCL, G, H, POW>(tl, rb, slot_g, R, maxR, p, l.abeg, l.aend, l.nchunks, q, active, mask, nullptr, h0, pa, bv, l.h);   // :148
         group_first_max<G>(bv, pa);
         if (active) {
             pa = e_greedy(ag, pa, row, 0u, (uint32_t)step);

@@ -3,7 +3,8 @@
 // frirl_hip_rollout_record + frirl_hip_log_points give, without a record ever being written.
 //
 // Launches of a call, nothing read back in between:
-//   roll      a workgroup serves rows of ONE agent through shared_sweep (the step loop of rollout_record_episodes.h) and keeps the
+//   roll      a workgroup serves rows of ONE agent through shared_sweep (a COPY of the step loop of rollout_record_episodes.h with one
+//             episode per row; one loop with a sink for both cost this kernel 0.7 %, profiles/r24_rollout_loop.md) and keeps the
 //             points of its rows in an LDS hash table, each entry with the mask of the rows that visited it; when every row has
 //             ended it writes the entries whose visitors include a contributing row to ITS segment of the workspace
 //   finalise  one workgroup per agent merges the segments of the agent's workgroups (bit-wise de-duplication against the list so
@@ -34,14 +35,11 @@ struct PointSegment {
 
 __host__ __device__ inline size_t rp_segment_bytes(int ns, int cap) { return sizeof(PointSegment) + sizeof(uint64_t) * (size_t)ns * (size_t)cap; }
 
-// rows of agent e that are rolled out
+// rows of agent e that are rolled out.  The descriptor goes by reference on purpose: the roll kernel's registers depend on it
+// (profiles/r24_rollout_loop.md, section 3).
 __device__ __forceinline__ int points_rows(const frirl_hip_rollout_points_desc &rp, const int32_t *__restrict__ nrules, int maxR, int e)
 {
-    int rows = rp.row_count ? rp.row_count[e] : rp.n;
-    rows = rows < 0 ? 0 : (rows > rp.n ? rp.n : rows);
-    const int R = nrules[e];
-    if ((rp.active && rp.active[e] == 0) || R < 1 || R > maxR) rows = 0;
-    return rows;
+    return agent_rows(rp.row_count, rp.active, rp.n, nrules, maxR, e);
 }
 
 template <int NS>
@@ -110,24 +108,18 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_points_kernel(const double *
     const int e = (int)(blockIdx.x / (unsigned)wpa), wg = (int)(blockIdx.x % (unsigned)wpa);
     const int row0 = wg * EPB;
     const int rows = points_rows(rp, nrules, maxR, e);
-    if (row0 >= rows || wg >= segs) return;                           // nothing to roll out here (wg < segs by the host's arithmetic)
+    if (row0 >= rows || wg >= segs) return;                          // nothing to roll out here (wg < segs by the host's arithmetic)
     const int lrow = threadIdx.x / GH, j = row0 + lrow;
     const bool exists = j < rows;
     const size_t q = (size_t)e * rp.n + (exists ? j : 0);
-    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
-    POW p;
-    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
+    using POW = KernelPow<NANT, PN>;
+    POW p = kernel_pow<NANT, PN>(ag);
     const double *rb = rb_all + (size_t)e * (NANT + 1) * maxR;
     const int R = nrules[e];
 
-    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
-    const bool leader = gl == 0;
-    const int apl = (ag.A + G - 1) / G;                              // actions per lane
-    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
-    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
-    const int nchunks = (apl + AMAX - 1) / AMAX;
-    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
-    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+    const GroupLane l = group_lane<G, H, AMAX>(ag.A);
+    const bool leader = l.leader;
+    stage_agent<NANT>(tl, grid_s, ag);
     for (int i = threadIdx.x; i < pt.slots; i += SH_BLOCK) pt.visitors[i] = 0ull;
     if (threadIdx.x == 0) { st.staged_rows = 0ull; st.good = 0ull; st.entries = 0; st.overflow = 0; }
     const unsigned long long mybit = 1ull << lrow;
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_points_kernel(const double *
         unsigned h0;
         int pa;
         double bv;
-        shared_sweep<NANT, AMAX, true, false, G, H, POW>(tl, rb, nullptr, R, maxR, p, abeg, aend, nchunks, qv, !fin, 0u, nullptr, h0, pa, bv, h);   // :78 / :148
+        shared_sweep<NANT, AMAX, true, false, G, H, POW>(tl, rb, nullptr, R, maxR, p, l.abeg, l.aend, l.nchunks, qv, !fin, 0u, nullptr, h0, pa, bv, l.h);   // :78 / :148
         group_first_max<G>(bv, pa);
         if (threadIdx.x == 0) {                                      // the serial phase: this step's misses, in local-row order
             unsigned long long todo = st.staged_rows;
@@ -233,23 +225,16 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_points_kernel(const double *
     char *seg = segments + ((size_t)e * segs + wg) * rp_segment_bytes(NS, rp.cap);
     uint64_t *out = reinterpret_cast<uint64_t *>(seg + sizeof(PointSegment));
     const unsigned long long good = st.good;
-    const int lane = threadIdx.x & (FRIRL_WAVE - 1), wave = threadIdx.x / FRIRL_WAVE;
     int count = 0, over = st.overflow;                               // the same in every thread
     for (int s0 = 0; s0 < pt.slots; s0 += SH_BLOCK) {                // slots is a multiple of the workgroup
         const int s = s0 + threadIdx.x;
         const bool keep = (pt.visitors[s] & good) != 0ull;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) st.wave_kept[wave] = __popcll(bal);
-        __syncthreads();
-        int pos = count + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
-        for (int i = 0; i < SH_BLOCK / FRIRL_WAVE; i++) { pos += i < wave ? st.wave_kept[i] : 0; tot += st.wave_kept[i]; }
+        const int pos = block_append<SH_BLOCK>(keep, st.wave_kept, rp.cap, count, over);
         if (keep && pos < rp.cap) {
 #pragma unroll
             for (int k = 0; k < NS; k++) out[(size_t)pos * NS + k] = pt.key[(size_t)s * NS + k];
         }
-        over |= count + tot > rp.cap ? 1 : 0;
-        count = count + tot > rp.cap ? rp.cap : count + tot;
-        __syncthreads();                                             // wave_kept is rewritten by the next chunk
+        __syncthreads();                                            // wave_kept is rewritten by the next chunk
     }
     if (threadIdx.x == 0) {
         PointSegment *hd = reinterpret_cast<PointSegment *>(seg);
@@ -268,7 +253,7 @@ __global__ __launch_bounds__(RPF_BLOCK) void rollout_points_finalise_kernel(cons
                                                                              const frirl_hip_rollout_points_desc rp, const char *__restrict__ segments)
 {
     __shared__ int wave_new[RPF_BLOCK / FRIRL_WAVE];
-    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & (FRIRL_WAVE - 1), wave = tid / FRIRL_WAVE;
+    const int e = blockIdx.x, tid = threadIdx.x;
     const int rows = points_rows(rp, nrules, maxR, e);
     for (int j = rows + tid; j < rp.n; j += RPF_BLOCK) {              // the rows that were not rolled out
         const size_t q = (size_t)e * rp.n + j;
@@ -302,18 +287,12 @@ __global__ __launch_bounds__(RPF_BLOCK) void rollout_points_finalise_kernel(cons
                 for (int k = 0; k < NS; k++) same = same && list[(size_t)i * NS + k] == x[k];
                 fresh = !same;
             }
-            const unsigned long long bal = __ballot(fresh);
-            if (lane == 0) wave_new[wave] = __popcll(bal);
-            __syncthreads();
-            int pos = count + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
-            for (int i = 0; i < RPF_BLOCK / FRIRL_WAVE; i++) { pos += i < wave ? wave_new[i] : 0; tot += wave_new[i]; }
+            const int pos = block_append<RPF_BLOCK>(fresh, wave_new, rp.cap, count, over);
             if (fresh && pos < rp.cap) {
 #pragma unroll
                 for (int k = 0; k < NS; k++) list[(size_t)pos * NS + k] = x[k];
             }
-            over |= count + tot > rp.cap ? 1 : 0;
-            count = count + tot > rp.cap ? rp.cap : count + tot;
-            __syncthreads();                                          // wave_new is rewritten by the next chunk; the rows written are visible
+            __syncthreads();                                         // wave_new is rewritten by the next chunk; the rows written are visible
         }
     }
     if (tid == 0) { rp.point_count[e] = count; rp.overflow[e] = over; }
@@ -342,15 +321,11 @@ void launch_points(const frirl_hip_tables *t, const frirl_hip_rulebases *b, cons
                        segments);
 }
 
-// rule slices: as the recorded roll-out (rollout_record.hip); the option rollout_points_slices forces 1 / 4 / 8 (16 for up to 4 actions)
 template <int N>
 void launch_points_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_rollout_points_desc *rp, char *segments,
                      hipStream_t s)
 {
-    int H = rp->n == 1 ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)b->E * rp->n, ag->A);
-    const int forced = opts().rollout_points_slices;
-    if (forced == 1 || forced == 4 || forced == 8 || (forced == 16 && ag->A <= 4)) H = forced;
-    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+    frirl::for_batch_shape<N>(ag, rb_rollout_slices(b->E, rp->n, ag->A, opts().rollout_points_slices), [&](auto sh) {
         using S = decltype(sh);
         launch_points<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, rp, segments, s);
     });
@@ -370,7 +345,7 @@ extern "C" int frirl_hip_rollout_points(const frirl_hip_tables *t, const frirl_h
     static const char *who = "frirl_hip_rollout_points";
     int rc = check_rulebases(t, b);
     if (rc) return rc;
-    if (!agent || !rp || !agent->grid_values || !agent->action_ve) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_rollout_agent_null(agent, rp != nullptr, who))) return rc;
     if (!rp->points || !rp->point_count || !rp->overflow) { set_error("%s: NULL points / point_count / overflow", who); return FRIRL_HIP_EINVAL; }
     if (rp->n < 1 || rp->n > FRIRL_HIP_REDUCE_MAX_STARTS) { set_error("%s: n=%d outside 1..%d", who, rp->n, FRIRL_HIP_REDUCE_MAX_STARTS); return FRIRL_HIP_EINVAL; }
     if (rp->cap < 1 || rp->cap > FRIRL_HIP_POINTS_MAX_CAP) { set_error("%s: cap=%d outside 1..%d", who, rp->cap, FRIRL_HIP_POINTS_MAX_CAP); return FRIRL_HIP_EINVAL; }
@@ -379,15 +354,9 @@ extern "C" int frirl_hip_rollout_points(const frirl_hip_tables *t, const frirl_h
         set_error("%s: E * n = %lld rows or E * cap = %lld points exceed INT32_MAX", who, (long long)b->E * rp->n, (long long)b->E * rp->cap);
         return FRIRL_HIP_EINVAL;
     }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_demo_kind(t, agent, who))) return rc;
-    if ((rc = check_grid_len(t, agent, who))) return rc;
+    if ((rc = check_rollout_agent(t, agent, who))) return rc;
     const size_t need = frirl_hip_rollout_points_workspace_bytes(t->nant, b->E, b->maxR, rp->n, rp->cap, agent->A);
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need) {
-        set_error("%s: workspace %p / %zu bytes: needs %zu bytes, 16-byte aligned (frirl_hip_rollout_points_workspace_bytes)", who, workspace, workspace_bytes, need);
-        return FRIRL_HIP_EINVAL;
-    }
-    if ((rc = check_device())) return rc;
+    if ((rc = check_workspace(who, workspace, workspace_bytes, need, "frirl_hip_rollout_points_workspace_bytes")) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     if (t->nant == 3) launch_points_n<3>(t, b, agent, rp, static_cast<char *>(workspace), s);
     else launch_points_n<5>(t, b, agent, rp, static_cast<char *>(workspace), s);

@@ -10,18 +10,14 @@
 #include "rollout_record_episodes.h"
 #include "batch_shape.h"
 #include "shape_ladder.h"
-#include <type_traits>
 
 namespace frirl {
 
-// logs of agent e that are recorded
+// logs of agent e that are recorded.  The descriptor goes by reference on purpose: the record kernel's registers depend on it
+// (profiles/r24_rollout_loop.md, section 3).
 __device__ __forceinline__ int record_rows(const frirl_hip_rollout_log &lg, const int32_t *__restrict__ nrules, int maxR, int e)
 {
-    int rows = lg.row_count ? lg.row_count[e] : lg.n;
-    rows = rows < 0 ? 0 : (rows > lg.n ? lg.n : rows);
-    const int R = nrules[e];
-    if ((lg.active && lg.active[e] == 0) || R < 1 || R > maxR) rows = 0;
-    return rows;
+    return agent_rows(lg.row_count, lg.active, lg.n, nrules, maxR, e);
 }
 
 __global__ __launch_bounds__(256) void rollout_record_prep_kernel(const int32_t *__restrict__ nrules, int E, int maxR, const frirl_hip_rollout_log lg)
@@ -56,9 +52,8 @@ __global__ __launch_bounds__(SH_BLOCK) void rollout_record_kernel(const double *
     const int j = row0 + threadIdx.x / GH;
     const bool exists = j < rows;
     const size_t q = (size_t)e * lg.n + (exists ? j : 0);
-    using POW = typename std::conditional<PN, PowC<NANT>, PowU>::type;
-    POW p;
-    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
+    using POW = KernelPow<NANT, PN>;
+    const POW p = kernel_pow<NANT, PN>(ag);
     rollout_record_episodes<NANT, AMAX, G, H, POW>(tl, grid_s, u, ve, U, rb + (size_t)e * (NANT + 1) * maxR, nrules[e], maxR, ag, p, exists, q, lg);
 }
 
@@ -77,15 +72,10 @@ void launch_record(const frirl_hip_tables *t, const frirl_hip_rulebases *b, cons
                        t->U, b->rb, b->nrules, b->maxR, *ag, wpa, *lg);
 }
 
-// rule slices: by the logs of the whole call, as the batched roll-out's tiled form (rb_slices); one log per agent: a full wave per log.
-// The option rollout_record_slices forces 1 / 4 / 8 (16 for up to 4 actions).
 template <int N>
 void launch_record_n(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_rollout_log *lg, hipStream_t s)
 {
-    int H = lg->n == 1 ? FRIRL_WAVE / rb_group(ag->A) : rb_slices((long)b->E * lg->n, ag->A);
-    const int forced = opts().rollout_record_slices;
-    if (forced == 1 || forced == 4 || forced == 8 || (forced == 16 && ag->A <= 4)) H = forced;
-    frirl::for_batch_shape<N>(ag, H, [&](auto sh) {
+    frirl::for_batch_shape<N>(ag, rb_rollout_slices(b->E, lg->n, ag->A, opts().rollout_record_slices), [&](auto sh) {
         using S = decltype(sh);
         launch_record<N, S::AMAX, S::G, S::H, S::PN>(t, b, ag, lg, s);
     });
@@ -99,7 +89,7 @@ extern "C" int frirl_hip_rollout_record(const frirl_hip_tables *t, const frirl_h
     static const char *who = "frirl_hip_rollout_record";
     int rc = check_rulebases(t, b);
     if (rc) return rc;
-    if (!agent || !log || !agent->grid_values || !agent->action_ve) { set_error("%s: NULL argument", who); return FRIRL_HIP_EINVAL; }
+    if ((rc = check_rollout_agent_null(agent, log != nullptr, who))) return rc;
     if (!log->obs || !log->action || !log->reward || !log->success || !log->start || !log->length) {
         set_error("%s: NULL obs / action / reward / success / start / length", who);
         return FRIRL_HIP_EINVAL;
@@ -113,10 +103,7 @@ extern "C" int frirl_hip_rollout_record(const frirl_hip_tables *t, const frirl_h
         set_error("%s: E * n * T overflows int64", who);
         return FRIRL_HIP_EINVAL;
     }
-    if (agent->A < 1 || agent->A > FRIRL_HIP_MAX_ACTIONS || agent->max_steps < 0) { set_error("%s: A=%d / max_steps=%d out of range", who, agent->A, agent->max_steps); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_demo_kind(t, agent, who))) return rc;
-    if ((rc = check_grid_len(t, agent, who))) return rc;
-    if ((rc = check_device())) return rc;
+    if ((rc = check_rollout_agent(t, agent, who)) || (rc = check_device())) return rc;
     hipStream_t s = as_stream(stream);
     const long Q = (long)b->E * log->n;
     hipLaunchKernelGGL(frirl::rollout_record_prep_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, b->nrules, b->E, b->maxR, *log);

@@ -19,15 +19,10 @@ __device__ __forceinline__ void rollout_record_episodes(SharedTile<NANT> &tl, do
                                                         int U, const double *__restrict__ rb, int R, int maxR, const frirl_hip_agent &ag, POW p,
                                                         bool exists, size_t q, const frirl_hip_rollout_log &lg)
 {
-    constexpr int NS = NANT - 1, GH = G * H;
-    const int gl = threadIdx.x % GH, sub = gl % G, h = gl / G;      // group lane = (rule slice h, action slot sub)
-    const bool leader = gl == 0;
-    const int apl = (ag.A + G - 1) / G;                              // actions per lane
-    const int abeg = (sub * apl < ag.A) ? sub * apl : ag.A;
-    const int aend = (abeg + apl < ag.A) ? abeg + apl : ag.A;
-    const int nchunks = (apl + AMAX - 1) / AMAX;
-    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
-    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+    constexpr int NS = NANT - 1;
+    const GroupLane l = group_lane<G, H, AMAX>(ag.A);
+    const bool leader = l.leader;
+    stage_agent<NANT>(tl, grid_s, ag);
     const int K = lg.episodes, T = lg.T;
     const size_t rec0 = q * (size_t)T, ep0 = q * (size_t)K;         // first record / first episode of this log
     double states[NS], cur[NS], qs[NS], qv[NS], total = 0.0, action = 0.0;
@@ -61,7 +56,7 @@ __device__ __forceinline__ void rollout_record_episodes(SharedTile<NANT> &tl, do
         unsigned h0;
         int pa;
         double bv;
-        shared_sweep<NANT, AMAX, true, false, G, H, POW>(tl, rb, nullptr, R, maxR, p, abeg, aend, nchunks, qv, !fin, 0u, nullptr, h0, pa, bv, h);   // :78 / :148
+        shared_sweep<NANT, AMAX, true, false, G, H, POW>(tl, rb, nullptr, R, maxR, p, l.abeg, l.aend, l.nchunks, qv, !fin, 0u, nullptr, h0, pa, bv, l.h);   // :78 / :148
         group_first_max<G>(bv, pa);
         if (!fin) {
             const size_t rec = rec0 + (size_t)pos;                   // pos < T: a log with fewer than 2 free records begins no episode, a full one is finished

@@ -186,7 +186,7 @@ extern "C" int frirl_hip_rule_usage(const frirl_hip_tables *t, const frirl_hip_r
     if (rc) return rc;
     if (!out || !out->sum) { set_error("%s: NULL out / out->sum", who); return FRIRL_HIP_EINVAL; }
     if ((long long)b->E * ((b->maxR + frirl::RU_BLOCK - 1) / frirl::RU_BLOCK) > INT32_MAX) { set_error("%s: E=%d x maxR=%d: too many rule blocks", who, b->E, b->maxR); return FRIRL_HIP_EINVAL; }
-    if ((rc = check_map_workspace(who, workspace, workspace_bytes, frirl_hip_rule_usage_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_rule_usage_workspace_bytes")) ||
+    if ((rc = check_workspace(who, workspace, workspace_bytes, frirl_hip_rule_usage_workspace_bytes(t->nant, b->E, pts->n), "frirl_hip_rule_usage_workspace_bytes")) ||
         (rc = check_device()))
         return rc;
     frirl::RuleUsageWs ws;

@@ -2,6 +2,7 @@
 // policy kernels, policy_kernel.h, instantiate the same code): LDS tile, one lane's conclusions, first maximum over a lane group.
 #pragma once
 #include "sweeps.h"
+#include <type_traits>
 
 namespace frirl {
 
@@ -146,6 +147,79 @@ __device__ __forceinline__ void group_first_max(double &bv, int &bi)
     }
     bv = cb;
     bi = ci;
+}
+
+// The share of a row's group of G * H consecutive lanes that one lane takes in shared_sweep: rule slice h and action slot sub, which
+// serves the actions [abeg, aend) in nchunks passes of AMAX accumulators (nchunks is uniform over the workgroup).
+struct GroupLane {
+    int sub, h, abeg, aend, nchunks;
+    bool leader;                   // the lane that answers for the row
+};
+
+template <int G, int H, int AMAX>
+__device__ __forceinline__ GroupLane group_lane(int A)
+{
+    GroupLane l;
+    const int gl = threadIdx.x % (G * H);
+    l.sub = gl % G;
+    l.h = gl / G;
+    l.leader = gl == 0;
+    const int apl = (A + G - 1) / G;                                 // actions per lane
+    l.abeg = (l.sub * apl < A) ? l.sub * apl : A;
+    l.aend = (l.abeg + apl < A) ? l.abeg + apl : A;
+    l.nchunks = (apl + AMAX - 1) / AMAX;
+    return l;
+}
+
+// The agent's grids ([NANT * FRIRL_HIP_MAX_GRID] doubles of LDS) and action VE points for the workgroup; the first barrier of
+// shared_sweep comes before anything reads them.
+template <int NANT>
+__device__ __forceinline__ void stage_agent(SharedTile<NANT> &tl, double *grid_s, const frirl_hip_agent &ag)
+{
+    for (int i = threadIdx.x; i < NANT * FRIRL_HIP_MAX_GRID; i += SH_BLOCK) grid_s[i] = ag.grid_values[i];
+    if ((int)threadIdx.x < ag.A) tl.ave[threadIdx.x] = ag.action_ve[threadIdx.x];
+}
+
+// The Shepard power of a kernel of the shape ladder: PN = the power is the antecedent count, known at compile time; else the agent's.
+template <int NANT, bool PN>
+using KernelPow = typename std::conditional<PN, PowC<NANT>, PowU>::type;
+
+template <int NANT, bool PN>
+__device__ __forceinline__ KernelPow<NANT, PN> kernel_pow(const frirl_hip_agent &ag)
+{
+    KernelPow<NANT, PN> p;
+    if constexpr (!PN) p.p = ag.p > 0 ? ag.p : NANT;
+    return p;
+}
+
+// Rows of agent e that a batched roll-out serves: row_count[e] (NULL = n) clamped to 0..n, and none for an inactive agent or one whose
+// rule count lies outside 1..maxR.
+__device__ __forceinline__ int agent_rows(const int32_t *__restrict__ row_count, const uint8_t *__restrict__ active, int n,
+                                          const int32_t *__restrict__ nrules, int maxR, int e)
+{
+    int rows = row_count ? row_count[e] : n;
+    rows = rows < 0 ? 0 : (rows > n ? n : rows);
+    const int R = nrules[e];
+    if ((active && active[e] == 0) || R < 1 || R > maxR) rows = 0;
+    return rows;
+}
+
+// Appends the flagged threads of a workgroup of BLOCK threads, in thread order, to a list that holds `count` of at most `cap` entries.
+// Returns this thread's position (to be written only if flagged and < cap) and updates count / over, the same in every thread.
+// Every thread must call it (one barrier inside); wave_cnt: one int of LDS per wave.  The caller writes its entry and then
+// passes a barrier of its own before the next call: wave_cnt is rewritten there, and the entries written become visible.
+template <int BLOCK>
+__device__ __forceinline__ int block_append(bool flag, int (&wave_cnt)[BLOCK / FRIRL_WAVE], int cap, int &count, int &over)
+{
+    const int lane = threadIdx.x & (FRIRL_WAVE - 1), wave = threadIdx.x / FRIRL_WAVE;
+    const unsigned long long bal = __ballot(flag);
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int pos = count + __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+    for (int i = 0; i < BLOCK / FRIRL_WAVE; i++) { pos += i < wave ? wave_cnt[i] : 0; tot += wave_cnt[i]; }
+    over |= count + tot > cap ? 1 : 0;
+    count = count + tot > cap ? cap : count + tot;
+    return pos;
 }
 
 }  // namespace frirl

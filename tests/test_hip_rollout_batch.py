@@ -339,3 +339,21 @@ def test_shepard_power_two_runs_the_tiled_form(hip_option):
         hip_option(opt, v)
         again = run(env, n, agent=agent)
         assert all(same_bits(a.astype(np.float64), g.astype(np.float64)) for a, g in zip(again, got)), opt
+
+
+# ---- 8. no step allowed -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("resident", [0, 1])
+def test_max_steps_zero_ends_every_row_on_its_start(resident, hip_option):
+    """max_steps = 0: the reference's step loop, range(1, max_steps + 1), is empty.  The tiled form never enters its loop, the resident
+    form ends the row on the iteration of its start sweep."""
+    env, n = "mountaincar", 3
+    hip_option("rollout_batch_resident", resident)
+    # which form serves the two agents: 0 = never the resident one; 1 = wherever it fits, and by the library's own capacity both fit
+    cap = frirl_amd.lib().frirl_hip_rollout_resident_rules(3, 3, 0, frirl_amd.ENV_KINDS[env])
+    assert cap >= max(a.R0 for a in case(env)[:2]), "both agents fit the resident form"
+    starts = starts_for(env, n)[:2 * n]
+    agent = agent_for(env)
+    agent.desc.max_steps = 0
+    steps, reward, success, final = run(env, n, agent=agent, prob=upload(case(env)[:2])[0], starts=starts)
+    assert (steps == 0).all() and (reward == 0.0).all() and (success == 0).all() and len(steps) == 2 * n
+    assert same_bits(final, starts), "no step: the final state is the start state"

@@ -192,6 +192,26 @@ def test_agents_with_a_bad_rule_count_are_skipped(skipped):
     assert (got[3] == want[1]).all() and same_bits(got[4], want[2]) and (got[5] == want[3]).all()
 
 
+def test_max_steps_zero_keeps_the_start_states():
+    """max_steps = 0: the reference's episode (policy_map_ref.episode_points, range(max_steps)) asks the policy at the un-quantised start
+    and nowhere else; the row ends on the iteration that began it.  An agent's set is the set of its rows' start states."""
+    env, n = "mountaincar", 3
+    agents = case(env)[:2]
+    starts = starts_for(env, n)[:2 * n]
+    agent = agent_for(env)
+    agent.desc.max_steps = 0
+    got = points_call(upload(agents)[0], agent, n, starts)
+    want = []
+    for e, a in enumerate(agents):
+        a.restore(a.rant, a.rconc)
+        rows = [ref.episode_points(a.fr, x0, 0) for x0 in starts[e * n:(e + 1) * n]]
+        assert all(same_bits(r, x0[None]) for r, x0 in zip(rows, starts[e * n:(e + 1) * n]))
+        want.append(ref.dedup(np.concatenate(rows)))
+    assert [len(w) for w in want] == [n, n], "the start rows differ"
+    assert_same_sets(got, want, "max_steps = 0")
+    assert (got[3] == 0).all() and (got[4] == 0.0).all() and (got[5] == 0).all() and len(got[3]) == 2 * n
+
+
 # ---- 2. lane shapes ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("env", ["mountaincar", "acrobot", "cartpole"])
 def test_every_lane_shape(env, hip_option):

@@ -291,6 +291,32 @@ def test_logs_that_are_not_recorded():
     assert same_bits(got["obs"][6, :116], w["obs"][:116]) and same_bits(got["obs"][7, 116:232], w["obs"][:116])
 
 
+def test_max_steps_zero_records_one_start_record_per_episode():
+    """max_steps = 0: oracle_episode's step loop, range(1, max_steps + 1), is empty -- an episode is its start record, which carries
+    the greedy pick at the un-quantised start; the episode ends on the iteration that began it."""
+    env, n, K, T = "mountaincar", 3, 2, 4
+    agents = case(env)[:2]
+    av = frirl_amd.demo_describe(env)["grids"][-1]
+    starts = starts_for(env, n * K)[:2 * n * K]                      # log q = e * n + j, episode k: row q * K + k
+    agent = agent_for(env)
+    agent.desc.max_steps = 0
+    got = record(env, n, K, T, starts, agent=agent, prob=upload(agents)[0])
+    picks = set()
+    for q in range(2 * n):
+        a = agents[q // n]
+        a.restore(a.rant, a.rconc)
+        recs = [oracle_episode(a, av, starts[q * K + k], 0) for k in range(K)]
+        assert all(len(ep) == 1 for ep in recs)
+        recs = [ep[0] for ep in recs]
+        want = dict(obs=np.array([r[0] for r in recs]), q_obs=np.array([r[1] for r in recs]), action=np.array([r[2] for r in recs], np.int32),
+                    reward=np.array([r[3] for r in recs]), success=np.array([r[4] for r in recs], np.int32), start=np.array([r[5] for r in recs], np.uint8),
+                    ep_steps=np.zeros(K, np.int32), ep_reward=np.zeros(K), ep_success=np.zeros(K, np.int32))
+        assert want["start"].tolist() == [1] * K and same_bits(want["obs"], starts[q * K:(q + 1) * K])
+        assert_log_equals(got, q, want, (env, q, "max_steps = 0"))
+        picks |= set(want["action"].tolist())
+    print("picks", sorted(picks))
+
+
 # ---- 6. record -> learn on the device ----------------------------------------------------------------------------------------------
 def taught_reference(E, passes, skip=()):
     """TaughtMirror.replay of the oracle-built log of mountaincar agent 3 by E fresh students: (description, mirrors, consumed)."""
