@@ -48,6 +48,14 @@ class AgentDesc(C.Structure):
                 ("reward_good_above", C.c_double), ("qdiff_final_tolerance", C.c_double), ("seed", C.c_uint64), ("evaluate", C.c_int32), ("debug_flags", C.c_int32), ("env_id_base", C.c_uint64)]
 
 
+HP_COLUMNS = ("alpha", "gamma", "qdiff_pos_boundary", "qdiff_neg_boundary", "weight_significant", "skip_rules")
+
+
+class HparamRowsDesc(C.Structure):
+    """struct frirl_hip_hparam_rows (include/frirl_hip.h)."""
+    _fields_ = [(k, C.c_void_p) for k in HP_COLUMNS]
+
+
 class EnvsDesc(C.Structure):
     """struct frirl_hip_envs (include/frirl_hip.h)."""
     _fields_ = [("states", C.c_void_p), ("q_ant", C.c_void_p), ("fus", C.c_void_p), ("done", C.c_void_p), ("ep_steps", C.c_void_p),
@@ -297,6 +305,12 @@ SIGNATURES = {
     "frirl_hip_learn_train": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32),
                                         LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
+    "frirl_hip_learn_run_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
+                                           C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "frirl_hip_learn_train_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
+                                             C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
     "five_hip_add_rule": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "frirl_hip_update_sarsa": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p,
@@ -313,6 +327,10 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     "frirl_hip_agent_observe_taught": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
                                                  C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_begin_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
+                                             C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_observe_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
+                                               C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
     "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
                                                 C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
@@ -355,6 +373,9 @@ SIGNATURES = {
     "frirl_hip_batch_episode": (C.c_int, [C.c_void_p]),
     "frirl_hip_batch_train": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "frirl_hip_batch_agent_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP]),
+    "frirl_hip_batch_set_hparams": (C.c_int, [C.c_void_p, C.POINTER(HparamRowsDesc)]),
+    "frirl_hip_hparam_rows_check": (C.c_int, [C.POINTER(HparamRowsDesc), C.c_int32, C.POINTER(AgentDesc)]),
     "frirl_hip_batch_get_rulebase": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _DP, _DP]),
     "frirl_hip_batch_save_rulebases": (C.c_int, [C.c_void_p, C.c_char_p]),
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -1055,6 +1076,34 @@ class Envs:
                              self.spread_ant.data_ptr(), self.spread_R.data_ptr())
 
 
+class HparamRows:
+    """Per-agent learning hyper-parameters (struct frirl_hip_hparam_rows): one value per agent of a batch of E for each column given
+    -- alpha, gamma, qdiff_pos_boundary, qdiff_neg_boundary, weight_significant (float64) and skip_rules (int32, 0 / 1) -- as anything
+    torch.as_tensor takes, of length E; a column left None keeps the Agent's value for every agent.  Owns the device tensors and the
+    struct.  Taken by agent_begin / agent_observe / train_persistent / train as rows=."""
+
+    def __init__(self, E, device, alpha=None, gamma=None, qdiff_pos_boundary=None, qdiff_neg_boundary=None, weight_significant=None,
+                 skip_rules=None):
+        import torch
+        self.E, self.desc = E, HparamRowsDesc()
+        given = dict(alpha=alpha, gamma=gamma, qdiff_pos_boundary=qdiff_pos_boundary, qdiff_neg_boundary=qdiff_neg_boundary,
+                     weight_significant=weight_significant, skip_rules=skip_rules)
+        for k in HP_COLUMNS:
+            t = None
+            if given[k] is not None:
+                t = torch.as_tensor(given[k], dtype=torch.int32 if k == "skip_rules" else torch.float64).to(device).contiguous()
+                assert t.shape == (E,), (k, tuple(t.shape), E)
+                setattr(self.desc, k, t.data_ptr())
+            setattr(self, k, t)
+
+
+def _rows(rows, E):
+    if rows is None:
+        return None
+    assert rows.E == E, (rows.E, E)
+    return C.byref(rows.desc)
+
+
 def rollout_scores(sc):
     """The [E, 40] uint8 tensor Problem.rollout_batch(scores=True) returns as a host array of RolloutScore (synchronises)."""
     raw = sc.cpu().numpy().tobytes()
@@ -1133,13 +1182,18 @@ def _teacher(teacher, E):
     return _ptr(teacher)
 
 
-def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None):
+def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None, rows=None):
     """frirl_hip_agent_begin: start an episode from the caller's observations obs [E, nant-1] (float64, on the device) for the rows
     selected by `reset` ([E] uint8 / bool, None = all).  Returns (action values [E] float64, action indices [E] int32): the first
     action of every restarted row (the other rows' entries are not written).  teacher [E] int32 (frirl_hip_agent_begin_taught): a row
-    whose entry is an action index 0..A-1 takes that action, any other value leaves the row its own pick.  Does not synchronise."""
+    whose entry is an action index 0..A-1 takes that action, any other value leaves the row its own pick.  rows: an HparamRows
+    (frirl_hip_agent_begin_rows; the begin call reads no learning hyper-parameter).  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, reset=reset)
-    if teacher is None:
+    if rows is not None:
+        check(lib().frirl_hip_agent_begin_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
+                                               C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
+              "frirl_hip_agent_begin_rows")
+    elif teacher is None:
         check(lib().frirl_hip_agent_begin(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
                                           _stream(stream)), "frirl_hip_agent_begin")
     else:
@@ -1148,14 +1202,19 @@ def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None
     return action, action_idx
 
 
-def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None):
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None):
     """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
     last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
     quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
     rows that were done are not written.  teacher [E] int32 (frirl_hip_agent_observe_taught): a row whose entry is an action index
-    takes it as its next action and learns towards Q(s', a_teacher).  Does not synchronise."""
+    takes it as its next action and learns towards Q(s', a_teacher).  rows: an HparamRows (frirl_hip_agent_observe_rows): row e
+    learns under its own values of the columns given.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    if teacher is None:
+    if rows is not None:
+        check(lib().frirl_hip_agent_observe_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
+                                                 C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
+              "frirl_hip_agent_observe_rows")
+    elif teacher is None:
         check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
                                             _stream(stream)), "frirl_hip_agent_observe")
     else:
@@ -1297,6 +1356,39 @@ def demo_batch_object(env, E, maxR, start_states=None):
     if not b:
         raise FrirlHipError("frirl_hip_batch_create: " + lib().frirl_hip_last_error().decode())
     return b
+
+
+def batch_set_hparams(batch, **columns):
+    """frirl_hip_batch_set_hparams on a library-owned batch: per-agent hyper-parameters for frirl_hip_batch_train, one host array of
+    length E per keyword (HP_COLUMNS: alpha, gamma, qdiff_pos_boundary, qdiff_neg_boundary, weight_significant, skip_rules); a column
+    left out keeps the batch's value.  No keyword at all clears every row.  The library validates and copies before it returns."""
+    import numpy as np
+    unknown = set(columns) - set(HP_COLUMNS)
+    if unknown:
+        raise TypeError(f"batch_set_hparams: unknown column(s) {sorted(unknown)}; the columns are {HP_COLUMNS}")
+    desc, keep = HparamRowsDesc(), []
+    for k, v in columns.items():
+        if v is None:
+            continue
+        a = np.ascontiguousarray(v, dtype=np.int32 if k == "skip_rules" else np.float64)
+        keep.append(a)
+        setattr(desc, k, a.ctypes.data)
+    check(lib().frirl_hip_batch_set_hparams(batch, C.byref(desc) if keep else None), "frirl_hip_batch_set_hparams")
+
+
+def batch_agent_report(batch):
+    """frirl_hip_batch_agent_report on a library-owned batch: dict of host arrays [E] -- converged, episodes, rules (int32), ep_steps
+    (int32) and ep_reward (float64) of the last finished episode: per agent what frirl_hip_batch_stats sums (E is its `agents`)."""
+    import numpy as np
+    st = BatchStats()
+    check(lib().frirl_hip_batch_stats(batch, C.byref(st)), "frirl_hip_batch_stats")
+    E = int(st.agents)
+    out = {k: np.zeros(E, dtype=np.int32) for k in ("converged", "episodes", "rules", "ep_steps")}
+    out["ep_reward"] = np.zeros(E)
+    i32 = C.POINTER(C.c_int32)
+    check(lib().frirl_hip_batch_agent_report(batch, out["converged"].ctypes.data_as(i32), out["episodes"].ctypes.data_as(i32), out["rules"].ctypes.data_as(i32),
+                                             out["ep_steps"].ctypes.data_as(i32), out["ep_reward"].ctypes.data_as(_DP)), "frirl_hip_batch_agent_report")
+    return out
 
 
 def batch_teach(batch, teacher, episodes, start_states=None, passes=1, students=None):
@@ -1683,11 +1775,18 @@ class Convergence:
                                                  _stream(stream)), "frirl_hip_convergence_update")
 
 
-def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None):
+def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None, rows=None):
     """Batched construct run: frirl_sequential_run's loop (reference frirl_sequential_run.c:55-165) for E agents
     at once.  Episodes run until every environment's rule base is "considered complete" or max_episodes-1 episodes
-    have run (:51,59).  Converged environments are masked out of later episodes.  Returns the Convergence object."""
+    have run (:51,59).  Converged environments are masked out of later episodes.  Returns the Convergence object.
+    rows (an HparamRows): only the persistent learner takes per-agent hyper-parameters, so the run goes through train_persistent
+    (on_episode is not called) or raises FrirlHipError where it does not cover the shape."""
     import torch
+    if rows is not None:
+        if not learn_supported(problem, agent):
+            raise FrirlHipError("frirl_amd.train: rows= needs the persistent learner (learn_supported), which does not cover this shape; "
+                                "the per-episode kernels take no per-agent hyper-parameters")
+        return train_persistent(problem, agent, envs, max_episodes=max_episodes, rows=rows).conv
     conv = Convergence(problem, problem.rb.device)
     max_steps = agent.desc.max_steps
     if lanes is None:           # lane-group kernel where it is the faster form (many agents / small rule bases)
@@ -1740,12 +1839,13 @@ class LearnRun:
         self.conv, self.steps_total, self.work, self.launches = conv, steps_total, work, launches
 
 
-def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None):
+def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None):
     """The construct loop of frirl_sequential_run for E agents through frirl_hip_learn_train: every agent runs its episodes
     back to back on the device; after each launch (the work of `budget` steps of a mean agent) the agents that are still
     learning are compacted and launched again until none is left -- the launch plan, the queue and the compaction are the
     library's (csrc/learn.hip), the host reads two counters per launch.  on_chunk(launch index, live agent ids, conv) is
-    called after every launch (the place for the per-chunk reward statistics).  Returns a LearnRun."""
+    called after every launch (the place for the per-chunk reward statistics).  rows: an HparamRows (frirl_hip_learn_train_rows):
+    agent e learns under its own values of the columns given.  Returns a LearnRun."""
     import torch
     dev_ = problem.rb.device
     conv = Convergence(problem, dev_)
@@ -1770,9 +1870,14 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     cb = LEARN_CHUNK_FN(chunk) if on_chunk is not None else C.cast(None, LEARN_CHUNK_FN)
     launches = C.c_int32(0)
     refused = conv.full.view(torch.uint8)
-    check(lib().frirl_hip_learn_train(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(conv.desc),
-                                      budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
-                                      C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train")
+    if rows is not None:
+        check(lib().frirl_hip_learn_train_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
+                                               C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
+                                               C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_rows")
+    else:
+        check(lib().frirl_hip_learn_train(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(conv.desc),
+                                          budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
+                                          C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train")
     if failure:
         raise failure[0]
     if conv.full_envs:

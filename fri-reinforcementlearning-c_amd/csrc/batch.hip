@@ -35,6 +35,10 @@ struct frirl_hip_batch {
     frirl_hip_envs envs;
     frirl_hip_convergence conv;
     int64_t total_env_steps;
+    double *d_hp;                // [5][E] per-agent hyper-parameter columns of frirl_hip_batch_set_hparams (allocated on first use) ...
+    int32_t *d_hp_skip;          // [E]    ... and skip_rules
+    frirl_hip_hparam_rows hp;    // the device columns that are set (all NULL: no rows)
+    bool hp_set;
     std::vector<int32_t> h_i;
     std::vector<double> h_d;
 };
@@ -113,7 +117,7 @@ extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
     if (b->s) (void)hipStreamSynchronize(b->s);
     void *ptrs[] = {b->d_u, b->d_ve, b->d_rb, b->d_rant, b->d_grid, b->d_ave, b->d_states, b->d_q_ant, b->d_ep_reward, b->d_start, b->d_prev_reward,
                     b->d_prev_rconc, b->d_tmp, b->d_nrules, b->d_fus, b->d_done, b->d_ep_steps, b->d_status, b->d_episode, b->d_prev_nrules,
-                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R};
+                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -174,9 +178,18 @@ extern "C" frirl_hip_batch *frirl_hip_batch_create(const frirl_hip_batch_desc *d
     return b;
 }
 
+// the calls that learn without honouring per-agent hyper-parameters refuse while rows are set (frirl_hip_batch_set_hparams)
+static int refuse_rows(const frirl_hip_batch *b, const char *who)
+{
+    if (!b->hp_set) return FRIRL_HIP_OK;
+    set_error("%s: per-agent hyper-parameters are set (frirl_hip_batch_set_hparams) and this call does not honour them: use frirl_hip_batch_train, or clear them", who);
+    return FRIRL_HIP_EINVAL;
+}
+
 extern "C" int frirl_hip_batch_episode(frirl_hip_batch *b)
 {
     if (!b) { set_error("frirl_hip_batch_episode: NULL batch"); return FRIRL_HIP_EINVAL; }
+    if (refuse_rows(b, "frirl_hip_batch_episode")) return FRIRL_HIP_EINVAL;
     DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
     int rc = frirl_hip_episode_begin(&b->t, &b->rb, &b->agent, &b->envs, b->s);
     if (rc) return rc;
@@ -248,8 +261,10 @@ static int batch_train_persistent(frirl_hip_batch *b, int32_t max_episodes, int3
     BCHK(hipMemsetD32Async((hipDeviceptr_t)b->d_done, 1, E, b->s), "episode flags");       // every agent is between two episodes here
     // agents that are still learning have all run `before` episodes (the per-episode form keeps them in step): up to max_episodes - 1 more
     int32_t launches = 0;
-    int rc = frirl_hip_learn_train(&b->t, &b->rb, &b->agent, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr,
-                                   b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s);
+    int rc = b->hp_set ? frirl_hip_learn_train_rows(&b->t, &b->rb, &b->agent, &b->hp, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total,
+                                                    nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
+                       : frirl_hip_learn_train(&b->t, &b->rb, &b->agent, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr,
+                                               b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s);
     if (rc) return rc;
     std::vector<int64_t> st(E);
     BCHK(hipMemcpy(st.data(), b->d_steps_total, sizeof(int64_t) * E, hipMemcpyDeviceToHost), "steps download");
@@ -308,6 +323,84 @@ int frirl_host::batch_stats_first(frirl_hip_batch *b, frirl_hip_batch_stats_t *o
     }
     out->total_env_steps = b->total_env_steps;
     if (first_converged) *first_converged = cv[0];
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_agent_report(frirl_hip_batch *b, int32_t *converged, int32_t *episodes, int32_t *rules, int32_t *ep_steps, double *ep_reward)
+{
+    if (!b) { set_error("frirl_hip_batch_agent_report: NULL batch"); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    const size_t E = (size_t)b->E;
+    BCHK(hipStreamSynchronize(b->s), "report sync");
+    if (converged) BCHK(hipMemcpy(converged, b->d_converged, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "report download");
+    if (episodes) BCHK(hipMemcpy(episodes, b->d_episodes, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "report download");
+    if (rules) BCHK(hipMemcpy(rules, b->d_nrules, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "report download");
+    if (ep_steps) BCHK(hipMemcpy(ep_steps, b->d_prev_steps, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "report download");      // last finished episode
+    if (ep_reward) BCHK(hipMemcpy(ep_reward, b->d_prev_reward, sizeof(double) * E, hipMemcpyDeviceToHost), "report download");
+    return FRIRL_HIP_OK;
+}
+
+// what a valid set of per-agent hyper-parameters is (include/frirl_hip.h): host columns [E], no device
+static int rows_check(const char *who, const frirl_hip_hparam_rows &h, int E, const frirl_hip_agent &agent)
+{
+    const double *cols[5] = {h.alpha, h.gamma, h.qdiff_pos_boundary, h.qdiff_neg_boundary, h.weight_significant};
+    static const char *names[5] = {"alpha", "gamma", "qdiff_pos_boundary", "qdiff_neg_boundary", "weight_significant"};
+    for (int e = 0; e < E; e++) {
+        for (int c = 0; c < 5; c++)
+            if (cols[c] && !(cols[c][e] - cols[c][e] == 0.0)) { set_error("%s: agent %d: %s is not finite", who, e, names[c]); return FRIRL_HIP_EINVAL; }
+        const double pos = h.qdiff_pos_boundary ? h.qdiff_pos_boundary[e] : agent.qdiff_pos_boundary;
+        const double neg = h.qdiff_neg_boundary ? h.qdiff_neg_boundary[e] : agent.qdiff_neg_boundary;
+        if ((h.qdiff_pos_boundary || h.qdiff_neg_boundary) && !(pos >= neg)) {
+            set_error("%s: agent %d: qdiff_pos_boundary %g < qdiff_neg_boundary %g", who, e, pos, neg);
+            return FRIRL_HIP_EINVAL;
+        }
+        if (h.weight_significant && !(h.weight_significant[e] >= 0.0)) { set_error("%s: agent %d: weight_significant %g is negative", who, e, h.weight_significant[e]); return FRIRL_HIP_EINVAL; }
+        if (h.skip_rules && h.skip_rules[e] != 0 && h.skip_rules[e] != 1) { set_error("%s: agent %d: skip_rules %d is neither 0 nor 1", who, e, h.skip_rules[e]); return FRIRL_HIP_EINVAL; }
+    }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_hparam_rows_check(const frirl_hip_hparam_rows *host_rows, int32_t E, const frirl_hip_agent *agent)
+{
+    if (E < 1 || !agent) { set_error("frirl_hip_hparam_rows_check: E=%d / NULL agent", E); return FRIRL_HIP_EINVAL; }
+    return host_rows ? rows_check("frirl_hip_hparam_rows_check", *host_rows, E, *agent) : FRIRL_HIP_OK;
+}
+
+// Per-agent hyper-parameter columns for frirl_hip_batch_train (include/frirl_hip.h): validated on the host, then copied.
+extern "C" int frirl_hip_batch_set_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows *host_rows)
+{
+    static const char *who = "frirl_hip_batch_set_hparams";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    const frirl_hip_hparam_rows none = {};
+    const frirl_hip_hparam_rows &h = host_rows ? *host_rows : none;
+    const double *cols[5] = {h.alpha, h.gamma, h.qdiff_pos_boundary, h.qdiff_neg_boundary, h.weight_significant};
+    if (!cols[0] && !cols[1] && !cols[2] && !cols[3] && !cols[4] && !h.skip_rules) {          // clear
+        b->hp = none;
+        b->hp_set = false;
+        return FRIRL_HIP_OK;
+    }
+    if (!b->d_uidx || !frirl_hip_learn_supported(b->nant, b->U, b->agent.A, b->agent.p, b->agent.env_kind)) {
+        set_error("%s: only the persistent learner takes per-agent hyper-parameters, and it does not cover this batch (frirl_hip_learn_supported: nant=%d U=%d A=%d p=%d; "
+                  "index mirror: %s)", who, b->nant, b->U, b->agent.A, b->agent.p, b->d_uidx ? "yes" : "no");
+        return FRIRL_HIP_EINVAL;
+    }
+    const int E = b->E;
+    if (rows_check(who, h, E, b->agent)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    if (!b->d_hp) {
+        if (!dalloc(&b->d_hp, (size_t)5 * E) || !dalloc(&b->d_hp_skip, (size_t)E)) { set_error("%s: HIP allocation failed: %s", who, hipGetErrorString(hipGetLastError())); return FRIRL_HIP_ELAUNCH; }
+    }
+    BCHK(hipStreamSynchronize(b->s), "hyper-parameter sync");           // nothing in flight reads the columns being replaced
+    for (int c = 0; c < 5; c++)
+        if (cols[c]) BCHK(hipMemcpy(b->d_hp + (size_t)c * E, cols[c], sizeof(double) * E, hipMemcpyHostToDevice), "hyper-parameter upload");
+    if (h.skip_rules) BCHK(hipMemcpy(b->d_hp_skip, h.skip_rules, sizeof(int32_t) * E, hipMemcpyHostToDevice), "hyper-parameter upload");
+    b->hp.alpha = cols[0] ? b->d_hp : nullptr;
+    b->hp.gamma = cols[1] ? b->d_hp + (size_t)E : nullptr;
+    b->hp.qdiff_pos_boundary = cols[2] ? b->d_hp + (size_t)2 * E : nullptr;
+    b->hp.qdiff_neg_boundary = cols[3] ? b->d_hp + (size_t)3 * E : nullptr;
+    b->hp.weight_significant = cols[4] ? b->d_hp + (size_t)4 * E : nullptr;
+    b->hp.skip_rules = h.skip_rules ? b->d_hp_skip : nullptr;
+    b->hp_set = true;
     return FRIRL_HIP_OK;
 }
 
@@ -563,6 +656,7 @@ extern "C" int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_
 {
     static const char *who = "frirl_hip_batch_teach";
     if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (refuse_rows(b, who)) return FRIRL_HIP_EINVAL;
     if (teacher < 0 || teacher >= b->E) { set_error("%s: teacher=%d outside 0..%d", who, teacher, b->E - 1); return FRIRL_HIP_EINVAL; }
     if (episodes < 1 || (int64_t)episodes * ((int64_t)b->agent.max_steps + 1) > INT32_MAX) { set_error("%s: episodes=%d outside 1..INT32_MAX / (max_steps + 1)", who, episodes); return FRIRL_HIP_EINVAL; }
     if (passes < 1 || passes > 1024) { set_error("%s: passes=%d outside 1..1024", who, passes); return FRIRL_HIP_EINVAL; }
@@ -745,6 +839,7 @@ int batch_merge_finish(frirl_hip_batch *b, int32_t *full_agents, bool first_is_m
 extern "C" int frirl_hip_batch_merge_round(frirl_hip_batch *b, int32_t *full_agents)
 {
     if (!b) { set_error("frirl_hip_batch_merge_round: NULL batch"); return FRIRL_HIP_EINVAL; }
+    if (refuse_rows(b, "frirl_hip_batch_merge_round")) return FRIRL_HIP_EINVAL;
     if (full_agents) *full_agents = 0;
     if (b->E < 2) return FRIRL_HIP_OK;
     std::vector<int32_t> conv;
@@ -770,6 +865,7 @@ extern "C" int frirl_hip_batch_merge_round(frirl_hip_batch *b, int32_t *full_age
 extern "C" int frirl_hip_batch_train_merged(frirl_hip_batch *b, int32_t max_episodes, int32_t chunk, int32_t *episodes_run, int32_t *rounds)
 {
     if (!b || chunk < 2) { set_error("frirl_hip_batch_train_merged: bad arguments"); return FRIRL_HIP_EINVAL; }
+    if (refuse_rows(b, "frirl_hip_batch_train_merged")) return FRIRL_HIP_EINVAL;
     DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
     int episode_num = 1, episodes = 0, nrounds = 0;         // frirl_desc.episode_num of the master starts at 1 (frirl_init.c)
     for (;;) {

@@ -16,8 +16,10 @@ namespace frirl {
 // the caller's step data (frirl_hip_agent_io) for EXT kernels, nothing for the demo kernels
 struct NoIo {};
 // ... plus the teacher's actions of frirl_hip_agent_begin_taught / _observe_taught: [E] action indices, or NULL (the untaught calls)
+// ... and the per-agent hyper-parameters of frirl_hip_agent_begin_rows / _observe_rows: columns [E] or NULL (all NULL: the calls without rows)
 struct ExtIo : frirl_hip_agent_io {
     const int32_t *teacher;
+    frirl_hip_hparam_rows rows;
 };
 template <bool EXT>
 using IoArg = std::conditional_t<EXT, ExtIo, NoIo>;
@@ -30,6 +32,28 @@ __device__ __forceinline__ int taught_action(const ExtIo &io, int e, int A, int 
     if (!io.teacher) return chosen;
     const int32_t k = io.teacher[e];
     return (k >= 0 && k < A) ? k : chosen;
+}
+
+// The learning hyper-parameters the step reads (frirl_update_sarsa.c:358,363, update_rules :30-126), under the field names of
+// frirl_hip_agent: the demo kernels read them from the launch's agent itself; the EXT kernels build the workgroup's own copy, row e
+// of every column of io.rows that is given.  One workgroup serves one row, so the values are wave-uniform: they are moved to scalar
+// registers, where the launch's own live (as vector registers they cost some variants a wave per SIMD).
+struct StepHparams {
+    double alpha, gamma, qdiff_pos_boundary, qdiff_neg_boundary, weight_significant;
+    int32_t skip_rules;
+};
+__device__ __forceinline__ const frirl_hip_agent &step_hparams(const frirl_hip_agent &ag, const NoIo &, int) { return ag; }
+__device__ __forceinline__ StepHparams step_hparams(const frirl_hip_agent &ag, const ExtIo &io, int e)
+{
+    const frirl_hip_hparam_rows &r = io.rows;
+    StepHparams h;
+    h.alpha = r.alpha ? wave_uniform(r.alpha[e]) : ag.alpha;
+    h.gamma = r.gamma ? wave_uniform(r.gamma[e]) : ag.gamma;
+    h.qdiff_pos_boundary = r.qdiff_pos_boundary ? wave_uniform(r.qdiff_pos_boundary[e]) : ag.qdiff_pos_boundary;
+    h.qdiff_neg_boundary = r.qdiff_neg_boundary ? wave_uniform(r.qdiff_neg_boundary[e]) : ag.qdiff_neg_boundary;
+    h.weight_significant = r.weight_significant ? wave_uniform(r.weight_significant[e]) : ag.weight_significant;
+    h.skip_rules = r.skip_rules ? __builtin_amdgcn_readfirstlane(r.skip_rules[e]) : ag.skip_rules;
+    return h;
 }
 
 struct StepShared {
@@ -51,12 +75,13 @@ __device__ __forceinline__ bool frirl_no_spread_candidates(const frirl_hip_agent
 
 // frirl_update_sarsa + update_rules (reference src/frirl/frirl_update_sarsa.c:348-385, :22-143).
 // `qp_known`: Q(s',a') already available (fused step: the greedy sweep produced it, identical
-// operands and order -- SURVEY 7(i)); otherwise it is computed by a sweep over ve2.
-template <int NANT, int BLOCK, bool TRACK = false, class COLS, class POW>
-__device__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u, const double *__restrict__ ve, int U, double *__restrict__ base,
-                                  int maxR, int32_t *nrules_e, const frirl_hip_agent &ag, StepShared &sh, double reward,
-                                  bool qp_known, double qp, int32_t *fus_e, double *rant_e, BlockRed<BLOCK> &red,
-                                  const QResult *rn_known, uint16_t *uidx_e, POW p, SpreadCand *slot, double *spread_ant_e = nullptr, int32_t *spread_R_e = nullptr)
+// operands and order -- SURVEY 7(i)); otherwise it is computed by a sweep over ve2.  `hp`: the six learning hyper-parameters, `ag` itself
+// or a StepHparams (of `ag` only the grids and the debug flags are read).
+template <int NANT, int BLOCK, bool TRACK = false, class COLS, class POW, class HP>
+__device__ int update_sarsa_block_hp(const COLS &cols, const double *__restrict__ u, const double *__restrict__ ve, int U, double *__restrict__ base,
+                                     int maxR, int32_t *nrules_e, const frirl_hip_agent &ag, const HP &hp, StepShared &sh, double reward,
+                                     bool qp_known, double qp, int32_t *fus_e, double *rant_e, BlockRed<BLOCK> &red,
+                                     const QResult *rn_known, uint16_t *uidx_e, POW p, SpreadCand *slot, double *spread_ant_e, int32_t *spread_R_e)
 {
     const int R = *nrules_e;
     double q1[NANT], q2[NANT];
@@ -68,13 +93,13 @@ __device__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u
         const QResult rp = sweep_q<NANT, BLOCK>(cols, qcol, R, q2, p, red);
         qp = (rp.hit != FRIRL_HIP_NO_HIT) ? qcol[rp.hit] : rp.vagc / rp.ws;
     }
-    const QResult rn = rn_known ? *rn_known : sweep_q<NANT, BLOCK, TRACK>(cols, qcol, R, q1, p, red, ag.weight_significant, slot);    // :357  Q(s,a)
+    const QResult rn = rn_known ? *rn_known : sweep_q<NANT, BLOCK, TRACK>(cols, qcol, R, q1, p, red, hp.weight_significant, slot);    // :357  Q(s,a)
     const double qnow = (rn.hit != FRIRL_HIP_NO_HIT) ? qcol[rn.hit] : rn.vagc / rn.ws;
-    const double qdiff = ag.alpha * (reward + ag.gamma * qp - qnow);        // :358
+    const double qdiff = hp.alpha * (reward + hp.gamma * qp - qnow);        // :358
     int fus = *fus_e;
     __syncthreads();   // every thread has read *fus_e / *nrules_e before thread 0 may rewrite them
 
-    if (qdiff > ag.qdiff_pos_boundary || qdiff < ag.qdiff_neg_boundary) {   // :363
+    if (qdiff > hp.qdiff_pos_boundary || qdiff < hp.qdiff_neg_boundary) {   // :363
         // snap the antecedents to the allowed grid (check_possible_states, :146-170)
         if (threadIdx.x < NANT) {
             const int k = threadIdx.x;
@@ -114,13 +139,13 @@ __device__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u
     int rules = R;
     if (fus) rules--;                                                       // :30-33
     int status;
-    if (rn.hit != FRIRL_HIP_NO_HIT && (ag.skip_rules == 0 || (ag.skip_rules == 1 && (int)rn.hit < rules))) {
+    if (rn.hit != FRIRL_HIP_NO_HIT && (hp.skip_rules == 0 || (hp.skip_rules == 1 && (int)rn.hit < rules))) {
         if (threadIdx.x == 0) qcol[rn.hit] = qnow + qdiff;                  // :55
         status = FRIRL_HIP_UPD_EXACT;
-    } else if (ag.skip_rules == 1 && rn.hit != FRIRL_HIP_NO_HIT && (int)rn.hit == rules) {
+    } else if (hp.skip_rules == 1 && rn.hit != FRIRL_HIP_NO_HIT && (int)rn.hit == rules) {
         status = FRIRL_HIP_UPD_SKIPPED;                                     // :61-63
     } else {
-        if (ag.skip_rules == 0) fus = 0;                                    // :70-73
+        if (hp.skip_rules == 0) fus = 0;                                    // :70-73
         const int r_skip = fus ? R - 1 : -1;                                // :76,124-126: the just-inserted rule keeps its Q
         if (rn.hit == FRIRL_HIP_NO_HIT) {      // FIVE_vag_concl_weight interpolated (:40): this call defines FIVERB.weights from now on
             if (spread_ant_e && threadIdx.x < NANT) spread_ant_e[threadIdx.x] = sh.q_ant[threadIdx.x];
@@ -128,12 +153,23 @@ __device__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u
         }
         // K6+K7: from the candidates tracked during the Q(s,a) sweep when possible (no second pass over the slab), else the sweep
         const bool from_cand = TRACK && rn.tracked && rn.hit == FRIRL_HIP_NO_HIT && !frirl_no_spread_candidates(ag) &&
-                               spread_from_candidates<BLOCK>(slot[threadIdx.x], qcol, rn.ws, qnow, qdiff, ag.weight_significant, r_skip, red);
-        if (!from_cand) sweep_update<NANT, BLOCK>(cols, qcol, R, q1, p, rn.ws, qnow, qdiff, ag.weight_significant, r_skip);
+                               spread_from_candidates<BLOCK>(slot[threadIdx.x], qcol, rn.ws, qnow, qdiff, hp.weight_significant, r_skip, red);
+        if (!from_cand) sweep_update<NANT, BLOCK>(cols, qcol, R, q1, p, rn.ws, qnow, qdiff, hp.weight_significant, r_skip);
         status = FRIRL_HIP_UPD_SPREAD;
     }
     if (threadIdx.x == 0) *fus_e = fus;
     return status;
+}
+
+// ... with the launch's own hyper-parameters (every caller but the EXT step kernel, which passes row e of frirl_hip_hparam_rows)
+template <int NANT, int BLOCK, bool TRACK = false, class COLS, class POW>
+__device__ __forceinline__ int update_sarsa_block(const COLS &cols, const double *__restrict__ u, const double *__restrict__ ve, int U, double *__restrict__ base,
+                                                  int maxR, int32_t *nrules_e, const frirl_hip_agent &ag, StepShared &sh, double reward,
+                                                  bool qp_known, double qp, int32_t *fus_e, double *rant_e, BlockRed<BLOCK> &red,
+                                                  const QResult *rn_known, uint16_t *uidx_e, POW p, SpreadCand *slot, double *spread_ant_e = nullptr, int32_t *spread_R_e = nullptr)
+{
+    return update_sarsa_block_hp<NANT, BLOCK, TRACK>(cols, u, ve, U, base, maxR, nrules_e, ag, ag, sh, reward, qp_known, qp, fus_e, rant_e, red, rn_known, uidx_e, p,
+                                                     slot, spread_ant_e, spread_R_e);
 }
 
 // frirl_episode(): start of an episode (reference src/frirl/frirl_episode.c:46-82).
@@ -241,6 +277,7 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         if (threadIdx.x == 0 && ev.status) ev.status[e] = FRIRL_HIP_UPD_INACTIVE;
         return;
     }
+    decltype(auto) hp = step_hparams(ag, io, e);           // `ag` itself; EXT: its own copy, row e of the columns of io.rows that are given
     extern __shared__ double tab_s[];
     __shared__ StepShared sh;
     __shared__ BlockRed<BLOCK> red;
@@ -286,7 +323,7 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
     // one pass over the slab: greedy action for s' (:148) AND Q(s,a) of the pending update (frirl_update_sarsa.c:357)
     int ap;
     if constexpr (AMAX == 24) ap = sweep_gba_many<NANT, AMAX, BLOCK, true>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, &rn);
-    else if constexpr (AMAX > 8) ap = sweep_gba_wide<NANT, 8, AMAX, BLOCK, true, TRACK>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, &rn, ag.weight_significant, cand_s);
+    else if constexpr (AMAX > 8) ap = sweep_gba_wide<NANT, 8, AMAX, BLOCK, true, TRACK>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, &rn, hp.weight_significant, cand_s);
     else {
         // the agent has not left its quantisation cell (workgroup-uniform): Q(s, a) of the pending update is the greedy sweep's conclusion
         // for action a at the new observation (sweeps.h: SAMES)
@@ -295,8 +332,8 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         for (int k = 0; k < NS; k++) same_cell = same_cell && (q[k] == q1[k]);
         int apend = -1;
         for (int a = ag.A - 1; a >= 0; a--) if (gs.ave[a] == q1[NS]) apend = a;
-        if (same_cell && apend >= 0) ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, true>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, ag.weight_significant, cand_s, apend);
-        else ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, false>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, ag.weight_significant, cand_s);
+        if (same_cell && apend >= 0) ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, true>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, hp.weight_significant, cand_s, apend);
+        else ap = sweep_gba_q<NANT, AMAX, BLOCK, TRACK, false>(cols, qcol, nrules[e], q, q1, pw, ag.A, gs, red, rn, hp.weight_significant, cand_s);
     }
 #ifdef FRIRL_STEP_TIMING
     const long long tm1 = wall_clock64();
@@ -317,8 +354,8 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
     double *rant_e = ev.rant ? ev.rant + (size_t)e * NANT * maxR : nullptr;
     int st = FRIRL_HIP_UPD_INACTIVE;
     if (!ag.evaluate)                                                                                 // :155 (reduction_state == 0)
-        st = update_sarsa_block<NANT, BLOCK, TRACK>(cols, u, ve, U, base, maxR, nrules + e, ag, sh, sh.reward, true, qp, ev.fus + e, rant_e, red, &rn, uidx_e, pw, cand_s,
-                                                    ev.spread_ant ? ev.spread_ant + (size_t)e * NANT : nullptr, ev.spread_R ? ev.spread_R + e : nullptr);  // :159
+        st = update_sarsa_block_hp<NANT, BLOCK, TRACK>(cols, u, ve, U, base, maxR, nrules + e, ag, hp, sh, sh.reward, true, qp, ev.fus + e, rant_e, red, &rn, uidx_e, pw, cand_s,
+                                                       ev.spread_ant ? ev.spread_ant + (size_t)e * NANT : nullptr, ev.spread_R ? ev.spread_R + e : nullptr);  // :159
     if (threadIdx.x < NS) ev.states[(size_t)e * NS + threadIdx.x] = sh.cur_states[threadIdx.x];      // :163-165
     if (threadIdx.x < NANT) ev.q_ant[(size_t)e * NANT + threadIdx.x] = sh.cur_q_ant[threadIdx.x];    // :166-168
     if (threadIdx.x == 0) {

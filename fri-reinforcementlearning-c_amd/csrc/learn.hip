@@ -1,4 +1,5 @@
-// learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, instantiated in learn_i0/1/2.hip).
+// learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, instantiated in learn_i0 .. i4.hip and, with per-agent
+// hyper-parameter rows, learn_r0 .. r4.hip).
 #include "learn_kernel.h"
 
 using namespace frirl_host;
@@ -105,20 +106,20 @@ extern "C" int frirl_hip_learn_timing(unsigned long long *out16)       // read a
 #endif
 
 // One chunk of the construct loop for the agents in `live` (device array of nlive agent ids, or NULL = agents 0..nlive-1):
-// see include/frirl_hip.h.
-extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
-                                   const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
-                                   int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+// see include/frirl_hip.h.  rows != NULL: the ROWS kernels (learn_r*.hip), every agent under its own hyper-parameters.
+static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                     const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                     int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = frirl_check_episode(t, b, agent, envs, "frirl_hip_learn_run");
+    int rc = frirl_check_episode(t, b, agent, envs, who);
     if (rc) return rc;
-    if (!conv || !conv->prev_nrules || !conv->prev_steps || !conv->prev_reward || !conv->prev_rconc || !conv->converged || !conv->episodes) { set_error("frirl_hip_learn_run: NULL convergence state"); return FRIRL_HIP_EINVAL; }
-    if (!frirl_hip_learn_supported(t->nant, t->U, agent->A, agent->p, agent->env_kind)) { set_error("frirl_hip_learn_run: shape nant=%d U=%d A=%d p=%d not covered (use frirl_hip_episode_run_lanes)", t->nant, t->U, agent->A, agent->p); return FRIRL_HIP_EINVAL; }
-    if (!b->uidx) { set_error("frirl_hip_learn_run: needs the 16-bit index mirror (frirl_hip_rulebases.uidx)"); return FRIRL_HIP_EINVAL; }
-    if (nlive < 1 || nlive > b->E || budget_steps < 0 || max_episodes < 1) { set_error("frirl_hip_learn_run: nlive=%d / budget=%d / max_episodes=%d", nlive, budget_steps, max_episodes); return FRIRL_HIP_EINVAL; }
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) { set_error("frirl_hip_learn_run: workspace must be a 16-byte aligned device buffer"); return FRIRL_HIP_EINVAL; }
+    if (!conv || !conv->prev_nrules || !conv->prev_steps || !conv->prev_reward || !conv->prev_rconc || !conv->converged || !conv->episodes) { set_error("%s: NULL convergence state", who); return FRIRL_HIP_EINVAL; }
+    if (!frirl_hip_learn_supported(t->nant, t->U, agent->A, agent->p, agent->env_kind)) { set_error("%s: shape nant=%d U=%d A=%d p=%d not covered (use frirl_hip_episode_run_lanes)", who, t->nant, t->U, agent->A, agent->p); return FRIRL_HIP_EINVAL; }
+    if (!b->uidx) { set_error("%s: needs the 16-bit index mirror (frirl_hip_rulebases.uidx)", who); return FRIRL_HIP_EINVAL; }
+    if (nlive < 1 || nlive > b->E || budget_steps < 0 || max_episodes < 1) { set_error("%s: nlive=%d / budget=%d / max_episodes=%d", who, nlive, budget_steps, max_episodes); return FRIRL_HIP_EINVAL; }
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) { set_error("%s: workspace must be a 16-byte aligned device buffer", who); return FRIRL_HIP_EINVAL; }
     const size_t need = frirl_hip_learn_workspace_bytes(t->nant, nlive, b->maxR, agent->A);
-    if (workspace_bytes < need) { set_error("frirl_hip_learn_run: workspace %zu B < %zu B (frirl_hip_learn_workspace_bytes)", workspace_bytes, need); return FRIRL_HIP_EINVAL; }
+    if (workspace_bytes < need) { set_error("%s: workspace %zu B < %zu B (frirl_hip_learn_workspace_bytes)", who, workspace_bytes, need); return FRIRL_HIP_EINVAL; }
     hipStream_t s = as_stream(stream);
     frirl::LearnArgs la = {};
     la.u = t->u; la.ve = t->ve; la.U = t->U;
@@ -131,10 +132,31 @@ extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_ru
 #endif
     int H = learn_slices(nlive);
     if (H < learn_min_slices(agent->A)) H = learn_min_slices(agent->A);
+    if (rows) {
+        la.hp = *rows;
+        if (t->nant == 3) frirl_learn_launch_mountaincar_rows(H, t, b, agent, envs, conv, la, s);
+        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_rows(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_rows(H, t, b, agent, envs, conv, la, s); }
+        else { if (H <= 8) frirl_learn_launch_cartpole_lo_rows(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_rows(H, t, b, agent, envs, conv, la, s); }
+        return check_launch(who);
+    }
     if (t->nant == 3) frirl_learn_launch_mountaincar(H, t, b, agent, envs, conv, la, s);
     else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi(H, t, b, agent, envs, conv, la, s); }
     else { if (H <= 8) frirl_learn_launch_cartpole_lo(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi(H, t, b, agent, envs, conv, la, s); }
-    return check_launch("frirl_hip_learn_run");
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
+                                   const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
+                                   int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+}
+
+extern "C" int frirl_hip_learn_run_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                        const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                                        int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 
@@ -227,18 +249,18 @@ extern "C" size_t frirl_hip_learn_train_workspace_bytes(int32_t nant, int32_t E,
     return a ? (a + 15) / 16 * 16 + learn_train_tail_bytes(E) : 0;
 }
 
-extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
-                                     const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
-                                     uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
-                                     frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                       const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                       int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                       frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    int rc = frirl_check_episode(t, b, agent, envs, "frirl_hip_learn_train");
+    int rc = frirl_check_episode(t, b, agent, envs, who);
     if (rc) return rc;
-    if (!conv || !conv->converged || !conv->episodes) { set_error("frirl_hip_learn_train: NULL convergence state"); return FRIRL_HIP_EINVAL; }
+    if (!conv || !conv->converged || !conv->episodes) { set_error("%s: NULL convergence state", who); return FRIRL_HIP_EINVAL; }
     const int E = b->E;
     const size_t run_bytes = (frirl_hip_learn_workspace_bytes(t->nant, E, b->maxR, agent->A) + 15) / 16 * 16;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < run_bytes + learn_train_tail_bytes(E)) {
-        set_error("frirl_hip_learn_train: workspace %zu B < %zu B (frirl_hip_learn_train_workspace_bytes) or not 16-byte aligned", workspace_bytes, run_bytes + learn_train_tail_bytes(E));
+        set_error("%s: workspace %zu B < %zu B (frirl_hip_learn_train_workspace_bytes) or not 16-byte aligned", who, workspace_bytes, run_bytes + learn_train_tail_bytes(E));
         return FRIRL_HIP_EINVAL;
     }
     hipStream_t s = as_stream(stream);
@@ -256,17 +278,36 @@ extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_
         if ((rc = frirl_hip_learn_plan(n, (int32_t)(mean_rules * (agent->A + 1) / 4), &H, &take)) != 0) return rc;
         if (H < learn_min_slices(agent->A)) { H = learn_min_slices(agent->A); const long fit = learn_lanes() / H; take = (int32_t)(n < fit ? n : fit); }
         hipLaunchKernelGGL(learn_queue_sort_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, take, b->nrules, shift, live);
-        if ((rc = frirl_hip_learn_run(t, b, agent, envs, conv, live, take, budget_steps, max_episodes, work, steps_total, workspace, run_bytes, stream)) != 0) return rc;
+        if ((rc = learn_run(rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
+                            workspace, run_bytes, stream)) != 0) return rc;
         launches++;
         hipLaunchKernelGGL(learn_queue_next_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, n, take, live, conv->converged, conv->episodes, max_episodes, b->nrules,
                            envs->status, refused, qb, counters);
         long long h[2] = {0, 0};
-        if (hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return check_launch("frirl_hip_learn_train");
+        if (hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return check_launch(who);
         if (on_chunk) on_chunk(user, launches, live, take);
         int32_t *x = qa; qa = qb; qb = x;
         n = (int)h[0];
         mean_rules = n > 0 ? h[1] / n : 0;
     }
     if (launches_out) *launches_out = launches;
-    return check_launch("frirl_hip_learn_train");
+    return check_launch(who);
+}
+
+extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
+                                     const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
+                                     uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                                     frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+{
+    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+                       launches_out, on_chunk, user, stream);
+}
+
+extern "C" int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                          const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                                          int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                                          frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+{
+    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+                       launches_out, on_chunk, user, stream);
 }

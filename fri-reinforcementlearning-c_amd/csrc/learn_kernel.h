@@ -62,6 +62,7 @@ struct LearnArgs {
     int budget;                  // environment steps in this launch for an agent with the launch's mean rule count (see work budget)
     long long *sum_rules;        // sum of the live agents' rule counts at the start of the launch (import kernel)
     int max_episodes;            // the loop runs episodes 1 .. max_episodes - 1 (frirl_sequential_run.c:51,59)
+    frirl_hip_hparam_rows hp;    // per-agent hyper-parameters [E], indexed by the agent id (ROWS kernels only; a NULL column = the launch's value)
 #ifdef LEARN_TIMING
     unsigned long long *timing;  // [16] cycles per section of the step, summed over waves (tools/exp builds only)
 #endif
@@ -131,7 +132,11 @@ __global__ __launch_bounds__(256) void learn_export_kernel(const LearnArgs la, i
 }
 
 // ---- the learner ------------------------------------------------------------------------------------------------------
-template <int NANT, int NA, int KIND, int H, int BITS, int WPS>
+// ROWS: the six learning hyper-parameters of frirl_hip_hparam_rows are per agent.  Agents share a wave, so they are per-lane values
+// (11 VGPRs) where the launch's own are scalars; the kernel is at its register limit during the rule sweep (see the cold state below),
+// so they are not held across it: every step reloads them from global memory after the sweep, where they are first used (48 B per
+// agent and step, cache-resident, against thousands of rule bytes).  ROWS = false compiles to the code without the parameter.
+template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false>
 __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la, const frirl_hip_agent ag, const frirl_hip_envs ev,
                                                               const frirl_hip_convergence cv)
 {
@@ -479,6 +484,16 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
         }
         LT_MARK(3);
         if (active) {
+            // the hyper-parameters of this step: the launch's scalars, or (ROWS) the agent's own row -- by agent id e, never by slot -- all
+            // six loads issued together here, after the sweep (one memory latency per step, not one per use)
+            // (the row index passes through an empty asm, so that the six row addresses are formed here and not hoisted out of the step
+            // loop as invariants: 12 VGPRs that would be live across the sweep)
+            int erow = e;
+            if constexpr (ROWS) asm volatile("" : "+v"(erow));
+            auto hp = [&](auto col, auto dflt) { if constexpr (ROWS) { return col ? col[erow] : dflt; } else { (void)col; return dflt; } };
+            const double hp_alpha = hp(la.hp.alpha, ag.alpha), hp_gamma = hp(la.hp.gamma, ag.gamma), hp_wsig = hp(la.hp.weight_significant, ag.weight_significant);
+            const double hp_pos = hp(la.hp.qdiff_pos_boundary, ag.qdiff_pos_boundary), hp_neg = hp(la.hp.qdiff_neg_boundary, ag.qdiff_neg_boundary);
+            const int hp_skip = hp(la.hp.skip_rules, ag.skip_rules);
             if (begin) {
                 episode++;
                 const int a0 = e_greedy(ag, ci, (uint32_t)e, episode, 0u);                              // :78-82
@@ -486,7 +501,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                 begin = false;
                 double w0 = swb;
                 if (a0 != ci) { double v0; unsigned h0; action_conclusion(a0, v0, w0, h0); }
-                thr = (ag.weight_significant * (1.0 - 4e-9)) * w0;
+                thr = (hp_wsig * (1.0 - 4e-9)) * w0;
 #pragma unroll
                 for (int k = 0; k < NS; k++) ve1[k] = ve2[k];                                           // (start state, a0) is the next pending point
                 ve1[NS] = ves[NS * TS + aidx_s[a0]];
@@ -510,7 +525,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                     action_conclusion(chosen, v, w0, hh);
                     qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0;
                 }
-                thr = (ag.weight_significant * (1.0 - 4e-9)) * w0;                                      // (s', a') is the next pending point
+                thr = (hp_wsig * (1.0 - 4e-9)) * w0;                                      // (s', a') is the next pending point
                 const double qnow = (hit1 != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hit1 / H) * 64 + (hit1 % H)] : vs1 / ws1;   // Q(s,a), :357
                 cur_q[NS] = grid_s[NS * FRIRL_HIP_MAX_GRID + chosen];                                    // frirl_episode.c:151
 
@@ -518,9 +533,9 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                 //      same branch; single stores are issued by lane 0, the weighted spread by every lane for its own rules
                 LT_MARK(4);
                 if (!ag.evaluate) {                                                                     // frirl_episode.c:155
-                    const double qdiff = ag.alpha * (reward + ag.gamma * qp - qnow);                    // :358
+                    const double qdiff = hp_alpha * (reward + hp_gamma * qp - qnow);                    // :358
                     bool finished = false;
-                    if (qdiff > ag.qdiff_pos_boundary || qdiff < ag.qdiff_neg_boundary) {               // :363
+                    if (qdiff > hp_pos || qdiff < hp_neg) {               // :363
                         double rant[NANT], ve3[NANT];
                         uint32_t pk3[W];
 #pragma unroll
@@ -589,12 +604,12 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                     LT_MARK(5);
                     if (!finished) {
                         const int rules = fus ? R - 1 : R;                                              // :30-33
-                        if (hit1 != FRIRL_HIP_NO_HIT && (ag.skip_rules == 0 || (ag.skip_rules == 1 && (int)hit1 < rules))) {
+                        if (hit1 != FRIRL_HIP_NO_HIT && (hp_skip == 0 || (hp_skip == 1 && (int)hit1 < rules))) {
                             if (h == 0) Tq_g[(size_t)(hit1 / H) * 64 + (hit1 % H)] = qnow + qdiff;       // :55
-                        } else if (ag.skip_rules == 1 && hit1 != FRIRL_HIP_NO_HIT && (int)hit1 == rules) {
+                        } else if (hp_skip == 1 && hit1 != FRIRL_HIP_NO_HIT && (int)hit1 == rules) {
                             // :61-63 hit on the just-inserted rule: skipped
                         } else {
-                            if (ag.skip_rules == 0) fus = 0;                                            // :70-73
+                            if (hp_skip == 0) fus = 0;                                               // :70-73
                             const int r_skip = fus ? R - 1 : -1;                                        // :76,124-126
                             if (hit1 == FRIRL_HIP_NO_HIT && h == 0 && ev.spread_ant) {   // this call defines FIVERB.weights from now on (frirl_hip.h)
 #pragma unroll
@@ -608,7 +623,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
 #pragma unroll
                                 for (int k = 1; k < NANT; k++) { const double d = ve1[k] - c[k]; s = __fma_rn(d, d, s); }
                                 const double w = shepard_w(s, pk) * iws;
-                                if (w > ag.weight_significant && r != r_skip) { const double t = qdiff * w; Tq_l[(size_t)(r / H) * 64] = qnow + t; }
+                                if (w > hp_wsig && r != r_skip) { const double t = qdiff * w; Tq_l[(size_t)(r / H) * 64] = qnow + t; }
                             };
                             const int jt0 = (R - h + H - 1) / H - 1;                                    // the walk the flags were taken on
                             if (group_or(!flags_known || jt0 >= MW * 32)) {
@@ -718,7 +733,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
 }  // namespace frirl
 
 
-template <int N, int NA, int KIND, int H, int BITS, int WPS>
+template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false>
 inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                          const frirl_hip_convergence *cv, frirl::LearnArgs la, hipStream_t s)
 {
@@ -735,32 +750,32 @@ inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     const size_t dyn = sizeof(double) * frirl::LR_WPB * EPW * NCOLD_;
     if (dyn > 40 * 1024) {                                                     // static (~24 KB) + dynamic beyond the 64 KB default
         static bool raised = false;                                            // per instantiation
-        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
+        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
     }
     hipLaunchKernelGGL((frirl::learn_import_kernel<N, BITS>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
     const int blocks = (la.tiles + frirl::LR_WPB - 1) / frirl::LR_WPB;
-    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
+    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
     hipLaunchKernelGGL((frirl::learn_export_kernel<N>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
 }
 
 
 // one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation file (learn_i*.hip) compiles a few kernels, so
 // that the build runs them in parallel
-template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI>
+template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false>
 inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                            const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s)
 {
-    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
 }
 
 // defined in learn_i0.hip (mountaincar), learn_i1.hip (acrobot, 1 .. 8 lanes per agent), learn_i2.hip (acrobot, 16 .. 64),
-// learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64)
+// learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64); the _rows twins (ROWS = true, la.hp set) in learn_r0.hip .. learn_r4.hip
 void frirl_learn_launch_cartpole_lo(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                     const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_cartpole_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
@@ -771,3 +786,13 @@ void frirl_learn_launch_acrobot_lo(int H, const frirl_hip_tables *t, const frirl
                                    const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_acrobot_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                    const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_lo_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_hi_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_mountaincar_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_lo_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_hi_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);

@@ -22,7 +22,8 @@ static int usage(const char *what)
     fprintf(stderr, "usage error: %s\n"
                     "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F] [--teach-best M [--teach-passes P]]   (K >= 1 rows per agent, 0 <= F <= 1, M >= 1 episodes, 1 <= P <= 1024)\n"
                     "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-starts K [--spread F]   (S = 1 | 2, 1 <= K <= 256 start states per agent, 0 <= F <= 1)\n"
-                    "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-map K [--spread F] [--reduce-map-all]   (removals validated on the policy map at the points visited from K start states; --reduce-map-all: of every start, not the successful ones alone)\n", what);
+                    "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-map K [--spread F] [--reduce-map-all]   (removals validated on the policy map at the points visited from K start states; --reduce-map-all: of every start, not the successful ones alone)\n"
+                    "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n", what);
     return 2;
 }
 
@@ -40,6 +41,7 @@ int main(int argc, char **argv)
     int reduce_starts = 0;          /* --reduce-starts K: with --reduce-all, every removal is validated against K start states per agent, 0 = not asked for */
     int reduce_map = 0;             /* --reduce-map K: with --reduce-all, every removal is validated on the policy map at the points visited from K start states, 0 = not asked for */
     int reduce_map_all = 0;         /* --reduce-map-all: the points of every start, not of the successful ones alone */
+    const char *hparams = NULL;     /* --hparams FILE: with --agents, agent e learns under the hyper-parameter set on line e mod L of FILE */
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -56,6 +58,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--reduce-starts") && i + 1 < argc) { reduce_starts = atoi(argv[++i]); if (reduce_starts < 1 || reduce_starts > 256) return usage("--reduce-starts needs 1 <= K <= 256"); }
         else if (!strcmp(argv[i], "--reduce-map") && i + 1 < argc) { reduce_map = atoi(argv[++i]); if (reduce_map < 1 || reduce_map > 256) return usage("--reduce-map needs 1 <= K <= 256"); }
         else if (!strcmp(argv[i], "--reduce-map-all")) reduce_map_all = 1;
+        else if (!strcmp(argv[i], "--hparams") && i + 1 < argc) hparams = argv[++i];
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
         else if (!strcmp(argv[i], "--teach-best") && i + 1 < argc) { teach_best = atoi(argv[++i]); if (teach_best < 1) return usage("--teach-best needs M >= 1"); }
         else if (!strcmp(argv[i], "--teach-passes") && i + 1 < argc) { teach_passes = atoi(argv[++i]); if (teach_passes < 1 || teach_passes > 1024) return usage("--teach-passes needs 1 <= P <= 1024"); }
@@ -69,7 +72,21 @@ int main(int argc, char **argv)
     if (reduce_map > 0 && (agents < 1 || !reduce_all || (reduce != 1 && reduce != 2) || merge || gpus >= 0))
         return usage("--reduce-map goes with --agents N --reduce S --reduce-all (one device, no --merge)");
     if (reduce_map_all && reduce_map < 1) return usage("--reduce-map-all goes with --reduce-map K");
+    if (hparams && (merge || teach_best > 0)) return usage("--hparams does not go with --merge or --teach-best: the rule-base exchange and the replay of a teacher's log do not honour per-agent hyper-parameters");
+    if (hparams && (agents < 1 || gpus >= 0 || reduce || evaluate > 0 || load_bin || save_bin)) return usage("--hparams goes with --agents N alone (one device, trained from scratch)");
     frirl_parse_cmdline(&fr, fargc, fargv);
+    if (hparams) {                  /* a sweep: one persistent-learner run, one report line per set */
+        double *sets = NULL;
+        int nsets = 0, rc;
+        char err[256];
+        if (frirl_demo_parse_hparams(hparams, &sets, &nsets, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --hparams %s: %s\n", hparams, err);
+            return 2;
+        }
+        rc = frirl_demo_batch_run_hparams(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, sets, nsets, 1);
+        free(sets);
+        return rc >= 0 ? 0 : 3;
+    }
     if (evaluate > 0) {             /* train (or --load), then every agent rolled out from K start states */
         int ns = 0, U = 0, A = 0, ms = 0, rc;
         double *units;

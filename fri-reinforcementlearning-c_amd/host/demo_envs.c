@@ -679,3 +679,88 @@ static int demo_batch_run(const char *env, int agents, int max_episodes, int red
     demo_desc_free(&mm);
     return (int)st.converged;
 }
+
+/* ---- a hyper-parameter sweep in one run: frirl_demo --agents N --hparams FILE ---------------------------------------------------------
+ * FILE: one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`; `#` starts a comment; blank lines are skipped.
+ * *sets = malloc'ed [*nsets][6]; err receives "line N: why" for the first malformed line, or why the file is unusable. */
+int frirl_demo_parse_hparams(const char *path, double **sets, int *nsets, char *err, size_t err_len)
+{
+    char line[512];
+    int lineno = 0, n = 0, cap = 0;
+    double *out = NULL;
+    FILE *fp = fopen(path, "r");
+    *sets = NULL; *nsets = 0;
+    if (!fp) { snprintf(err, err_len, "cannot open %s", path); return -1; }
+    while (fgets(line, sizeof line, fp)) {
+        double v[6];
+        char tail[2], *hash = strchr(line, '#');
+        int got, k;
+        lineno++;
+        if (!strchr(line, '\n') && !feof(fp)) { snprintf(err, err_len, "line %d: longer than %d characters", lineno, (int)sizeof line - 2); free(out); fclose(fp); return -1; }
+        if (hash) *hash = '\0';
+        if (line[strspn(line, " \t\r\n")] == '\0') continue;
+        got = sscanf(line, "%lf %lf %lf %lf %lf %lf %1s", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], tail);
+        if (got != 6) { snprintf(err, err_len, "line %d: expected 6 values (alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules), found %s", lineno, got > 6 ? "more" : "fewer"); free(out); fclose(fp); return -1; }
+        for (k = 0; k < 6; k++) if (!(v[k] - v[k] == 0.0)) { snprintf(err, err_len, "line %d: value %d is not finite", lineno, k + 1); free(out); fclose(fp); return -1; }
+        if (v[2] < v[3]) { snprintf(err, err_len, "line %d: qdiff_pos %g < qdiff_neg %g", lineno, v[2], v[3]); free(out); fclose(fp); return -1; }
+        if (v[4] < 0.0) { snprintf(err, err_len, "line %d: weight_thr %g is negative", lineno, v[4]); free(out); fclose(fp); return -1; }
+        if (v[5] != 0.0 && v[5] != 1.0) { snprintf(err, err_len, "line %d: skip_rules %g is neither 0 nor 1", lineno, v[5]); free(out); fclose(fp); return -1; }
+        if (n == cap) {
+            double *grown = realloc(out, sizeof(double) * 6 * (size_t)(cap = cap ? 2 * cap : 16));
+            if (!grown) { snprintf(err, err_len, "out of memory"); free(out); fclose(fp); return -1; }
+            out = grown;
+        }
+        memcpy(out + 6 * (size_t)n++, v, sizeof v);
+    }
+    fclose(fp);
+    if (n == 0) { snprintf(err, err_len, "%s holds no hyper-parameter set", path); free(out); return -1; }
+    *sets = out; *nsets = n;
+    return 0;
+}
+
+/* `agents` agents of a demo in one persistent-learner run, agent e under set e mod nsets (sets HOST [nsets][6], the columns of
+ * frirl_demo_parse_hparams): frirl_hip_batch_set_hparams + frirl_hip_batch_train, then one line per set from
+ * frirl_hip_batch_agent_report.  Returns the number of converged agents, or -1. */
+int frirl_demo_batch_run_hparams(const char *env, int agents, int max_episodes, const double *sets, int nsets, int verbose)
+{
+    int nant = 0, episodes = 0, rc, e, s, k, total = 0;
+    frirl_hip_batch_desc d;
+    struct demo_desc_mem mm;
+    frirl_hip_batch *b;
+    frirl_hip_hparam_rows rows;
+    double *col = malloc(sizeof(double) * 5 * (size_t)agents), *reward = malloc(sizeof(double) * (size_t)agents);
+    int32_t *skip = malloc(sizeof(int32_t) * 4 * (size_t)agents), *conv = skip + agents, *eps = conv + agents, *rules = eps + agents;
+    if (!col || !reward || !skip || nsets < 1) return -1;
+    if (demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    for (e = 0; e < agents; e++) {
+        for (k = 0; k < 5; k++) col[(size_t)k * agents + e] = sets[6 * (size_t)(e % nsets) + k];
+        skip[e] = (int32_t)sets[6 * (size_t)(e % nsets) + 5];
+    }
+    rows.alpha = col; rows.gamma = col + agents; rows.qdiff_pos_boundary = col + 2 * (size_t)agents; rows.qdiff_neg_boundary = col + 3 * (size_t)agents;
+    rows.weight_significant = col + 4 * (size_t)agents; rows.skip_rules = skip;
+    b = frirl_hip_batch_create(&d);
+    if (!b) five_dropin_fatal("frirl_demo_batch_run_hparams(create)", FRIRL_HIP_ENODEV);
+    rc = frirl_hip_batch_set_hparams(b, &rows);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_hparams(set)", rc);
+    rc = frirl_hip_batch_train(b, max_episodes, &episodes);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_hparams(train)", rc);
+    rc = frirl_hip_batch_agent_report(b, conv, eps, rules, NULL, reward);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_hparams(report)", rc);
+    for (s = 0; s < nsets && s < agents; s++) {
+        long long n = 0, nconv = 0, ep_sum = 0, rule_sum = 0;
+        int ep_max = 0;
+        double rew_sum = 0.0;
+        for (e = s; e < agents; e += nsets) {
+            n++; nconv += conv[e] != 0; ep_sum += eps[e]; rule_sum += rules[e]; rew_sum += reward[e];
+            if (eps[e] > ep_max) ep_max = eps[e];
+        }
+        total += (int)nconv;
+        if (verbose)
+            printf("hparams %s: set %d agents %lld converged %lld mean-episodes %.3f max-episodes %d mean-rules %.3f mean-reward %.6f\n", env, s, n, nconv,
+                   (double)ep_sum / n, ep_max, (double)rule_sum / n, rew_sum / n);
+    }
+    frirl_hip_batch_destroy(b);
+    demo_desc_free(&mm);
+    free(col); free(reward); free(skip);
+    return total;
+}

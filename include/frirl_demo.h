@@ -59,6 +59,17 @@ int frirl_demo_batch_run_evaluate(const char *env, int agents, int max_episodes,
 int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_episodes, const char *load_bin, const char *save_bin, int K, double spread,
                                         const double *units, int teach_episodes, int teach_passes, int verbose);
 
+/* A hyper-parameter sweep in one run (frirl_demo --agents N --hparams FILE).  frirl_demo_parse_hparams reads FILE: one set per line as
+ * `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, `#` starts a comment, blank lines are skipped; *sets = malloc'ed
+ * [*nsets][6] (the caller frees it).  -1 with err = "line N: why" for the first malformed line (not six numbers, a value that is not
+ * finite, qdiff_pos < qdiff_neg, weight_thr < 0, skip_rules not 0 / 1), or why the file cannot be used (unreadable, no set in it).
+ * No device is touched.
+ * frirl_demo_batch_run_hparams: agent e learns under set e mod nsets (frirl_hip_batch_set_hparams, frirl_hip_batch_train: the
+ * persistent learner), then one line per set: set index, agents, converged, mean and max episodes, mean rules, mean reward of the
+ * last episode (frirl_hip_batch_agent_report).  Returns the number of converged agents, or -1. */
+int frirl_demo_parse_hparams(const char *path, double **sets, int *nsets, char *err, size_t err_len);
+int frirl_demo_batch_run_hparams(const char *env, int agents, int max_episodes, const double *sets, int nsets, int verbose);
+
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */
 /* many agents WITH the reference's rule-base exchange (frirl_omp_run: chunks of 9 episodes, merge_rb in both directions after each,

@@ -241,6 +241,20 @@ typedef struct frirl_hip_agent {
                                                   its low 32 bits count: streams repeat with a period of 2^32 global ids */
 } frirl_hip_agent;
 
+/* Per-agent overrides of the learning hyper-parameters of frirl_hip_agent.  Every column is [dev] [E] (E = b->E, indexed by the
+ * agent's index in the batch, the index of frirl_hip_envs' arrays -- not by a launch slot and not by env_id_base + e) or NULL =
+ * every agent takes the value in frirl_hip_agent.  A NULL struct pointer = all columns NULL.
+ * Only these six are per agent.  epsilon, p, max_steps, no_random, seed, the convergence thresholds (reward_good_above,
+ * qdiff_final_tolerance), evaluate and everything about the environment (env_kind, grids, action values) stay per batch: greedy
+ * roll-outs and evaluation read epsilon too, so a per-agent epsilon would need a reference of its own.
+ * Read by frirl_hip_learn_run_rows / _train_rows and frirl_hip_agent_begin_rows / _observe_rows only.  The fused step
+ * (frirl_hip_episode_begin / _step / _steps, frirl_hip_update_sarsa), the lane groups (frirl_hip_episode_run_lanes), demonstration
+ * replay (frirl_hip_learn_demonstration) and frirl_hip_multi_* take no rows: they keep using frirl_hip_agent for every agent. */
+typedef struct frirl_hip_hparam_rows {
+    const double *alpha, *gamma, *qdiff_pos_boundary, *qdiff_neg_boundary, *weight_significant;
+    const int32_t *skip_rules;                 /* 0 / 1 */
+} frirl_hip_hparam_rows;                       /* 48 bytes */
+
 /* Test probe of the exploration stream, in the form every learning and roll-out kernel calls it.  For key tuple i the global id is
  * agent->env_id_base + env[i] and the word is the SplitMix64 output function of
  *     seed + 0x9E3779B97F4A7C15 * ((id << 32) | episode[i]) + 0xD1B54A32D192ED03 * ((step[i] << 8) | draw)      (mod 2^64);
@@ -834,6 +848,18 @@ int frirl_hip_agent_begin_taught(const frirl_hip_tables *t, const frirl_hip_rule
 int frirl_hip_agent_observe_taught(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
                                    const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
 
+/* ---- per-agent hyper-parameters: the taught pair with frirl_hip_hparam_rows (above).  Row e learns with rows->X[e] for every column
+ * X that is not NULL and with agent->X otherwise; rows == NULL or all columns NULL is the taught call, bit for bit (teacher NULL: the
+ * untaught one).  One workgroup serves one row, so the override costs six loads per row and step.  frirl_hip_agent_begin_rows reads
+ * no learning hyper-parameter: it is frirl_hip_agent_begin_taught and takes `rows` for symmetry.  The values are not validated here
+ * (they are device memory): frirl_hip_batch_set_hparams states what a valid set is.  Refusals as the taught pair, in its order. */
+int frirl_hip_agent_begin_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                               const frirl_hip_hparam_rows *rows, const frirl_hip_envs *envs, const frirl_hip_agent_io *io,
+                               const int32_t *teacher, void *stream);
+int frirl_hip_agent_observe_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                 const frirl_hip_hparam_rows *rows, const frirl_hip_envs *envs, const frirl_hip_agent_io *io,
+                                 const int32_t *teacher, void *stream);
+
 /* ---- one-launch replay of recorded demonstrations: every agent learns a log of (observation, action, reward, success) records in
  * ONE launch, one workgroup per agent looping over its records; no environment runs.  nant 2..8, A 1..32, any Shepard power.
  * Per record r of agent e (its log starts at record e * agent_stride of every array):
@@ -1074,6 +1100,19 @@ int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_rulebases *
                           const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
                           uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                           frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
+/* The same two calls with per-agent hyper-parameters (frirl_hip_hparam_rows, above): agent e -- the id in `live`, never the launch
+ * slot: the queue re-sorts agents between launches -- learns with rows->X[e] for every column X that is not NULL and with agent->X
+ * otherwise.  Same shapes (frirl_hip_learn_supported), same workspace sizes, same refusals in the same order; rows == NULL calls the
+ * unsuffixed kernels.  Several agents share a wave, so the six values are per lane; the kernel re-reads them from global memory
+ * after every rule sweep instead of holding them across it (48 B per agent and step, cache-resident).  With every column equal to
+ * the agent's values the results are those of the unsuffixed call, bit for bit. */
+int frirl_hip_learn_run_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                             const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                             int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream);
+int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                               const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                               int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                               frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
 
 /* Persistent form for SMALL rule bases (the demos' learning regime): one wave keeps its environment's rule base,
  * the tables and the episode state in LDS and runs up to nsteps consecutive steps without a global round trip per
@@ -1191,6 +1230,24 @@ int frirl_hip_batch_episode(frirl_hip_batch *b);
  * episode by episode (frirl_hip_batch_episode).  Same results per agent either way. */
 int frirl_hip_batch_train(frirl_hip_batch *b, int32_t max_episodes, int32_t *episodes_run);
 int frirl_hip_batch_stats(frirl_hip_batch *b, frirl_hip_batch_stats_t *out);
+/* The per-agent view of what frirl_hip_batch_stats sums, HOST [E] each or NULL: converged (0 / 1), episodes run, rule count, and
+ * the steps and reward of the last finished episode. */
+int frirl_hip_batch_agent_report(frirl_hip_batch *b, int32_t *converged, int32_t *episodes, int32_t *rules, int32_t *ep_steps, double *ep_reward);
+/* Per-agent hyper-parameters for a sweep in one run: host_rows holds HOST columns [E] (NULL column = every agent keeps the batch's
+ * value), copied to the device; NULL (or all columns NULL) clears every row.  Validated on the host before anything is copied: every
+ * double finite (bounds as large as +-1e30 are fine), qdiff_pos_boundary >= qdiff_neg_boundary (against the batch's value where only
+ * one of the two columns is given), weight_significant >= 0, skip_rules 0 or 1; a violation returns FRIRL_HIP_EINVAL, names agent
+ * and column, and leaves the batch as it was.  FRIRL_HIP_EINVAL too when the batch's shape is not one frirl_hip_learn_supported
+ * covers or the batch has no index mirror: only the persistent learner takes rows.
+ * While rows are set frirl_hip_batch_train passes them to frirl_hip_learn_train_rows, and the calls that learn without honouring
+ * them -- frirl_hip_batch_episode, _train_merged, _merge_round and _teach -- return FRIRL_HIP_EINVAL naming themselves.  Evaluation,
+ * roll-outs, reductions, save / load and the statistics read no learning hyper-parameter and are unaffected.  Not built: rows
+ * across GPUs (frirl_hip_multi_*). */
+int frirl_hip_batch_set_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows *host_rows);
+/* The validation frirl_hip_batch_set_hparams applies, on its own (no device is touched): HOST columns [E] checked against the
+ * rules above, `agent` supplying the bound that a missing qdiff column leaves to the batch.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with
+ * agent and column named in frirl_hip_last_error (also for E < 1 or a NULL agent; NULL host_rows is valid: nothing to check). */
+int frirl_hip_hparam_rows_check(const frirl_hip_hparam_rows *host_rows, int32_t E, const frirl_hip_agent *agent);
 /* rule base of agent e: *R rules, rant HOST [>= *R][nant] (AoS), rconc HOST [>= *R] (pass NULL to query *R only) */
 int frirl_hip_batch_get_rulebase(frirl_hip_batch *b, int32_t e, int32_t *R, double *rant, double *rconc);
 /* Rule bases of all agents to / from one file.  The file is E records back to back, each exactly what
