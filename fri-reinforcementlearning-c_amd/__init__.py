@@ -56,6 +56,11 @@ class HparamRowsDesc(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in HP_COLUMNS]
 
 
+class ExploreRowsDesc(C.Structure):
+    """struct frirl_hip_explore_rows (include/frirl_hip.h)."""
+    _fields_ = [("epsilon", C.c_void_p), ("horizon", C.c_void_p), ("horizon_all", C.c_int32), ("reserved", C.c_int32)]
+
+
 class EnvsDesc(C.Structure):
     """struct frirl_hip_envs (include/frirl_hip.h)."""
     _fields_ = [("states", C.c_void_p), ("q_ant", C.c_void_p), ("fus", C.c_void_p), ("done", C.c_void_p), ("ep_steps", C.c_void_p),
@@ -311,6 +316,12 @@ SIGNATURES = {
     "frirl_hip_learn_train_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
                                              C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
+    "frirl_hip_learn_run_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                              C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_learn_train_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                                C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
     "five_hip_add_rule": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "frirl_hip_update_sarsa": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p,
@@ -331,6 +342,10 @@ SIGNATURES = {
                                              C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
     "frirl_hip_agent_observe_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
                                                C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_begin_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                                C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_observe_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                                  C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
     "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
                                                 C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
@@ -376,6 +391,9 @@ SIGNATURES = {
     "frirl_hip_batch_agent_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP]),
     "frirl_hip_batch_set_hparams": (C.c_int, [C.c_void_p, C.POINTER(HparamRowsDesc)]),
     "frirl_hip_hparam_rows_check": (C.c_int, [C.POINTER(HparamRowsDesc), C.c_int32, C.POINTER(AgentDesc)]),
+    "frirl_hip_batch_set_exploration": (C.c_int, [C.c_void_p, C.POINTER(ExploreRowsDesc)]),
+    "frirl_hip_explore_rows_check": (C.c_int, [C.POINTER(ExploreRowsDesc), C.c_int32, C.POINTER(AgentDesc)]),
+    "frirl_hip_explore_epsilon": (C.c_double, [C.c_double, C.c_int32, C.c_uint32]),
     "frirl_hip_batch_get_rulebase": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _DP, _DP]),
     "frirl_hip_batch_save_rulebases": (C.c_int, [C.c_void_p, C.c_char_p]),
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -1101,7 +1119,39 @@ def _rows(rows, E):
     if rows is None:
         return None
     assert rows.E == E, (rows.E, E)
-    return C.byref(rows.desc)
+    return None if rows.desc is None else C.byref(rows.desc)
+
+
+class ExploreRows:
+    """Per-agent exploration (struct frirl_hip_explore_rows): agent e of a batch of E picks at epsilon[e], falling linearly to zero
+    over horizon[e] episodes (0 = constant; explore_epsilon gives the rate of an episode).  epsilon (float64) and horizon (int32) are
+    anything torch.as_tensor takes, of length E; epsilon None keeps the Agent's epsilon, horizon None gives every agent horizon_all.
+    Owns the device tensors and the struct.  Taken by agent_begin / agent_observe / train_persistent / train as explore=."""
+
+    def __init__(self, E, device, epsilon=None, horizon=None, horizon_all=0):
+        import torch
+        self.E, self.desc = E, ExploreRowsDesc()
+        self.desc.horizon_all = int(horizon_all)
+        for k, v, dt in (("epsilon", epsilon, torch.float64), ("horizon", horizon, torch.int32)):
+            t = None
+            if v is not None:
+                t = torch.as_tensor(v, dtype=dt).to(device).contiguous()
+                assert t.shape == (E,), (k, tuple(t.shape), E)
+                setattr(self.desc, k, t.data_ptr())
+            setattr(self, k, t)
+
+    @classmethod
+    def null(cls, E):
+        """The NULL struct pointer: explore=ExploreRows.null(E) goes through the _explore entry point with no rows at all."""
+        self = cls.__new__(cls)
+        self.E, self.desc, self.epsilon, self.horizon = E, None, None, None
+        return self
+
+
+def explore_epsilon(eps, horizon, episode):
+    """frirl_hip_explore_epsilon: the exploration rate of an agent with row values (eps, horizon) in the episode whose stream key is
+    `episode` (the first learning episode is 1) -- the host build of the function the kernels call."""
+    return float(lib().frirl_hip_explore_epsilon(float(eps), int(horizon), int(episode)))
 
 
 def rollout_scores(sc):
@@ -1182,14 +1232,19 @@ def _teacher(teacher, E):
     return _ptr(teacher)
 
 
-def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None, rows=None):
+def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None, rows=None, explore=None):
     """frirl_hip_agent_begin: start an episode from the caller's observations obs [E, nant-1] (float64, on the device) for the rows
     selected by `reset` ([E] uint8 / bool, None = all).  Returns (action values [E] float64, action indices [E] int32): the first
     action of every restarted row (the other rows' entries are not written).  teacher [E] int32 (frirl_hip_agent_begin_taught): a row
     whose entry is an action index 0..A-1 takes that action, any other value leaves the row its own pick.  rows: an HparamRows
-    (frirl_hip_agent_begin_rows; the begin call reads no learning hyper-parameter).  Does not synchronise."""
+    (frirl_hip_agent_begin_rows; the begin call reads no learning hyper-parameter).  explore: an ExploreRows
+    (frirl_hip_agent_begin_explore): row e picks at its own rate for the episode it starts.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, reset=reset)
-    if rows is not None:
+    if explore is not None:
+        check(lib().frirl_hip_agent_begin_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
+                                                  C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
+              "frirl_hip_agent_begin_explore")
+    elif rows is not None:
         check(lib().frirl_hip_agent_begin_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
                                                C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
               "frirl_hip_agent_begin_rows")
@@ -1202,15 +1257,20 @@ def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None
     return action, action_idx
 
 
-def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None):
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None, explore=None):
     """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
     last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
     quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
     rows that were done are not written.  teacher [E] int32 (frirl_hip_agent_observe_taught): a row whose entry is an action index
     takes it as its next action and learns towards Q(s', a_teacher).  rows: an HparamRows (frirl_hip_agent_observe_rows): row e
-    learns under its own values of the columns given.  Does not synchronise."""
+    learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_agent_observe_explore): row e picks at
+    its own rate in its current episode.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    if rows is not None:
+    if explore is not None:
+        check(lib().frirl_hip_agent_observe_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
+                                                    C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
+              "frirl_hip_agent_observe_explore")
+    elif rows is not None:
         check(lib().frirl_hip_agent_observe_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
                                                  C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
               "frirl_hip_agent_observe_rows")
@@ -1322,9 +1382,10 @@ def grid_points(desc, device=None):
     return torch.cartesian_prod(*axes).reshape(-1, len(axes)).contiguous()
 
 
-def demo_batch_object(env, E, maxR, start_states=None):
+def demo_batch_object(env, E, maxR, start_states=None, seed=0, env_id_base=0):
     """frirl_hip_batch_create for a demo: E agents from the reference's initial rule base (the 2^nant corner rules, Q = 0), agent e
-    starting its episodes at start_states[e] (host [E, nant-1], None = values_def).  Returns the handle for the frirl_hip_batch_*
+    starting its episodes at start_states[e] (host [E, nant-1], None = values_def); seed and env_id_base key the exploration stream
+    (the batch is greedy, no_random = 1, until frirl_hip_batch_set_exploration gives it rows).  Returns the handle for the frirl_hip_batch_*
     calls of lib(); release it with lib().frirl_hip_batch_destroy."""
     import numpy as np
     d = demo_describe(env)
@@ -1349,6 +1410,7 @@ def demo_batch_object(env, E, maxR, start_states=None):
     ag.alpha, ag.gamma, ag.qdiff_pos_boundary, ag.qdiff_neg_boundary = d["alpha"], d["gamma"], d["qdiff_pos"], d["qdiff_neg"]
     ag.weight_significant, ag.skip_rules, ag.A, ag.env_kind, ag.max_steps, ag.no_random = d["weight_thr"], d["skip_rules"], d["A"], d["kind"], d["max_steps"], 1
     ag.reward_good_above, ag.qdiff_final_tolerance = d["reward_good_above"], d["qdiff_final_tolerance"]
+    ag.seed, ag.env_id_base = seed, env_id_base
     for k in range(nant):
         ag.grid_len[k], ag.grid_div[k], ag.values_def[k] = len(d["grids"][k]), d["grid_div"][k], d["values_def"][k]
     ag.grid_values, ag.action_ve = grid.ctypes.data, ave.ctypes.data
@@ -1374,6 +1436,25 @@ def batch_set_hparams(batch, **columns):
         keep.append(a)
         setattr(desc, k, a.ctypes.data)
     check(lib().frirl_hip_batch_set_hparams(batch, C.byref(desc) if keep else None), "frirl_hip_batch_set_hparams")
+
+
+def batch_set_exploration(batch, epsilon=None, horizon=None, horizon_all=0, clear=False):
+    """frirl_hip_batch_set_exploration on a library-owned batch: per-agent exploration for frirl_hip_batch_train, host arrays of
+    length E -- epsilon (None: the batch's epsilon for every agent) and horizon in episodes (None: horizon_all for every agent).
+    clear=True (or no argument at all) clears the rows.  The library validates and copies before it returns."""
+    import numpy as np
+    if clear or (epsilon is None and horizon is None and horizon_all == 0):
+        check(lib().frirl_hip_batch_set_exploration(batch, None), "frirl_hip_batch_set_exploration")
+        return
+    desc = ExploreRowsDesc()
+    desc.horizon_all = int(horizon_all)
+    eps = None if epsilon is None else np.ascontiguousarray(epsilon, dtype=np.float64)
+    hor = None if horizon is None else np.ascontiguousarray(horizon, dtype=np.int32)
+    if eps is not None:
+        desc.epsilon = eps.ctypes.data
+    if hor is not None:
+        desc.horizon = hor.ctypes.data
+    check(lib().frirl_hip_batch_set_exploration(batch, C.byref(desc)), "frirl_hip_batch_set_exploration")
 
 
 def batch_agent_report(batch):
@@ -1775,18 +1856,18 @@ class Convergence:
                                                  _stream(stream)), "frirl_hip_convergence_update")
 
 
-def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None, rows=None):
+def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None, rows=None, explore=None):
     """Batched construct run: frirl_sequential_run's loop (reference frirl_sequential_run.c:55-165) for E agents
     at once.  Episodes run until every environment's rule base is "considered complete" or max_episodes-1 episodes
     have run (:51,59).  Converged environments are masked out of later episodes.  Returns the Convergence object.
     rows (an HparamRows): only the persistent learner takes per-agent hyper-parameters, so the run goes through train_persistent
-    (on_episode is not called) or raises FrirlHipError where it does not cover the shape."""
+    (on_episode is not called) or raises FrirlHipError where it does not cover the shape.  explore (an ExploreRows): likewise."""
     import torch
-    if rows is not None:
+    if rows is not None or explore is not None:
         if not learn_supported(problem, agent):
-            raise FrirlHipError("frirl_amd.train: rows= needs the persistent learner (learn_supported), which does not cover this shape; "
-                                "the per-episode kernels take no per-agent hyper-parameters")
-        return train_persistent(problem, agent, envs, max_episodes=max_episodes, rows=rows).conv
+            raise FrirlHipError("frirl_amd.train: rows= / explore= need the persistent learner (learn_supported), which does not cover this shape; "
+                                "the per-episode kernels take no per-agent hyper-parameters or exploration")
+        return train_persistent(problem, agent, envs, max_episodes=max_episodes, rows=rows, explore=explore).conv
     conv = Convergence(problem, problem.rb.device)
     max_steps = agent.desc.max_steps
     if lanes is None:           # lane-group kernel where it is the faster form (many agents / small rule bases)
@@ -1839,13 +1920,14 @@ class LearnRun:
         self.conv, self.steps_total, self.work, self.launches = conv, steps_total, work, launches
 
 
-def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None):
+def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None, explore=None):
     """The construct loop of frirl_sequential_run for E agents through frirl_hip_learn_train: every agent runs its episodes
     back to back on the device; after each launch (the work of `budget` steps of a mean agent) the agents that are still
     learning are compacted and launched again until none is left -- the launch plan, the queue and the compaction are the
     library's (csrc/learn.hip), the host reads two counters per launch.  on_chunk(launch index, live agent ids, conv) is
     called after every launch (the place for the per-chunk reward statistics).  rows: an HparamRows (frirl_hip_learn_train_rows):
-    agent e learns under its own values of the columns given.  Returns a LearnRun."""
+    agent e learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_learn_train_explore): agent e
+    picks at its own epsilon, annealed over its own horizon.  Returns a LearnRun."""
     import torch
     dev_ = problem.rb.device
     conv = Convergence(problem, dev_)
@@ -1870,7 +1952,11 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     cb = LEARN_CHUNK_FN(chunk) if on_chunk is not None else C.cast(None, LEARN_CHUNK_FN)
     launches = C.c_int32(0)
     refused = conv.full.view(torch.uint8)
-    if rows is not None:
+    if explore is not None:
+        check(lib().frirl_hip_learn_train_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
+                                                  C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws),
+                                                  ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_explore")
+    elif rows is not None:
         check(lib().frirl_hip_learn_train_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
                                                C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
                                                C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_rows")

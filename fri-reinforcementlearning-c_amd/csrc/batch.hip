@@ -39,6 +39,10 @@ struct frirl_hip_batch {
     int32_t *d_hp_skip;          // [E]    ... and skip_rules
     frirl_hip_hparam_rows hp;    // the device columns that are set (all NULL: no rows)
     bool hp_set;
+    double *d_ex_eps;            // [E] per-agent exploration columns of frirl_hip_batch_set_exploration (allocated on first use) ...
+    int32_t *d_ex_h;             // [E] ... and horizons
+    frirl_hip_explore_rows ex;   // the device columns that are set, and horizon_all
+    bool ex_set;
     std::vector<int32_t> h_i;
     std::vector<double> h_d;
 };
@@ -117,7 +121,7 @@ extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
     if (b->s) (void)hipStreamSynchronize(b->s);
     void *ptrs[] = {b->d_u, b->d_ve, b->d_rb, b->d_rant, b->d_grid, b->d_ave, b->d_states, b->d_q_ant, b->d_ep_reward, b->d_start, b->d_prev_reward,
                     b->d_prev_rconc, b->d_tmp, b->d_nrules, b->d_fus, b->d_done, b->d_ep_steps, b->d_status, b->d_episode, b->d_prev_nrules,
-                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip};
+                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -181,6 +185,10 @@ extern "C" frirl_hip_batch *frirl_hip_batch_create(const frirl_hip_batch_desc *d
 // the calls that learn without honouring per-agent hyper-parameters refuse while rows are set (frirl_hip_batch_set_hparams)
 static int refuse_rows(const frirl_hip_batch *b, const char *who)
 {
+    if (b->ex_set && !b->hp_set) {
+        set_error("%s: per-agent exploration is set (frirl_hip_batch_set_exploration) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
+        return FRIRL_HIP_EINVAL;
+    }
     if (!b->hp_set) return FRIRL_HIP_OK;
     set_error("%s: per-agent hyper-parameters are set (frirl_hip_batch_set_hparams) and this call does not honour them: use frirl_hip_batch_train, or clear them", who);
     return FRIRL_HIP_EINVAL;
@@ -261,7 +269,11 @@ static int batch_train_persistent(frirl_hip_batch *b, int32_t max_episodes, int3
     BCHK(hipMemsetD32Async((hipDeviceptr_t)b->d_done, 1, E, b->s), "episode flags");       // every agent is between two episodes here
     // agents that are still learning have all run `before` episodes (the per-episode form keeps them in step): up to max_episodes - 1 more
     int32_t launches = 0;
-    int rc = b->hp_set ? frirl_hip_learn_train_rows(&b->t, &b->rb, &b->agent, &b->hp, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total,
+    frirl_hip_agent exploring = b->agent;
+    exploring.no_random = 0;                // exploration rows ask for exploration, whatever the batch's own flag (which every other call keeps reading)
+    int rc = b->ex_set ? frirl_hip_learn_train_explore(&b->t, &b->rb, &exploring, b->hp_set ? &b->hp : nullptr, &b->ex, &b->envs, &b->conv, 512, max_episodes + before,
+                                                       nullptr, b->d_steps_total, nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
+           : b->hp_set ? frirl_hip_learn_train_rows(&b->t, &b->rb, &b->agent, &b->hp, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total,
                                                     nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
                        : frirl_hip_learn_train(&b->t, &b->rb, &b->agent, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr,
                                                b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s);
@@ -401,6 +413,58 @@ extern "C" int frirl_hip_batch_set_hparams(frirl_hip_batch *b, const frirl_hip_h
     b->hp.weight_significant = cols[4] ? b->d_hp + (size_t)4 * E : nullptr;
     b->hp.skip_rules = h.skip_rules ? b->d_hp_skip : nullptr;
     b->hp_set = true;
+    return FRIRL_HIP_OK;
+}
+
+// what a valid set of per-agent exploration rows is (include/frirl_hip.h): host columns [E], no device
+static int explore_check(const char *who, const frirl_hip_explore_rows &x, int E, const frirl_hip_agent &agent)
+{
+    const int32_t hmax = 1 << 30;
+    if (x.reserved != 0) { set_error("%s: reserved is %d, not 0", who, x.reserved); return FRIRL_HIP_EINVAL; }
+    if (x.horizon_all < 0 || x.horizon_all > hmax) { set_error("%s: horizon_all %d outside 0..2^30", who, x.horizon_all); return FRIRL_HIP_EINVAL; }
+    if (!x.epsilon && !(agent.epsilon >= 0.0 && agent.epsilon <= 1.0)) { set_error("%s: the agent's epsilon %g (no epsilon column) is not in [0, 1]", who, agent.epsilon); return FRIRL_HIP_EINVAL; }
+    for (int e = 0; e < E; e++) {
+        if (x.epsilon && !(x.epsilon[e] >= 0.0 && x.epsilon[e] <= 1.0)) { set_error("%s: agent %d: epsilon %g is not in [0, 1]", who, e, x.epsilon[e]); return FRIRL_HIP_EINVAL; }
+        if (x.horizon && (x.horizon[e] < 0 || x.horizon[e] > hmax)) { set_error("%s: agent %d: horizon %d outside 0..2^30", who, e, x.horizon[e]); return FRIRL_HIP_EINVAL; }
+    }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_explore_rows_check(const frirl_hip_explore_rows *host_rows, int32_t E, const frirl_hip_agent *agent)
+{
+    if (E < 1 || !agent) { set_error("frirl_hip_explore_rows_check: E=%d / NULL agent", E); return FRIRL_HIP_EINVAL; }
+    return host_rows ? explore_check("frirl_hip_explore_rows_check", *host_rows, E, *agent) : FRIRL_HIP_OK;
+}
+
+// Per-agent exploration for frirl_hip_batch_train (include/frirl_hip.h): validated on the host, then copied.
+extern "C" int frirl_hip_batch_set_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_rows)
+{
+    static const char *who = "frirl_hip_batch_set_exploration";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (!host_rows) {                                                                          // clear
+        b->ex = frirl_hip_explore_rows{};
+        b->ex_set = false;
+        return FRIRL_HIP_OK;
+    }
+    if (!b->d_uidx || !frirl_hip_learn_supported(b->nant, b->U, b->agent.A, b->agent.p, b->agent.env_kind)) {
+        set_error("%s: only the persistent learner takes per-agent exploration, and it does not cover this batch (frirl_hip_learn_supported: nant=%d U=%d A=%d p=%d; "
+                  "index mirror: %s)", who, b->nant, b->U, b->agent.A, b->agent.p, b->d_uidx ? "yes" : "no");
+        return FRIRL_HIP_EINVAL;
+    }
+    const int E = b->E;
+    if (explore_check(who, *host_rows, E, b->agent)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    if (!b->d_ex_eps) {
+        if (!dalloc(&b->d_ex_eps, (size_t)E) || !dalloc(&b->d_ex_h, (size_t)E)) { set_error("%s: HIP allocation failed: %s", who, hipGetErrorString(hipGetLastError())); return FRIRL_HIP_ELAUNCH; }
+    }
+    BCHK(hipStreamSynchronize(b->s), "exploration sync");               // nothing in flight reads the columns being replaced
+    if (host_rows->epsilon) BCHK(hipMemcpy(b->d_ex_eps, host_rows->epsilon, sizeof(double) * E, hipMemcpyHostToDevice), "exploration upload");
+    if (host_rows->horizon) BCHK(hipMemcpy(b->d_ex_h, host_rows->horizon, sizeof(int32_t) * E, hipMemcpyHostToDevice), "exploration upload");
+    b->ex = frirl_hip_explore_rows{};
+    b->ex.epsilon = host_rows->epsilon ? b->d_ex_eps : nullptr;
+    b->ex.horizon = host_rows->horizon ? b->d_ex_h : nullptr;
+    b->ex.horizon_all = host_rows->horizon_all;
+    b->ex_set = true;
     return FRIRL_HIP_OK;
 }
 

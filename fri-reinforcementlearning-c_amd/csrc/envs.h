@@ -236,4 +236,30 @@ __device__ __forceinline__ int e_greedy(const frirl_hip_agent &ag, int greedy, u
     return a >= ag.A ? ag.A - 1 : a;
 }
 
+// The exploration rate of an agent whose row of frirl_hip_explore_rows holds (eps, horizon), in the episode whose stream key is
+// `episode` (include/frirl_hip.h): eps itself without a horizon, 0 past it, and in between eps scaled by the share of the horizon
+// that is left -- one correctly rounded division, then one correctly rounded multiplication, no add that a compiler could fuse, so
+// host and device give the same bits.  Key 0 (roll-outs; callers without an episode counter) is outside every horizon: eps.
+__host__ __device__ __forceinline__ double explore_epsilon(double eps, int32_t horizon, uint32_t episode)
+{
+    if (horizon <= 0 || episode == 0u) return eps;
+    if (episode > (uint32_t)horizon) return 0.0;
+    const double left = (double)(horizon - (int32_t)(episode - 1u)), all = (double)horizon;
+#ifdef __HIP_DEVICE_COMPILE__
+    return __dmul_rn(eps, __ddiv_rn(left, all));
+#else
+    return eps * (left / all);
+#endif
+}
+
+// ... and the pick at that rate instead of ag.epsilon: same stream, keys and seed
+__device__ __forceinline__ int e_greedy(const frirl_hip_agent &ag, double epsilon, int greedy, uint32_t env, uint32_t episode, uint32_t step)
+{
+    if (ag.no_random == 1 || epsilon == 0.0) return greedy;
+    const uint64_t gid = ag.env_id_base + env;
+    if (rng_unit(ag.seed, gid, episode, step, 0) > epsilon) return greedy;
+    int a = (int)round(rng_unit(ag.seed, gid, episode, step, 1) * ag.A);
+    return a >= ag.A ? ag.A - 1 : a;
+}
+
 }  // namespace frirl

@@ -17,9 +17,11 @@ namespace frirl {
 struct NoIo {};
 // ... plus the teacher's actions of frirl_hip_agent_begin_taught / _observe_taught: [E] action indices, or NULL (the untaught calls)
 // ... and the per-agent hyper-parameters of frirl_hip_agent_begin_rows / _observe_rows: columns [E] or NULL (all NULL: the calls without rows)
+// ... and the per-agent exploration of frirl_hip_agent_begin_explore / _observe_explore: columns [E] or NULL (agent->epsilon, horizon_all)
 struct ExtIo : frirl_hip_agent_io {
     const int32_t *teacher;
     frirl_hip_hparam_rows rows;
+    frirl_hip_explore_rows ex;
 };
 template <bool EXT>
 using IoArg = std::conditional_t<EXT, ExtIo, NoIo>;
@@ -38,12 +40,19 @@ __device__ __forceinline__ int taught_action(const ExtIo &io, int e, int A, int 
 // frirl_hip_agent: the demo kernels read them from the launch's agent itself; the EXT kernels build the workgroup's own copy, row e
 // of every column of io.rows that is given.  One workgroup serves one row, so the values are wave-uniform: they are moved to scalar
 // registers, where the launch's own live (as vector registers they cost some variants a wave per SIMD).
+// `epsilon` is the row's exploration rate in the episode whose stream key is `key` (frirl_hip_explore_rows, envs.h: explore_epsilon).
 struct StepHparams {
-    double alpha, gamma, qdiff_pos_boundary, qdiff_neg_boundary, weight_significant;
+    double alpha, gamma, qdiff_pos_boundary, qdiff_neg_boundary, weight_significant, epsilon;
     int32_t skip_rules;
 };
-__device__ __forceinline__ const frirl_hip_agent &step_hparams(const frirl_hip_agent &ag, const NoIo &, int) { return ag; }
-__device__ __forceinline__ StepHparams step_hparams(const frirl_hip_agent &ag, const ExtIo &io, int e)
+__device__ __forceinline__ double explore_rate(const frirl_hip_agent &ag, const ExtIo &io, int e, uint32_t key)
+{
+    const double eps = io.ex.epsilon ? io.ex.epsilon[e] : ag.epsilon;
+    const int32_t h = io.ex.horizon ? io.ex.horizon[e] : io.ex.horizon_all;
+    return explore_epsilon(eps, h, key);
+}
+__device__ __forceinline__ const frirl_hip_agent &step_hparams(const frirl_hip_agent &ag, const NoIo &, const frirl_hip_envs &, int) { return ag; }
+__device__ __forceinline__ StepHparams step_hparams(const frirl_hip_agent &ag, const ExtIo &io, const frirl_hip_envs &ev, int e)
 {
     const frirl_hip_hparam_rows &r = io.rows;
     StepHparams h;
@@ -53,6 +62,7 @@ __device__ __forceinline__ StepHparams step_hparams(const frirl_hip_agent &ag, c
     h.qdiff_neg_boundary = r.qdiff_neg_boundary ? wave_uniform(r.qdiff_neg_boundary[e]) : ag.qdiff_neg_boundary;
     h.weight_significant = r.weight_significant ? wave_uniform(r.weight_significant[e]) : ag.weight_significant;
     h.skip_rules = r.skip_rules ? __builtin_amdgcn_readfirstlane(r.skip_rules[e]) : ag.skip_rules;
+    h.epsilon = wave_uniform(explore_rate(ag, io, e, ev.episode ? (uint32_t)ev.episode[e] : 0u));
     return h;
 }
 
@@ -222,7 +232,8 @@ __global__ __launch_bounds__(BLOCK) void episode_begin_kernel(const double *__re
     if (threadIdx.x == 0) {
         const uint32_t epi = ev.episode ? (uint32_t)(ev.episode[e] + 1) : 0u;
         if (ev.episode) ev.episode[e] = (int32_t)epi;
-        a0 = e_greedy(ag, a0, (uint32_t)e, epi, 0u);
+        if constexpr (EXT) a0 = e_greedy(ag, explore_rate(ag, io, e, epi), a0, (uint32_t)e, epi, 0u);        // the rate of the episode that starts
+        else a0 = e_greedy(ag, a0, (uint32_t)e, epi, 0u);
         if constexpr (EXT) a0 = taught_action(io, e, ag.A, a0);                                                    // :58-79
         ev.q_ant[(size_t)e * NANT + NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + a0];                 // :82
         if constexpr (EXT) {
@@ -277,7 +288,7 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         if (threadIdx.x == 0 && ev.status) ev.status[e] = FRIRL_HIP_UPD_INACTIVE;
         return;
     }
-    decltype(auto) hp = step_hparams(ag, io, e);           // `ag` itself; EXT: its own copy, row e of the columns of io.rows that are given
+    decltype(auto) hp = step_hparams(ag, io, ev, e);         // `ag` itself; EXT: its own copy, row e of the columns of io.rows that are given
     extern __shared__ double tab_s[];
     __shared__ StepShared sh;
     __shared__ BlockRed<BLOCK> red;
@@ -339,7 +350,9 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
     const long long tm1 = wall_clock64();
 #endif
     if (threadIdx.x == 0) {
-        int chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
+        int chosen;
+        if constexpr (EXT) chosen = e_greedy(ag, hp.epsilon, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
+        else chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
         if constexpr (EXT) chosen = taught_action(io, e, ag.A, chosen);                               // :127-151: Q(s', a_teacher) below
         gs.best = chosen;
         sh.cur_q_ant[NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + chosen];                  // :151

@@ -1,5 +1,5 @@
 // learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, instantiated in learn_i0 .. i4.hip and, with per-agent
-// hyper-parameter rows, learn_r0 .. r4.hip).
+// hyper-parameter rows, learn_r0 .. r4.hip, with per-agent exploration too, learn_x0 .. x4.hip).
 #include "learn_kernel.h"
 
 using namespace frirl_host;
@@ -106,9 +106,10 @@ extern "C" int frirl_hip_learn_timing(unsigned long long *out16)       // read a
 #endif
 
 // One chunk of the construct loop for the agents in `live` (device array of nlive agent ids, or NULL = agents 0..nlive-1):
-// see include/frirl_hip.h.  rows != NULL: the ROWS kernels (learn_r*.hip), every agent under its own hyper-parameters.
+// see include/frirl_hip.h.  rows != NULL: the ROWS kernels (learn_r*.hip), every agent under its own hyper-parameters; explore != NULL: the
+// EXPLORE kernels (learn_x*.hip), every agent at its own exploration rate as well.
 static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                     const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                     const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                      int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = frirl_check_episode(t, b, agent, envs, who);
@@ -132,6 +133,14 @@ static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip
 #endif
     int H = learn_slices(nlive);
     if (H < learn_min_slices(agent->A)) H = learn_min_slices(agent->A);
+    if (explore) {                          // the EXPLORE kernels (learn_x*.hip) take both structs
+        if (rows) la.hp = *rows;
+        la.ex = *explore;
+        if (t->nant == 3) frirl_learn_launch_mountaincar_explore(H, t, b, agent, envs, conv, la, s);
+        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_explore(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_explore(H, t, b, agent, envs, conv, la, s); }
+        else { if (H <= 8) frirl_learn_launch_cartpole_lo_explore(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_explore(H, t, b, agent, envs, conv, la, s); }
+        return check_launch(who);
+    }
     if (rows) {
         la.hp = *rows;
         if (t->nant == 3) frirl_learn_launch_mountaincar_rows(H, t, b, agent, envs, conv, la, s);
@@ -149,14 +158,23 @@ extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_ru
                                    const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
                                    int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 extern "C" int frirl_hip_learn_run_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
                                         const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                                         int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+}
+
+// per-agent exploration (frirl_hip_explore_rows) beside the hyper-parameter rows: the EXPLORE kernels; explore NULL = the _rows call
+extern "C" int frirl_hip_learn_run_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                           const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live,
+                                           int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    return learn_run("frirl_hip_learn_run_explore", t, b, agent, rows, explore, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 
@@ -250,7 +268,7 @@ extern "C" size_t frirl_hip_learn_train_workspace_bytes(int32_t nant, int32_t E,
 }
 
 static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                       const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                       const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
                        int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                        frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
@@ -278,7 +296,7 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
         if ((rc = frirl_hip_learn_plan(n, (int32_t)(mean_rules * (agent->A + 1) / 4), &H, &take)) != 0) return rc;
         if (H < learn_min_slices(agent->A)) { H = learn_min_slices(agent->A); const long fit = learn_lanes() / H; take = (int32_t)(n < fit ? n : fit); }
         hipLaunchKernelGGL(learn_queue_sort_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, take, b->nrules, shift, live);
-        if ((rc = learn_run(rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
+        if ((rc = learn_run(explore ? "frirl_hip_learn_run_explore" : rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, explore, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
                             workspace, run_bytes, stream)) != 0) return rc;
         launches++;
         hipLaunchKernelGGL(learn_queue_next_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, n, take, live, conv->converged, conv->episodes, max_episodes, b->nrules,
@@ -299,7 +317,7 @@ extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_
                                      uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                      frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
 }
 
@@ -308,6 +326,15 @@ extern "C" int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl
                                           int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                           frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
+}
+
+extern "C" int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                             const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps,
+                                             int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes,
+                                             int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+{
+    return learn_train("frirl_hip_learn_train_explore", t, b, agent, rows, explore, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+                       workspace_bytes, launches_out, on_chunk, user, stream);
 }

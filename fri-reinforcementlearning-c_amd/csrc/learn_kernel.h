@@ -63,6 +63,7 @@ struct LearnArgs {
     long long *sum_rules;        // sum of the live agents' rule counts at the start of the launch (import kernel)
     int max_episodes;            // the loop runs episodes 1 .. max_episodes - 1 (frirl_sequential_run.c:51,59)
     frirl_hip_hparam_rows hp;    // per-agent hyper-parameters [E], indexed by the agent id (ROWS kernels only; a NULL column = the launch's value)
+    frirl_hip_explore_rows ex;   // per-agent exploration [E], indexed likewise (EXPLORE kernels only; NULL columns = ag.epsilon / ex.horizon_all)
 #ifdef LEARN_TIMING
     unsigned long long *timing;  // [16] cycles per section of the step, summed over waves (tools/exp builds only)
 #endif
@@ -136,7 +137,10 @@ __global__ __launch_bounds__(256) void learn_export_kernel(const LearnArgs la, i
 // (11 VGPRs) where the launch's own are scalars; the kernel is at its register limit during the rule sweep (see the cold state below),
 // so they are not held across it: every step reloads them from global memory after the sweep, where they are first used (48 B per
 // agent and step, cache-resident, against thousands of rule bytes).  ROWS = false compiles to the code without the parameter.
-template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false>
+// EXPLORE (with ROWS): the agent's epsilon and annealing horizon of frirl_hip_explore_rows are per agent too, loaded with the six and
+// consumed at once by the step's pick.  A parameter of its own: inside the ROWS kernels the two columns cost their users 4.4 % on
+// mountaincar with both columns NULL (profiles/r26_explore_rows.md), so ROWS alone compiles to the code without them.
+template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false>
 __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la, const frirl_hip_agent ag, const frirl_hip_envs ev,
                                                               const frirl_hip_convergence cv)
 {
@@ -494,9 +498,16 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
             const double hp_alpha = hp(la.hp.alpha, ag.alpha), hp_gamma = hp(la.hp.gamma, ag.gamma), hp_wsig = hp(la.hp.weight_significant, ag.weight_significant);
             const double hp_pos = hp(la.hp.qdiff_pos_boundary, ag.qdiff_pos_boundary), hp_neg = hp(la.hp.qdiff_neg_boundary, ag.qdiff_neg_boundary);
             const int hp_skip = hp(la.hp.skip_rules, ag.skip_rules);
+            // ... and (EXPLORE) its exploration row, two more loads in the same clause, consumed at once by the pick of this step
+            static_assert(ROWS || !EXPLORE, "EXPLORE kernels take the hyper-parameter rows too");
+            [[maybe_unused]] double ex_eps = 0.0;
+            [[maybe_unused]] int ex_h = 0;
+            if constexpr (EXPLORE) { ex_eps = la.ex.epsilon ? la.ex.epsilon[erow] : ag.epsilon; ex_h = la.ex.horizon ? la.ex.horizon[erow] : la.ex.horizon_all; }
             if (begin) {
                 episode++;
-                const int a0 = e_greedy(ag, ci, (uint32_t)e, episode, 0u);                              // :78-82
+                int a0;                                                                                 // :78-82
+                if constexpr (EXPLORE) a0 = e_greedy(ag, explore_epsilon(ex_eps, ex_h, episode), ci, (uint32_t)e, episode, 0u);
+                else a0 = e_greedy(ag, ci, (uint32_t)e, episode, 0u);
                 q_ant[NS] = grid_s[NS * FRIRL_HIP_MAX_GRID + a0];
                 begin = false;
                 double w0 = swb;
@@ -516,7 +527,9 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                     for (int k = 0; k < NS; k++) ongrid = ongrid && (sq[k] == q_ant[k]);
                 }
             } else {
-                const int chosen = e_greedy(ag, ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
+                int chosen;
+                if constexpr (EXPLORE) chosen = e_greedy(ag, explore_epsilon(ex_eps, ex_h, episode), ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
+                else chosen = e_greedy(ag, ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
                 const bool flags_known = thr > 0.0 && thr < __builtin_inf();                            // this step's flags were taken against a real bound
                 double qp = bv, w0 = swb;                                                                // Q(s',a'), frirl_update_sarsa.c:356
                 if (chosen != ci) {                                                                      // an exploratory action: its own conclusion
@@ -733,7 +746,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
 }  // namespace frirl
 
 
-template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false>
+template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false>
 inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                          const frirl_hip_convergence *cv, frirl::LearnArgs la, hipStream_t s)
 {
@@ -750,32 +763,33 @@ inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     const size_t dyn = sizeof(double) * frirl::LR_WPB * EPW * NCOLD_;
     if (dyn > 40 * 1024) {                                                     // static (~24 KB) + dynamic beyond the 64 KB default
         static bool raised = false;                                            // per instantiation
-        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
+        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
     }
     hipLaunchKernelGGL((frirl::learn_import_kernel<N, BITS>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
     const int blocks = (la.tiles + frirl::LR_WPB - 1) / frirl::LR_WPB;
-    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
+    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
     hipLaunchKernelGGL((frirl::learn_export_kernel<N>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
 }
 
 
 // one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation file (learn_i*.hip) compiles a few kernels, so
 // that the build runs them in parallel
-template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false>
+template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false>
 inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                            const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s)
 {
-    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
 }
 
 // defined in learn_i0.hip (mountaincar), learn_i1.hip (acrobot, 1 .. 8 lanes per agent), learn_i2.hip (acrobot, 16 .. 64),
-// learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64); the _rows twins (ROWS = true, la.hp set) in learn_r0.hip .. learn_r4.hip
+// learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64); the _rows twins (ROWS = true, la.hp set) in learn_r0.hip .. learn_r4.hip,
+// the _explore ones (ROWS and EXPLORE, la.hp and la.ex set) in learn_x0.hip .. learn_x4.hip
 void frirl_learn_launch_cartpole_lo(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                     const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_cartpole_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
@@ -796,3 +810,13 @@ void frirl_learn_launch_acrobot_lo_rows(int H, const frirl_hip_tables *t, const 
                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_acrobot_hi_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_lo_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_hi_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_mountaincar_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_lo_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_hi_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);

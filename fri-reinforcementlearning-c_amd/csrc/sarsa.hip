@@ -94,6 +94,9 @@ __global__ void env_step_kernel(const frirl_hip_agent ag, int E, int ns, const d
     success[e] = f;
 }
 
+// The exploration rate of frirl_hip_explore_rows on the host: envs.h's explore_epsilon, the function the kernels call.
+extern "C" double frirl_hip_explore_epsilon(double eps, int32_t horizon, uint32_t episode) { return frirl::explore_epsilon(eps, horizon, episode); }
+
 // Probe for the tests (frirl_hip_explore_check): rng_unit and e_greedy of envs.h exactly as every learning and roll-out kernel calls
 // them, one key tuple per thread.
 __global__ void explore_check_kernel(const frirl_hip_agent ag, long n, const uint32_t *__restrict__ env, const uint32_t *__restrict__ episode,

@@ -23,7 +23,8 @@ static int usage(const char *what)
                     "usage: frirl_demo --env NAME --agents N [--load f.bin] [--save f.bin] --evaluate K [--spread F] [--teach-best M [--teach-passes P]]   (K >= 1 rows per agent, 0 <= F <= 1, M >= 1 episodes, 1 <= P <= 1024)\n"
                     "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-starts K [--spread F]   (S = 1 | 2, 1 <= K <= 256 start states per agent, 0 <= F <= 1)\n"
                     "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-map K [--spread F] [--reduce-map-all]   (removals validated on the policy map at the points visited from K start states; --reduce-map-all: of every start, not the successful ones alone)\n"
-                    "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n", what);
+                    "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n"
+                    "       frirl_demo --env NAME --agents N --explore FILE [--hparams FILE] [--seed S] [--id-base B] [--max-episodes M]   (an exploration sweep in one run: FILE holds one `epsilon horizon` pair per line, epsilon falling linearly to zero over `horizon` episodes, 0 = constant; agent e takes line e mod L; S seeds the exploration stream, agent e draws under the global id B + e)\n", what);
     return 2;
 }
 
@@ -42,6 +43,10 @@ int main(int argc, char **argv)
     int reduce_map = 0;             /* --reduce-map K: with --reduce-all, every removal is validated on the policy map at the points visited from K start states, 0 = not asked for */
     int reduce_map_all = 0;         /* --reduce-map-all: the points of every start, not of the successful ones alone */
     const char *hparams = NULL;     /* --hparams FILE: with --agents, agent e learns under the hyper-parameter set on line e mod L of FILE */
+    const char *explore = NULL;     /* --explore FILE: with --agents, agent e explores under the `epsilon horizon` pair on line e mod L of FILE */
+    unsigned long long seed = 0;    /* --seed S: seed of the exploration stream (with --explore) */
+    unsigned long long id_base = 0; /* --id-base B: global id of agent 0 on that stream (frirl_hip_agent.env_id_base; with --explore) */
+    int stream_given = 0;           /* --seed or --id-base was given */
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -59,6 +64,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--reduce-map") && i + 1 < argc) { reduce_map = atoi(argv[++i]); if (reduce_map < 1 || reduce_map > 256) return usage("--reduce-map needs 1 <= K <= 256"); }
         else if (!strcmp(argv[i], "--reduce-map-all")) reduce_map_all = 1;
         else if (!strcmp(argv[i], "--hparams") && i + 1 < argc) hparams = argv[++i];
+        else if (!strcmp(argv[i], "--explore") && i + 1 < argc) explore = argv[++i];
+        else if (!strcmp(argv[i], "--seed") && i + 1 < argc) { char *end; seed = strtoull(argv[++i], &end, 10); stream_given = 1; if (*end || end == argv[i]) return usage("--seed needs a whole number S >= 0"); }
+        else if (!strcmp(argv[i], "--id-base") && i + 1 < argc) { char *end; id_base = strtoull(argv[++i], &end, 10); stream_given = 1; if (*end || end == argv[i]) return usage("--id-base needs a whole number B >= 0"); }
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
         else if (!strcmp(argv[i], "--teach-best") && i + 1 < argc) { teach_best = atoi(argv[++i]); if (teach_best < 1) return usage("--teach-best needs M >= 1"); }
         else if (!strcmp(argv[i], "--teach-passes") && i + 1 < argc) { teach_passes = atoi(argv[++i]); if (teach_passes < 1 || teach_passes > 1024) return usage("--teach-passes needs 1 <= P <= 1024"); }
@@ -74,7 +82,27 @@ int main(int argc, char **argv)
     if (reduce_map_all && reduce_map < 1) return usage("--reduce-map-all goes with --reduce-map K");
     if (hparams && (merge || teach_best > 0)) return usage("--hparams does not go with --merge or --teach-best: the rule-base exchange and the replay of a teacher's log do not honour per-agent hyper-parameters");
     if (hparams && (agents < 1 || gpus >= 0 || reduce || evaluate > 0 || load_bin || save_bin)) return usage("--hparams goes with --agents N alone (one device, trained from scratch)");
+    if (explore && (merge || teach_best > 0)) return usage("--explore does not go with --merge or --teach-best: the rule-base exchange and the replay of a teacher's log do not honour per-agent exploration");
+    if (explore && (agents < 1 || gpus >= 0 || reduce || evaluate > 0 || load_bin || save_bin)) return usage("--explore goes with --agents N alone, or with --hparams FILE (one device, trained from scratch)");
+    if (stream_given && !explore) return usage("--seed and --id-base go with --explore FILE");
     frirl_parse_cmdline(&fr, fargc, fargv);
+    if (explore) {                  /* an exploration sweep (with --hparams: crossed with a hyper-parameter sweep): one persistent-learner run */
+        double *sets = NULL, *eps = NULL;
+        int *horizon = NULL, nsets = 0, n = 0, rc;
+        char err[256];
+        if (frirl_demo_parse_explore(explore, &eps, &horizon, &n, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --explore %s: %s\n", explore, err);
+            return 2;
+        }
+        if (hparams && frirl_demo_parse_hparams(hparams, &sets, &nsets, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --hparams %s: %s\n", hparams, err);
+            free(eps); free(horizon);
+            return 2;
+        }
+        rc = frirl_demo_batch_run_explore(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, eps, horizon, n, seed, id_base, sets, nsets, 1);
+        free(sets); free(eps); free(horizon);
+        return rc >= 0 ? 0 : 3;
+    }
     if (hparams) {                  /* a sweep: one persistent-learner run, one report line per set */
         double *sets = NULL;
         int nsets = 0, rc;

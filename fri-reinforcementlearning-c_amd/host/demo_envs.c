@@ -764,3 +764,109 @@ int frirl_demo_batch_run_hparams(const char *env, int agents, int max_episodes, 
     free(col); free(reward); free(skip);
     return total;
 }
+
+/* ---- an exploration sweep in one run: frirl_demo --agents N --explore FILE [--hparams FILE] [--seed S] ---------------------------------
+ * FILE: one `epsilon horizon` pair per line; `#` starts a comment; blank lines are skipped.  *eps = malloc'ed [*n], *horizon =
+ * malloc'ed [*n]; err receives "line N: why" for the first malformed line, or why the file is unusable. */
+int frirl_demo_parse_explore(const char *path, double **eps, int **horizon, int *n_out, char *err, size_t err_len)
+{
+    char line[512];
+    int lineno = 0, n = 0, cap = 0;
+    double *oe = NULL;
+    int *oh = NULL;
+    FILE *fp = fopen(path, "r");
+    *eps = NULL; *horizon = NULL; *n_out = 0;
+    if (!fp) { snprintf(err, err_len, "cannot open %s", path); return -1; }
+    while (fgets(line, sizeof line, fp)) {
+        double e, h;
+        char tail[2], *hash = strchr(line, '#');
+        int got;
+        lineno++;
+        if (!strchr(line, '\n') && !feof(fp)) { snprintf(err, err_len, "line %d: longer than %d characters", lineno, (int)sizeof line - 2); goto bad; }
+        if (hash) *hash = '\0';
+        if (line[strspn(line, " \t\r\n")] == '\0') continue;
+        got = sscanf(line, "%lf %lf %1s", &e, &h, tail);
+        if (got != 2) { snprintf(err, err_len, "line %d: expected 2 values (epsilon horizon), found %s", lineno, got > 2 ? "more" : "fewer"); goto bad; }
+        if (!(e >= 0.0 && e <= 1.0)) { snprintf(err, err_len, "line %d: epsilon %g is not in [0, 1]", lineno, e); goto bad; }
+        if (!(h >= 0.0 && h <= 1073741824.0) || h != (double)(int)h) { snprintf(err, err_len, "line %d: horizon %g is not a whole number in 0..2^30", lineno, h); goto bad; }
+        if (n == cap) {
+            double *ge;
+            int *gh;
+            cap = cap ? 2 * cap : 16;
+            ge = realloc(oe, sizeof(double) * (size_t)cap);
+            if (ge) oe = ge;
+            gh = realloc(oh, sizeof(int) * (size_t)cap);
+            if (gh) oh = gh;
+            if (!ge || !gh) { snprintf(err, err_len, "out of memory"); goto bad; }
+        }
+        oe[n] = e; oh[n] = (int)h; n++;
+    }
+    fclose(fp);
+    if (n == 0) { snprintf(err, err_len, "%s holds no epsilon / horizon pair", path); free(oe); free(oh); return -1; }
+    *eps = oe; *horizon = oh; *n_out = n;
+    return 0;
+bad:
+    free(oe); free(oh); fclose(fp);
+    return -1;
+}
+
+/* `agents` agents of a demo in one persistent-learner run, agent e exploring under pair e mod n (eps, horizon: HOST [n], the columns
+ * of frirl_demo_parse_explore) on the stream of `seed`, global ids id_base .. id_base + agents - 1, and -- sets != NULL -- learning under
+ * hyper-parameter set e mod nsets: frirl_hip_batch_set_exploration (+ _set_hparams) + frirl_hip_batch_train, then one line per pair
+ * (and per set) from frirl_hip_batch_agent_report.  Returns the number of converged agents, or -1. */
+int frirl_demo_batch_run_explore(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int n, unsigned long long seed,
+                                 unsigned long long id_base, const double *sets, int nsets, int verbose)
+{
+    int nant = 0, episodes = 0, rc, e, s, k, total = 0, pass;
+    frirl_hip_batch_desc d;
+    struct demo_desc_mem mm;
+    frirl_hip_batch *b;
+    frirl_hip_hparam_rows rows;
+    frirl_hip_explore_rows ex;
+    double *col = malloc(sizeof(double) * 6 * (size_t)agents), *reward = malloc(sizeof(double) * (size_t)agents), *xe = col + 5 * (size_t)agents;
+    int32_t *skip = malloc(sizeof(int32_t) * 5 * (size_t)agents), *conv = skip + agents, *eps_run = conv + agents, *rules = eps_run + agents, *xh = rules + agents;
+    if (!col || !reward || !skip || n < 1 || (sets && nsets < 1)) return -1;
+    if (demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    d.agent.seed = seed; d.agent.env_id_base = id_base;
+    for (e = 0; e < agents; e++) { xe[e] = eps[e % n]; xh[e] = horizon[e % n]; }
+    memset(&ex, 0, sizeof ex);
+    ex.epsilon = xe; ex.horizon = xh;
+    b = frirl_hip_batch_create(&d);
+    if (!b) five_dropin_fatal("frirl_demo_batch_run_explore(create)", FRIRL_HIP_ENODEV);
+    if (sets) {
+        for (e = 0; e < agents; e++) {
+            for (k = 0; k < 5; k++) col[(size_t)k * agents + e] = sets[6 * (size_t)(e % nsets) + k];
+            skip[e] = (int32_t)sets[6 * (size_t)(e % nsets) + 5];
+        }
+        rows.alpha = col; rows.gamma = col + agents; rows.qdiff_pos_boundary = col + 2 * (size_t)agents; rows.qdiff_neg_boundary = col + 3 * (size_t)agents;
+        rows.weight_significant = col + 4 * (size_t)agents; rows.skip_rules = skip;
+        rc = frirl_hip_batch_set_hparams(b, &rows);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_explore(hparams)", rc);
+    }
+    rc = frirl_hip_batch_set_exploration(b, &ex);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_explore(set)", rc);
+    rc = frirl_hip_batch_train(b, max_episodes, &episodes);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_explore(train)", rc);
+    rc = frirl_hip_batch_agent_report(b, conv, eps_run, rules, NULL, reward);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_explore(report)", rc);
+    for (pass = 0; pass < (sets ? 2 : 1); pass++) {                /* the agents grouped by exploration line, then by hyper-parameter set */
+        const int groups = pass ? nsets : n;
+        for (s = 0; s < groups && s < agents; s++) {
+            long long cnt = 0, nconv = 0, ep_sum = 0, rule_sum = 0;
+            int ep_max = 0;
+            double rew_sum = 0.0;
+            for (e = s; e < agents; e += groups) {
+                cnt++; nconv += conv[e] != 0; ep_sum += eps_run[e]; rule_sum += rules[e]; rew_sum += reward[e];
+                if (eps_run[e] > ep_max) ep_max = eps_run[e];
+            }
+            if (!pass) total += (int)nconv;
+            if (verbose)
+                printf("%s %s: %s %d agents %lld converged %lld mean-episodes %.3f max-episodes %d mean-rules %.3f mean-reward %.6f\n", pass ? "hparams" : "explore", env,
+                       pass ? "set" : "line", s, cnt, nconv, (double)ep_sum / cnt, ep_max, (double)rule_sum / cnt, rew_sum / cnt);
+        }
+    }
+    frirl_hip_batch_destroy(b);
+    demo_desc_free(&mm);
+    free(col); free(reward); free(skip);
+    return total;
+}

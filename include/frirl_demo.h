@@ -70,6 +70,19 @@ int frirl_demo_batch_run_evaluate_teach(const char *env, int agents, int max_epi
 int frirl_demo_parse_hparams(const char *path, double **sets, int *nsets, char *err, size_t err_len);
 int frirl_demo_batch_run_hparams(const char *env, int agents, int max_episodes, const double *sets, int nsets, int verbose);
 
+/* An exploration sweep in one run (frirl_demo --agents N --explore FILE [--hparams FILE] [--seed S]).  frirl_demo_parse_explore
+ * reads FILE: one `epsilon horizon` pair per line (frirl_hip_explore_rows: the agent's exploration rate and the number of episodes
+ * over which it falls linearly to zero, 0 = constant), `#` starts a comment, blank lines are skipped; *eps and *horizon = malloc'ed
+ * [*n] (the caller frees them).  -1 with err = "line N: why" for the first malformed line (not two numbers, epsilon outside [0, 1],
+ * a horizon that is negative, fractional or above 2^30), or why the file cannot be used.  No device is touched.
+ * frirl_demo_batch_run_explore: agent e (global id id_base + e, stream seed `seed`) explores under pair e mod n and, with sets != NULL, learns
+ * under hyper-parameter set e mod nsets ([nsets][6], frirl_demo_parse_hparams; NULL: the demo's own values) -- one run of the
+ * persistent learner (frirl_hip_batch_set_exploration, frirl_hip_batch_train), then one `explore ENV: line s ...` line per pair in
+ * the format of the `hparams` lines, followed by those when sets are given.  Returns the number of converged agents, or -1. */
+int frirl_demo_parse_explore(const char *path, double **eps, int **horizon, int *n, char *err, size_t err_len);
+int frirl_demo_batch_run_explore(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int n, unsigned long long seed,
+                                 unsigned long long id_base, const double *sets, int nsets, int verbose);
+
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */
 /* many agents WITH the reference's rule-base exchange (frirl_omp_run: chunks of 9 episodes, merge_rb in both directions after each,

@@ -244,9 +244,10 @@ typedef struct frirl_hip_agent {
 /* Per-agent overrides of the learning hyper-parameters of frirl_hip_agent.  Every column is [dev] [E] (E = b->E, indexed by the
  * agent's index in the batch, the index of frirl_hip_envs' arrays -- not by a launch slot and not by env_id_base + e) or NULL =
  * every agent takes the value in frirl_hip_agent.  A NULL struct pointer = all columns NULL.
- * Only these six are per agent.  epsilon, p, max_steps, no_random, seed, the convergence thresholds (reward_good_above,
- * qdiff_final_tolerance), evaluate and everything about the environment (env_kind, grids, action values) stay per batch: greedy
- * roll-outs and evaluation read epsilon too, so a per-agent epsilon would need a reference of its own.
+ * Only these six are per agent here; the exploration rate has rows of its own (frirl_hip_explore_rows, below), read by the learning
+ * picks alone.  p, max_steps, no_random, seed, the convergence thresholds (reward_good_above, qdiff_final_tolerance), evaluate and
+ * everything about the environment (env_kind, grids, action values) stay per batch, and so does the epsilon that roll-outs and
+ * evaluation read (episode key 0: agent->epsilon for every agent).
  * Read by frirl_hip_learn_run_rows / _train_rows and frirl_hip_agent_begin_rows / _observe_rows only.  The fused step
  * (frirl_hip_episode_begin / _step / _steps, frirl_hip_update_sarsa), the lane groups (frirl_hip_episode_run_lanes), demonstration
  * replay (frirl_hip_learn_demonstration) and frirl_hip_multi_* take no rows: they keep using frirl_hip_agent for every agent. */
@@ -254,6 +255,37 @@ typedef struct frirl_hip_hparam_rows {
     const double *alpha, *gamma, *qdiff_pos_boundary, *qdiff_neg_boundary, *weight_significant;
     const int32_t *skip_rules;                 /* 0 / 1 */
 } frirl_hip_hparam_rows;                       /* 48 bytes */
+
+/* Per-agent exploration: agent e's epsilon and the number of episodes over which it falls linearly to zero.  Columns are [dev] [E],
+ * indexed as the columns of frirl_hip_hparam_rows (the agent's index in the batch, never the launch slot).  A NULL struct pointer =
+ * both columns NULL and horizon_all 0: every agent explores at agent->epsilon in every episode, as without rows.
+ * The rate of agent e with row values (eps, h) in the episode whose stream key is k (the key the kernels pass to the stream below; the
+ * first learning episode is 1):
+ *     h == 0   eps                                          the reference's constant rate
+ *     k >  h   0.0                                          greedy from episode h + 1 on: nothing is drawn, as for epsilon == 0
+ *     else     eps * ((double)(h - (k - 1)) / (double)h)    one rounded division, then one rounded multiplication, nothing fused:
+ *                                                           episode 1 explores at exactly eps, episode h at eps / h
+ * (k == 0, the key of roll-outs and of callers without an episode counter, is outside every horizon: eps.)  The pick is
+ * frirl_e_greedy_selection at that rate -- greedy when agent->no_random == 1, the rate is 0 or draw 0 exceeds it, else
+ * round(draw 1 * A) clamped to A - 1; stream, keys and seed are those of frirl_hip_explore_check.  A constant rate never meets the
+ * construct loop's stopping rule except by luck; an annealed agent is greedy after its horizon and converges as a greedy one does.
+ * Read by frirl_hip_learn_run_explore / _train_explore and frirl_hip_agent_begin_explore / _observe_explore only.  Not built: rows in
+ * the fused step (frirl_hip_episode_begin / _step / _steps), the lane groups, demonstration replay, merged training and
+ * frirl_hip_multi_*; a per-agent epsilon in roll-outs and evaluation; per-agent seed, no_random, max_steps, p; any other decay (a
+ * geometric one would need per-agent state in frirl_hip_envs). */
+typedef struct frirl_hip_explore_rows {
+    const double  *epsilon;    /* [dev][E] or NULL = agent->epsilon for every agent */
+    const int32_t *horizon;    /* [dev][E] or NULL = horizon_all for every agent */
+    int32_t horizon_all;       /* annealing horizon in episodes when the column is NULL; 0 = constant */
+    int32_t reserved;          /* 0 */
+} frirl_hip_explore_rows;      /* 24 bytes */
+
+/* The rate above, on the host, compiled from the inline function the kernels call (csrc/envs.h: explore_epsilon). */
+double frirl_hip_explore_epsilon(double eps, int32_t horizon, uint32_t episode);
+/* What a valid frirl_hip_explore_rows with HOST columns [E] is (no device is touched): epsilon finite and in [0, 1], horizon and
+ * horizon_all in 0 .. 2^30, reserved 0.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with agent and column named in frirl_hip_last_error (also
+ * for E < 1 or a NULL agent, whose epsilon is checked when the column is NULL; NULL host_rows is valid). */
+int frirl_hip_explore_rows_check(const frirl_hip_explore_rows *host_rows, int32_t E, const frirl_hip_agent *agent);
 
 /* Test probe of the exploration stream, in the form every learning and roll-out kernel calls it.  For key tuple i the global id is
  * agent->env_id_base + env[i] and the word is the SplitMix64 output function of
@@ -860,6 +892,17 @@ int frirl_hip_agent_observe_rows(const frirl_hip_tables *t, const frirl_hip_rule
                                  const frirl_hip_hparam_rows *rows, const frirl_hip_envs *envs, const frirl_hip_agent_io *io,
                                  const int32_t *teacher, void *stream);
 
+/* ---- per-agent exploration: the _rows pair with frirl_hip_explore_rows (above).  Row e picks at its own rate; _begin draws under
+ * the key envs->episode[e] + 1 (the episode it starts), _observe under envs->episode[e].  Either struct may be NULL; explore NULL or
+ * all NULL with horizon_all 0 is the _rows call, bit for bit.  Values are not validated here (frirl_hip_explore_rows_check does that
+ * for host columns).  Refusals as the taught pair, in its order. */
+int frirl_hip_agent_begin_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                  const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs,
+                                  const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
+int frirl_hip_agent_observe_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                    const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs,
+                                    const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
+
 /* ---- one-launch replay of recorded demonstrations: every agent learns a log of (observation, action, reward, success) records in
  * ONE launch, one workgroup per agent looping over its records; no environment runs.  nant 2..8, A 1..32, any Shepard power.
  * Per record r of agent e (its log starts at record e * agent_stride of every array):
@@ -1113,6 +1156,20 @@ int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl_hip_ruleba
                                const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
                                int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
+/* ... and with per-agent exploration (frirl_hip_explore_rows, above) after `rows`: agent e picks at its own rate in every episode.
+ * Either struct may be NULL; explore == NULL is the _rows call (both NULL: the unsuffixed kernels), anything else runs a third kernel
+ * family (EXPLORE, learn_x*.hip), which loads the agent's epsilon and horizon together with the six hyper-parameters after the rule
+ * sweep -- a family of its own because inside the ROWS kernels the two columns cost the rows users 4.4 % on mountaincar
+ * (profiles/r26_explore_rows.md).  Same shapes, workspace sizes and refusals, in the same order.  With the epsilon column equal to
+ * agent->epsilon and no horizon the results are those of the unsuffixed call, bit for bit. */
+int frirl_hip_learn_run_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live,
+                                int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                  const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps,
+                                  int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes,
+                                  int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
 
 /* Persistent form for SMALL rule bases (the demos' learning regime): one wave keeps its environment's rule base,
  * the tables and the episode state in LDS and runs up to nsteps consecutive steps without a global round trip per
@@ -1248,6 +1305,13 @@ int frirl_hip_batch_set_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows 
  * rules above, `agent` supplying the bound that a missing qdiff column leaves to the batch.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with
  * agent and column named in frirl_hip_last_error (also for E < 1 or a NULL agent; NULL host_rows is valid: nothing to check). */
 int frirl_hip_hparam_rows_check(const frirl_hip_hparam_rows *host_rows, int32_t E, const frirl_hip_agent *agent);
+/* Per-agent exploration for frirl_hip_batch_train: host_rows holds HOST columns [E], validated as frirl_hip_explore_rows_check does
+ * and copied; NULL clears the rows.  A rejected call leaves the batch as it was; the shape restriction is that of
+ * frirl_hip_batch_set_hparams.  While exploration rows are set frirl_hip_batch_train passes them on (with any hyper-parameter rows)
+ * and launches with no_random = 0 whatever the batch's own value, which holds again once they are cleared; frirl_hip_batch_episode,
+ * _train_merged, _merge_round and _teach return FRIRL_HIP_EINVAL naming themselves.  Evaluation, roll-outs, reductions, save / load
+ * and the statistics are unaffected: they force greedy or read the batch's epsilon. */
+int frirl_hip_batch_set_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_rows);
 /* rule base of agent e: *R rules, rant HOST [>= *R][nant] (AoS), rconc HOST [>= *R] (pass NULL to query *R only) */
 int frirl_hip_batch_get_rulebase(frirl_hip_batch *b, int32_t e, int32_t *R, double *rant, double *rconc);
 /* Rule bases of all agents to / from one file.  The file is E records back to back, each exactly what
