@@ -100,6 +100,14 @@ class TeachResult(C.Structure):
                 ("students", C.c_int32), ("refused", C.c_int32), ("records_replayed", C.c_int64)]
 
 
+class SelectResult(C.Structure):
+    """struct frirl_hip_select_result (include/frirl_hip.h)."""
+    _fields_ = [("best", C.c_int32), ("parents", C.c_int32), ("replaced", C.c_int32), ("reserved", C.c_int32), ("rules_copied", C.c_int64)]
+
+
+CLONE_KEPT, CLONE_CLONED, CLONE_BAD_SRC, CLONE_CHAINED, CLONE_BAD_RULES = range(5)      # FRIRL_HIP_CLONE_*
+
+
 class BatchDesc(C.Structure):
     """struct frirl_hip_batch_desc (include/frirl_hip.h)."""
     _fields_ = [("nant", C.c_int32), ("U", C.c_int32), ("E", C.c_int32), ("maxR", C.c_int32), ("u", C.c_void_p), ("ve", C.c_void_p),
@@ -407,6 +415,15 @@ SIGNATURES = {
                                                         C.POINTER(C.c_int32), C.POINTER(ReduceMapTotals)]),
     "frirl_hip_batch_evaluate": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.POINTER(RolloutScore), C.POINTER(C.c_int32)]),
     "frirl_hip_batch_teach": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(TeachResult)]),
+    "frirl_hip_clone_agents": (C.c_int, [C.POINTER(RuleBases), C.c_int32, C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "frirl_hip_select_plan": (C.c_int, [C.POINTER(RolloutScore), C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
+    "frirl_hip_batch_select": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_int, C.POINTER(RolloutScore), C.POINTER(C.c_int32),
+                                         C.POINTER(SelectResult)]),
+    "frirl_hip_batch_get_hparams": (C.c_int, [C.c_void_p, C.POINTER(HparamRowsDesc)]),
+    "frirl_hip_batch_get_exploration": (C.c_int, [C.c_void_p, C.POINTER(ExploreRowsDesc)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_train_merged": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "frirl_hip_merge_rb": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.c_void_p, C.POINTER(SenderDesc), C.c_void_p,
@@ -1029,6 +1046,20 @@ class Problem:
                                        _ptr(active), _ptr(full), _stream(stream)), "frirl_hip_merge_rb")
         return full
 
+    def clone_agents(self, envs, src, conv=None, weights=None, stream=None):
+        """frirl_hip_clone_agents: agent e becomes a copy of the learner state of agent src[e] (int32 [E] on the device) -- rule base,
+        index mirror, and with envs (Envs or None) / conv (Convergence or None) / weights ([E, maxR] or None) the raw antecedents,
+        sticky flag, spread state, merge weights and a cleared convergence state.  Returns the status tensor [E] int32 (CLONE_*).
+        Does not synchronise.  The packed index mirror and the codes are marked stale, as for every call that may rewrite uidx."""
+        import torch
+        assert src.is_cuda and src.dtype == torch.int32 and src.shape == (self.E,) and src.is_contiguous()
+        assert weights is None or (weights.shape == (self.E, self.maxR) and weights.dtype == torch.float64 and weights.is_contiguous())
+        status = torch.empty((self.E,), dtype=torch.int32, device=self.rb.device)
+        check(lib().frirl_hip_clone_agents(C.byref(self.bases), self.nant, None if envs is None else C.byref(envs.desc),
+                                           None if conv is None else C.byref(conv.desc), _ptr(weights), _ptr(src), _ptr(status), _stream(stream)),
+              "frirl_hip_clone_agents")
+        return status
+
     def add_rule(self, rant, rconc, active=None, rant_store=None, stream=None):
         """five_hip_add_rule: appends rant[e] -> rconc[e]; returns added [E] int32."""
         import torch
@@ -1483,6 +1514,82 @@ def batch_teach(batch, teacher, episodes, start_states=None, passes=1, students=
     check(lib().frirl_hip_batch_teach(batch, teacher, episodes, None if st is None else st.ctypes.data_as(_DP), passes,
                                       None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(res)), "frirl_hip_batch_teach")
     return res
+
+
+def _batch_agents(batch):
+    st = BatchStats()
+    check(lib().frirl_hip_batch_stats(batch, C.byref(st)), "frirl_hip_batch_stats")
+    return int(st.agents)
+
+
+def select_plan(scores, parents, replace, eligible=None):
+    """frirl_hip_select_plan (host only): scores is a sequence of RolloutScore, or of (successes, reward_sum) pairs; eligible a
+    sequence of 0 / 1 or None = all.  Returns (src [E], rank [N]) as numpy int32: rank orders the eligible agents best first, and the
+    `replace` worst of them get the best `parents` as sources in turn."""
+    import numpy as np
+    E = len(scores)
+    sc = (RolloutScore * max(E, 1))()
+    for e, s in enumerate(scores):
+        if isinstance(s, RolloutScore):
+            sc[e] = s
+        else:
+            sc[e].successes, sc[e].reward_sum = int(s[0]), float(s[1])
+    el = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+    assert el is None or el.shape == (E,)
+    src, rank = np.zeros(max(E, 1), dtype=np.int32), np.zeros(max(E, 1), dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    check(lib().frirl_hip_select_plan(sc, E, None if el is None else el.ctypes.data_as(C.POINTER(C.c_uint8)), parents, replace, src.ctypes.data_as(i32),
+                                      rank.ctypes.data_as(i32)), "frirl_hip_select_plan")
+    return src[:E], rank[: E if el is None else int((el != 0).sum())]
+
+
+def batch_clone(batch, src, inherit_rows=False):
+    """frirl_hip_batch_clone on a library-owned batch: agent e becomes a copy of agent src[e] (host sequence [E]); with inherit_rows
+    the clones also take their sources' hyper-parameter and exploration rows.  Returns the number of agents cloned."""
+    import numpy as np
+    s = np.ascontiguousarray(src, dtype=np.int32)
+    assert s.shape == (_batch_agents(batch),)
+    cloned = C.c_int32(0)
+    check(lib().frirl_hip_batch_clone(batch, s.ctypes.data_as(C.POINTER(C.c_int32)), 1 if inherit_rows else 0, C.byref(cloned)), "frirl_hip_batch_clone")
+    return cloned.value
+
+
+def batch_select(batch, n, parents, replace, start_states=None, inherit_rows=False):
+    """frirl_hip_batch_select on a library-owned batch: evaluate every agent from n start states (host [E, n, nant-1] or None = its own),
+    replace the `replace` worst by copies of the `parents` best.  Returns (list of RolloutScore, src numpy int32 [E], SelectResult)."""
+    import numpy as np
+    E = _batch_agents(batch)
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    assert st is None or (st.ndim == 3 and st.shape[:2] == (E, n))
+    scores, src, res = (RolloutScore * E)(), np.zeros(E, dtype=np.int32), SelectResult()
+    check(lib().frirl_hip_batch_select(batch, n, None if st is None else st.ctypes.data_as(_DP), parents, replace, 1 if inherit_rows else 0, scores,
+                                       src.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)), "frirl_hip_batch_select")
+    return list(scores), src, res
+
+
+def batch_get_hparams(batch):
+    """frirl_hip_batch_get_hparams: dict of host arrays [E], one per column of HP_COLUMNS -- the row each agent trains under (the
+    batch's own value where the column is not set)."""
+    import numpy as np
+    E = _batch_agents(batch)
+    out = {k: np.zeros(E, dtype=np.int32 if k == "skip_rules" else np.float64) for k in HP_COLUMNS}
+    desc = HparamRowsDesc()
+    for k in HP_COLUMNS:
+        setattr(desc, k, out[k].ctypes.data)
+    check(lib().frirl_hip_batch_get_hparams(batch, C.byref(desc)), "frirl_hip_batch_get_hparams")
+    return out
+
+
+def batch_get_exploration(batch):
+    """frirl_hip_batch_get_exploration: dict(epsilon float64 [E], horizon int32 [E]) -- the exploration row of every agent (the batch's
+    epsilon / the rows' horizon_all where the column is not set)."""
+    import numpy as np
+    E = _batch_agents(batch)
+    out = dict(epsilon=np.zeros(E), horizon=np.zeros(E, dtype=np.int32))
+    desc = ExploreRowsDesc()
+    desc.epsilon, desc.horizon = out["epsilon"].ctypes.data, out["horizon"].ctypes.data
+    check(lib().frirl_hip_batch_get_exploration(batch, C.byref(desc)), "frirl_hip_batch_get_exploration")
+    return out
 
 
 def batch_reduce_all_map(batch, strategy, n, start_states=None, only_successful=True, cap=0):

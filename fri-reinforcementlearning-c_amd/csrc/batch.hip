@@ -821,6 +821,129 @@ extern "C" int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_
     return FRIRL_HIP_OK;
 }
 
+// ---- selection: clone the best agents over the worst (frirl_hip_clone_agents, clone.hip) -----------------------------------------
+namespace frirl {
+// inherit_rows: every set column takes the source's value for the cloned agents; in place, since a source is no destination
+__global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ status, int E, double *d0, double *d1, double *d2, double *d3,
+                                    double *d4, double *d5, int32_t *i0, int32_t *i1)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || status[e] != FRIRL_HIP_CLONE_CLONED) return;
+    const int s = src[e];
+    double *d[6] = {d0, d1, d2, d3, d4, d5};
+#pragma unroll
+    for (int c = 0; c < 6; c++) if (d[c]) d[c][e] = d[c][s];
+    if (i0) i0[e] = i0[s];
+    if (i1) i1[e] = i1[s];
+}
+}  // namespace frirl
+
+static int batch_clone_run(const char *who, frirl_hip_batch *b, const int32_t *src, int inherit_rows, int32_t *cloned, int64_t *rules_copied)
+{
+    if (!b || !src) { set_error("%s: NULL batch or src", who); return FRIRL_HIP_EINVAL; }
+    const int E = b->E;
+    for (int e = 0; e < E; e++) {
+        if (src[e] < 0 || src[e] >= E) { set_error("%s: agent %d: src=%d outside 0..%d", who, e, src[e], E - 1); return FRIRL_HIP_EINVAL; }
+        if (src[src[e]] != src[e]) { set_error("%s: agent %d: its source %d is itself replaced (by %d)", who, e, src[e], src[src[e]]); return FRIRL_HIP_EINVAL; }
+    }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    int32_t *d_src = nullptr;                                         // src, then status
+    BCHK(hipMalloc(reinterpret_cast<void **>(&d_src), sizeof(int32_t) * 2 * (size_t)E), "clone buffers");
+    int32_t *d_status = d_src + E;
+    std::vector<int32_t> st(E), nr(E);
+    int rc = FRIRL_HIP_OK;
+    hipError_t he = hipMemcpyAsync(d_src, src, sizeof(int32_t) * E, hipMemcpyHostToDevice, b->s);
+    // no image of a rule base outlives a call (d_lanes_ws and d_learn_ws are imported from rb / uidx at the start of every call that
+    // uses them), so there is nothing to invalidate beside the arrays the clone itself rewrites
+    if (he == hipSuccess) rc = frirl_hip_clone_agents(&b->rb, b->nant, &b->envs, &b->conv, b->d_weights, d_src, d_status, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set)) {
+        const frirl_hip_hparam_rows &h = b->hp;
+        hipLaunchKernelGGL(frirl::inherit_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, b->s, d_src, d_status, E, const_cast<double *>(h.alpha),
+                           const_cast<double *>(h.gamma), const_cast<double *>(h.qdiff_pos_boundary), const_cast<double *>(h.qdiff_neg_boundary),
+                           const_cast<double *>(h.weight_significant), const_cast<double *>(b->ex.epsilon), const_cast<int32_t *>(h.skip_rules),
+                           const_cast<int32_t *>(b->ex.horizon));
+    }
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(nr.data(), b->d_nrules, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `src` may be in use by the upload
+    else (void)hipStreamSynchronize(b->s);
+    (void)hipFree(d_src);
+    if (rc) return rc;
+    if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
+    if ((rc = check_launch(who))) return rc;
+    int32_t count = 0;
+    int64_t rules = 0;
+    for (int e = 0; e < E; e++)
+        if (st[e] == FRIRL_HIP_CLONE_CLONED) { count++; rules += nr[e]; }         // nrules[e] is nrules[src[e]] now
+    if (cloned) *cloned = count;
+    if (rules_copied) *rules_copied = rules;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_clone(frirl_hip_batch *b, const int32_t *src, int inherit_rows, int32_t *cloned)
+{
+    return batch_clone_run("frirl_hip_batch_clone", b, src, inherit_rows, cloned, nullptr);
+}
+
+extern "C" int frirl_hip_batch_select(frirl_hip_batch *b, int32_t n, const double *start_states, int32_t parents, int32_t replace, int inherit_rows,
+                                      frirl_hip_rollout_score *scores, int32_t *src_out, frirl_hip_select_result *result)
+{
+    static const char *who = "frirl_hip_batch_select";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    std::vector<frirl_hip_rollout_score> sc(b->E);
+    std::vector<int32_t> src(b->E);
+    int32_t best = 0, cloned = 0;
+    int64_t rules = 0;
+    int rc = frirl_hip_batch_evaluate(b, n, start_states, sc.data(), &best);
+    if (rc == FRIRL_HIP_OK) rc = frirl_hip_select_plan(sc.data(), b->E, nullptr, parents, replace, src.data(), nullptr);
+    if (rc == FRIRL_HIP_OK) rc = batch_clone_run(who, b, src.data(), inherit_rows, &cloned, &rules);
+    if (rc) return rc;
+    if (scores) memcpy(scores, sc.data(), sizeof(frirl_hip_rollout_score) * b->E);
+    if (src_out) memcpy(src_out, src.data(), sizeof(int32_t) * b->E);
+    if (result) *result = frirl_hip_select_result{best, parents, cloned, 0, rules};
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_get_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows *host_out)
+{
+    static const char *who = "frirl_hip_batch_get_hparams";
+    if (!b || !host_out) { set_error("%s: NULL batch or host_out", who); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    BCHK(hipStreamSynchronize(b->s), "hyper-parameter sync");
+    const size_t E = (size_t)b->E;
+    const double *out[5] = {host_out->alpha, host_out->gamma, host_out->qdiff_pos_boundary, host_out->qdiff_neg_boundary, host_out->weight_significant};
+    const double *set[5] = {b->hp.alpha, b->hp.gamma, b->hp.qdiff_pos_boundary, b->hp.qdiff_neg_boundary, b->hp.weight_significant};
+    const double own[5] = {b->agent.alpha, b->agent.gamma, b->agent.qdiff_pos_boundary, b->agent.qdiff_neg_boundary, b->agent.weight_significant};
+    for (int c = 0; c < 5; c++) {
+        if (!out[c]) continue;
+        if (set[c]) BCHK(hipMemcpy(const_cast<double *>(out[c]), set[c], sizeof(double) * E, hipMemcpyDeviceToHost), "hyper-parameter download");
+        else std::fill_n(const_cast<double *>(out[c]), E, own[c]);
+    }
+    if (host_out->skip_rules) {
+        if (b->hp.skip_rules) BCHK(hipMemcpy(const_cast<int32_t *>(host_out->skip_rules), b->hp.skip_rules, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "hyper-parameter download");
+        else std::fill_n(const_cast<int32_t *>(host_out->skip_rules), E, (int32_t)b->agent.skip_rules);
+    }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_get_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_out)
+{
+    static const char *who = "frirl_hip_batch_get_exploration";
+    if (!b || !host_out) { set_error("%s: NULL batch or host_out", who); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    BCHK(hipStreamSynchronize(b->s), "exploration sync");
+    const size_t E = (size_t)b->E;
+    if (host_out->epsilon) {
+        if (b->ex.epsilon) BCHK(hipMemcpy(const_cast<double *>(host_out->epsilon), b->ex.epsilon, sizeof(double) * E, hipMemcpyDeviceToHost), "exploration download");
+        else std::fill_n(const_cast<double *>(host_out->epsilon), E, b->agent.epsilon);
+    }
+    if (host_out->horizon) {
+        if (b->ex.horizon) BCHK(hipMemcpy(const_cast<int32_t *>(host_out->horizon), b->ex.horizon, sizeof(int32_t) * E, hipMemcpyDeviceToHost), "exploration download");
+        else std::fill_n(const_cast<int32_t *>(host_out->horizon), E, b->ex.horizon_all);
+    }
+    return FRIRL_HIP_OK;
+}
+
 // ---- multi-agent rule-base merge: one round of the reference's many-agent loop (frirl_agent.c:426-462) -------------------
 // (1) every agent id >= 1 takes over the master's (agent 0's) rules -- all receivers in ONE launch; (2) the master takes over the
 // rules of agent 1, 2, ... one after the other (sequential by definition: each merge changes the master).  Agents whose rule base

@@ -24,7 +24,8 @@ static int usage(const char *what)
                     "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-starts K [--spread F]   (S = 1 | 2, 1 <= K <= 256 start states per agent, 0 <= F <= 1)\n"
                     "       frirl_demo --env NAME --agents N --reduce S --reduce-all --reduce-map K [--spread F] [--reduce-map-all]   (removals validated on the policy map at the points visited from K start states; --reduce-map-all: of every start, not the successful ones alone)\n"
                     "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n"
-                    "       frirl_demo --env NAME --agents N --explore FILE [--hparams FILE] [--seed S] [--id-base B] [--max-episodes M]   (an exploration sweep in one run: FILE holds one `epsilon horizon` pair per line, epsilon falling linearly to zero over `horizon` episodes, 0 = constant; agent e takes line e mod L; S seeds the exploration stream, agent e draws under the global id B + e)\n", what);
+                    "       frirl_demo --env NAME --agents N --explore FILE [--hparams FILE] [--seed S] [--id-base B] [--max-episodes M]   (an exploration sweep in one run: FILE holds one `epsilon horizon` pair per line, epsilon falling linearly to zero over `horizon` episodes, 0 = constant; agent e takes line e mod L; S seeds the exploration stream, agent e draws under the global id B + e)\n"
+                    "       frirl_demo --env NAME --agents N [--hparams FILE] [--explore FILE] --select G --select-episodes M --select-parents P --select-replace K [--select-inherit] [--evaluate n] [--spread F]   (G generations of M episodes; after each, every agent is evaluated from n start states, default 1, and the K worst become copies of the P best, with --select-inherit also of their rows)\n", what);
     return 2;
 }
 
@@ -47,6 +48,8 @@ int main(int argc, char **argv)
     unsigned long long seed = 0;    /* --seed S: seed of the exploration stream (with --explore) */
     unsigned long long id_base = 0; /* --id-base B: global id of agent 0 on that stream (frirl_hip_agent.env_id_base; with --explore) */
     int stream_given = 0;           /* --seed or --id-base was given */
+    int select_gen = 0;             /* --select G: generations of train + frirl_hip_batch_select, 0 = not asked for */
+    int select_episodes = 0, select_parents = 0, select_replace = -1, select_inherit = 0;
     char *fargv[16];
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
@@ -70,8 +73,44 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
         else if (!strcmp(argv[i], "--teach-best") && i + 1 < argc) { teach_best = atoi(argv[++i]); if (teach_best < 1) return usage("--teach-best needs M >= 1"); }
         else if (!strcmp(argv[i], "--teach-passes") && i + 1 < argc) { teach_passes = atoi(argv[++i]); if (teach_passes < 1 || teach_passes > 1024) return usage("--teach-passes needs 1 <= P <= 1024"); }
+        else if (!strcmp(argv[i], "--select") && i + 1 < argc) { select_gen = atoi(argv[++i]); if (select_gen < 1) return usage("--select needs G >= 1 generations"); }
+        else if (!strcmp(argv[i], "--select-episodes") && i + 1 < argc) { select_episodes = atoi(argv[++i]); if (select_episodes < 1) return usage("--select-episodes needs M >= 1"); }
+        else if (!strcmp(argv[i], "--select-parents") && i + 1 < argc) { select_parents = atoi(argv[++i]); if (select_parents < 1) return usage("--select-parents needs P >= 1"); }
+        else if (!strcmp(argv[i], "--select-replace") && i + 1 < argc) { select_replace = atoi(argv[++i]); if (select_replace < 0) return usage("--select-replace needs K >= 0"); }
+        else if (!strcmp(argv[i], "--select-inherit")) select_inherit = 1;
         else if (fargc < 15) fargv[fargc++] = argv[i];
     }
+    if (select_gen > 0) {           /* generations of train + select; --evaluate n, --hparams and --explore go with it */
+        double *sets = NULL, *eps = NULL, *units;
+        int *horizon = NULL, nsets = 0, nx = 0, ns = 0, U = 0, A = 0, ms = 0, rc, rows = evaluate > 0 ? evaluate : 1;
+        char err[256];
+        if (merge) return usage("--select does not go with --merge: selection replaces rule bases, the exchange merges them");
+        if (gpus >= 0) return usage("--select does not go with --gpus: selection across devices is not built");
+        if (teach_best > 0) return usage("--select does not go with --teach-best: a clone takes the rule base over, it is not taught");
+        if (agents < 1 || reduce || load_bin || save_bin) return usage("--select goes with --agents N (one device, trained from scratch, no --reduce)");
+        if (select_episodes < 1 || select_parents < 1 || select_replace < 0) return usage("--select needs --select-episodes M, --select-parents P and --select-replace K");
+        if (select_parents + select_replace > agents) return usage("--select-parents P + --select-replace K exceeds --agents N: a parent would be replaced");
+        if (stream_given && !explore) return usage("--seed and --id-base go with --explore FILE");
+        frirl_parse_cmdline(&fr, fargc, fargv);
+        if (frirl_demo_describe(env, &ns, &U, &A, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &ms) != 0) return 2;
+        if (hparams && frirl_demo_parse_hparams(hparams, &sets, &nsets, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --hparams %s: %s\n", hparams, err);
+            return 2;
+        }
+        if (explore && frirl_demo_parse_explore(explore, &eps, &horizon, &nx, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --explore %s: %s\n", explore, err);
+            free(sets);
+            return 2;
+        }
+        units = malloc(sizeof(double) * (size_t)agents * (size_t)rows * (size_t)ns);
+        if (!units) return 1;
+        frirl_demo_row_units(agents, rows, ns, units);
+        rc = frirl_demo_batch_run_select(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, select_gen, select_episodes, select_parents, select_replace,
+                                         select_inherit, rows, spread, units, eps, horizon, nx, seed, id_base, sets, nsets, 1);
+        free(units); free(sets); free(eps); free(horizon);
+        return rc >= 0 ? 0 : 3;
+    }
+    if (select_episodes || select_parents || select_replace >= 0 || select_inherit) return usage("--select-episodes / -parents / -replace / -inherit go with --select G");
     if (evaluate > 0 && (agents < 1 || merge || gpus >= 0 || reduce)) return usage("--evaluate goes with --agents N (one device, no --merge / --reduce)");
     if (teach_best > 0 && evaluate < 1) return usage("--teach-best goes with --evaluate K");
     if (reduce_starts > 0 && (agents < 1 || !reduce_all || (reduce != 1 && reduce != 2) || merge || gpus >= 0))

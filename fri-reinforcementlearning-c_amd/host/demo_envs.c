@@ -870,3 +870,81 @@ int frirl_demo_batch_run_explore(const char *env, int agents, int max_episodes, 
     free(col); free(reward); free(skip);
     return total;
 }
+
+/* ---- selection inside a population: frirl_demo --agents N --select G --select-episodes M --select-parents P --select-replace K ----------
+ * G generations of frirl_hip_batch_train(M + 1) followed by frirl_hip_batch_select (every agent evaluated from `rows` start states, as
+ * --evaluate maps them; the `replace` worst become copies of the `parents` best, with `inherit` also of their rows), one `select ENV:
+ * generation g ...` line each; then training goes on to max_episodes and the report line follows.  sets / eps + horizon: the sweeps of
+ * frirl_demo_batch_run_hparams / _explore, or NULL.  Returns the number of converged agents, or -1. */
+int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const double *sets, int nsets, int verbose)
+{
+    int nant = 0, ns, episodes = 0, rc, e, k, g;
+    frirl_hip_batch_desc d;
+    struct demo_desc_mem mm;
+    frirl_hip_batch *b;
+    frirl_hip_batch_stats_t st;
+    frirl_hip_rollout_score *sc;
+    double *col, *start;
+    int32_t *skip, *xh;
+    if (agents < 1 || generations < 1 || gen_episodes < 1 || rows < 1 || !units || !(spread >= 0.0) || (eps && nx < 1) || (sets && nsets < 1)) return -1;
+    if (demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    ns = nant - 1;
+    if (eps) { d.agent.seed = seed; d.agent.env_id_base = id_base; }
+    sc = malloc(sizeof *sc * (size_t)agents);
+    col = malloc(sizeof(double) * 6 * (size_t)agents);
+    skip = malloc(sizeof(int32_t) * 2 * (size_t)agents);
+    start = malloc(sizeof(double) * (size_t)agents * (size_t)rows * (size_t)ns);
+    if (!sc || !col || !skip || !start) return -1;
+    xh = skip + agents;
+    demo_row_starts(&d, &mm, agents, rows, ns, spread, units, start);
+    b = frirl_hip_batch_create(&d);
+    if (!b) five_dropin_fatal("frirl_demo_batch_run_select(create)", FRIRL_HIP_ENODEV);
+    if (sets) {
+        frirl_hip_hparam_rows hp;
+        for (e = 0; e < agents; e++) {
+            for (k = 0; k < 5; k++) col[(size_t)k * agents + e] = sets[6 * (size_t)(e % nsets) + k];
+            skip[e] = (int32_t)sets[6 * (size_t)(e % nsets) + 5];
+        }
+        hp.alpha = col; hp.gamma = col + agents; hp.qdiff_pos_boundary = col + 2 * (size_t)agents; hp.qdiff_neg_boundary = col + 3 * (size_t)agents;
+        hp.weight_significant = col + 4 * (size_t)agents; hp.skip_rules = skip;
+        rc = frirl_hip_batch_set_hparams(b, &hp);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(hparams)", rc);
+    }
+    if (eps) {
+        frirl_hip_explore_rows ex;
+        double *xe = col + 5 * (size_t)agents;
+        for (e = 0; e < agents; e++) { xe[e] = eps[e % nx]; xh[e] = horizon[e % nx]; }
+        memset(&ex, 0, sizeof ex);
+        ex.epsilon = xe; ex.horizon = xh;
+        rc = frirl_hip_batch_set_exploration(b, &ex);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(explore)", rc);
+    }
+    for (g = 0; g < generations; g++) {
+        frirl_hip_select_result res;
+        rc = frirl_hip_batch_train(b, gen_episodes + 1, &episodes);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(train)", rc);
+        rc = frirl_hip_batch_select(b, rows, start, parents, replace, inherit, sc, NULL, &res);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(select)", rc);
+        if (verbose)
+            printf("select %s: generation %d best %d successes %d reward %.6f replaced %d rules_copied %lld\n", env, g, (int)res.best, (int)sc[res.best].successes,
+                   sc[res.best].reward_sum, (int)res.replaced, (long long)res.rules_copied);
+    }
+    rc = frirl_hip_batch_stats(b, &st);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_select(stats)", rc);
+    if (max_episodes - (int)st.episodes_max > 1) {
+        rc = frirl_hip_batch_train(b, max_episodes - (int)st.episodes_max, &episodes);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(train on)", rc);
+        rc = frirl_hip_batch_stats(b, &st);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_select(stats)", rc);
+    }
+    if (verbose)                    /* the report line of frirl_demo --agents N; episodes = the most any agent ran */
+        printf("batch %s: agents %lld episodes %d converged %lld env-steps %lld mean-rules %.3f mean-reward %.6f (min %.6f max %.6f)\n", env,
+               (long long)st.agents, (int)st.episodes_max, (long long)st.converged, (long long)st.total_env_steps, st.rules_sum / st.agents,
+               st.reward_sum / st.agents, st.reward_min, st.reward_max);
+    frirl_hip_batch_destroy(b);
+    demo_desc_free(&mm);
+    free(sc); free(col); free(skip); free(start);
+    return (int)st.converged;
+}

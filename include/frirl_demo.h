@@ -83,6 +83,17 @@ int frirl_demo_parse_explore(const char *path, double **eps, int **horizon, int 
 int frirl_demo_batch_run_explore(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int n, unsigned long long seed,
                                  unsigned long long id_base, const double *sets, int nsets, int verbose);
 
+/* Selection inside a population (frirl_demo --agents N --select G --select-episodes M --select-parents P --select-replace K
+ * [--select-inherit] [--evaluate n] [--hparams FILE] [--explore FILE]): G generations of frirl_hip_batch_train(M + 1) followed by
+ * frirl_hip_batch_select -- every agent evaluated from `rows` start states (units / spread as frirl_demo_batch_run_evaluate maps them), the
+ * `replace` worst replaced by copies of the `parents` best, with inherit != 0 also of their rows -- and one line per generation,
+ *     select ENV: generation g best B successes S reward R replaced K rules_copied C
+ * then training goes on to max_episodes and the `batch ENV: ...` report line of frirl_demo --agents N follows.  sets ([nsets][6]) and
+ * eps / horizon ([nx]): the sweeps of frirl_demo_batch_run_hparams / _explore, or NULL.  Returns the number of converged agents, or -1. */
+int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const double *sets, int nsets, int verbose);
+
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */
 /* many agents WITH the reference's rule-base exchange (frirl_omp_run: chunks of 9 episodes, merge_rb in both directions after each,

@@ -1392,6 +1392,61 @@ int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_t episodes,
                           const double *start_states /* HOST [episodes][nant-1], or NULL */, int32_t passes,
                           const uint8_t *students /* HOST [E], or NULL = every agent but the teacher */,
                           frirl_hip_teach_result *result);
+
+/* ---- selection inside a population: the worst agents become copies of the best, on the device (csrc/clone.hip) -----------------------
+ * frirl_hip_clone_agents: agent e with src[e] != e becomes a copy of the LEARNER STATE of s = src[e]; status[e] (or NULL) says what
+ * happened.  Everything is decided on the device from src and nrules: the call reads nothing back, does not synchronise and
+ * allocates nothing (two launches on `stream`: the copy, then the per-agent scalars).
+ *   copied from s   the rb slab (all nant + 1 rows) and nrules; the uidx rows (b->uidx != NULL); envs->rant (!= NULL); envs->fus (the
+ *                   sticky flag names the last inserted rule of THAT rule base); envs->spread_ant / spread_R; the weights row
+ *                   (weights != NULL: [dev][E][maxR], FIVERB.weights as frirl_hip_merge_rb keeps it)
+ *   kept            envs->start_states, episode (the exploration stream position), states, q_ant, done, ep_steps, ep_reward, status;
+ *                   conv->episodes
+ *   cleared         as frirl_hip_batch_teach clears a student: conv->prev_rconc[e] = the new consequent row, prev_nrules = nrules,
+ *                   prev_steps = -1, prev_reward = -1.0, converged = 0, epended = 0 (where present)
+ * Every copied row is moved over the columns c < max(old nrules[e], nrules[s]) only, as c < nrules[s] ? the source's value : 0
+ * (prev_rconc: the bound also covers the old prev_nrules[e]; a destination count outside 0..maxR counts as maxR), so a row that was
+ * zero beyond its own count is zero beyond nrules[e] afterwards, also where the destination held more rules than the source; columns
+ * beyond the bound are not written.  A source is never written (CHAINED), so no result depends on the order of the workgroups.
+ * FRIRL_HIP_EINVAL, before the device is looked for: NULL b / b->rb / b->nrules / src, nant outside 2..9, E < 1, an odd maxR, a conv
+ * with a NULL array other than epended, rb / rant / prev_rconc / weights not 16-byte aligned, uidx not 4-byte aligned (uidx rows are
+ * moved in 16-byte units where maxR % 8 == 0 and the base is 16-byte aligned, else in 4-byte units). */
+#define FRIRL_HIP_CLONE_KEPT      0   /* src[e] == e: agent untouched, bit for bit                                  */
+#define FRIRL_HIP_CLONE_CLONED    1
+#define FRIRL_HIP_CLONE_BAD_SRC   2   /* src[e] outside 0..E-1: agent untouched                                     */
+#define FRIRL_HIP_CLONE_CHAINED   3   /* src[src[e]] != src[e] (the source is itself replaced): agent untouched     */
+#define FRIRL_HIP_CLONE_BAD_RULES 4   /* nrules[src[e]] outside 1..maxR: agent untouched                            */
+int frirl_hip_clone_agents(const frirl_hip_rulebases *b, int32_t nant, const frirl_hip_envs *envs /* or NULL */,
+                           const frirl_hip_convergence *conv /* or NULL */, double *weights /* [dev][E][maxR], or NULL */,
+                           const int32_t *src /* [dev][E] */, int32_t *status /* [dev][E] or NULL */, void *stream);
+/* The src table of a truncation selection, on the host (no device is touched).  N = the eligible agents (eligible: HOST [E] of 0 / 1,
+ * NULL = all); rank (HOST [N], or NULL) orders them by frirl_hip_batch_evaluate's rule -- most successes, then the largest
+ * reward_sum, then the lowest index -- so rank[0] is that call's *best.  src[e] = e for everybody, then for k = 0 .. replace-1:
+ * src[rank[N-1-k]] = rank[k % parents].  FRIRL_HIP_EINVAL naming the cause: NULL scores / src, E < 1, parents < 1, replace < 0,
+ * parents + replace > N (the bound that keeps a parent from being replaced), a NaN reward_sum of an eligible agent (named). */
+int frirl_hip_select_plan(const frirl_hip_rollout_score *scores /* HOST [E] */, int32_t E, const uint8_t *eligible /* HOST [E] or NULL */,
+                          int32_t parents, int32_t replace, int32_t *src /* HOST [E] out */, int32_t *rank /* HOST [N] out, or NULL */);
+/* frirl_hip_clone_agents on the batch's own arrays (index mirror, raw antecedents, sticky flag, spread state, the merge weights once
+ * allocated, convergence state).  src is validated on the host first: an entry outside 0..E-1 or a chain (src[src[e]] != src[e])
+ * returns FRIRL_HIP_EINVAL naming the agent and leaves the batch as it was.  Works while hyper-parameter or exploration rows are set:
+ * with inherit_rows == 0 a clone keeps its own row (it goes on from the winner's rule base under its own hyper-parameters); with
+ * inherit_rows != 0 every SET column of both row sets gets col[e] = col[src[e]] for the cloned agents, unset columns stay unset.
+ * total_env_steps and the batch's agent are not touched; frirl_hip_batch_train continues afterwards as after frirl_hip_batch_teach.
+ * *cloned (or NULL) = agents with status CLONED.  Synchronises. */
+int frirl_hip_batch_clone(frirl_hip_batch *b, const int32_t *src /* HOST [E] */, int inherit_rows, int32_t *cloned /* or NULL */);
+/* frirl_hip_batch_evaluate(n, start_states), frirl_hip_select_plan over all agents, frirl_hip_batch_clone: one generation's selection.
+ * result->best = the evaluation's best agent, parents / replaced as given, rules_copied = the sum of nrules[src[e]] over the cloned
+ * agents.  scores / src_out: HOST [E] or NULL.  The refusals of its three parts, each leaving the batch as it was. */
+typedef struct frirl_hip_select_result { int32_t best, parents, replaced, reserved; int64_t rules_copied; } frirl_hip_select_result;   /* 24 bytes */
+int frirl_hip_batch_select(frirl_hip_batch *b, int32_t n, const double *start_states /* as frirl_hip_batch_evaluate */, int32_t parents,
+                           int32_t replace, int inherit_rows, frirl_hip_rollout_score *scores /* HOST [E] or NULL */,
+                           int32_t *src_out /* HOST [E] or NULL */, frirl_hip_select_result *result /* or NULL */);
+/* The rows a batch trains under, back on the host: every non-NULL HOST column [E] of host_out is filled -- a set column with the
+ * device column, an unset one with the batch's own value for every agent (agent.alpha ..., agent.epsilon, the rows' horizon_all) --
+ * so that a caller can read, perturb and frirl_hip_batch_set_* again.  horizon_all / reserved of host_out are not read. */
+int frirl_hip_batch_get_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows *host_out);
+int frirl_hip_batch_get_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_out);
+
 /* One round of the reference's multi-agent rule-base exchange (frirl_omp_run, frirl_agent.c:426-462) inside the batch: every agent
  * id >= 1 takes over the master's (agent 0's) rules -- all of them in one launch of frirl_hip_merge_rb --, then the master takes
  * over the rules of agent 1, 2, ... in turn.  Agents whose rule base is complete do not send (:432,:444).  *full_agents (or NULL):
