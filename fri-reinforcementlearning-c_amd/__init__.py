@@ -61,6 +61,14 @@ class ExploreRowsDesc(C.Structure):
     _fields_ = [("epsilon", C.c_void_p), ("horizon", C.c_void_p), ("horizon_all", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TargetRowsDesc(C.Structure):
+    """struct frirl_hip_target_rows (include/frirl_hip.h)."""
+    _fields_ = [("target", C.c_void_p), ("target_all", C.c_int32), ("reserved", C.c_int32)]
+
+
+TARGET_SARSA, TARGET_Q = 0, 1       # FRIRL_HIP_TARGET_*
+
+
 class EnvsDesc(C.Structure):
     """struct frirl_hip_envs (include/frirl_hip.h)."""
     _fields_ = [("states", C.c_void_p), ("q_ant", C.c_void_p), ("fus", C.c_void_p), ("done", C.c_void_p), ("ep_steps", C.c_void_p),
@@ -330,6 +338,12 @@ SIGNATURES = {
     "frirl_hip_learn_train_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
                                                 C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
+    "frirl_hip_learn_run_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                             C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "frirl_hip_learn_train_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                               C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
     "five_hip_add_rule": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "frirl_hip_update_sarsa": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p,
@@ -354,6 +368,8 @@ SIGNATURES = {
                                                 C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
     "frirl_hip_agent_observe_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
                                                   C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
+    "frirl_hip_agent_observe_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                                 C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
     "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
                                                 C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
@@ -402,6 +418,9 @@ SIGNATURES = {
     "frirl_hip_batch_set_exploration": (C.c_int, [C.c_void_p, C.POINTER(ExploreRowsDesc)]),
     "frirl_hip_explore_rows_check": (C.c_int, [C.POINTER(ExploreRowsDesc), C.c_int32, C.POINTER(AgentDesc)]),
     "frirl_hip_explore_epsilon": (C.c_double, [C.c_double, C.c_int32, C.c_uint32]),
+    "frirl_hip_batch_set_target": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "frirl_hip_batch_get_target": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "frirl_hip_target_rows_check": (C.c_int, [C.POINTER(TargetRowsDesc), C.c_int32]),
     "frirl_hip_batch_get_rulebase": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _DP, _DP]),
     "frirl_hip_batch_save_rulebases": (C.c_int, [C.c_void_p, C.c_char_p]),
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -1179,6 +1198,29 @@ class ExploreRows:
         return self
 
 
+class TargetRows:
+    """Per-agent TD target (struct frirl_hip_target_rows): agent e of a batch of E learns towards Q(s', a') of the action it takes
+    (TARGET_SARSA, 0) or towards Q(s', g) of the greedy action its pick started from (TARGET_Q, 1).  target (uint8) is anything
+    torch.as_tensor takes, of length E; None gives every agent target_all.  Owns the device tensor and the struct.  Taken by
+    agent_observe / train_persistent / train as target=."""
+
+    def __init__(self, E, device, target=None, target_all=TARGET_SARSA):
+        import torch
+        self.E, self.desc, self.target = E, TargetRowsDesc(), None
+        self.desc.target_all = int(target_all)
+        if target is not None:
+            self.target = torch.as_tensor(target, dtype=torch.uint8).to(device).contiguous()
+            assert self.target.shape == (E,), (tuple(self.target.shape), E)
+            self.desc.target = self.target.data_ptr()
+
+    @classmethod
+    def null(cls, E):
+        """The NULL struct pointer: target=TargetRows.null(E) goes through the _target entry point, which calls the _explore one."""
+        self = cls.__new__(cls)
+        self.E, self.desc, self.target = E, None, None
+        return self
+
+
 def explore_epsilon(eps, horizon, episode):
     """frirl_hip_explore_epsilon: the exploration rate of an agent with row values (eps, horizon) in the episode whose stream key is
     `episode` (the first learning episode is 1) -- the host build of the function the kernels call."""
@@ -1288,16 +1330,21 @@ def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None
     return action, action_idx
 
 
-def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None, explore=None):
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None, explore=None, target=None):
     """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
     last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
     quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
     rows that were done are not written.  teacher [E] int32 (frirl_hip_agent_observe_taught): a row whose entry is an action index
     takes it as its next action and learns towards Q(s', a_teacher).  rows: an HparamRows (frirl_hip_agent_observe_rows): row e
     learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_agent_observe_explore): row e picks at
-    its own rate in its current episode.  Does not synchronise."""
+    its own rate in its current episode.  target: a TargetRows (frirl_hip_agent_observe_target): row e learns towards Q(s', a') or
+    Q(s', g); a taught row under TARGET_Q takes the teacher's action and learns towards Q(s', g).  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    if explore is not None:
+    if target is not None:
+        check(lib().frirl_hip_agent_observe_target(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
+                                                   _rows(target, problem.E), C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E),
+                                                   _stream(stream)), "frirl_hip_agent_observe_target")
+    elif explore is not None:
         check(lib().frirl_hip_agent_observe_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
                                                     C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
               "frirl_hip_agent_observe_explore")
@@ -1488,6 +1535,24 @@ def batch_set_exploration(batch, epsilon=None, horizon=None, horizon_all=0, clea
     check(lib().frirl_hip_batch_set_exploration(batch, C.byref(desc)), "frirl_hip_batch_set_exploration")
 
 
+def batch_set_target(batch, target=None, target_all=TARGET_SARSA):
+    """frirl_hip_batch_set_target on a library-owned batch: the TD target of every agent for frirl_hip_batch_train -- a host array of
+    length E of TARGET_SARSA / TARGET_Q, or None: target_all for every agent.  (None, TARGET_SARSA) clears the target.  The library
+    validates and copies before it returns."""
+    import numpy as np
+    col = None if target is None else np.ascontiguousarray(target, dtype=np.uint8)
+    assert col is None or col.shape == (_batch_agents(batch),)
+    check(lib().frirl_hip_batch_set_target(batch, None if col is None else col.ctypes.data, int(target_all)), "frirl_hip_batch_set_target")
+
+
+def batch_get_target(batch):
+    """frirl_hip_batch_get_target: uint8 [E], the TD target every agent trains under (TARGET_SARSA while none is set)."""
+    import numpy as np
+    out = np.zeros(_batch_agents(batch), dtype=np.uint8)
+    check(lib().frirl_hip_batch_get_target(batch, out.ctypes.data), "frirl_hip_batch_get_target")
+    return out
+
+
 def batch_agent_report(batch):
     """frirl_hip_batch_agent_report on a library-owned batch: dict of host arrays [E] -- converged, episodes, rules (int32), ep_steps
     (int32) and ep_reward (float64) of the last finished episode: per agent what frirl_hip_batch_stats sums (E is its `agents`)."""
@@ -1545,7 +1610,7 @@ def select_plan(scores, parents, replace, eligible=None):
 
 def batch_clone(batch, src, inherit_rows=False):
     """frirl_hip_batch_clone on a library-owned batch: agent e becomes a copy of agent src[e] (host sequence [E]); with inherit_rows
-    the clones also take their sources' hyper-parameter and exploration rows.  Returns the number of agents cloned."""
+    the clones also take their sources' hyper-parameter, exploration and target rows.  Returns the number of agents cloned."""
     import numpy as np
     s = np.ascontiguousarray(src, dtype=np.int32)
     assert s.shape == (_batch_agents(batch),)
@@ -1963,18 +2028,18 @@ class Convergence:
                                                  _stream(stream)), "frirl_hip_convergence_update")
 
 
-def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None, rows=None, explore=None):
+def train(problem, agent, envs, max_episodes=1000, check_every=50, on_episode=None, persistent=True, persistent_max_rules=256, lanes=None, rows=None, explore=None, target=None):
     """Batched construct run: frirl_sequential_run's loop (reference frirl_sequential_run.c:55-165) for E agents
     at once.  Episodes run until every environment's rule base is "considered complete" or max_episodes-1 episodes
     have run (:51,59).  Converged environments are masked out of later episodes.  Returns the Convergence object.
     rows (an HparamRows): only the persistent learner takes per-agent hyper-parameters, so the run goes through train_persistent
-    (on_episode is not called) or raises FrirlHipError where it does not cover the shape.  explore (an ExploreRows): likewise."""
+    (on_episode is not called) or raises FrirlHipError where it does not cover the shape.  explore (an ExploreRows), target (a TargetRows): likewise."""
     import torch
-    if rows is not None or explore is not None:
+    if rows is not None or explore is not None or target is not None:
         if not learn_supported(problem, agent):
-            raise FrirlHipError("frirl_amd.train: rows= / explore= need the persistent learner (learn_supported), which does not cover this shape; "
-                                "the per-episode kernels take no per-agent hyper-parameters or exploration")
-        return train_persistent(problem, agent, envs, max_episodes=max_episodes, rows=rows, explore=explore).conv
+            raise FrirlHipError("frirl_amd.train: rows= / explore= / target= need the persistent learner (learn_supported), which does not cover this shape; "
+                                "the per-episode kernels take no per-agent hyper-parameters, exploration or TD target")
+        return train_persistent(problem, agent, envs, max_episodes=max_episodes, rows=rows, explore=explore, target=target).conv
     conv = Convergence(problem, problem.rb.device)
     max_steps = agent.desc.max_steps
     if lanes is None:           # lane-group kernel where it is the faster form (many agents / small rule bases)
@@ -2027,14 +2092,15 @@ class LearnRun:
         self.conv, self.steps_total, self.work, self.launches = conv, steps_total, work, launches
 
 
-def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None, explore=None):
+def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None, explore=None, target=None):
     """The construct loop of frirl_sequential_run for E agents through frirl_hip_learn_train: every agent runs its episodes
     back to back on the device; after each launch (the work of `budget` steps of a mean agent) the agents that are still
     learning are compacted and launched again until none is left -- the launch plan, the queue and the compaction are the
     library's (csrc/learn.hip), the host reads two counters per launch.  on_chunk(launch index, live agent ids, conv) is
     called after every launch (the place for the per-chunk reward statistics).  rows: an HparamRows (frirl_hip_learn_train_rows):
     agent e learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_learn_train_explore): agent e
-    picks at its own epsilon, annealed over its own horizon.  Returns a LearnRun."""
+    picks at its own epsilon, annealed over its own horizon.  target: a TargetRows (frirl_hip_learn_train_target): agent e learns
+    towards Q(s', a') or Q(s', g).  Returns a LearnRun."""
     import torch
     dev_ = problem.rb.device
     conv = Convergence(problem, dev_)
@@ -2059,7 +2125,11 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     cb = LEARN_CHUNK_FN(chunk) if on_chunk is not None else C.cast(None, LEARN_CHUNK_FN)
     launches = C.c_int32(0)
     refused = conv.full.view(torch.uint8)
-    if explore is not None:
+    if target is not None:
+        check(lib().frirl_hip_learn_train_target(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
+                                                 _rows(target, problem.E), C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total),
+                                                 _ptr(refused), _ptr(ws), ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_target")
+    elif explore is not None:
         check(lib().frirl_hip_learn_train_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
                                                   C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws),
                                                   ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_explore")

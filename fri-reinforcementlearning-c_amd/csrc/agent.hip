@@ -9,7 +9,7 @@ using namespace frirl_host;
 #define FRIRL_AGENT_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
 #define M(N) void frirl_agent_launch_##N(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
                                          const frirl_hip_envs *ev, const frirl_hip_agent_io &io, const int32_t *teacher, const frirl_hip_hparam_rows *rows, \
-                                         const frirl_hip_explore_rows *explore, hipStream_t s);
+                                         const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, hipStream_t s);
 FRIRL_AGENT_NANT_CASES(M)
 #undef M
 
@@ -40,12 +40,12 @@ static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases
 
 static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
                       const frirl_hip_agent_io *io, const int32_t *teacher, void *stream, bool begin, const char *who, const frirl_hip_hparam_rows *rows = nullptr,
-                      const frirl_hip_explore_rows *explore = nullptr)
+                      const frirl_hip_explore_rows *explore = nullptr, const frirl_hip_target_rows *target = nullptr)
 {
     int rc = check_agent_call(t, b, agent, envs, io, begin, who);
     if (rc) return rc;
     switch (t->nant) {
-#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, teacher, rows, explore, as_stream(stream)); break;
+#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, teacher, rows, explore, target, as_stream(stream)); break;
         FRIRL_AGENT_NANT_CASES(M)
 #undef M
     }
@@ -104,4 +104,14 @@ extern "C" int frirl_hip_agent_observe_explore(const frirl_hip_tables *t, const 
                                                void *stream)
 {
     return agent_call(t, b, agent, envs, io, teacher, stream, false, "frirl_hip_agent_observe_explore", rows, explore);
+}
+
+// per-agent TD target (frirl_hip_target_rows): row e learns towards Q(s', a') or Q(s', g); NULL target = the _explore call.  No _begin_target:
+// begin performs no update
+extern "C" int frirl_hip_agent_observe_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                              const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                                              const frirl_hip_agent_io *io, const int32_t *teacher, void *stream)
+{
+    if (!target) return frirl_hip_agent_observe_explore(t, b, agent, rows, explore, envs, io, teacher, stream);
+    return agent_call(t, b, agent, envs, io, teacher, stream, false, "frirl_hip_agent_observe_target", rows, explore, target);
 }

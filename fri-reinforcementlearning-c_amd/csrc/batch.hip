@@ -43,6 +43,9 @@ struct frirl_hip_batch {
     int32_t *d_ex_h;             // [E] ... and horizons
     frirl_hip_explore_rows ex;   // the device columns that are set, and horizon_all
     bool ex_set;
+    uint8_t *d_tq;               // [E] per-agent TD target of frirl_hip_batch_set_target (allocated on first use)
+    frirl_hip_target_rows tq;    // the device column if one is set, and target_all
+    bool tq_set;                 // a target other than SARSA for everybody is set
     std::vector<int32_t> h_i;
     std::vector<double> h_d;
 };
@@ -121,7 +124,7 @@ extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
     if (b->s) (void)hipStreamSynchronize(b->s);
     void *ptrs[] = {b->d_u, b->d_ve, b->d_rb, b->d_rant, b->d_grid, b->d_ave, b->d_states, b->d_q_ant, b->d_ep_reward, b->d_start, b->d_prev_reward,
                     b->d_prev_rconc, b->d_tmp, b->d_nrules, b->d_fus, b->d_done, b->d_ep_steps, b->d_status, b->d_episode, b->d_prev_nrules,
-                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h};
+                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h, b->d_tq};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -189,8 +192,12 @@ static int refuse_rows(const frirl_hip_batch *b, const char *who)
         set_error("%s: per-agent exploration is set (frirl_hip_batch_set_exploration) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
         return FRIRL_HIP_EINVAL;
     }
-    if (!b->hp_set) return FRIRL_HIP_OK;
-    set_error("%s: per-agent hyper-parameters are set (frirl_hip_batch_set_hparams) and this call does not honour them: use frirl_hip_batch_train, or clear them", who);
+    if (b->hp_set) {
+        set_error("%s: per-agent hyper-parameters are set (frirl_hip_batch_set_hparams) and this call does not honour them: use frirl_hip_batch_train, or clear them", who);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (!b->tq_set) return FRIRL_HIP_OK;
+    set_error("%s: a per-agent TD target is set (frirl_hip_batch_set_target) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
     return FRIRL_HIP_EINVAL;
 }
 
@@ -271,7 +278,10 @@ static int batch_train_persistent(frirl_hip_batch *b, int32_t max_episodes, int3
     int32_t launches = 0;
     frirl_hip_agent exploring = b->agent;
     exploring.no_random = 0;                // exploration rows ask for exploration, whatever the batch's own flag (which every other call keeps reading)
-    int rc = b->ex_set ? frirl_hip_learn_train_explore(&b->t, &b->rb, &exploring, b->hp_set ? &b->hp : nullptr, &b->ex, &b->envs, &b->conv, 512, max_episodes + before,
+    int rc = b->tq_set ? frirl_hip_learn_train_target(&b->t, &b->rb, b->ex_set ? &exploring : &b->agent, b->hp_set ? &b->hp : nullptr, b->ex_set ? &b->ex : nullptr, &b->tq,
+                                                      &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr, b->d_learn_ws, b->learn_ws_bytes,
+                                                      &launches, nullptr, nullptr, b->s)
+           : b->ex_set ? frirl_hip_learn_train_explore(&b->t, &b->rb, &exploring, b->hp_set ? &b->hp : nullptr, &b->ex, &b->envs, &b->conv, 512, max_episodes + before,
                                                        nullptr, b->d_steps_total, nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
            : b->hp_set ? frirl_hip_learn_train_rows(&b->t, &b->rb, &b->agent, &b->hp, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total,
                                                     nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
@@ -465,6 +475,63 @@ extern "C" int frirl_hip_batch_set_exploration(frirl_hip_batch *b, const frirl_h
     b->ex.horizon = host_rows->horizon ? b->d_ex_h : nullptr;
     b->ex.horizon_all = host_rows->horizon_all;
     b->ex_set = true;
+    return FRIRL_HIP_OK;
+}
+
+// what a valid per-agent TD target is (include/frirl_hip.h): host column [E], no device
+static int target_check(const char *who, const frirl_hip_target_rows &x, int E)
+{
+    if (x.reserved != 0) { set_error("%s: reserved is %d, not 0", who, x.reserved); return FRIRL_HIP_EINVAL; }
+    if (x.target_all != FRIRL_HIP_TARGET_SARSA && x.target_all != FRIRL_HIP_TARGET_Q) { set_error("%s: target_all %d is neither 0 (SARSA) nor 1 (Q)", who, x.target_all); return FRIRL_HIP_EINVAL; }
+    for (int e = 0; e < E; e++)
+        if (x.target && x.target[e] > FRIRL_HIP_TARGET_Q) { set_error("%s: agent %d: target %d is neither 0 (SARSA) nor 1 (Q)", who, e, (int)x.target[e]); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_target_rows_check(const frirl_hip_target_rows *host_rows, int32_t E)
+{
+    if (E < 1) { set_error("frirl_hip_target_rows_check: E=%d", E); return FRIRL_HIP_EINVAL; }
+    return host_rows ? target_check("frirl_hip_target_rows_check", *host_rows, E) : FRIRL_HIP_OK;
+}
+
+// Per-agent TD target for frirl_hip_batch_train (include/frirl_hip.h): validated on the host, then copied.
+extern "C" int frirl_hip_batch_set_target(frirl_hip_batch *b, const uint8_t *host_target, int32_t target_all)
+{
+    static const char *who = "frirl_hip_batch_set_target";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (!host_target && target_all == FRIRL_HIP_TARGET_SARSA) {                                // clear
+        b->tq = frirl_hip_target_rows{};
+        b->tq_set = false;
+        return FRIRL_HIP_OK;
+    }
+    if (!b->d_uidx || !frirl_hip_learn_supported(b->nant, b->U, b->agent.A, b->agent.p, b->agent.env_kind)) {
+        set_error("%s: only the persistent learner takes a per-agent TD target, and it does not cover this batch (frirl_hip_learn_supported: nant=%d U=%d A=%d p=%d; "
+                  "index mirror: %s)", who, b->nant, b->U, b->agent.A, b->agent.p, b->d_uidx ? "yes" : "no");
+        return FRIRL_HIP_EINVAL;
+    }
+    const int E = b->E;
+    frirl_hip_target_rows host = {};
+    host.target = host_target; host.target_all = target_all;
+    if (target_check(who, host, E)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    if (host_target && !b->d_tq && !dalloc(&b->d_tq, (size_t)E)) { set_error("%s: HIP allocation failed: %s", who, hipGetErrorString(hipGetLastError())); return FRIRL_HIP_ELAUNCH; }
+    BCHK(hipStreamSynchronize(b->s), "target sync");                    // nothing in flight reads the column being replaced
+    if (host_target) BCHK(hipMemcpy(b->d_tq, host_target, sizeof(uint8_t) * E, hipMemcpyHostToDevice), "target upload");
+    b->tq = frirl_hip_target_rows{};
+    b->tq.target = host_target ? b->d_tq : nullptr;
+    b->tq.target_all = target_all;
+    b->tq_set = true;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_get_target(frirl_hip_batch *b, uint8_t *host_target)
+{
+    static const char *who = "frirl_hip_batch_get_target";
+    if (!b || !host_target) { set_error("%s: NULL batch or host_target", who); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    BCHK(hipStreamSynchronize(b->s), "target sync");
+    if (b->tq.target) BCHK(hipMemcpy(host_target, b->tq.target, sizeof(uint8_t) * (size_t)b->E, hipMemcpyDeviceToHost), "target download");
+    else std::fill_n(host_target, b->E, (uint8_t)b->tq.target_all);
     return FRIRL_HIP_OK;
 }
 
@@ -825,7 +892,7 @@ extern "C" int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_
 namespace frirl {
 // inherit_rows: every set column takes the source's value for the cloned agents; in place, since a source is no destination
 __global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ status, int E, double *d0, double *d1, double *d2, double *d3,
-                                    double *d4, double *d5, int32_t *i0, int32_t *i1)
+                                    double *d4, double *d5, int32_t *i0, int32_t *i1, uint8_t *b0)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E || status[e] != FRIRL_HIP_CLONE_CLONED) return;
@@ -835,6 +902,7 @@ __global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32
     for (int c = 0; c < 6; c++) if (d[c]) d[c][e] = d[c][s];
     if (i0) i0[e] = i0[s];
     if (i1) i1[e] = i1[s];
+    if (b0) b0[e] = b0[s];
 }
 }  // namespace frirl
 
@@ -856,12 +924,12 @@ static int batch_clone_run(const char *who, frirl_hip_batch *b, const int32_t *s
     // no image of a rule base outlives a call (d_lanes_ws and d_learn_ws are imported from rb / uidx at the start of every call that
     // uses them), so there is nothing to invalidate beside the arrays the clone itself rewrites
     if (he == hipSuccess) rc = frirl_hip_clone_agents(&b->rb, b->nant, &b->envs, &b->conv, b->d_weights, d_src, d_status, b->s);
-    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set)) {
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set || b->tq_set)) {
         const frirl_hip_hparam_rows &h = b->hp;
         hipLaunchKernelGGL(frirl::inherit_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, b->s, d_src, d_status, E, const_cast<double *>(h.alpha),
                            const_cast<double *>(h.gamma), const_cast<double *>(h.qdiff_pos_boundary), const_cast<double *>(h.qdiff_neg_boundary),
                            const_cast<double *>(h.weight_significant), const_cast<double *>(b->ex.epsilon), const_cast<int32_t *>(h.skip_rules),
-                           const_cast<int32_t *>(b->ex.horizon));
+                           const_cast<int32_t *>(b->ex.horizon), const_cast<uint8_t *>(b->tq.target));
     }
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(nr.data(), b->d_nrules, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);

@@ -18,10 +18,12 @@ struct NoIo {};
 // ... plus the teacher's actions of frirl_hip_agent_begin_taught / _observe_taught: [E] action indices, or NULL (the untaught calls)
 // ... and the per-agent hyper-parameters of frirl_hip_agent_begin_rows / _observe_rows: columns [E] or NULL (all NULL: the calls without rows)
 // ... and the per-agent exploration of frirl_hip_agent_begin_explore / _observe_explore: columns [E] or NULL (agent->epsilon, horizon_all)
+// ... and the per-agent TD target of frirl_hip_agent_observe_target: column [E] or NULL (target_all; all zero: SARSA, the _explore call)
 struct ExtIo : frirl_hip_agent_io {
     const int32_t *teacher;
     frirl_hip_hparam_rows rows;
     frirl_hip_explore_rows ex;
+    frirl_hip_target_rows tq;
 };
 template <bool EXT>
 using IoArg = std::conditional_t<EXT, ExtIo, NoIo>;
@@ -355,6 +357,9 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         else chosen = e_greedy(ag, ap, (uint32_t)e, ev.episode ? (uint32_t)ev.episode[e] : 0u, (uint32_t)ev.ep_steps[e] + 1u);
         if constexpr (EXT) chosen = taught_action(io, e, ag.A, chosen);                               // :127-151: Q(s', a_teacher) below
         gs.best = chosen;
+        // EXT under FRIRL_HIP_TARGET_Q (frirl_hip_target_rows): the update goes towards Q(s', g) of the greedy action `ap` the pick started
+        // from, whatever the pick or the teacher chose; the episode goes on from (s', chosen) all the same
+        if constexpr (EXT) { if ((io.tq.target ? (int)io.tq.target[e] : io.tq.target_all) == FRIRL_HIP_TARGET_Q) gs.best = ap; }
         sh.cur_q_ant[NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + chosen];                  // :151
         sh.ve2[NS] = gs.ave[chosen];
         if constexpr (EXT) {
@@ -363,7 +368,7 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         }
     }
     __syncthreads();
-    const double qp = gs.actconc[gs.best];     // Q(s',a') of the chosen action == FIVE_vag_concl(cur_q_ant), frirl_update_sarsa.c:356
+    const double qp = gs.actconc[gs.best];     // Q(s',a') of the chosen action == FIVE_vag_concl(cur_q_ant), frirl_update_sarsa.c:356 (EXT, target Q: Q(s', g))
     double *rant_e = ev.rant ? ev.rant + (size_t)e * NANT * maxR : nullptr;
     int st = FRIRL_HIP_UPD_INACTIVE;
     if (!ag.evaluate)                                                                                 // :155 (reduction_state == 0)

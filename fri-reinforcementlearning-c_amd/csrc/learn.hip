@@ -1,5 +1,5 @@
 // learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, instantiated in learn_i0 .. i4.hip and, with per-agent
-// hyper-parameter rows, learn_r0 .. r4.hip, with per-agent exploration too, learn_x0 .. x4.hip).
+// hyper-parameter rows, learn_r0 .. r4.hip, with per-agent exploration too, learn_x0 .. x4.hip, with a per-agent TD target as well, learn_q0 .. q4.hip).
 #include "learn_kernel.h"
 
 using namespace frirl_host;
@@ -107,9 +107,10 @@ extern "C" int frirl_hip_learn_timing(unsigned long long *out16)       // read a
 
 // One chunk of the construct loop for the agents in `live` (device array of nlive agent ids, or NULL = agents 0..nlive-1):
 // see include/frirl_hip.h.  rows != NULL: the ROWS kernels (learn_r*.hip), every agent under its own hyper-parameters; explore != NULL: the
-// EXPLORE kernels (learn_x*.hip), every agent at its own exploration rate as well.
+// EXPLORE kernels (learn_x*.hip), every agent at its own exploration rate as well; target != NULL: the TARGET kernels (learn_q*.hip), every
+// agent learning towards its own TD target, whichever of the other two structs are given.
 static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                     const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                     const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                      int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = frirl_check_episode(t, b, agent, envs, who);
@@ -133,6 +134,15 @@ static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip
 #endif
     int H = learn_slices(nlive);
     if (H < learn_min_slices(agent->A)) H = learn_min_slices(agent->A);
+    if (target) {                           // the TARGET kernels (learn_q*.hip) take all three structs
+        if (rows) la.hp = *rows;
+        if (explore) la.ex = *explore;
+        la.tq = *target;
+        if (t->nant == 3) frirl_learn_launch_mountaincar_target(H, t, b, agent, envs, conv, la, s);
+        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_target(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_target(H, t, b, agent, envs, conv, la, s); }
+        else { if (H <= 8) frirl_learn_launch_cartpole_lo_target(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_target(H, t, b, agent, envs, conv, la, s); }
+        return check_launch(who);
+    }
     if (explore) {                          // the EXPLORE kernels (learn_x*.hip) take both structs
         if (rows) la.hp = *rows;
         la.ex = *explore;
@@ -158,14 +168,14 @@ extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_ru
                                    const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
                                    int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 extern "C" int frirl_hip_learn_run_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
                                         const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                                         int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 // per-agent exploration (frirl_hip_explore_rows) beside the hyper-parameter rows: the EXPLORE kernels; explore NULL = the _rows call
@@ -174,7 +184,17 @@ extern "C" int frirl_hip_learn_run_explore(const frirl_hip_tables *t, const frir
                                            int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run_explore", t, b, agent, rows, explore, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_explore", t, b, agent, rows, explore, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+}
+
+// per-agent TD target (frirl_hip_target_rows) beside the other rows: the TARGET kernels; target NULL = the _explore call
+extern "C" int frirl_hip_learn_run_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                          const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                                          const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                                          int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!target) return frirl_hip_learn_run_explore(t, b, agent, rows, explore, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_target", t, b, agent, rows, explore, target, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 
@@ -268,7 +288,7 @@ extern "C" size_t frirl_hip_learn_train_workspace_bytes(int32_t nant, int32_t E,
 }
 
 static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                       const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                       const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
                        int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                        frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
@@ -296,7 +316,7 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
         if ((rc = frirl_hip_learn_plan(n, (int32_t)(mean_rules * (agent->A + 1) / 4), &H, &take)) != 0) return rc;
         if (H < learn_min_slices(agent->A)) { H = learn_min_slices(agent->A); const long fit = learn_lanes() / H; take = (int32_t)(n < fit ? n : fit); }
         hipLaunchKernelGGL(learn_queue_sort_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, take, b->nrules, shift, live);
-        if ((rc = learn_run(explore ? "frirl_hip_learn_run_explore" : rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, explore, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
+        if ((rc = learn_run(target ? "frirl_hip_learn_run_target" : explore ? "frirl_hip_learn_run_explore" : rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, explore, target, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
                             workspace, run_bytes, stream)) != 0) return rc;
         launches++;
         hipLaunchKernelGGL(learn_queue_next_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, n, take, live, conv->converged, conv->episodes, max_episodes, b->nrules,
@@ -317,7 +337,7 @@ extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_
                                      uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                      frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
 }
 
@@ -326,7 +346,7 @@ extern "C" int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl
                                           int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                           frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
 }
 
@@ -335,6 +355,18 @@ extern "C" int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const fr
                                              int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes,
                                              int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train_explore", t, b, agent, rows, explore, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+    return learn_train("frirl_hip_learn_train_explore", t, b, agent, rows, explore, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+                       workspace_bytes, launches_out, on_chunk, user, stream);
+}
+
+extern "C" int frirl_hip_learn_train_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                            const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                                            const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
+                                            uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user,
+                                            void *stream)
+{
+    if (!target) return frirl_hip_learn_train_explore(t, b, agent, rows, explore, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+                                                      launches_out, on_chunk, user, stream);
+    return learn_train("frirl_hip_learn_train_target", t, b, agent, rows, explore, target, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
                        workspace_bytes, launches_out, on_chunk, user, stream);
 }

@@ -64,6 +64,7 @@ struct LearnArgs {
     int max_episodes;            // the loop runs episodes 1 .. max_episodes - 1 (frirl_sequential_run.c:51,59)
     frirl_hip_hparam_rows hp;    // per-agent hyper-parameters [E], indexed by the agent id (ROWS kernels only; a NULL column = the launch's value)
     frirl_hip_explore_rows ex;   // per-agent exploration [E], indexed likewise (EXPLORE kernels only; NULL columns = ag.epsilon / ex.horizon_all)
+    frirl_hip_target_rows tq;    // per-agent TD target [E], indexed likewise (TARGET kernels only; NULL column = tq.target_all)
 #ifdef LEARN_TIMING
     unsigned long long *timing;  // [16] cycles per section of the step, summed over waves (tools/exp builds only)
 #endif
@@ -140,7 +141,11 @@ __global__ __launch_bounds__(256) void learn_export_kernel(const LearnArgs la, i
 // EXPLORE (with ROWS): the agent's epsilon and annealing horizon of frirl_hip_explore_rows are per agent too, loaded with the six and
 // consumed at once by the step's pick.  A parameter of its own: inside the ROWS kernels the two columns cost their users 4.4 % on
 // mountaincar with both columns NULL (profiles/r26_explore_rows.md), so ROWS alone compiles to the code without them.
-template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false>
+// TARGET (with EXPLORE): the agent's TD target of frirl_hip_target_rows is per agent as well, one byte loaded with the eight row values.
+// Under FRIRL_HIP_TARGET_Q the update goes towards the greedy conclusion `bv` of the fused sweep -- the maximum over both halves of the
+// action walk and over the lanes of the group -- whatever action the pick takes; the pick's own walk still runs for its weight sum.
+// A parameter of its own for the reason EXPLORE is one: EXPLORE alone compiles to the code without the byte.
+template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
 __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la, const frirl_hip_agent ag, const frirl_hip_envs ev,
                                                               const frirl_hip_convergence cv)
 {
@@ -503,6 +508,10 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
             [[maybe_unused]] double ex_eps = 0.0;
             [[maybe_unused]] int ex_h = 0;
             if constexpr (EXPLORE) { ex_eps = la.ex.epsilon ? la.ex.epsilon[erow] : ag.epsilon; ex_h = la.ex.horizon ? la.ex.horizon[erow] : la.ex.horizon_all; }
+            // ... and (TARGET) its TD target, one byte in the same clause: what the update of this step learns towards
+            static_assert(EXPLORE || !TARGET, "TARGET kernels take the exploration rows too");
+            [[maybe_unused]] int tq = FRIRL_HIP_TARGET_SARSA;
+            if constexpr (TARGET) tq = la.tq.target ? (int)la.tq.target[erow] : la.tq.target_all;
             if (begin) {
                 episode++;
                 int a0;                                                                                 // :78-82
@@ -536,7 +545,8 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                     double v;
                     unsigned hh;
                     action_conclusion(chosen, v, w0, hh);
-                    qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0;
+                    if constexpr (TARGET) { if (tq != FRIRL_HIP_TARGET_Q) qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0; }   // Q: Q(s', g) = bv stays, w0 is a''s
+                    else qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0;
                 }
                 thr = (hp_wsig * (1.0 - 4e-9)) * w0;                                      // (s', a') is the next pending point
                 const double qnow = (hit1 != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hit1 / H) * 64 + (hit1 % H)] : vs1 / ws1;   // Q(s,a), :357
@@ -746,7 +756,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
 }  // namespace frirl
 
 
-template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false>
+template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
 inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                          const frirl_hip_convergence *cv, frirl::LearnArgs la, hipStream_t s)
 {
@@ -763,33 +773,34 @@ inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     const size_t dyn = sizeof(double) * frirl::LR_WPB * EPW * NCOLD_;
     if (dyn > 40 * 1024) {                                                     // static (~24 KB) + dynamic beyond the 64 KB default
         static bool raised = false;                                            // per instantiation
-        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
+        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
     }
     hipLaunchKernelGGL((frirl::learn_import_kernel<N, BITS>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
     const int blocks = (la.tiles + frirl::LR_WPB - 1) / frirl::LR_WPB;
-    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
+    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
     hipLaunchKernelGGL((frirl::learn_export_kernel<N>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
 }
 
 
 // one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation file (learn_i*.hip) compiles a few kernels, so
 // that the build runs them in parallel
-template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false>
+template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
 inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                            const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s)
 {
-    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
 }
 
 // defined in learn_i0.hip (mountaincar), learn_i1.hip (acrobot, 1 .. 8 lanes per agent), learn_i2.hip (acrobot, 16 .. 64),
 // learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64); the _rows twins (ROWS = true, la.hp set) in learn_r0.hip .. learn_r4.hip,
-// the _explore ones (ROWS and EXPLORE, la.hp and la.ex set) in learn_x0.hip .. learn_x4.hip
+// the _explore ones (ROWS and EXPLORE, la.hp and la.ex set) in learn_x0.hip .. learn_x4.hip, the _target ones (ROWS, EXPLORE and TARGET,
+// la.tq set as well) in learn_q0.hip .. learn_q4.hip
 void frirl_learn_launch_cartpole_lo(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                     const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_cartpole_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
@@ -819,4 +830,14 @@ void frirl_learn_launch_mountaincar_explore(int H, const frirl_hip_tables *t, co
 void frirl_learn_launch_acrobot_lo_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
 void frirl_learn_launch_acrobot_hi_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_lo_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_cartpole_hi_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_mountaincar_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_lo_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
+                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+void frirl_learn_launch_acrobot_hi_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);

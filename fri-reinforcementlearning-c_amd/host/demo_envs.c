@@ -871,6 +871,109 @@ int frirl_demo_batch_run_explore(const char *env, int agents, int max_episodes, 
     return total;
 }
 
+/* ---- a TD target per agent: frirl_demo --agents N [--explore FILE] --target sarsa|q  or  --target-rows FILE ------------------------------
+ * FILE: one 0 (SARSA) or 1 (Q) per line; `#` starts a comment; blank lines are skipped.  *target = malloc'ed [*n]; err receives
+ * "line N: why" for the first malformed line, or why the file is unusable. */
+int frirl_demo_parse_target(const char *path, unsigned char **target, int *n_out, char *err, size_t err_len)
+{
+    char line[512];
+    int lineno = 0, n = 0, cap = 0;
+    unsigned char *ot = NULL;
+    FILE *fp = fopen(path, "r");
+    *target = NULL; *n_out = 0;
+    if (!fp) { snprintf(err, err_len, "cannot open %s", path); return -1; }
+    while (fgets(line, sizeof line, fp)) {
+        double v;
+        char tail[2], *hash = strchr(line, '#');
+        int got;
+        lineno++;
+        if (!strchr(line, '\n') && !feof(fp)) { snprintf(err, err_len, "line %d: longer than %d characters", lineno, (int)sizeof line - 2); goto bad; }
+        if (hash) *hash = '\0';
+        if (line[strspn(line, " \t\r\n")] == '\0') continue;
+        got = sscanf(line, "%lf %1s", &v, tail);
+        if (got != 1) { snprintf(err, err_len, "line %d: expected 1 value (target), found %s", lineno, got > 1 ? "more" : "fewer"); goto bad; }
+        if (!(v == 0.0 || v == 1.0)) { snprintf(err, err_len, "line %d: target %g is neither 0 (SARSA) nor 1 (Q)", lineno, v); goto bad; }
+        if (n == cap) {
+            unsigned char *gt;
+            cap = cap ? 2 * cap : 16;
+            gt = realloc(ot, (size_t)cap);
+            if (!gt) { snprintf(err, err_len, "out of memory"); goto bad; }
+            ot = gt;
+        }
+        ot[n++] = (unsigned char)v;
+    }
+    fclose(fp);
+    if (n == 0) { snprintf(err, err_len, "%s holds no target", path); free(ot); return -1; }
+    *target = ot; *n_out = n;
+    return 0;
+bad:
+    free(ot); fclose(fp);
+    return -1;
+}
+
+/* `agents` agents of a demo in one persistent-learner run, agent e learning towards target[e mod nt] (HOST [nt], the column of
+ * frirl_demo_parse_target; NULL: target_all for every agent) and -- eps != NULL -- exploring under pair e mod nx as in
+ * frirl_demo_batch_run_explore: frirl_hip_batch_set_target (+ _set_exploration) + frirl_hip_batch_train, then the `batch ENV:` report
+ * line with the target at its end and, with eps, one `explore ENV: line s ...` line per pair.  Returns the converged agents, or -1. */
+int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const unsigned char *target, int nt, int target_all, int verbose)
+{
+    int nant = 0, episodes = 0, rc, e, s, nq = 0;
+    frirl_hip_batch_desc d;
+    struct demo_desc_mem mm;
+    frirl_hip_batch *b;
+    frirl_hip_batch_stats_t st;
+    double *xe = malloc(sizeof(double) * 2 * (size_t)agents), *reward = xe ? xe + agents : NULL;
+    int32_t *xh = malloc(sizeof(int32_t) * 4 * (size_t)agents), *conv = xh ? xh + agents : NULL, *eps_run = xh ? conv + agents : NULL, *rules = xh ? eps_run + agents : NULL;
+    uint8_t *tq = malloc((size_t)(agents > 0 ? agents : 1));
+    if (!xe || !xh || !tq || agents < 1 || (eps && nx < 1) || (target && nt < 1)) return -1;
+    if (demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
+    if (eps) { d.agent.seed = seed; d.agent.env_id_base = id_base; }
+    b = frirl_hip_batch_create(&d);
+    if (!b) five_dropin_fatal("frirl_demo_batch_run_target(create)", FRIRL_HIP_ENODEV);
+    if (eps) {
+        frirl_hip_explore_rows ex;
+        for (e = 0; e < agents; e++) { xe[e] = eps[e % nx]; xh[e] = horizon[e % nx]; }
+        memset(&ex, 0, sizeof ex);
+        ex.epsilon = xe; ex.horizon = xh;
+        rc = frirl_hip_batch_set_exploration(b, &ex);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_target(explore)", rc);
+    }
+    for (e = 0; e < agents; e++) { tq[e] = target ? target[e % nt] : (uint8_t)target_all; nq += tq[e] == FRIRL_HIP_TARGET_Q; }
+    rc = frirl_hip_batch_set_target(b, target ? tq : NULL, target ? FRIRL_HIP_TARGET_SARSA : target_all);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(set)", rc);
+    rc = frirl_hip_batch_train(b, max_episodes, &episodes);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(train)", rc);
+    rc = frirl_hip_batch_stats(b, &st);
+    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(stats)", rc);
+    if (verbose) {
+        printf("batch %s: agents %lld episodes %d converged %lld env-steps %lld mean-rules %.3f mean-reward %.6f (min %.6f max %.6f) target ", env,
+               (long long)st.agents, episodes, (long long)st.converged, (long long)st.total_env_steps, st.rules_sum / st.agents,
+               st.reward_sum / st.agents, st.reward_min, st.reward_max);
+        if (target) printf("rows (%d of %d agents q)\n", nq, agents);
+        else printf("%s\n", target_all == FRIRL_HIP_TARGET_Q ? "q" : "sarsa");
+    }
+    if (eps && verbose) {
+        rc = frirl_hip_batch_agent_report(b, conv, eps_run, rules, NULL, reward);
+        if (rc) five_dropin_fatal("frirl_demo_batch_run_target(report)", rc);
+        for (s = 0; s < nx && s < agents; s++) {
+            long long cnt = 0, nconv = 0, ep_sum = 0, rule_sum = 0;
+            int ep_max = 0;
+            double rew_sum = 0.0;
+            for (e = s; e < agents; e += nx) {
+                cnt++; nconv += conv[e] != 0; ep_sum += eps_run[e]; rule_sum += rules[e]; rew_sum += reward[e];
+                if (eps_run[e] > ep_max) ep_max = eps_run[e];
+            }
+            printf("explore %s: line %d agents %lld converged %lld mean-episodes %.3f max-episodes %d mean-rules %.3f mean-reward %.6f\n", env, s, cnt, nconv,
+                   (double)ep_sum / cnt, ep_max, (double)rule_sum / cnt, rew_sum / cnt);
+        }
+    }
+    frirl_hip_batch_destroy(b);
+    demo_desc_free(&mm);
+    free(xe); free(xh); free(tq);
+    return (int)st.converged;
+}
+
 /* ---- selection inside a population: frirl_demo --agents N --select G --select-episodes M --select-parents P --select-replace K ----------
  * G generations of frirl_hip_batch_train(M + 1) followed by frirl_hip_batch_select (every agent evaluated from `rows` start states, as
  * --evaluate maps them; the `replace` worst become copies of the `parents` best, with `inherit` also of their rows), one `select ENV:

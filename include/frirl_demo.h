@@ -94,6 +94,18 @@ int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, i
                                 int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
                                 unsigned long long id_base, const double *sets, int nsets, int verbose);
 
+/* A TD target per agent in one run (frirl_demo --agents N [--explore FILE] --target sarsa|q, or --target-rows FILE).
+ * frirl_demo_parse_target reads FILE: one 0 (FRIRL_HIP_TARGET_SARSA) or 1 (FRIRL_HIP_TARGET_Q) per line, `#` starts a comment, blank
+ * lines are skipped; *target = malloc'ed [*n] (the caller frees it).  -1 with err = "line N: why" for the first malformed line (not one
+ * number, a value other than 0 or 1), or why the file cannot be used.  No device is touched.
+ * frirl_demo_batch_run_target: agent e learns towards target[e mod nt] (NULL: target_all for every agent) and, with eps != NULL,
+ * explores under pair e mod nx on the stream of `seed` and id_base as in frirl_demo_batch_run_explore -- one run of the persistent
+ * learner (frirl_hip_batch_set_target, frirl_hip_batch_train), then the `batch ENV: ...` report line ending in `target sarsa`, `target q`
+ * or `target rows (K of N agents q)`, followed with eps by the `explore ENV: line s ...` lines.  Returns the converged agents, or -1. */
+int frirl_demo_parse_target(const char *path, unsigned char **target, int *n, char *err, size_t err_len);
+int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const unsigned char *target, int nt, int target_all, int verbose);
+
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */
 /* many agents WITH the reference's rule-base exchange (frirl_omp_run: chunks of 9 episodes, merge_rb in both directions after each,

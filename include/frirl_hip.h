@@ -287,6 +287,34 @@ double frirl_hip_explore_epsilon(double eps, int32_t horizon, uint32_t episode);
  * for E < 1 or a NULL agent, whose epsilon is checked when the column is NULL; NULL host_rows is valid). */
 int frirl_hip_explore_rows_check(const frirl_hip_explore_rows *host_rows, int32_t E, const frirl_hip_agent *agent);
 
+/* Per-agent TD target: what agent e's update learns towards.  At a learning step, let g be the greedy action at s': the first maximum
+ * of the fused sweep, the index the pick starts from.  Let a' be the action taken: the epsilon-greedy pick, or the teacher's action.
+ *     FRIRL_HIP_TARGET_SARSA (0)   qp = Q(s', a'), the reference's target and the behaviour of every call without this struct
+ *     FRIRL_HIP_TARGET_Q     (1)   qp = Q(s', g): the greedy conclusion exactly as the sweep formed it, exact-hit consequent or Shepard
+ *                                  quotient -- the same value SARSA uses on a step where a' == g
+ * Nothing else moves: Q(s, a) of the pending point, qdiff = alpha * (reward + gamma * qp - qnow), the insertion test, the snap, the
+ * append, the spread and the sticky flag stay as they are; the next pending point is still (s', a'), and in the learner the weight
+ * bound of the next step is still formed from the weight sum of a'.  agent->evaluate skips the update as before, and the first action
+ * of an episode has no update.  This is the reference's frirl_update_sarsa called with cur_q_ant = (q(s'), value of action g) while the
+ * episode goes on from (q(s'), value of a').  Without exploration and without a teacher a' == g at every step and the two targets give
+ * the same bits.
+ * The column is [dev] [E], indexed as the columns of frirl_hip_hparam_rows (the agent's index in the batch, never the launch slot).
+ * A NULL struct pointer = SARSA for everybody.  Read by frirl_hip_learn_run_target / _train_target and frirl_hip_agent_observe_target
+ * only.  Not built: expected SARSA (it needs an update that takes a value instead of a point); a target in the fused demo step
+ * (frirl_hip_episode_begin / _step / _steps), frirl_hip_update_sarsa, the lane groups and frirl_hip_episode_run; a target in
+ * demonstration replay (its sweep forms two conclusions, not A, so Q(s', g) is not there); a target in merged training and
+ * frirl_hip_multi_*. */
+#define FRIRL_HIP_TARGET_SARSA 0
+#define FRIRL_HIP_TARGET_Q     1
+typedef struct frirl_hip_target_rows {
+    const uint8_t *target;     /* [dev][E], indexed like the other rows (agent index in the batch, never the launch slot); NULL = target_all */
+    int32_t target_all;        /* 0 / 1 */
+    int32_t reserved;          /* 0 */
+} frirl_hip_target_rows;       /* 16 bytes; NULL struct pointer = SARSA for everybody */
+/* What a valid frirl_hip_target_rows with a HOST column [E] is (no device is touched): reserved 0, target_all 0 or 1, every target[e]
+ * 0 or 1.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with the agent named in frirl_hip_last_error (also for E < 1; NULL host_rows is valid). */
+int frirl_hip_target_rows_check(const frirl_hip_target_rows *host_rows, int32_t E);
+
 /* Test probe of the exploration stream, in the form every learning and roll-out kernel calls it.  For key tuple i the global id is
  * agent->env_id_base + env[i] and the word is the SplitMix64 output function of
  *     seed + 0x9E3779B97F4A7C15 * ((id << 32) | episode[i]) + 0xD1B54A32D192ED03 * ((step[i] << 8) | draw)      (mod 2^64);
@@ -903,6 +931,16 @@ int frirl_hip_agent_observe_explore(const frirl_hip_tables *t, const frirl_hip_r
                                     const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs,
                                     const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
 
+/* ---- per-agent TD target: _observe_explore with frirl_hip_target_rows (above) after `explore`.  Row e takes its action as in the
+ * _explore call -- its own pick, or the teacher's action -- and updates towards Q(s', a') or, under FRIRL_HIP_TARGET_Q, towards Q(s', g)
+ * of the greedy action its pick started from: a taught row under target Q takes the teacher's action and learns towards Q(s', g).
+ * target NULL is the _explore call, bit for bit; so is an all-zero column or target_all 0.  Values are not validated here
+ * (frirl_hip_target_rows_check does that for a host column).  Refusals as the taught pair, in its order.  There is no _begin_target:
+ * begin performs no update, so frirl_hip_agent_begin_explore starts the episodes of either target. */
+int frirl_hip_agent_observe_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                   const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target,
+                                   const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
+
 /* ---- one-launch replay of recorded demonstrations: every agent learns a log of (observation, action, reward, success) records in
  * ONE launch, one workgroup per agent looping over its records; no environment runs.  nant 2..8, A 1..32, any Shepard power.
  * Per record r of agent e (its log starts at record e * agent_stride of every array):
@@ -1170,6 +1208,22 @@ int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const frirl_hip_rul
                                   const frirl_hip_explore_rows *explore, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps,
                                   int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes,
                                   int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
+/* ... and with a per-agent TD target (frirl_hip_target_rows, above) after `explore`: agent e learns towards Q(s', a') or Q(s', g).
+ * Any of the three structs may be NULL; target == NULL calls the _explore entry point, anything else runs a fourth kernel family
+ * (TARGET, learn_q*.hip), which loads the agent's target byte together with its eight row values after the rule sweep -- a family of
+ * its own for the reason EXPLORE is one: nobody who does not ask for it pays for it (the byte costs this family's users 0.7 to 1.9 % over
+ * the _explore call on identical work, profiles/r28_target.md).  Same shapes, workspace sizes and refusals, in the
+ * same order.  With an all-zero column or target_all 0 the results are those of the _explore call, bit for bit; with every agent
+ * under FRIRL_HIP_TARGET_Q, agent->no_random == 1 and no rows they are those of the unsuffixed call. */
+int frirl_hip_learn_run_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                               const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                               const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
+                               int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream);
+int frirl_hip_learn_train_target(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                 const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                                 const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
+                                 uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk,
+                                 void *user, void *stream);
 
 /* Persistent form for SMALL rule bases (the demos' learning regime): one wave keeps its environment's rule base,
  * the tables and the episode state in LDS and runs up to nsteps consecutive steps without a global round trip per
@@ -1312,6 +1366,17 @@ int frirl_hip_hparam_rows_check(const frirl_hip_hparam_rows *host_rows, int32_t 
  * _train_merged, _merge_round and _teach return FRIRL_HIP_EINVAL naming themselves.  Evaluation, roll-outs, reductions, save / load
  * and the statistics are unaffected: they force greedy or read the batch's epsilon. */
 int frirl_hip_batch_set_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_rows);
+/* Per-agent TD target for frirl_hip_batch_train: host_target holds a HOST column [E] of FRIRL_HIP_TARGET_* values (NULL: target_all
+ * for every agent), validated as frirl_hip_target_rows_check does and copied; (NULL, FRIRL_HIP_TARGET_SARSA) clears the target.  A
+ * rejected call leaves the batch as it was; the shape restriction is that of frirl_hip_batch_set_hparams.  While a target is set
+ * frirl_hip_batch_train goes through frirl_hip_learn_train_target (with any hyper-parameter and exploration rows);
+ * frirl_hip_batch_episode, _train_merged, _merge_round and _teach return FRIRL_HIP_EINVAL naming themselves.  Evaluation, roll-outs,
+ * reductions, save / load and the statistics perform no update and are unaffected.  frirl_hip_batch_clone(inherit_rows != 0) gathers
+ * a set column like any other set column; with target_all alone there is no column to gather. */
+int frirl_hip_batch_set_target(frirl_hip_batch *b, const uint8_t *host_target /* HOST [E] or NULL */, int32_t target_all);
+/* The target a batch trains under, back on the host: host_target HOST [E] is filled with the set column, or with target_all (0 while
+ * none is set) for every agent. */
+int frirl_hip_batch_get_target(frirl_hip_batch *b, uint8_t *host_target /* HOST [E] out */);
 /* rule base of agent e: *R rules, rant HOST [>= *R][nant] (AoS), rconc HOST [>= *R] (pass NULL to query *R only) */
 int frirl_hip_batch_get_rulebase(frirl_hip_batch *b, int32_t e, int32_t *R, double *rant, double *rconc);
 /* Rule bases of all agents to / from one file.  The file is E records back to back, each exactly what
@@ -1428,9 +1493,9 @@ int frirl_hip_select_plan(const frirl_hip_rollout_score *scores /* HOST [E] */, 
                           int32_t parents, int32_t replace, int32_t *src /* HOST [E] out */, int32_t *rank /* HOST [N] out, or NULL */);
 /* frirl_hip_clone_agents on the batch's own arrays (index mirror, raw antecedents, sticky flag, spread state, the merge weights once
  * allocated, convergence state).  src is validated on the host first: an entry outside 0..E-1 or a chain (src[src[e]] != src[e])
- * returns FRIRL_HIP_EINVAL naming the agent and leaves the batch as it was.  Works while hyper-parameter or exploration rows are set:
+ * returns FRIRL_HIP_EINVAL naming the agent and leaves the batch as it was.  Works while hyper-parameter, exploration or target rows are set:
  * with inherit_rows == 0 a clone keeps its own row (it goes on from the winner's rule base under its own hyper-parameters); with
- * inherit_rows != 0 every SET column of both row sets gets col[e] = col[src[e]] for the cloned agents, unset columns stay unset.
+ * inherit_rows != 0 every SET column of the three row sets gets col[e] = col[src[e]] for the cloned agents, unset columns stay unset.
  * total_env_steps and the batch's agent are not touched; frirl_hip_batch_train continues afterwards as after frirl_hip_batch_teach.
  * *cloned (or NULL) = agents with status CLONED.  Synchronises. */
 int frirl_hip_batch_clone(frirl_hip_batch *b, const int32_t *src /* HOST [E] */, int inherit_rows, int32_t *cloned /* or NULL */);
