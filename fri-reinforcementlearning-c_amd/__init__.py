@@ -237,6 +237,23 @@ _lib = None
 _DP = C.POINTER(C.c_double)
 LEARN_CHUNK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32)      # frirl_hip_learn_chunk_fn
 
+# The entry points that come in levels: base (level 0), base_rows, base_explore, base_target take the first 0 .. 3 of the per-agent structs
+# between the agent and the rest of their arguments.
+_HEAD = [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc)]
+_ROW_STRUCTS = [HparamRowsDesc, ExploreRowsDesc, TargetRowsDesc]
+_SUFFIX = ("", "_rows", "_explore", "_target")
+_LEARN_RUN_TAIL = [C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                   C.c_void_p]
+_LEARN_TRAIN_TAIL = [C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                     C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]
+_AGENT_TAIL = [C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]                    # ..., stream
+_TAUGHT_TAIL = [C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]      # ..., teacher, stream
+
+
+def _levels(base, tail, levels=range(4)):
+    return {base + _SUFFIX[n]: (C.c_int, _HEAD + [C.POINTER(s) for s in _ROW_STRUCTS[:n]] + tail) for n in levels}
+
+
 # name -> (restype, argtypes); every symbol include/frirl_hip.h declares
 SIGNATURES = {
     "frirl_hip_version": (C.c_char_p, []),
@@ -320,30 +337,9 @@ SIGNATURES = {
     "frirl_hip_learn_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "frirl_hip_learn_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "frirl_hip_learn_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "frirl_hip_learn_run": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
-                                      C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    **_levels("frirl_hip_learn_run", _LEARN_RUN_TAIL),
     "frirl_hip_learn_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "frirl_hip_learn_train": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc),
-                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32),
-                                        LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
-    "frirl_hip_learn_run_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
-                                           C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]),
-    "frirl_hip_learn_train_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
-                                             C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                             C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
-    "frirl_hip_learn_run_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                              C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_size_t, C.c_void_p]),
-    "frirl_hip_learn_train_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                                C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_size_t, C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
-    "frirl_hip_learn_run_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                             C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "frirl_hip_learn_train_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                               C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), LEARN_CHUNK_FN, C.c_void_p, C.c_void_p]),
+    **_levels("frirl_hip_learn_train", _LEARN_TRAIN_TAIL),
     "five_hip_add_rule": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "frirl_hip_update_sarsa": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p,
@@ -353,23 +349,10 @@ SIGNATURES = {
     "frirl_hip_episode_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p]),
     "frirl_hip_episode_step": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_void_p]),
     "frirl_hip_episode_steps": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.c_int32, C.c_void_p]),
-    "frirl_hip_agent_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]),
-    "frirl_hip_agent_observe": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
-                                          C.c_void_p]),
-    "frirl_hip_agent_begin_taught": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
-                                               C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_observe_taught": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO),
-                                                 C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_begin_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
-                                             C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_observe_rows": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(EnvsDesc),
-                                               C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_begin_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                                C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_observe_explore": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                                  C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
-    "frirl_hip_agent_observe_target": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
-                                                 C.POINTER(TargetRowsDesc), C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]),
+    **_levels("frirl_hip_agent_begin", _AGENT_TAIL, [0]), "frirl_hip_agent_begin_taught": (C.c_int, _HEAD + _TAUGHT_TAIL),
+    **_levels("frirl_hip_agent_begin", _TAUGHT_TAIL, [1, 2]),              # begin performs no update: no _begin_target
+    **_levels("frirl_hip_agent_observe", _AGENT_TAIL, [0]), "frirl_hip_agent_observe_taught": (C.c_int, _HEAD + _TAUGHT_TAIL),
+    **_levels("frirl_hip_agent_observe", _TAUGHT_TAIL, [1, 2, 3]),
     "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
                                                 C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
@@ -1172,6 +1155,18 @@ def _rows(rows, E):
     return None if rows.desc is None else C.byref(rows.desc)
 
 
+def _level_entry(base, E, rows=None, explore=None, target=None, teacher=None):
+    """The entry point of the family `base` (SIGNATURES: _levels) for the per-agent structs given: the last one given picks base_rows,
+    base_explore or base_target, which take the structs before it as well (None = NULL); with none of them `base` itself or, with a
+    teacher, base_taught.  Returns (the function, its name for check(), the struct arguments that follow the agent, the teacher
+    argument that precedes the stream in the agent calls: nothing for `base` itself, which has none)."""
+    level = 3 if target is not None else 2 if explore is not None else 1 if rows is not None else 0
+    name = base + (_SUFFIX[level] if level or teacher is None else "_taught")
+    structs = [_rows(r, E) for r in (rows, explore, target)[:level]]
+    taught = [] if name == base else [None if teacher is None else _teacher(teacher, E)]
+    return getattr(lib(), name), name, structs, taught
+
+
 class ExploreRows:
     """Per-agent exploration (struct frirl_hip_explore_rows): agent e of a batch of E picks at epsilon[e], falling linearly to zero
     over horizon[e] episodes (0 = constant; explore_epsilon gives the rate of an episode).  epsilon (float64) and horizon (int32) are
@@ -1313,20 +1308,8 @@ def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None
     (frirl_hip_agent_begin_rows; the begin call reads no learning hyper-parameter).  explore: an ExploreRows
     (frirl_hip_agent_begin_explore): row e picks at its own rate for the episode it starts.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, reset=reset)
-    if explore is not None:
-        check(lib().frirl_hip_agent_begin_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
-                                                  C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
-              "frirl_hip_agent_begin_explore")
-    elif rows is not None:
-        check(lib().frirl_hip_agent_begin_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
-                                               C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
-              "frirl_hip_agent_begin_rows")
-    elif teacher is None:
-        check(lib().frirl_hip_agent_begin(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
-                                          _stream(stream)), "frirl_hip_agent_begin")
-    else:
-        check(lib().frirl_hip_agent_begin_taught(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc),
-                                                 C.byref(io), _teacher(teacher, problem.E), _stream(stream)), "frirl_hip_agent_begin_taught")
+    fn, name, structs, taught = _level_entry("frirl_hip_agent_begin", problem.E, rows, explore, teacher=teacher)
+    check(fn(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), *structs, C.byref(envs.desc), C.byref(io), *taught, _stream(stream)), name)
     return action, action_idx
 
 
@@ -1340,24 +1323,8 @@ def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream
     its own rate in its current episode.  target: a TargetRows (frirl_hip_agent_observe_target): row e learns towards Q(s', a') or
     Q(s', g); a taught row under TARGET_Q takes the teacher's action and learns towards Q(s', g).  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    if target is not None:
-        check(lib().frirl_hip_agent_observe_target(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
-                                                   _rows(target, problem.E), C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E),
-                                                   _stream(stream)), "frirl_hip_agent_observe_target")
-    elif explore is not None:
-        check(lib().frirl_hip_agent_observe_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
-                                                    C.byref(envs.desc), C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
-              "frirl_hip_agent_observe_explore")
-    elif rows is not None:
-        check(lib().frirl_hip_agent_observe_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
-                                                 C.byref(io), None if teacher is None else _teacher(teacher, problem.E), _stream(stream)),
-              "frirl_hip_agent_observe_rows")
-    elif teacher is None:
-        check(lib().frirl_hip_agent_observe(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(io),
-                                            _stream(stream)), "frirl_hip_agent_observe")
-    else:
-        check(lib().frirl_hip_agent_observe_taught(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc),
-                                                   C.byref(io), _teacher(teacher, problem.E), _stream(stream)), "frirl_hip_agent_observe_taught")
+    fn, name, structs, taught = _level_entry("frirl_hip_agent_observe", problem.E, rows, explore, target, teacher)
+    check(fn(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), *structs, C.byref(envs.desc), C.byref(io), *taught, _stream(stream)), name)
     return action, action_idx
 
 
@@ -2125,22 +2092,9 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     cb = LEARN_CHUNK_FN(chunk) if on_chunk is not None else C.cast(None, LEARN_CHUNK_FN)
     launches = C.c_int32(0)
     refused = conv.full.view(torch.uint8)
-    if target is not None:
-        check(lib().frirl_hip_learn_train_target(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
-                                                 _rows(target, problem.E), C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total),
-                                                 _ptr(refused), _ptr(ws), ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_target")
-    elif explore is not None:
-        check(lib().frirl_hip_learn_train_explore(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), _rows(explore, problem.E),
-                                                  C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws),
-                                                  ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_explore")
-    elif rows is not None:
-        check(lib().frirl_hip_learn_train_rows(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), _rows(rows, problem.E), C.byref(envs.desc),
-                                               C.byref(conv.desc), budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
-                                               C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train_rows")
-    else:
-        check(lib().frirl_hip_learn_train(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), C.byref(envs.desc), C.byref(conv.desc),
-                                          budget, max_episodes, _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8,
-                                          C.byref(launches), cb, None, _stream(stream)), "frirl_hip_learn_train")
+    fn, name, structs, _ = _level_entry("frirl_hip_learn_train", problem.E, rows, explore, target)
+    check(fn(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), *structs, C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes,
+             _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), name)
     if failure:
         raise failure[0]
     if conv.full_envs:

@@ -1,15 +1,14 @@
 // agent.hip -- frirl_episode with the caller's environment: frirl_hip_agent_begin / frirl_hip_agent_observe and their taught forms
 // (include/frirl_hip.h).
 // The kernels are the fused episode kernels of sarsa.hip with EXT = true (episode_kernel.h), instantiated per antecedent count in
-// agent_i<N>.hip.
-#include "device_common.h"
+// agent_i<N>.hip; agent_call packs their caller's-data argument (ext_io.h) for all of them.
+#include "ext_io.h"
 
 using namespace frirl_host;
 
 #define FRIRL_AGENT_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)
 #define M(N) void frirl_agent_launch_##N(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, \
-                                         const frirl_hip_envs *ev, const frirl_hip_agent_io &io, const int32_t *teacher, const frirl_hip_hparam_rows *rows, \
-                                         const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, hipStream_t s);
+                                         const frirl_hip_envs *ev, const frirl::ExtIo &io, hipStream_t s);
 FRIRL_AGENT_NANT_CASES(M)
 #undef M
 
@@ -44,8 +43,14 @@ static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, c
 {
     int rc = check_agent_call(t, b, agent, envs, io, begin, who);
     if (rc) return rc;
+    frirl::ExtIo x;
+    static_cast<frirl_hip_agent_io &>(x) = *io;
+    x.teacher = teacher;
+    x.rows = rows ? *rows : frirl_hip_hparam_rows{};
+    x.ex = explore ? *explore : frirl_hip_explore_rows{};
+    x.tq = target ? *target : frirl_hip_target_rows{};
     switch (t->nant) {
-#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, *io, teacher, rows, explore, target, as_stream(stream)); break;
+#define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, x, as_stream(stream)); break;
         FRIRL_AGENT_NANT_CASES(M)
 #undef M
     }

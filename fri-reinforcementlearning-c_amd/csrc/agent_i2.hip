@@ -2,15 +2,8 @@
 #include "episode_kernel.h"
 
 void frirl_agent_launch_2(bool begin, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                          const frirl_hip_agent_io &io, const int32_t *teacher, const frirl_hip_hparam_rows *rows,
-                          const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, hipStream_t s)
+                          const frirl::ExtIo &io, hipStream_t s)
 {
-    frirl::ExtIo x;
-    static_cast<frirl_hip_agent_io &>(x) = io;
-    x.teacher = teacher;
-    x.rows = rows ? *rows : frirl_hip_hparam_rows{};
-    x.ex = explore ? *explore : frirl_hip_explore_rows{};
-    x.tq = target ? *target : frirl_hip_target_rows{};
-    if (begin) frirl::launch_episode<2, true, true>(t, b, ag, ev, s, x);
-    else frirl::launch_episode<2, false, true>(t, b, ag, ev, s, x);
+    if (begin) frirl::launch_episode<2, true, true>(t, b, ag, ev, s, io);
+    else frirl::launch_episode<2, false, true>(t, b, ag, ev, s, io);
 }

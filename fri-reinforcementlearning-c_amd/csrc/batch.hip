@@ -278,15 +278,9 @@ static int batch_train_persistent(frirl_hip_batch *b, int32_t max_episodes, int3
     int32_t launches = 0;
     frirl_hip_agent exploring = b->agent;
     exploring.no_random = 0;                // exploration rows ask for exploration, whatever the batch's own flag (which every other call keeps reading)
-    int rc = b->tq_set ? frirl_hip_learn_train_target(&b->t, &b->rb, b->ex_set ? &exploring : &b->agent, b->hp_set ? &b->hp : nullptr, b->ex_set ? &b->ex : nullptr, &b->tq,
-                                                      &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr, b->d_learn_ws, b->learn_ws_bytes,
-                                                      &launches, nullptr, nullptr, b->s)
-           : b->ex_set ? frirl_hip_learn_train_explore(&b->t, &b->rb, &exploring, b->hp_set ? &b->hp : nullptr, &b->ex, &b->envs, &b->conv, 512, max_episodes + before,
-                                                       nullptr, b->d_steps_total, nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
-           : b->hp_set ? frirl_hip_learn_train_rows(&b->t, &b->rb, &b->agent, &b->hp, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total,
-                                                    nullptr, b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s)
-                       : frirl_hip_learn_train(&b->t, &b->rb, &b->agent, &b->envs, &b->conv, 512, max_episodes + before, nullptr, b->d_steps_total, nullptr,
-                                               b->d_learn_ws, b->learn_ws_bytes, &launches, nullptr, nullptr, b->s);
+    int rc = learn_train_structs(&b->t, &b->rb, b->ex_set ? &exploring : &b->agent, b->hp_set ? &b->hp : nullptr, b->ex_set ? &b->ex : nullptr,
+                                 b->tq_set ? &b->tq : nullptr, &b->envs, &b->conv, 512, max_episodes + before, b->d_steps_total, b->d_learn_ws, b->learn_ws_bytes,
+                                 &launches, b->s);
     if (rc) return rc;
     std::vector<int64_t> st(E);
     BCHK(hipMemcpy(st.data(), b->d_steps_total, sizeof(int64_t) * E, hipMemcpyDeviceToHost), "steps download");

@@ -3,30 +3,15 @@
 // Shared by sarsa.hip (the demo environments: the dynamics run on the device, picked by agent.env_kind) and agent_i<N>.hip
 // (EXT = true: the caller steps its own environment and hands the observation, reward and success flag to
 // frirl_hip_agent_observe; one translation unit per antecedent count so the build compiles them in parallel).  With EXT =
-// false the kernels are the demo kernels: the caller's-data argument is an empty struct and every EXT branch is compiled out.
+// false the kernels are the demo kernels: the caller's-data argument (ext_io.h; agent.hip packs it once per call) is an empty struct
+// and every EXT branch is compiled out.
 #pragma once
 
-#include <type_traits>
-
 #include "envs.h"
+#include "ext_io.h"
 #include "sweeps.h"
 
 namespace frirl {
-
-// the caller's step data (frirl_hip_agent_io) for EXT kernels, nothing for the demo kernels
-struct NoIo {};
-// ... plus the teacher's actions of frirl_hip_agent_begin_taught / _observe_taught: [E] action indices, or NULL (the untaught calls)
-// ... and the per-agent hyper-parameters of frirl_hip_agent_begin_rows / _observe_rows: columns [E] or NULL (all NULL: the calls without rows)
-// ... and the per-agent exploration of frirl_hip_agent_begin_explore / _observe_explore: columns [E] or NULL (agent->epsilon, horizon_all)
-// ... and the per-agent TD target of frirl_hip_agent_observe_target: column [E] or NULL (target_all; all zero: SARSA, the _explore call)
-struct ExtIo : frirl_hip_agent_io {
-    const int32_t *teacher;
-    frirl_hip_hparam_rows rows;
-    frirl_hip_explore_rows ex;
-    frirl_hip_target_rows tq;
-};
-template <bool EXT>
-using IoArg = std::conditional_t<EXT, ExtIo, NoIo>;
 
 // imitation (reference frirl_episode.c:58-79,127-151: keyaction replaces the epsilon-greedy action; key 32 = the agent chooses): row e
 // takes teacher[e] when it is an action index, and keeps `chosen` for any other value.  The exploration stream is counter-based, so

@@ -1,5 +1,5 @@
-// learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, instantiated in learn_i0 .. i4.hip and, with per-agent
-// hyper-parameter rows, learn_r0 .. r4.hip, with per-agent exploration too, learn_x0 .. x4.hip, with a per-agent TD target as well, learn_q0 .. q4.hip).
+// learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, one unit learn_<shape>_<level>.hip per entry of its launch
+// table: five shapes, and the levels 0 = plain, 1 = per-agent hyper-parameter rows, 2 = per-agent exploration too, 3 = a per-agent TD target as well).
 #include "learn_kernel.h"
 
 using namespace frirl_host;
@@ -105,10 +105,32 @@ extern "C" int frirl_hip_learn_timing(unsigned long long *out16)       // read a
 }
 #endif
 
+// The last struct given picks the level (learn_kernel.h): rows != NULL: the ROWS kernels, every agent under its own hyper-parameters;
+// explore != NULL: the EXPLORE kernels, every agent at its own exploration rate as well; target != NULL: the TARGET kernels, every agent
+// learning towards its own TD target, whichever of the other two structs are given.
+static int learn_level(const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target)
+{
+    return target ? 3 : explore ? 2 : rows ? 1 : 0;
+}
+
+// the entry points of a level, as messages name them
+static const struct { const char *run, *train; } LEARN_NAME[LEARN_NLEVELS] = {
+    {"frirl_hip_learn_run", "frirl_hip_learn_train"},
+    {"frirl_hip_learn_run_rows", "frirl_hip_learn_train_rows"},
+    {"frirl_hip_learn_run_explore", "frirl_hip_learn_train_explore"},
+    {"frirl_hip_learn_run_target", "frirl_hip_learn_train_target"},
+};
+
+// the launch table: one launcher per shape and level, built from the list that instantiates them (learn_kernel.h)
+#define LEARN_ENTRY(name, level) frirl_learn_launch<LEARN_##name, level>,
+#define X(name, ...) {FRIRL_LEARN_LEVELS(LEARN_ENTRY, name)},
+static const frirl_learn_launch_fn LEARN_LAUNCH[LEARN_NSHAPES][LEARN_NLEVELS] = {FRIRL_LEARN_SHAPES(X)};
+#undef X
+#undef LEARN_ENTRY
+static_assert(LEARN_acrobot_hi == LEARN_acrobot_lo + 1 && LEARN_cartpole_hi == LEARN_cartpole_lo + 1, "learn_run steps from a _lo entry to the _hi one after it");
+
 // One chunk of the construct loop for the agents in `live` (device array of nlive agent ids, or NULL = agents 0..nlive-1):
-// see include/frirl_hip.h.  rows != NULL: the ROWS kernels (learn_r*.hip), every agent under its own hyper-parameters; explore != NULL: the
-// EXPLORE kernels (learn_x*.hip), every agent at its own exploration rate as well; target != NULL: the TARGET kernels (learn_q*.hip), every
-// agent learning towards its own TD target, whichever of the other two structs are given.
+// see include/frirl_hip.h.
 static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
                      const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                      int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
@@ -134,33 +156,14 @@ static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip
 #endif
     int H = learn_slices(nlive);
     if (H < learn_min_slices(agent->A)) H = learn_min_slices(agent->A);
-    if (target) {                           // the TARGET kernels (learn_q*.hip) take all three structs
-        if (rows) la.hp = *rows;
-        if (explore) la.ex = *explore;
-        la.tq = *target;
-        if (t->nant == 3) frirl_learn_launch_mountaincar_target(H, t, b, agent, envs, conv, la, s);
-        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_target(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_target(H, t, b, agent, envs, conv, la, s); }
-        else { if (H <= 8) frirl_learn_launch_cartpole_lo_target(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_target(H, t, b, agent, envs, conv, la, s); }
-        return check_launch(who);
-    }
-    if (explore) {                          // the EXPLORE kernels (learn_x*.hip) take both structs
-        if (rows) la.hp = *rows;
-        la.ex = *explore;
-        if (t->nant == 3) frirl_learn_launch_mountaincar_explore(H, t, b, agent, envs, conv, la, s);
-        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_explore(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_explore(H, t, b, agent, envs, conv, la, s); }
-        else { if (H <= 8) frirl_learn_launch_cartpole_lo_explore(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_explore(H, t, b, agent, envs, conv, la, s); }
-        return check_launch(who);
-    }
-    if (rows) {
-        la.hp = *rows;
-        if (t->nant == 3) frirl_learn_launch_mountaincar_rows(H, t, b, agent, envs, conv, la, s);
-        else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo_rows(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi_rows(H, t, b, agent, envs, conv, la, s); }
-        else { if (H <= 8) frirl_learn_launch_cartpole_lo_rows(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi_rows(H, t, b, agent, envs, conv, la, s); }
-        return check_launch(who);
-    }
-    if (t->nant == 3) frirl_learn_launch_mountaincar(H, t, b, agent, envs, conv, la, s);
-    else if (agent->A == 3) { if (H <= 8) frirl_learn_launch_acrobot_lo(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_acrobot_hi(H, t, b, agent, envs, conv, la, s); }
-    else { if (H <= 8) frirl_learn_launch_cartpole_lo(H, t, b, agent, envs, conv, la, s); else frirl_learn_launch_cartpole_hi(H, t, b, agent, envs, conv, la, s); }
+    // A kernel reads only the structs its level enables (learn_kernel.h), so the copies below cost the lower levels nothing on the device.
+    if (rows) la.hp = *rows;
+    if (explore) la.ex = *explore;
+    if (target) la.tq = *target;
+    int shape = t->nant == 3 ? LEARN_mountaincar : agent->A == 3 ? LEARN_acrobot_lo : LEARN_cartpole_lo;
+    if (H > LEARN_SHAPE[shape].HHI) shape++;                // the _hi entry follows its _lo one
+    if (H < LEARN_SHAPE[shape].HLO || H > LEARN_SHAPE[shape].HHI) { set_error("%s: no kernel for %d lanes per agent", who, H); return FRIRL_HIP_EINVAL; }
+    LEARN_LAUNCH[shape][learn_level(rows, explore, target)](H, t, b, agent, envs, conv, la, s);
     return check_launch(who);
 }
 
@@ -316,7 +319,7 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
         if ((rc = frirl_hip_learn_plan(n, (int32_t)(mean_rules * (agent->A + 1) / 4), &H, &take)) != 0) return rc;
         if (H < learn_min_slices(agent->A)) { H = learn_min_slices(agent->A); const long fit = learn_lanes() / H; take = (int32_t)(n < fit ? n : fit); }
         hipLaunchKernelGGL(learn_queue_sort_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, take, b->nrules, shift, live);
-        if ((rc = learn_run(target ? "frirl_hip_learn_run_target" : explore ? "frirl_hip_learn_run_explore" : rows ? "frirl_hip_learn_run_rows" : "frirl_hip_learn_run", t, b, agent, rows, explore, target, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
+        if ((rc = learn_run(LEARN_NAME[learn_level(rows, explore, target)].run, t, b, agent, rows, explore, target, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
                             workspace, run_bytes, stream)) != 0) return rc;
         launches++;
         hipLaunchKernelGGL(learn_queue_next_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, n, take, live, conv->converged, conv->episodes, max_episodes, b->nrules,
@@ -330,6 +333,16 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
     }
     if (launches_out) *launches_out = launches;
     return check_launch(who);
+}
+
+// batch.hip's call: the frirl_hip_learn_train* entry point that the structs given select, under that entry point's name
+int frirl_host::learn_train_structs(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                    const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
+                                    const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *steps_total, void *workspace,
+                                    size_t workspace_bytes, int32_t *launches_out, void *stream)
+{
+    return learn_train(LEARN_NAME[learn_level(rows, explore, target)].train, t, b, agent, rows, explore, target, envs, conv, budget_steps, max_episodes, nullptr,
+                       steps_total, nullptr, workspace, workspace_bytes, launches_out, nullptr, nullptr, stream);
 }
 
 extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,

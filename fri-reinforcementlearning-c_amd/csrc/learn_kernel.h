@@ -782,8 +782,8 @@ inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b
 }
 
 
-// one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation file (learn_i*.hip) compiles a few kernels, so
-// that the build runs them in parallel
+// one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation unit (FRIRL_LEARN_UNIT below) compiles a few
+// kernels, so that the build runs them in parallel
 template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
 inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
                            const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s)
@@ -797,47 +797,44 @@ inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rul
     if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
 }
 
-// defined in learn_i0.hip (mountaincar), learn_i1.hip (acrobot, 1 .. 8 lanes per agent), learn_i2.hip (acrobot, 16 .. 64),
-// learn_i3.hip / learn_i4.hip (cartpole, 2 .. 8 / 16 .. 64); the _rows twins (ROWS = true, la.hp set) in learn_r0.hip .. learn_r4.hip,
-// the _explore ones (ROWS and EXPLORE, la.hp and la.ex set) in learn_x0.hip .. learn_x4.hip, the _target ones (ROWS, EXPLORE and TARGET,
-// la.tq set as well) in learn_q0.hip .. learn_q4.hip
-void frirl_learn_launch_cartpole_lo(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                    const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                    const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_mountaincar(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                    const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_lo(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                   const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_hi(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                   const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_lo_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_hi_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_mountaincar_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                         const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_lo_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_hi_rows(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_lo_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_hi_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_mountaincar_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_lo_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_hi_explore(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_lo_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_cartpole_hi_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_mountaincar_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_lo_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
-void frirl_learn_launch_acrobot_hi_target(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                                       const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s);
+// ---- the launch table ---------------------------------------------------------------------------------------------------------
+// The learner's shapes, each written once: X(name, NANT, NA, KIND, BITS, WPS, HLO, HHI).  A shape whose lane-group sizes are split
+// over two entries lists the _hi entry right after its _lo one (learn.hip steps from one to the other at the _lo entry's HHI).
+#define FRIRL_LEARN_SHAPES(X)                                   \
+    X(mountaincar, 3, 3, FRIRL_HIP_ENV_MOUNTAINCAR, 6, 2, 1, 64) \
+    X(acrobot_lo, 5, 3, FRIRL_HIP_ENV_ACROBOT, 6, 2, 1, 8)       \
+    X(acrobot_hi, 5, 3, FRIRL_HIP_ENV_ACROBOT, 6, 2, 16, 64)     \
+    X(cartpole_lo, 5, 21, FRIRL_HIP_ENV_CARTPOLE, 10, 2, 2, 8)   \
+    X(cartpole_hi, 5, 21, FRIRL_HIP_ENV_CARTPOLE, 10, 2, 16, 64)
+// The families are levels, each with the structs of the one below: 0 = plain, 1 = ROWS (la.hp), 2 = ROWS and EXPLORE (la.ex too),
+// 3 = ROWS, EXPLORE and TARGET (la.tq as well).
+#define FRIRL_LEARN_LEVELS(M, name) M(name, 0) M(name, 1) M(name, 2) M(name, 3)
+constexpr int LEARN_NLEVELS = 4;
+
+struct LearnShape { int NANT, NA, KIND, BITS, WPS, HLO, HHI; };
+#define X(name, ...) LEARN_##name,
+enum { FRIRL_LEARN_SHAPES(X) LEARN_NSHAPES };
+#undef X
+#define X(name, ...) {__VA_ARGS__},
+constexpr LearnShape LEARN_SHAPE[LEARN_NSHAPES] = {FRIRL_LEARN_SHAPES(X)};
+#undef X
+
+#define FRIRL_LEARN_LAUNCH_ARGS                                                                                                       \
+    int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev, \
+        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s
+typedef void (*frirl_learn_launch_fn)(FRIRL_LEARN_LAUNCH_ARGS);
+
+template <int SHAPE, int LEVEL>
+void frirl_learn_launch(FRIRL_LEARN_LAUNCH_ARGS)
+{
+    constexpr LearnShape k = LEARN_SHAPE[SHAPE];
+    launch_learn_h<k.NANT, k.NA, k.KIND, k.BITS, k.WPS, k.HLO, k.HHI, (LEVEL >= 1), (LEVEL >= 2), (LEVEL >= 3)>(H, t, b, ag, ev, cv, la, s);
+}
+
+// Every entry of the table is compiled in a unit of its own, learn_<shape>_<level>.hip, which holds FRIRL_LEARN_UNIT(shape, level)
+// and nothing else: the build runs them in parallel, and no other unit (learn.hip, which calls through the table) compiles a kernel.
+#define FRIRL_LEARN_EXTERN(name, level) extern template void frirl_learn_launch<LEARN_##name, level>(FRIRL_LEARN_LAUNCH_ARGS);
+#define X(name, ...) FRIRL_LEARN_LEVELS(FRIRL_LEARN_EXTERN, name)
+FRIRL_LEARN_SHAPES(X)
+#undef X
+#define FRIRL_LEARN_UNIT(name, level) template void frirl_learn_launch<LEARN_##name, level>(FRIRL_LEARN_LAUNCH_ARGS);

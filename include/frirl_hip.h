@@ -1196,7 +1196,7 @@ int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl_hip_ruleba
                                frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
 /* ... and with per-agent exploration (frirl_hip_explore_rows, above) after `rows`: agent e picks at its own rate in every episode.
  * Either struct may be NULL; explore == NULL is the _rows call (both NULL: the unsuffixed kernels), anything else runs a third kernel
- * family (EXPLORE, learn_x*.hip), which loads the agent's epsilon and horizon together with the six hyper-parameters after the rule
+ * family (EXPLORE, level 2 of the learner's launch table), which loads the agent's epsilon and horizon together with the six hyper-parameters after the rule
  * sweep -- a family of its own because inside the ROWS kernels the two columns cost the rows users 4.4 % on mountaincar
  * (profiles/r26_explore_rows.md).  Same shapes, workspace sizes and refusals, in the same order.  With the epsilon column equal to
  * agent->epsilon and no horizon the results are those of the unsuffixed call, bit for bit. */
@@ -1210,7 +1210,7 @@ int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const frirl_hip_rul
                                   int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
 /* ... and with a per-agent TD target (frirl_hip_target_rows, above) after `explore`: agent e learns towards Q(s', a') or Q(s', g).
  * Any of the three structs may be NULL; target == NULL calls the _explore entry point, anything else runs a fourth kernel family
- * (TARGET, learn_q*.hip), which loads the agent's target byte together with its eight row values after the rule sweep -- a family of
+ * (TARGET, level 3 of the launch table), which loads the agent's target byte together with its eight row values after the rule sweep -- a family of
  * its own for the reason EXPLORE is one: nobody who does not ask for it pays for it (the byte costs this family's users 0.7 to 1.9 % over
  * the _explore call on identical work, profiles/r28_target.md).  Same shapes, workspace sizes and refusals, in the
  * same order.  With an all-zero column or target_all 0 the results are those of the _explore call, bit for bit; with every agent

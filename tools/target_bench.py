@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the TD-target byte costs the users of the TARGET learner kernels (learn_q*.hip), measured against the EXPLORE kernels on
+"""What the TD-target byte costs the users of the TARGET learner kernels (level 3 of the launch table, learn_*_3.hip), measured against the EXPLORE kernels on
 identical inputs, and a record of how the two targets learn.
    python tools/target_bench.py [--env mountaincar --env acrobot] [--agents 65536 --agents 4096] [--rounds 5] [--max-episodes 400]
                                 [--quality-agents 4096] [--quality-episodes 60] [--out FILE]
