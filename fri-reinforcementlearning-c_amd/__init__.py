@@ -69,6 +69,11 @@ class TargetRowsDesc(C.Structure):
 TARGET_SARSA, TARGET_Q = 0, 1       # FRIRL_HIP_TARGET_*
 
 
+class ExpectRowsDesc(C.Structure):
+    """struct frirl_hip_expect_rows (include/frirl_hip.h)."""
+    _fields_ = [("expected", C.c_void_p), ("expected_all", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class EnvsDesc(C.Structure):
     """struct frirl_hip_envs (include/frirl_hip.h)."""
     _fields_ = [("states", C.c_void_p), ("q_ant", C.c_void_p), ("fus", C.c_void_p), ("done", C.c_void_p), ("ep_steps", C.c_void_p),
@@ -237,11 +242,11 @@ _lib = None
 _DP = C.POINTER(C.c_double)
 LEARN_CHUNK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32)      # frirl_hip_learn_chunk_fn
 
-# The entry points that come in levels: base (level 0), base_rows, base_explore, base_target take the first 0 .. 3 of the per-agent structs
-# between the agent and the rest of their arguments.
+# The entry points that come in levels: base (level 0), base_rows, base_explore, base_target, base_expect take the first 0 .. 4 of the
+# per-agent structs between the agent and the rest of their arguments.
 _HEAD = [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc)]
-_ROW_STRUCTS = [HparamRowsDesc, ExploreRowsDesc, TargetRowsDesc]
-_SUFFIX = ("", "_rows", "_explore", "_target")
+_ROW_STRUCTS = [HparamRowsDesc, ExploreRowsDesc, TargetRowsDesc, ExpectRowsDesc]
+_SUFFIX = ("", "_rows", "_explore", "_target", "_expect")
 _LEARN_RUN_TAIL = [C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                    C.c_void_p]
 _LEARN_TRAIN_TAIL = [C.POINTER(EnvsDesc), C.POINTER(ConvergenceDesc), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -250,7 +255,7 @@ _AGENT_TAIL = [C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p]             
 _TAUGHT_TAIL = [C.POINTER(EnvsDesc), C.POINTER(AgentIO), C.c_void_p, C.c_void_p]      # ..., teacher, stream
 
 
-def _levels(base, tail, levels=range(4)):
+def _levels(base, tail, levels=range(5)):
     return {base + _SUFFIX[n]: (C.c_int, _HEAD + [C.POINTER(s) for s in _ROW_STRUCTS[:n]] + tail) for n in levels}
 
 
@@ -352,7 +357,7 @@ SIGNATURES = {
     **_levels("frirl_hip_agent_begin", _AGENT_TAIL, [0]), "frirl_hip_agent_begin_taught": (C.c_int, _HEAD + _TAUGHT_TAIL),
     **_levels("frirl_hip_agent_begin", _TAUGHT_TAIL, [1, 2]),              # begin performs no update: no _begin_target
     **_levels("frirl_hip_agent_observe", _AGENT_TAIL, [0]), "frirl_hip_agent_observe_taught": (C.c_int, _HEAD + _TAUGHT_TAIL),
-    **_levels("frirl_hip_agent_observe", _TAUGHT_TAIL, [1, 2, 3]),
+    **_levels("frirl_hip_agent_observe", _TAUGHT_TAIL, [1, 2, 3, 4]),
     "frirl_hip_learn_demonstration": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(EnvsDesc),
                                                 C.POINTER(DemonstrationDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "frirl_hip_policy_begin": (C.c_int, [C.POINTER(Tables), C.POINTER(RuleBases), C.POINTER(AgentDesc), C.POINTER(PolicyRowsDesc), C.POINTER(AgentIO), C.c_void_p]),
@@ -404,6 +409,9 @@ SIGNATURES = {
     "frirl_hip_batch_set_target": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "frirl_hip_batch_get_target": (C.c_int, [C.c_void_p, C.c_void_p]),
     "frirl_hip_target_rows_check": (C.c_int, [C.POINTER(TargetRowsDesc), C.c_int32]),
+    "frirl_hip_batch_set_expected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "frirl_hip_batch_get_expected": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "frirl_hip_expect_rows_check": (C.c_int, [C.POINTER(ExpectRowsDesc), C.c_int32]),
     "frirl_hip_batch_get_rulebase": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _DP, _DP]),
     "frirl_hip_batch_save_rulebases": (C.c_int, [C.c_void_p, C.c_char_p]),
     "frirl_hip_batch_load_rulebases": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]),
@@ -1155,14 +1163,14 @@ def _rows(rows, E):
     return None if rows.desc is None else C.byref(rows.desc)
 
 
-def _level_entry(base, E, rows=None, explore=None, target=None, teacher=None):
+def _level_entry(base, E, rows=None, explore=None, target=None, teacher=None, expect=None):
     """The entry point of the family `base` (SIGNATURES: _levels) for the per-agent structs given: the last one given picks base_rows,
-    base_explore or base_target, which take the structs before it as well (None = NULL); with none of them `base` itself or, with a
+    base_explore, base_target or base_expect, which take the structs before it as well (None = NULL); with none of them `base` itself or, with a
     teacher, base_taught.  Returns (the function, its name for check(), the struct arguments that follow the agent, the teacher
     argument that precedes the stream in the agent calls: nothing for `base` itself, which has none)."""
-    level = 3 if target is not None else 2 if explore is not None else 1 if rows is not None else 0
+    level = 4 if expect is not None else 3 if target is not None else 2 if explore is not None else 1 if rows is not None else 0
     name = base + (_SUFFIX[level] if level or teacher is None else "_taught")
-    structs = [_rows(r, E) for r in (rows, explore, target)[:level]]
+    structs = [_rows(r, E) for r in (rows, explore, target, expect)[:level]]
     taught = [] if name == base else [None if teacher is None else _teacher(teacher, E)]
     return getattr(lib(), name), name, structs, taught
 
@@ -1213,6 +1221,29 @@ class TargetRows:
         """The NULL struct pointer: target=TargetRows.null(E) goes through the _target entry point, which calls the _explore one."""
         self = cls.__new__(cls)
         self.E, self.desc, self.target = E, None, None
+        return self
+
+
+class ExpectRows:
+    """Per-agent expected SARSA (struct frirl_hip_expect_rows): an agent e of a batch of E whose flag is 1 learns towards the expectation
+    of Q(s', .) under its own epsilon-greedy pick; its TD target is then not consulted.  expected (uint8 0 / 1) is anything
+    torch.as_tensor takes, of length E; None gives every agent expected_all.  Owns the device tensor and the struct.  Taken by
+    agent_observe / train_persistent / train as expect=."""
+
+    def __init__(self, E, device, expected=None, expected_all=0):
+        import torch
+        self.E, self.desc, self.expected = E, ExpectRowsDesc(), None
+        self.desc.expected_all = int(expected_all)
+        if expected is not None:
+            self.expected = torch.as_tensor(expected, dtype=torch.uint8).to(device).contiguous()
+            assert self.expected.shape == (E,), (tuple(self.expected.shape), E)
+            self.desc.expected = self.expected.data_ptr()
+
+    @classmethod
+    def null(cls, E):
+        """The NULL struct pointer: expect=ExpectRows.null(E) goes through the _expect entry point, which calls the _target one."""
+        self = cls.__new__(cls)
+        self.E, self.desc, self.expected = E, None, None
         return self
 
 
@@ -1313,7 +1344,7 @@ def agent_begin(problem, agent, envs, obs, reset=None, stream=None, teacher=None
     return action, action_idx
 
 
-def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None, explore=None, target=None):
+def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream=None, teacher=None, rows=None, explore=None, target=None, expect=None):
     """frirl_hip_agent_observe: one SARSA step of every row that is not done, from what the caller's environment returned for the
     last action -- obs [E, nant-1] float64, reward [E] float64, success [E] int32 (1 ends the episode), q_obs [E, nant-1] its
     quantised form or None (the generic grid rule on the device).  Returns (action values, action indices) of the next action;
@@ -1321,9 +1352,11 @@ def agent_observe(problem, agent, envs, obs, reward, success, q_obs=None, stream
     takes it as its next action and learns towards Q(s', a_teacher).  rows: an HparamRows (frirl_hip_agent_observe_rows): row e
     learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_agent_observe_explore): row e picks at
     its own rate in its current episode.  target: a TargetRows (frirl_hip_agent_observe_target): row e learns towards Q(s', a') or
-    Q(s', g); a taught row under TARGET_Q takes the teacher's action and learns towards Q(s', g).  Does not synchronise."""
+    Q(s', g); a taught row under TARGET_Q takes the teacher's action and learns towards Q(s', g).  expect: an ExpectRows
+    (frirl_hip_agent_observe_expect): a flagged row learns towards the expectation of Q(s', .) under its own pick, whatever action it
+    takes.  Does not synchronise."""
     io, action, action_idx = _agent_io(problem, obs, q_obs, reward, success)
-    fn, name, structs, taught = _level_entry("frirl_hip_agent_observe", problem.E, rows, explore, target, teacher)
+    fn, name, structs, taught = _level_entry("frirl_hip_agent_observe", problem.E, rows, explore, target, teacher, expect)
     check(fn(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), *structs, C.byref(envs.desc), C.byref(io), *taught, _stream(stream)), name)
     return action, action_idx
 
@@ -1517,6 +1550,24 @@ def batch_get_target(batch):
     import numpy as np
     out = np.zeros(_batch_agents(batch), dtype=np.uint8)
     check(lib().frirl_hip_batch_get_target(batch, out.ctypes.data), "frirl_hip_batch_get_target")
+    return out
+
+
+def batch_set_expected(batch, expected=None, expected_all=0):
+    """frirl_hip_batch_set_expected on a library-owned batch: the expected-SARSA flag of every agent for frirl_hip_batch_train -- a host
+    array of length E of 0 / 1, or None: expected_all for every agent.  (None, 0) clears the flags.  The library validates and copies
+    before it returns."""
+    import numpy as np
+    col = None if expected is None else np.ascontiguousarray(expected, dtype=np.uint8)
+    assert col is None or col.shape == (_batch_agents(batch),)
+    check(lib().frirl_hip_batch_set_expected(batch, None if col is None else col.ctypes.data, int(expected_all)), "frirl_hip_batch_set_expected")
+
+
+def batch_get_expected(batch):
+    """frirl_hip_batch_get_expected: uint8 [E], the expected-SARSA flag every agent trains under (0 while none is set)."""
+    import numpy as np
+    out = np.zeros(_batch_agents(batch), dtype=np.uint8)
+    check(lib().frirl_hip_batch_get_expected(batch, out.ctypes.data), "frirl_hip_batch_get_expected")
     return out
 
 
@@ -2059,7 +2110,7 @@ class LearnRun:
         self.conv, self.steps_total, self.work, self.launches = conv, steps_total, work, launches
 
 
-def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None, explore=None, target=None):
+def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_chunk=None, stream=None, rows=None, explore=None, target=None, expect=None):
     """The construct loop of frirl_sequential_run for E agents through frirl_hip_learn_train: every agent runs its episodes
     back to back on the device; after each launch (the work of `budget` steps of a mean agent) the agents that are still
     learning are compacted and launched again until none is left -- the launch plan, the queue and the compaction are the
@@ -2067,7 +2118,8 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     called after every launch (the place for the per-chunk reward statistics).  rows: an HparamRows (frirl_hip_learn_train_rows):
     agent e learns under its own values of the columns given.  explore: an ExploreRows (frirl_hip_learn_train_explore): agent e
     picks at its own epsilon, annealed over its own horizon.  target: a TargetRows (frirl_hip_learn_train_target): agent e learns
-    towards Q(s', a') or Q(s', g).  Returns a LearnRun."""
+    towards Q(s', a') or Q(s', g).  expect: an ExpectRows (frirl_hip_learn_train_expect): a flagged agent learns towards the expectation
+    of Q(s', .) under its own pick.  Returns a LearnRun."""
     import torch
     dev_ = problem.rb.device
     conv = Convergence(problem, dev_)
@@ -2092,7 +2144,7 @@ def train_persistent(problem, agent, envs, max_episodes=1000, budget=4096, on_ch
     cb = LEARN_CHUNK_FN(chunk) if on_chunk is not None else C.cast(None, LEARN_CHUNK_FN)
     launches = C.c_int32(0)
     refused = conv.full.view(torch.uint8)
-    fn, name, structs, _ = _level_entry("frirl_hip_learn_train", problem.E, rows, explore, target)
+    fn, name, structs, _ = _level_entry("frirl_hip_learn_train", problem.E, rows, explore, target, expect=expect)
     check(fn(C.byref(problem.tables), C.byref(problem.bases), C.byref(agent.desc), *structs, C.byref(envs.desc), C.byref(conv.desc), budget, max_episodes,
              _ptr(work), _ptr(steps_total), _ptr(refused), _ptr(ws), ws.numel() * 8, C.byref(launches), cb, None, _stream(stream)), name)
     if failure:

@@ -39,7 +39,8 @@ static int check_agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases
 
 static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
                       const frirl_hip_agent_io *io, const int32_t *teacher, void *stream, bool begin, const char *who, const frirl_hip_hparam_rows *rows = nullptr,
-                      const frirl_hip_explore_rows *explore = nullptr, const frirl_hip_target_rows *target = nullptr)
+                      const frirl_hip_explore_rows *explore = nullptr, const frirl_hip_target_rows *target = nullptr,
+                      const frirl_hip_expect_rows *expect = nullptr)
 {
     int rc = check_agent_call(t, b, agent, envs, io, begin, who);
     if (rc) return rc;
@@ -49,6 +50,7 @@ static int agent_call(const frirl_hip_tables *t, const frirl_hip_rulebases *b, c
     x.rows = rows ? *rows : frirl_hip_hparam_rows{};
     x.ex = explore ? *explore : frirl_hip_explore_rows{};
     x.tq = target ? *target : frirl_hip_target_rows{};
+    x.xp = expect ? *expect : frirl_hip_expect_rows{};
     switch (t->nant) {
 #define M(N) case N: frirl_agent_launch_##N(begin, t, b, agent, envs, x, as_stream(stream)); break;
         FRIRL_AGENT_NANT_CASES(M)
@@ -119,4 +121,14 @@ extern "C" int frirl_hip_agent_observe_target(const frirl_hip_tables *t, const f
 {
     if (!target) return frirl_hip_agent_observe_explore(t, b, agent, rows, explore, envs, io, teacher, stream);
     return agent_call(t, b, agent, envs, io, teacher, stream, false, "frirl_hip_agent_observe_target", rows, explore, target);
+}
+
+// per-agent expected SARSA (frirl_hip_expect_rows): a flagged row e learns towards the expectation of Q(s', .) under its own pick; NULL
+// expect = the _target call.  No _begin_expect: begin performs no update
+extern "C" int frirl_hip_agent_observe_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                              const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                                              const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream)
+{
+    if (!expect) return frirl_hip_agent_observe_target(t, b, agent, rows, explore, target, envs, io, teacher, stream);
+    return agent_call(t, b, agent, envs, io, teacher, stream, false, "frirl_hip_agent_observe_expect", rows, explore, target, expect);
 }

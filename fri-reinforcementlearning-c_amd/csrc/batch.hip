@@ -46,6 +46,9 @@ struct frirl_hip_batch {
     uint8_t *d_tq;               // [E] per-agent TD target of frirl_hip_batch_set_target (allocated on first use)
     frirl_hip_target_rows tq;    // the device column if one is set, and target_all
     bool tq_set;                 // a target other than SARSA for everybody is set
+    uint8_t *d_xp;               // [E] per-agent expected-SARSA flags of frirl_hip_batch_set_expected (allocated on first use)
+    frirl_hip_expect_rows xp;    // the device column if one is set, and expected_all
+    bool xp_set;                 // flags other than 0 for everybody are set
     std::vector<int32_t> h_i;
     std::vector<double> h_d;
 };
@@ -124,7 +127,7 @@ extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
     if (b->s) (void)hipStreamSynchronize(b->s);
     void *ptrs[] = {b->d_u, b->d_ve, b->d_rb, b->d_rant, b->d_grid, b->d_ave, b->d_states, b->d_q_ant, b->d_ep_reward, b->d_start, b->d_prev_reward,
                     b->d_prev_rconc, b->d_tmp, b->d_nrules, b->d_fus, b->d_done, b->d_ep_steps, b->d_status, b->d_episode, b->d_prev_nrules,
-                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h, b->d_tq};
+                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h, b->d_tq, b->d_xp};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -196,8 +199,12 @@ static int refuse_rows(const frirl_hip_batch *b, const char *who)
         set_error("%s: per-agent hyper-parameters are set (frirl_hip_batch_set_hparams) and this call does not honour them: use frirl_hip_batch_train, or clear them", who);
         return FRIRL_HIP_EINVAL;
     }
-    if (!b->tq_set) return FRIRL_HIP_OK;
-    set_error("%s: a per-agent TD target is set (frirl_hip_batch_set_target) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
+    if (b->tq_set) {
+        set_error("%s: a per-agent TD target is set (frirl_hip_batch_set_target) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (!b->xp_set) return FRIRL_HIP_OK;
+    set_error("%s: per-agent expected SARSA is set (frirl_hip_batch_set_expected) and this call does not honour it: use frirl_hip_batch_train, or clear it", who);
     return FRIRL_HIP_EINVAL;
 }
 
@@ -279,7 +286,7 @@ static int batch_train_persistent(frirl_hip_batch *b, int32_t max_episodes, int3
     frirl_hip_agent exploring = b->agent;
     exploring.no_random = 0;                // exploration rows ask for exploration, whatever the batch's own flag (which every other call keeps reading)
     int rc = learn_train_structs(&b->t, &b->rb, b->ex_set ? &exploring : &b->agent, b->hp_set ? &b->hp : nullptr, b->ex_set ? &b->ex : nullptr,
-                                 b->tq_set ? &b->tq : nullptr, &b->envs, &b->conv, 512, max_episodes + before, b->d_steps_total, b->d_learn_ws, b->learn_ws_bytes,
+                                 b->tq_set ? &b->tq : nullptr, b->xp_set ? &b->xp : nullptr, &b->envs, &b->conv, 512, max_episodes + before, b->d_steps_total, b->d_learn_ws, b->learn_ws_bytes,
                                  &launches, b->s);
     if (rc) return rc;
     std::vector<int64_t> st(E);
@@ -526,6 +533,63 @@ extern "C" int frirl_hip_batch_get_target(frirl_hip_batch *b, uint8_t *host_targ
     BCHK(hipStreamSynchronize(b->s), "target sync");
     if (b->tq.target) BCHK(hipMemcpy(host_target, b->tq.target, sizeof(uint8_t) * (size_t)b->E, hipMemcpyDeviceToHost), "target download");
     else std::fill_n(host_target, b->E, (uint8_t)b->tq.target_all);
+    return FRIRL_HIP_OK;
+}
+
+// what valid per-agent expected-SARSA flags are (include/frirl_hip.h): host column [E], no device
+static int expect_check(const char *who, const frirl_hip_expect_rows &x, int E)
+{
+    if (x.reserved != 0) { set_error("%s: reserved is %u, not 0", who, x.reserved); return FRIRL_HIP_EINVAL; }
+    if (x.expected_all != 0 && x.expected_all != 1) { set_error("%s: expected_all %d is neither 0 nor 1", who, x.expected_all); return FRIRL_HIP_EINVAL; }
+    for (int e = 0; e < E; e++)
+        if (x.expected && x.expected[e] > 1) { set_error("%s: agent %d: expected %d is neither 0 nor 1", who, e, (int)x.expected[e]); return FRIRL_HIP_EINVAL; }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_expect_rows_check(const frirl_hip_expect_rows *host_rows, int32_t E)
+{
+    if (E < 1) { set_error("frirl_hip_expect_rows_check: E=%d", E); return FRIRL_HIP_EINVAL; }
+    return host_rows ? expect_check("frirl_hip_expect_rows_check", *host_rows, E) : FRIRL_HIP_OK;
+}
+
+// Per-agent expected SARSA for frirl_hip_batch_train (include/frirl_hip.h): validated on the host, then copied.
+extern "C" int frirl_hip_batch_set_expected(frirl_hip_batch *b, const uint8_t *host_expected, int32_t expected_all)
+{
+    static const char *who = "frirl_hip_batch_set_expected";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (!host_expected && expected_all == 0) {                                                 // clear
+        b->xp = frirl_hip_expect_rows{};
+        b->xp_set = false;
+        return FRIRL_HIP_OK;
+    }
+    if (!b->d_uidx || !frirl_hip_learn_supported(b->nant, b->U, b->agent.A, b->agent.p, b->agent.env_kind)) {
+        set_error("%s: only the persistent learner takes per-agent expected SARSA, and it does not cover this batch (frirl_hip_learn_supported: nant=%d U=%d A=%d p=%d; "
+                  "index mirror: %s)", who, b->nant, b->U, b->agent.A, b->agent.p, b->d_uidx ? "yes" : "no");
+        return FRIRL_HIP_EINVAL;
+    }
+    const int E = b->E;
+    frirl_hip_expect_rows host = {};
+    host.expected = host_expected; host.expected_all = expected_all;
+    if (expect_check(who, host, E)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    if (host_expected && !b->d_xp && !dalloc(&b->d_xp, (size_t)E)) { set_error("%s: HIP allocation failed: %s", who, hipGetErrorString(hipGetLastError())); return FRIRL_HIP_ELAUNCH; }
+    BCHK(hipStreamSynchronize(b->s), "expected sync");                  // nothing in flight reads the column being replaced
+    if (host_expected) BCHK(hipMemcpy(b->d_xp, host_expected, sizeof(uint8_t) * E, hipMemcpyHostToDevice), "expected upload");
+    b->xp = frirl_hip_expect_rows{};
+    b->xp.expected = host_expected ? b->d_xp : nullptr;
+    b->xp.expected_all = expected_all;
+    b->xp_set = true;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_get_expected(frirl_hip_batch *b, uint8_t *host_expected)
+{
+    static const char *who = "frirl_hip_batch_get_expected";
+    if (!b || !host_expected) { set_error("%s: NULL batch or host_expected", who); return FRIRL_HIP_EINVAL; }
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    BCHK(hipStreamSynchronize(b->s), "expected sync");
+    if (b->xp.expected) BCHK(hipMemcpy(host_expected, b->xp.expected, sizeof(uint8_t) * (size_t)b->E, hipMemcpyDeviceToHost), "expected download");
+    else std::fill_n(host_expected, b->E, (uint8_t)b->xp.expected_all);
     return FRIRL_HIP_OK;
 }
 
@@ -886,7 +950,7 @@ extern "C" int frirl_hip_batch_teach(frirl_hip_batch *b, int32_t teacher, int32_
 namespace frirl {
 // inherit_rows: every set column takes the source's value for the cloned agents; in place, since a source is no destination
 __global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32_t *__restrict__ status, int E, double *d0, double *d1, double *d2, double *d3,
-                                    double *d4, double *d5, int32_t *i0, int32_t *i1, uint8_t *b0)
+                                    double *d4, double *d5, int32_t *i0, int32_t *i1, uint8_t *b0, uint8_t *b1)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E || status[e] != FRIRL_HIP_CLONE_CLONED) return;
@@ -897,6 +961,7 @@ __global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32
     if (i0) i0[e] = i0[s];
     if (i1) i1[e] = i1[s];
     if (b0) b0[e] = b0[s];
+    if (b1) b1[e] = b1[s];
 }
 }  // namespace frirl
 
@@ -918,12 +983,12 @@ static int batch_clone_run(const char *who, frirl_hip_batch *b, const int32_t *s
     // no image of a rule base outlives a call (d_lanes_ws and d_learn_ws are imported from rb / uidx at the start of every call that
     // uses them), so there is nothing to invalidate beside the arrays the clone itself rewrites
     if (he == hipSuccess) rc = frirl_hip_clone_agents(&b->rb, b->nant, &b->envs, &b->conv, b->d_weights, d_src, d_status, b->s);
-    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set || b->tq_set)) {
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set || b->tq_set || b->xp_set)) {
         const frirl_hip_hparam_rows &h = b->hp;
         hipLaunchKernelGGL(frirl::inherit_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, b->s, d_src, d_status, E, const_cast<double *>(h.alpha),
                            const_cast<double *>(h.gamma), const_cast<double *>(h.qdiff_pos_boundary), const_cast<double *>(h.qdiff_neg_boundary),
                            const_cast<double *>(h.weight_significant), const_cast<double *>(b->ex.epsilon), const_cast<int32_t *>(h.skip_rules),
-                           const_cast<int32_t *>(b->ex.horizon), const_cast<uint8_t *>(b->tq.target));
+                           const_cast<int32_t *>(b->ex.horizon), const_cast<uint8_t *>(b->tq.target), const_cast<uint8_t *>(b->xp.expected));
     }
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(nr.data(), b->d_nrules, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);

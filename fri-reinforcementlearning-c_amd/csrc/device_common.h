@@ -154,12 +154,12 @@ int check_policy_io(const frirl_hip_agent_io *io, bool begin, const char *who);
 #define FRIRL_POLICY_NANT_CASES(M) M(2) M(3) M(4) M(5) M(6) M(7) M(8)      // antecedent counts the policy kernels are instantiated for
 int check_agent_shape(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_envs *envs,
                       const char *who);   // agent.hip: nant 2..8, rule bases, grids, A 1..32, env state; not the device
-// learn.hip: frirl_hip_learn_train, _rows, _explore or _target, whichever the last non-NULL struct selects (messages name that one),
-// without work counters, refusal flags or a chunk callback
+// learn.hip: frirl_hip_learn_train, _rows, _explore, _target or _expect, whichever the last non-NULL struct selects (messages name that
+// one), without work counters, refusal flags or a chunk callback
 int learn_train_structs(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                        const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
-                        const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *steps_total, void *workspace,
-                        size_t workspace_bytes, int32_t *launches_out, void *stream);
+                        const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                        const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *steps_total,
+                        void *workspace, size_t workspace_bytes, int32_t *launches_out, void *stream);
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // a HIP call that must succeed: otherwise the error text becomes "who: expression: hipGetErrorString" and `on_fail` runs

@@ -281,6 +281,7 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
     __shared__ BlockRed<BLOCK> red;
     __shared__ GbaScratch<AMAX, BLOCK> gs;
     __shared__ SpreadCand cand_s[TRACK ? BLOCK : 1];       // one slot per lane: candidates of update_rules' write-back (sweeps.h)
+    __shared__ double qp_s;                                // EXT: what the update learns towards, formed by thread 0 at the pick
     if (IDX) for (int i = threadIdx.x; i < NANT * U; i += BLOCK) tab_s[i] = ve[i];
     if (threadIdx.x == 0) {
         double s[FRIRL_HIP_MAX_NANT], q[FRIRL_HIP_MAX_NANT];
@@ -345,6 +346,22 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         // EXT under FRIRL_HIP_TARGET_Q (frirl_hip_target_rows): the update goes towards Q(s', g) of the greedy action `ap` the pick started
         // from, whatever the pick or the teacher chose; the episode goes on from (s', chosen) all the same
         if constexpr (EXT) { if ((io.tq.target ? (int)io.tq.target[e] : io.tq.target_all) == FRIRL_HIP_TARGET_Q) gs.best = ap; }
+        // EXT under a set flag of frirl_hip_expect_rows: the update goes towards the expectation of the A conclusions under the pick at this
+        // row's rate (frirl_hip.h), formed here from gs.actconc[] in action order; the target byte is then not consulted
+        if constexpr (EXT) {
+            double v = gs.actconc[gs.best];
+            if (io.xp.expected ? (int)io.xp.expected[e] : io.xp.expected_all) {
+                const double eps = ag.no_random == 1 ? 0.0 : hp.epsilon;
+                v = gs.actconc[ap];
+                if (eps != 0.0) {
+                    double S = gs.actconc[0];
+                    for (int a = 1; a < ag.A; a++) S = S + gs.actconc[a];
+                    const double M = (S - 0.5 * gs.actconc[0]) + 0.5 * gs.actconc[ag.A - 1];
+                    v = (1.0 - eps) * v + (eps / (double)ag.A) * M;
+                }
+            }
+            qp_s = v;
+        }
         sh.cur_q_ant[NS] = ag.grid_values[(size_t)NS * FRIRL_HIP_MAX_GRID + chosen];                  // :151
         sh.ve2[NS] = gs.ave[chosen];
         if constexpr (EXT) {
@@ -353,7 +370,8 @@ __global__ __launch_bounds__(BLOCK, step_min_waves(NANT, AMAX)) void episode_ste
         }
     }
     __syncthreads();
-    const double qp = gs.actconc[gs.best];     // Q(s',a') of the chosen action == FIVE_vag_concl(cur_q_ant), frirl_update_sarsa.c:356 (EXT, target Q: Q(s', g))
+    double qp;                                 // Q(s',a') of the chosen action == FIVE_vag_concl(cur_q_ant), frirl_update_sarsa.c:356 (EXT, target Q: Q(s', g))
+    if constexpr (EXT) qp = qp_s; else qp = gs.actconc[gs.best];
     double *rant_e = ev.rant ? ev.rant + (size_t)e * NANT * maxR : nullptr;
     int st = FRIRL_HIP_UPD_INACTIVE;
     if (!ag.evaluate)                                                                                 // :155 (reduction_state == 0)

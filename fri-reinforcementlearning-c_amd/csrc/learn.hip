@@ -1,5 +1,6 @@
 // learn.hip -- entry point of the persistent construct loop (kernels: learn_kernel.h, one unit learn_<shape>_<level>.hip per entry of its launch
-// table: five shapes, and the levels 0 = plain, 1 = per-agent hyper-parameter rows, 2 = per-agent exploration too, 3 = a per-agent TD target as well).
+// table: five shapes, and the levels 0 = plain, 1 = per-agent hyper-parameter rows, 2 = per-agent exploration too, 3 = a per-agent TD target as well,
+// 4 = per-agent expected SARSA on top of those).
 #include "learn_kernel.h"
 
 using namespace frirl_host;
@@ -107,10 +108,12 @@ extern "C" int frirl_hip_learn_timing(unsigned long long *out16)       // read a
 
 // The last struct given picks the level (learn_kernel.h): rows != NULL: the ROWS kernels, every agent under its own hyper-parameters;
 // explore != NULL: the EXPLORE kernels, every agent at its own exploration rate as well; target != NULL: the TARGET kernels, every agent
-// learning towards its own TD target, whichever of the other two structs are given.
-static int learn_level(const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target)
+// learning towards its own TD target, whichever of the other two structs are given; expect != NULL: the EXPECT kernels, the flagged agents
+// learning towards the expectation under their pick, whichever of the other three are given.
+static int learn_level(const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target,
+                       const frirl_hip_expect_rows *expect)
 {
-    return target ? 3 : explore ? 2 : rows ? 1 : 0;
+    return expect ? 4 : target ? 3 : explore ? 2 : rows ? 1 : 0;
 }
 
 // the entry points of a level, as messages name them
@@ -119,6 +122,7 @@ static const struct { const char *run, *train; } LEARN_NAME[LEARN_NLEVELS] = {
     {"frirl_hip_learn_run_rows", "frirl_hip_learn_train_rows"},
     {"frirl_hip_learn_run_explore", "frirl_hip_learn_train_explore"},
     {"frirl_hip_learn_run_target", "frirl_hip_learn_train_target"},
+    {"frirl_hip_learn_run_expect", "frirl_hip_learn_train_expect"},
 };
 
 // the launch table: one launcher per shape and level, built from the list that instantiates them (learn_kernel.h)
@@ -132,8 +136,9 @@ static_assert(LEARN_acrobot_hi == LEARN_acrobot_lo + 1 && LEARN_cartpole_hi == L
 // One chunk of the construct loop for the agents in `live` (device array of nlive agent ids, or NULL = agents 0..nlive-1):
 // see include/frirl_hip.h.
 static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                     const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
-                     int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+                     const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect, const frirl_hip_envs *envs,
+                     const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
+                     void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = frirl_check_episode(t, b, agent, envs, who);
     if (rc) return rc;
@@ -145,7 +150,7 @@ static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip
     const size_t need = frirl_hip_learn_workspace_bytes(t->nant, nlive, b->maxR, agent->A);
     if (workspace_bytes < need) { set_error("%s: workspace %zu B < %zu B (frirl_hip_learn_workspace_bytes)", who, workspace_bytes, need); return FRIRL_HIP_EINVAL; }
     hipStream_t s = as_stream(stream);
-    frirl::LearnArgs la = {};
+    frirl::LearnArgsX la = {};
     la.u = t->u; la.ve = t->ve; la.U = t->U;
     la.Ti = static_cast<uint32_t *>(workspace);
     la.live = live; la.nlive = nlive;
@@ -160,10 +165,11 @@ static int learn_run(const char *who, const frirl_hip_tables *t, const frirl_hip
     if (rows) la.hp = *rows;
     if (explore) la.ex = *explore;
     if (target) la.tq = *target;
+    if (expect) la.xp = *expect;
     int shape = t->nant == 3 ? LEARN_mountaincar : agent->A == 3 ? LEARN_acrobot_lo : LEARN_cartpole_lo;
     if (H > LEARN_SHAPE[shape].HHI) shape++;                // the _hi entry follows its _lo one
     if (H < LEARN_SHAPE[shape].HLO || H > LEARN_SHAPE[shape].HHI) { set_error("%s: no kernel for %d lanes per agent", who, H); return FRIRL_HIP_EINVAL; }
-    LEARN_LAUNCH[shape][learn_level(rows, explore, target)](H, t, b, agent, envs, conv, la, s);
+    LEARN_LAUNCH[shape][learn_level(rows, explore, target, expect)](H, t, b, agent, envs, conv, la, s);
     return check_launch(who);
 }
 
@@ -171,14 +177,14 @@ extern "C" int frirl_hip_learn_run(const frirl_hip_tables *t, const frirl_hip_ru
                                    const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps, int32_t max_episodes,
                                    int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run", t, b, agent, nullptr, nullptr, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 extern "C" int frirl_hip_learn_run_rows(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
                                         const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
                                         int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_rows", t, b, agent, rows, nullptr, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 // per-agent exploration (frirl_hip_explore_rows) beside the hyper-parameter rows: the EXPLORE kernels; explore NULL = the _rows call
@@ -187,7 +193,7 @@ extern "C" int frirl_hip_learn_run_explore(const frirl_hip_tables *t, const frir
                                            int32_t nlive, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    return learn_run("frirl_hip_learn_run_explore", t, b, agent, rows, explore, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_explore", t, b, agent, rows, explore, nullptr, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 // per-agent TD target (frirl_hip_target_rows) beside the other rows: the TARGET kernels; target NULL = the _explore call
@@ -197,7 +203,17 @@ extern "C" int frirl_hip_learn_run_target(const frirl_hip_tables *t, const frirl
                                           int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!target) return frirl_hip_learn_run_explore(t, b, agent, rows, explore, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
-    return learn_run("frirl_hip_learn_run_target", t, b, agent, rows, explore, target, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_target", t, b, agent, rows, explore, target, nullptr, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+}
+
+// per-agent expected SARSA (frirl_hip_expect_rows) beside the other rows: the EXPECT kernels; expect NULL = the _target call
+extern "C" int frirl_hip_learn_run_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                          const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                                          const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                                          int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!expect) return frirl_hip_learn_run_target(t, b, agent, rows, explore, target, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
+    return learn_run("frirl_hip_learn_run_expect", t, b, agent, rows, explore, target, expect, envs, conv, live, nlive, budget_steps, max_episodes, work, steps_total, workspace, workspace_bytes, stream);
 }
 
 
@@ -291,9 +307,9 @@ extern "C" size_t frirl_hip_learn_train_workspace_bytes(int32_t nant, int32_t E,
 }
 
 static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                       const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
-                       int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
-                       frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+                       const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect, const frirl_hip_envs *envs,
+                       const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace,
+                       size_t workspace_bytes, int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
     int rc = frirl_check_episode(t, b, agent, envs, who);
     if (rc) return rc;
@@ -319,7 +335,7 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
         if ((rc = frirl_hip_learn_plan(n, (int32_t)(mean_rules * (agent->A + 1) / 4), &H, &take)) != 0) return rc;
         if (H < learn_min_slices(agent->A)) { H = learn_min_slices(agent->A); const long fit = learn_lanes() / H; take = (int32_t)(n < fit ? n : fit); }
         hipLaunchKernelGGL(learn_queue_sort_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, take, b->nrules, shift, live);
-        if ((rc = learn_run(LEARN_NAME[learn_level(rows, explore, target)].run, t, b, agent, rows, explore, target, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
+        if ((rc = learn_run(LEARN_NAME[learn_level(rows, explore, target, expect)].run, t, b, agent, rows, explore, target, expect, envs, conv, live, take, budget_steps, max_episodes, work, steps_total,
                             workspace, run_bytes, stream)) != 0) return rc;
         launches++;
         hipLaunchKernelGGL(learn_queue_next_kernel, dim3(1), dim3(LQ_BLOCK), 0, s, qa, n, take, live, conv->converged, conv->episodes, max_episodes, b->nrules,
@@ -337,11 +353,11 @@ static int learn_train(const char *who, const frirl_hip_tables *t, const frirl_h
 
 // batch.hip's call: the frirl_hip_learn_train* entry point that the structs given select, under that entry point's name
 int frirl_host::learn_train_structs(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
-                                    const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_envs *envs,
-                                    const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *steps_total, void *workspace,
-                                    size_t workspace_bytes, int32_t *launches_out, void *stream)
+                                    const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                                    const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *steps_total,
+                                    void *workspace, size_t workspace_bytes, int32_t *launches_out, void *stream)
 {
-    return learn_train(LEARN_NAME[learn_level(rows, explore, target)].train, t, b, agent, rows, explore, target, envs, conv, budget_steps, max_episodes, nullptr,
+    return learn_train(LEARN_NAME[learn_level(rows, explore, target, expect)].train, t, b, agent, rows, explore, target, expect, envs, conv, budget_steps, max_episodes, nullptr,
                        steps_total, nullptr, workspace, workspace_bytes, launches_out, nullptr, nullptr, stream);
 }
 
@@ -350,7 +366,7 @@ extern "C" int frirl_hip_learn_train(const frirl_hip_tables *t, const frirl_hip_
                                      uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                      frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train", t, b, agent, nullptr, nullptr, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
 }
 
@@ -359,7 +375,7 @@ extern "C" int frirl_hip_learn_train_rows(const frirl_hip_tables *t, const frirl
                                           int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
                                           frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
+    return learn_train("frirl_hip_learn_train_rows", t, b, agent, rows, nullptr, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                        launches_out, on_chunk, user, stream);
 }
 
@@ -368,7 +384,7 @@ extern "C" int frirl_hip_learn_train_explore(const frirl_hip_tables *t, const fr
                                              int32_t max_episodes, int64_t *work, int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes,
                                              int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
 {
-    return learn_train("frirl_hip_learn_train_explore", t, b, agent, rows, explore, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+    return learn_train("frirl_hip_learn_train_explore", t, b, agent, rows, explore, nullptr, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
                        workspace_bytes, launches_out, on_chunk, user, stream);
 }
 
@@ -380,6 +396,18 @@ extern "C" int frirl_hip_learn_train_target(const frirl_hip_tables *t, const fri
 {
     if (!target) return frirl_hip_learn_train_explore(t, b, agent, rows, explore, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace, workspace_bytes,
                                                       launches_out, on_chunk, user, stream);
-    return learn_train("frirl_hip_learn_train_target", t, b, agent, rows, explore, target, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+    return learn_train("frirl_hip_learn_train_target", t, b, agent, rows, explore, target, nullptr, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+                       workspace_bytes, launches_out, on_chunk, user, stream);
+}
+
+extern "C" int frirl_hip_learn_train_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                            const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                                            const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                                            int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                                            frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream)
+{
+    if (!expect) return frirl_hip_learn_train_target(t, b, agent, rows, explore, target, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
+                                                     workspace_bytes, launches_out, on_chunk, user, stream);
+    return learn_train("frirl_hip_learn_train_expect", t, b, agent, rows, explore, target, expect, envs, conv, budget_steps, max_episodes, work, steps_total, refused, workspace,
                        workspace_bytes, launches_out, on_chunk, user, stream);
 }

@@ -74,6 +74,13 @@ struct LearnArgs {
 #else
 #define LT_MARK(i) do { } while (0)
 #endif
+// ... and the per-agent expected-SARSA flags [E], indexed likewise, for the EXPECT kernels: a struct of its own after the kernels' one,
+// so that the kernels of the lower levels keep their argument layout (they take the LearnArgs part alone)
+struct LearnArgsX : LearnArgs {
+    frirl_hip_expect_rows xp;    // NULL column = xp.expected_all
+};
+template <bool EXPECT>
+using LearnArgsOf = std::conditional_t<EXPECT, LearnArgsX, LearnArgs>;
 
 // ---- import / export: canonical rb[e][nant][r], uidx[e][k][r], prev_rconc[e][r]  <->  tiles --------------------------------
 template <int NANT, int BITS>
@@ -145,8 +152,13 @@ __global__ __launch_bounds__(256) void learn_export_kernel(const LearnArgs la, i
 // Under FRIRL_HIP_TARGET_Q the update goes towards the greedy conclusion `bv` of the fused sweep -- the maximum over both halves of the
 // action walk and over the lanes of the group -- whatever action the pick takes; the pick's own walk still runs for its weight sum.
 // A parameter of its own for the reason EXPLORE is one: EXPLORE alone compiles to the code without the byte.
-template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
-__global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la, const frirl_hip_agent ag, const frirl_hip_envs ev,
+// EXPECT (with TARGET): the agent's expected-SARSA flag of frirl_hip_expect_rows, one more byte in that clause.  A flagged agent learns
+// towards  v = (1 - eps) c[g] + (eps / A) ((S - c[0] / 2) + c[A-1] / 2)  (include/frirl_hip.h), so the action walk keeps the sum S of the
+// A conclusions and the first and the last of them beside the greedy one `bv` -- over both halves of the walk where there are two; the
+// conclusions are formed after the group's slices are combined, so every lane of the group holds the same three.  TARGET alone
+// compiles to the code without them.
+template <int NANT, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false, bool EXPECT = false>
+__global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgsOf<EXPECT> la, const frirl_hip_agent ag, const frirl_hip_envs ev,
                                                               const frirl_hip_convergence cv)
 {
     constexpr int NS = NANT - 1, EPW = FRIRL_WAVE / H;                        // NA + 1 conclusions per step: A actions at s', Q(s, a)
@@ -379,6 +391,7 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
         //      part reduces its conclusions to "best action so far" before the next one starts.
         double bv = 0.0, swb = 0.0;                                           // greedy: first maximum in action order (max.inl:21), its weight sum
         int ci = 0;
+        [[maybe_unused]] double xs = 0.0, xc0 = 0.0, xcl = 0.0;               // EXPECT: c[0] + ... + c[A-1] in action order, c[0], c[A-1]
         unsigned hit1 = FRIRL_HIP_NO_HIT;                                     // the pending conclusion
         double vs1 = 0.0, ws1 = 0.0;
         auto part = [&](auto a0c, auto napc, auto withpc, Pref &pf) {
@@ -444,6 +457,11 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                 for (int a = 0; a < NAP; a++) {
                     const double c = (sh[a] != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(sh[a] / H) * 64 + (sh[a] % H)] : sv[a] / sw[a];
                     if (A0 + a == 0 || bv < c) { bv = c; ci = A0 + a; swb = sw[a]; }
+                    if constexpr (EXPECT) {
+                        xs = (A0 + a == 0) ? c : xs + c;
+                        if (A0 + a == 0) xc0 = c;
+                        if (A0 + a == NA - 1) xcl = c;
+                    }
                 }
                 if constexpr (WITHP) { hit1 = sh[NAP]; vs1 = sv[NAP]; ws1 = sw[NAP]; }
             }
@@ -512,6 +530,10 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
             static_assert(EXPLORE || !TARGET, "TARGET kernels take the exploration rows too");
             [[maybe_unused]] int tq = FRIRL_HIP_TARGET_SARSA;
             if constexpr (TARGET) tq = la.tq.target ? (int)la.tq.target[erow] : la.tq.target_all;
+            // ... and (EXPECT) its expected-SARSA flag, one more byte in the same clause
+            static_assert(TARGET || !EXPECT, "EXPECT kernels take the TD target too");
+            [[maybe_unused]] int xf = 0;
+            if constexpr (EXPECT) xf = la.xp.expected ? (int)la.xp.expected[erow] : la.xp.expected_all;
             if (begin) {
                 episode++;
                 int a0;                                                                                 // :78-82
@@ -537,7 +559,9 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                 }
             } else {
                 int chosen;
-                if constexpr (EXPLORE) chosen = e_greedy(ag, explore_epsilon(ex_eps, ex_h, episode), ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
+                [[maybe_unused]] double xeps = 0.0;                                                      // EXPECT: the rate this step's pick runs at
+                if constexpr (EXPECT) { xeps = explore_epsilon(ex_eps, ex_h, episode); chosen = e_greedy(ag, xeps, ci, (uint32_t)e, episode, (uint32_t)steps + 1u); }
+                else if constexpr (EXPLORE) chosen = e_greedy(ag, explore_epsilon(ex_eps, ex_h, episode), ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
                 else chosen = e_greedy(ag, ci, (uint32_t)e, episode, (uint32_t)steps + 1u);
                 const bool flags_known = thr > 0.0 && thr < __builtin_inf();                            // this step's flags were taken against a real bound
                 double qp = bv, w0 = swb;                                                                // Q(s',a'), frirl_update_sarsa.c:356
@@ -545,8 +569,12 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
                     double v;
                     unsigned hh;
                     action_conclusion(chosen, v, w0, hh);
-                    if constexpr (TARGET) { if (tq != FRIRL_HIP_TARGET_Q) qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0; }   // Q: Q(s', g) = bv stays, w0 is a''s
+                    if constexpr (EXPECT) { if (tq != FRIRL_HIP_TARGET_Q && !xf) qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0; }   // flagged: bv stays, see below
+                    else if constexpr (TARGET) { if (tq != FRIRL_HIP_TARGET_Q) qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0; }   // Q: Q(s', g) = bv stays, w0 is a''s
                     else qp = (hh != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hh / H) * 64 + (hh % H)] : v / w0;
+                }
+                if constexpr (EXPECT) {                                                                  // the expectation under the pick (frirl_hip.h); eps == 0: c[g] itself
+                    if (xf && ag.no_random != 1 && xeps != 0.0) qp = (1.0 - xeps) * bv + (xeps / (double)NA) * ((xs - 0.5 * xc0) + 0.5 * xcl);
                 }
                 thr = (hp_wsig * (1.0 - 4e-9)) * w0;                                      // (s', a') is the next pending point
                 const double qnow = (hit1 != FRIRL_HIP_NO_HIT) ? Tq_g[(size_t)(hit1 / H) * 64 + (hit1 % H)] : vs1 / ws1;   // Q(s,a), :357
@@ -756,9 +784,9 @@ __global__ __launch_bounds__(LR_BLOCK, WPS) void learn_kernel(const LearnArgs la
 }  // namespace frirl
 
 
-template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
+template <int N, int NA, int KIND, int H, int BITS, int WPS, bool ROWS = false, bool EXPLORE = false, bool TARGET = false, bool EXPECT = false>
 inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                         const frirl_hip_convergence *cv, frirl::LearnArgs la, hipStream_t s)
+                         const frirl_hip_convergence *cv, frirl::LearnArgsX la, hipStream_t s)
 {
     constexpr int EPW = FRIRL_WAVE / H, W = frirl::Packed<BITS>::words(N);
     la.tiles = (la.nlive + EPW - 1) / EPW;
@@ -773,28 +801,28 @@ inline void launch_learn(const frirl_hip_tables *t, const frirl_hip_rulebases *b
     const size_t dyn = sizeof(double) * frirl::LR_WPB * EPW * NCOLD_;
     if (dyn > 40 * 1024) {                                                     // static (~24 KB) + dynamic beyond the 64 KB default
         static bool raised = false;                                            // per instantiation
-        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
+        if (!raised) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); raised = true; }
     }
-    hipLaunchKernelGGL((frirl::learn_import_kernel<N, BITS>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
+    hipLaunchKernelGGL((frirl::learn_import_kernel<N, BITS>), dim3(la.tiles), dim3(256), 0, s, static_cast<const frirl::LearnArgs &>(la), H, cv->prev_rconc);
     const int blocks = (la.tiles + frirl::LR_WPB - 1) / frirl::LR_WPB;
-    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, la, *ag, *ev, *cv);
-    hipLaunchKernelGGL((frirl::learn_export_kernel<N>), dim3(la.tiles), dim3(256), 0, s, la, H, cv->prev_rconc);
+    hipLaunchKernelGGL((frirl::learn_kernel<N, NA, KIND, H, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>), dim3(blocks), dim3(frirl::LR_BLOCK), dyn, s, static_cast<const frirl::LearnArgsOf<EXPECT> &>(la), *ag, *ev, *cv);
+    hipLaunchKernelGGL((frirl::learn_export_kernel<N>), dim3(la.tiles), dim3(256), 0, s, static_cast<const frirl::LearnArgs &>(la), H, cv->prev_rconc);
 }
 
 
 // one environment's launcher for the lane-group sizes [HLO, HHI]: each instantiation unit (FRIRL_LEARN_UNIT below) compiles a few
 // kernels, so that the build runs them in parallel
-template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false, bool TARGET = false>
+template <int N, int NA, int KIND, int BITS, int WPS, int HLO, int HHI, bool ROWS = false, bool EXPLORE = false, bool TARGET = false, bool EXPECT = false>
 inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev,
-                           const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s)
+                           const frirl_hip_convergence *cv, const frirl::LearnArgsX &la, hipStream_t s)
 {
-    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
-    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE, TARGET>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 1 && 1 <= HHI) if (H == 1) return launch_learn<N, NA, KIND, 1, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 2 && 2 <= HHI) if (H == 2) return launch_learn<N, NA, KIND, 2, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 4 && 4 <= HHI) if (H == 4) return launch_learn<N, NA, KIND, 4, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 8 && 8 <= HHI) if (H == 8) return launch_learn<N, NA, KIND, 8, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 16 && 16 <= HHI) if (H == 16) return launch_learn<N, NA, KIND, 16, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 32 && 32 <= HHI) if (H == 32) return launch_learn<N, NA, KIND, 32, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
+    if constexpr (HLO <= 64 && 64 <= HHI) if (H == 64) return launch_learn<N, NA, KIND, 64, BITS, WPS, ROWS, EXPLORE, TARGET, EXPECT>(t, b, ag, ev, cv, la, s);
 }
 
 // ---- the launch table ---------------------------------------------------------------------------------------------------------
@@ -807,9 +835,9 @@ inline void launch_learn_h(int H, const frirl_hip_tables *t, const frirl_hip_rul
     X(cartpole_lo, 5, 21, FRIRL_HIP_ENV_CARTPOLE, 10, 2, 2, 8)   \
     X(cartpole_hi, 5, 21, FRIRL_HIP_ENV_CARTPOLE, 10, 2, 16, 64)
 // The families are levels, each with the structs of the one below: 0 = plain, 1 = ROWS (la.hp), 2 = ROWS and EXPLORE (la.ex too),
-// 3 = ROWS, EXPLORE and TARGET (la.tq as well).
-#define FRIRL_LEARN_LEVELS(M, name) M(name, 0) M(name, 1) M(name, 2) M(name, 3)
-constexpr int LEARN_NLEVELS = 4;
+// 3 = ROWS, EXPLORE and TARGET (la.tq as well), 4 = those and EXPECT (la.xp as well).
+#define FRIRL_LEARN_LEVELS(M, name) M(name, 0) M(name, 1) M(name, 2) M(name, 3) M(name, 4)
+constexpr int LEARN_NLEVELS = 5;
 
 struct LearnShape { int NANT, NA, KIND, BITS, WPS, HLO, HHI; };
 #define X(name, ...) LEARN_##name,
@@ -821,14 +849,14 @@ constexpr LearnShape LEARN_SHAPE[LEARN_NSHAPES] = {FRIRL_LEARN_SHAPES(X)};
 
 #define FRIRL_LEARN_LAUNCH_ARGS                                                                                                       \
     int H, const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *ag, const frirl_hip_envs *ev, \
-        const frirl_hip_convergence *cv, const frirl::LearnArgs &la, hipStream_t s
+        const frirl_hip_convergence *cv, const frirl::LearnArgsX &la, hipStream_t s
 typedef void (*frirl_learn_launch_fn)(FRIRL_LEARN_LAUNCH_ARGS);
 
 template <int SHAPE, int LEVEL>
 void frirl_learn_launch(FRIRL_LEARN_LAUNCH_ARGS)
 {
     constexpr LearnShape k = LEARN_SHAPE[SHAPE];
-    launch_learn_h<k.NANT, k.NA, k.KIND, k.BITS, k.WPS, k.HLO, k.HHI, (LEVEL >= 1), (LEVEL >= 2), (LEVEL >= 3)>(H, t, b, ag, ev, cv, la, s);
+    launch_learn_h<k.NANT, k.NA, k.KIND, k.BITS, k.WPS, k.HLO, k.HHI, (LEVEL >= 1), (LEVEL >= 2), (LEVEL >= 3), (LEVEL >= 4)>(H, t, b, ag, ev, cv, la, s);
 }
 
 // Every entry of the table is compiled in a unit of its own, learn_<shape>_<level>.hip, which holds FRIRL_LEARN_UNIT(shape, level)

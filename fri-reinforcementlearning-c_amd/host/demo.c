@@ -26,7 +26,8 @@ static int usage(const char *what)
                     "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n"
                     "       frirl_demo --env NAME --agents N --explore FILE [--hparams FILE] [--seed S] [--id-base B] [--max-episodes M]   (an exploration sweep in one run: FILE holds one `epsilon horizon` pair per line, epsilon falling linearly to zero over `horizon` episodes, 0 = constant; agent e takes line e mod L; S seeds the exploration stream, agent e draws under the global id B + e)\n"
                     "       frirl_demo --env NAME --agents N [--hparams FILE] [--explore FILE] --select G --select-episodes M --select-parents P --select-replace K [--select-inherit] [--evaluate n] [--spread F]   (G generations of M episodes; after each, every agent is evaluated from n start states, default 1, and the K worst become copies of the P best, with --select-inherit also of their rows)\n"
-                    "       frirl_demo --env NAME --agents N [--explore FILE [--seed S] [--id-base B]] --target sarsa|q | --target-rows FILE [--max-episodes M]   (the TD target: every agent learns towards Q(s',a') of the action it takes, sarsa, or towards Q(s',g) of the greedy action, q; FILE holds one 0 (sarsa) or 1 (q) per line, agent e takes line e mod L)\n", what);
+                    "       frirl_demo --env NAME --agents N [--explore FILE [--seed S] [--id-base B]] --target sarsa|q | --target-rows FILE [--max-episodes M]   (the TD target: every agent learns towards Q(s',a') of the action it takes, sarsa, or towards Q(s',g) of the greedy action, q; FILE holds one 0 (sarsa) or 1 (q) per line, agent e takes line e mod L)\n"
+                    "       frirl_demo --env NAME --agents N [--explore FILE [--seed S] [--id-base B]] --expected | --expected-rows FILE [--max-episodes M]   (expected SARSA: a flagged agent learns towards the expectation of Q(s',.) under its own epsilon-greedy pick; FILE holds one 0 or 1 per line, agent e takes line e mod L)\n", what);
     return 2;
 }
 
@@ -51,6 +52,8 @@ int main(int argc, char **argv)
     int stream_given = 0;           /* --seed or --id-base was given */
     int target_all = -1;            /* --target sarsa|q: every agent's TD target (FRIRL_HIP_TARGET_*), -1 = not asked for */
     const char *target_rows = NULL; /* --target-rows FILE: with --agents, agent e learns towards the target on line e mod L of FILE */
+    int expected_all = 0;           /* --expected: every agent learns towards the expectation under its own pick (expected SARSA) */
+    const char *expected_rows = NULL; /* --expected-rows FILE: with --agents, agent e is flagged by the 0 / 1 on line e mod L of FILE */
     int select_gen = 0;             /* --select G: generations of train + frirl_hip_batch_select, 0 = not asked for */
     int select_episodes = 0, select_parents = 0, select_replace = -1, select_inherit = 0;
     char *fargv[16];
@@ -73,6 +76,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--explore") && i + 1 < argc) explore = argv[++i];
         else if (!strcmp(argv[i], "--target") && i + 1 < argc) { const char *v = argv[++i]; target_all = !strcmp(v, "sarsa") ? 0 : !strcmp(v, "q") ? 1 : -1; if (target_all < 0) return usage("--target needs sarsa or q"); }
         else if (!strcmp(argv[i], "--target-rows") && i + 1 < argc) target_rows = argv[++i];
+        else if (!strcmp(argv[i], "--expected")) expected_all = 1;
+        else if (!strcmp(argv[i], "--expected-rows") && i + 1 < argc) expected_rows = argv[++i];
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) { char *end; seed = strtoull(argv[++i], &end, 10); stream_given = 1; if (*end || end == argv[i]) return usage("--seed needs a whole number S >= 0"); }
         else if (!strcmp(argv[i], "--id-base") && i + 1 < argc) { char *end; id_base = strtoull(argv[++i], &end, 10); stream_given = 1; if (*end || end == argv[i]) return usage("--id-base needs a whole number B >= 0"); }
         else if (!strcmp(argv[i], "--spread") && i + 1 < argc) { spread = atof(argv[++i]); if (!(spread >= 0.0 && spread <= 1.0)) return usage("--spread needs 0 <= F <= 1"); }
@@ -84,6 +89,30 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--select-replace") && i + 1 < argc) { select_replace = atoi(argv[++i]); if (select_replace < 0) return usage("--select-replace needs K >= 0"); }
         else if (!strcmp(argv[i], "--select-inherit")) select_inherit = 1;
         else if (fargc < 15) fargv[fargc++] = argv[i];
+    }
+    if (expected_all || expected_rows) {        /* expected SARSA per agent; --explore goes with it */
+        const char *opt = expected_rows ? "--expected-rows" : "--expected";
+        double *eps = NULL;
+        int *horizon = NULL, nx = 0, nf = 0, rc;
+        unsigned char *xf = NULL;
+        char err[256], msg[256];
+        if (expected_all && expected_rows) return usage("--expected and --expected-rows exclude each other");
+        if (merge || gpus >= 0 || teach_best > 0) { snprintf(msg, sizeof msg, "%s does not go with --merge, --gpus or --teach-best: the rule-base exchange, frirl_hip_multi_* and the replay of a teacher's log take no expected SARSA", opt); return usage(msg); }
+        if (agents < 1 || reduce || evaluate > 0 || load_bin || save_bin || hparams || select_gen > 0 || target_all >= 0 || target_rows) { snprintf(msg, sizeof msg, "%s goes with --agents N alone, or with --explore FILE (one device, trained from scratch)", opt); return usage(msg); }
+        if (stream_given && !explore) return usage("--seed and --id-base go with --explore FILE");
+        frirl_parse_cmdline(&fr, fargc, fargv);
+        if (expected_rows && frirl_demo_parse_expected(expected_rows, &xf, &nf, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --expected-rows %s: %s\n", expected_rows, err);
+            return 2;
+        }
+        if (explore && frirl_demo_parse_explore(explore, &eps, &horizon, &nx, err, sizeof err) != 0) {
+            fprintf(stderr, "frirl_demo: --explore %s: %s\n", explore, err);
+            free(xf);
+            return 2;
+        }
+        rc = frirl_demo_batch_run_expected(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, eps, horizon, nx, seed, id_base, xf, nf, expected_all, 1);
+        free(xf); free(eps); free(horizon);
+        return rc >= 0 ? 0 : 3;
     }
     if (target_all >= 0 || target_rows) {       /* a TD target per agent; --explore goes with it */
         const char *opt = target_rows ? "--target-rows" : "--target";

@@ -911,51 +911,64 @@ bad:
     return -1;
 }
 
-/* `agents` agents of a demo in one persistent-learner run, agent e learning towards target[e mod nt] (HOST [nt], the column of
- * frirl_demo_parse_target; NULL: target_all for every agent) and -- eps != NULL -- exploring under pair e mod nx as in
- * frirl_demo_batch_run_explore: frirl_hip_batch_set_target (+ _set_exploration) + frirl_hip_batch_train, then the `batch ENV:` report
- * line with the target at its end and, with eps, one `explore ENV: line s ...` line per pair.  Returns the converged agents, or -1. */
-int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
-                                unsigned long long id_base, const unsigned char *target, int nt, int target_all, int verbose)
+/* The run behind frirl_demo_batch_run_target and frirl_demo_batch_run_expected (`who`: the one that calls, for fatal errors).  `agents`
+ * agents of a demo in one persistent-learner run, every agent under its byte of ONE per-agent column -- with_expected == 0: the TD target
+ * target[e mod nt] (HOST [nt], the column of frirl_demo_parse_target; NULL: target_all for every agent), set with
+ * frirl_hip_batch_set_target; with_expected != 0: the expected-SARSA flag expected[e mod nf] (frirl_demo_parse_expected; NULL:
+ * expected_all), set with frirl_hip_batch_set_expected -- and, eps != NULL, exploring under pair e mod nx as in
+ * frirl_demo_batch_run_explore.  Then frirl_hip_batch_train, the `batch ENV:` report line with the choice at its end and, with eps, one
+ * `explore ENV: line s ...` line per pair.  Returns the converged agents, or -1. */
+static int demo_batch_run_td(const char *who, const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                             unsigned long long id_base, const unsigned char *target, int nt, int target_all, int with_expected, const unsigned char *expected,
+                             int nf, int expected_all, int verbose)
 {
-    int nant = 0, episodes = 0, rc, e, s, nq = 0;
+    int nant = 0, episodes = 0, rc, e, s, nset = 0;      /* nset: agents whose byte is 1 (target Q / expected) */
+    char where[96];
     frirl_hip_batch_desc d;
     struct demo_desc_mem mm;
     frirl_hip_batch *b;
     frirl_hip_batch_stats_t st;
     double *xe = malloc(sizeof(double) * 2 * (size_t)agents), *reward = xe ? xe + agents : NULL;
     int32_t *xh = malloc(sizeof(int32_t) * 4 * (size_t)agents), *conv = xh ? xh + agents : NULL, *eps_run = xh ? conv + agents : NULL, *rules = xh ? eps_run + agents : NULL;
-    uint8_t *tq = malloc((size_t)(agents > 0 ? agents : 1));
-    if (!xe || !xh || !tq || agents < 1 || (eps && nx < 1) || (target && nt < 1)) return -1;
+    uint8_t *col = malloc((size_t)(agents > 0 ? agents : 1));
+    if (!xe || !xh || !col || agents < 1 || (eps && nx < 1) || (target && nt < 1) || (expected && nf < 1)) return -1;
     if (demo_desc_build(env, agents, &d, &mm, &nant) != 0) return -1;
     if (eps) { d.agent.seed = seed; d.agent.env_id_base = id_base; }
     b = frirl_hip_batch_create(&d);
-    if (!b) five_dropin_fatal("frirl_demo_batch_run_target(create)", FRIRL_HIP_ENODEV);
+    if (!b) { snprintf(where, sizeof where, "%s(create)", who); five_dropin_fatal(where, FRIRL_HIP_ENODEV); }
     if (eps) {
         frirl_hip_explore_rows ex;
         for (e = 0; e < agents; e++) { xe[e] = eps[e % nx]; xh[e] = horizon[e % nx]; }
         memset(&ex, 0, sizeof ex);
         ex.epsilon = xe; ex.horizon = xh;
         rc = frirl_hip_batch_set_exploration(b, &ex);
-        if (rc) five_dropin_fatal("frirl_demo_batch_run_target(explore)", rc);
+        if (rc) { snprintf(where, sizeof where, "%s(explore)", who); five_dropin_fatal(where, rc); }
     }
-    for (e = 0; e < agents; e++) { tq[e] = target ? target[e % nt] : (uint8_t)target_all; nq += tq[e] == FRIRL_HIP_TARGET_Q; }
-    rc = frirl_hip_batch_set_target(b, target ? tq : NULL, target ? FRIRL_HIP_TARGET_SARSA : target_all);
-    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(set)", rc);
+    if (with_expected) {
+        for (e = 0; e < agents; e++) { col[e] = expected ? expected[e % nf] : (uint8_t)expected_all; nset += col[e] != 0; }
+        rc = frirl_hip_batch_set_expected(b, expected ? col : NULL, expected ? 0 : expected_all);
+        if (rc) { snprintf(where, sizeof where, "%s(set)", who); five_dropin_fatal(where, rc); }
+    } else {
+        for (e = 0; e < agents; e++) { col[e] = target ? target[e % nt] : (uint8_t)target_all; nset += col[e] == FRIRL_HIP_TARGET_Q; }
+        rc = frirl_hip_batch_set_target(b, target ? col : NULL, target ? FRIRL_HIP_TARGET_SARSA : target_all);
+        if (rc) { snprintf(where, sizeof where, "%s(set)", who); five_dropin_fatal(where, rc); }
+    }
     rc = frirl_hip_batch_train(b, max_episodes, &episodes);
-    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(train)", rc);
+    if (rc) { snprintf(where, sizeof where, "%s(train)", who); five_dropin_fatal(where, rc); }
     rc = frirl_hip_batch_stats(b, &st);
-    if (rc) five_dropin_fatal("frirl_demo_batch_run_target(stats)", rc);
+    if (rc) { snprintf(where, sizeof where, "%s(stats)", who); five_dropin_fatal(where, rc); }
     if (verbose) {
-        printf("batch %s: agents %lld episodes %d converged %lld env-steps %lld mean-rules %.3f mean-reward %.6f (min %.6f max %.6f) target ", env,
+        printf("batch %s: agents %lld episodes %d converged %lld env-steps %lld mean-rules %.3f mean-reward %.6f (min %.6f max %.6f) %s ", env,
                (long long)st.agents, episodes, (long long)st.converged, (long long)st.total_env_steps, st.rules_sum / st.agents,
-               st.reward_sum / st.agents, st.reward_min, st.reward_max);
-        if (target) printf("rows (%d of %d agents q)\n", nq, agents);
+               st.reward_sum / st.agents, st.reward_min, st.reward_max, with_expected ? "expected" : "target");
+        if (with_expected && expected) printf("rows (%d of %d agents expected)\n", nset, agents);
+        else if (with_expected) printf("%s\n", expected_all ? "all" : "none");
+        else if (target) printf("rows (%d of %d agents q)\n", nset, agents);
         else printf("%s\n", target_all == FRIRL_HIP_TARGET_Q ? "q" : "sarsa");
     }
     if (eps && verbose) {
         rc = frirl_hip_batch_agent_report(b, conv, eps_run, rules, NULL, reward);
-        if (rc) five_dropin_fatal("frirl_demo_batch_run_target(report)", rc);
+        if (rc) { snprintf(where, sizeof where, "%s(report)", who); five_dropin_fatal(where, rc); }
         for (s = 0; s < nx && s < agents; s++) {
             long long cnt = 0, nconv = 0, ep_sum = 0, rule_sum = 0;
             int ep_max = 0;
@@ -970,8 +983,62 @@ int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, c
     }
     frirl_hip_batch_destroy(b);
     demo_desc_free(&mm);
-    free(xe); free(xh); free(tq);
+    free(xe); free(xh); free(col);
     return (int)st.converged;
+}
+
+int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const unsigned char *target, int nt, int target_all, int verbose)
+{
+    return demo_batch_run_td("frirl_demo_batch_run_target", env, agents, max_episodes, eps, horizon, nx, seed, id_base, target, nt, target_all, 0, NULL, 0, 0, verbose);
+}
+
+/* ---- expected SARSA per agent: frirl_demo --agents N [--explore FILE] --expected  or  --expected-rows FILE -------------------------------
+ * FILE: one 0 or 1 per line; `#` starts a comment; blank lines are skipped.  *expected = malloc'ed [*n]; err receives "line N: why"
+ * for the first malformed line, or why the file is unusable. */
+int frirl_demo_parse_expected(const char *path, unsigned char **expected, int *n_out, char *err, size_t err_len)
+{
+    char line[512];
+    int lineno = 0, n = 0, cap = 0;
+    unsigned char *ot = NULL;
+    FILE *fp = fopen(path, "r");
+    *expected = NULL; *n_out = 0;
+    if (!fp) { snprintf(err, err_len, "cannot open %s", path); return -1; }
+    while (fgets(line, sizeof line, fp)) {
+        double v;
+        char tail[2], *hash = strchr(line, '#');
+        int got;
+        lineno++;
+        if (!strchr(line, '\n') && !feof(fp)) { snprintf(err, err_len, "line %d: longer than %d characters", lineno, (int)sizeof line - 2); goto bad; }
+        if (hash) *hash = '\0';
+        if (line[strspn(line, " \t\r\n")] == '\0') continue;
+        got = sscanf(line, "%lf %1s", &v, tail);
+        if (got != 1) { snprintf(err, err_len, "line %d: expected 1 value (expected), found %s", lineno, got > 1 ? "more" : "fewer"); goto bad; }
+        if (!(v == 0.0 || v == 1.0)) { snprintf(err, err_len, "line %d: expected %g is neither 0 nor 1", lineno, v); goto bad; }
+        if (n == cap) {
+            unsigned char *gt;
+            cap = cap ? 2 * cap : 16;
+            gt = realloc(ot, (size_t)cap);
+            if (!gt) { snprintf(err, err_len, "out of memory"); goto bad; }
+            ot = gt;
+        }
+        ot[n++] = (unsigned char)v;
+    }
+    fclose(fp);
+    if (n == 0) { snprintf(err, err_len, "%s holds no flag", path); free(ot); return -1; }
+    *expected = ot; *n_out = n;
+    return 0;
+bad:
+    free(ot); fclose(fp);
+    return -1;
+}
+
+/* frirl_demo_batch_run_target with frirl_hip_batch_set_expected in place of _set_target: agent e learns towards the expectation where
+ * expected[e mod nf] is 1 (NULL: expected_all for every agent); the `batch ENV:` line ends in the choice. */
+int frirl_demo_batch_run_expected(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                  unsigned long long id_base, const unsigned char *expected, int nf, int expected_all, int verbose)
+{
+    return demo_batch_run_td("frirl_demo_batch_run_expected", env, agents, max_episodes, eps, horizon, nx, seed, id_base, NULL, 0, 0, 1, expected, nf, expected_all, verbose);
 }
 
 /* ---- selection inside a population: frirl_demo --agents N --select G --select-episodes M --select-parents P --select-replace K ----------

@@ -106,6 +106,17 @@ int frirl_demo_parse_target(const char *path, unsigned char **target, int *n, ch
 int frirl_demo_batch_run_target(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
                                 unsigned long long id_base, const unsigned char *target, int nt, int target_all, int verbose);
 
+/* Expected SARSA per agent in one run (frirl_demo --agents N [--explore FILE] --expected, or --expected-rows FILE).
+ * frirl_demo_parse_expected reads FILE: one 0 or 1 per line, `#` starts a comment, blank lines are skipped; *expected = malloc'ed [*n]
+ * (the caller frees it).  -1 with err = "line N: why" for the first malformed line (not one number, a value other than 0 or 1), or why
+ * the file cannot be used.  No device is touched.
+ * frirl_demo_batch_run_expected: frirl_demo_batch_run_target with frirl_hip_batch_set_expected in place of _set_target -- agent e learns
+ * towards the expectation under its own pick where expected[e mod nf] is 1 (NULL: expected_all for every agent); the `batch ENV: ...`
+ * report line ends in `expected all`, `expected none` or `expected rows (K of N agents expected)`.  Returns the converged agents, or -1. */
+int frirl_demo_parse_expected(const char *path, unsigned char **expected, int *n, char *err, size_t err_len);
+int frirl_demo_batch_run_expected(const char *env, int agents, int max_episodes, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                  unsigned long long id_base, const unsigned char *expected, int nf, int expected_all, int verbose);
+
 /* `agents` agents over `gpus` devices of this node (0 = every visible device) through frirl_hip_multi_* (one batch + host thread per
  * device, per-episode report all-reduced with RCCL); out_txt = rule base of global agent 0.  Returns the converged agents or -1. */
 /* many agents WITH the reference's rule-base exchange (frirl_omp_run: chunks of 9 episodes, merge_rb in both directions after each,

@@ -300,7 +300,7 @@ int frirl_hip_explore_rows_check(const frirl_hip_explore_rows *host_rows, int32_
  * the same bits.
  * The column is [dev] [E], indexed as the columns of frirl_hip_hparam_rows (the agent's index in the batch, never the launch slot).
  * A NULL struct pointer = SARSA for everybody.  Read by frirl_hip_learn_run_target / _train_target and frirl_hip_agent_observe_target
- * only.  Not built: expected SARSA (it needs an update that takes a value instead of a point); a target in the fused demo step
+ * only.  Expected SARSA is a struct of its own (frirl_hip_expect_rows, below).  Not built: a target in the fused demo step
  * (frirl_hip_episode_begin / _step / _steps), frirl_hip_update_sarsa, the lane groups and frirl_hip_episode_run; a target in
  * demonstration replay (its sweep forms two conclusions, not A, so Q(s', g) is not there); a target in merged training and
  * frirl_hip_multi_*. */
@@ -314,6 +314,36 @@ typedef struct frirl_hip_target_rows {
 /* What a valid frirl_hip_target_rows with a HOST column [E] is (no device is touched): reserved 0, target_all 0 or 1, every target[e]
  * 0 or 1.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with the agent named in frirl_hip_last_error (also for E < 1; NULL host_rows is valid). */
 int frirl_hip_target_rows_check(const frirl_hip_target_rows *host_rows, int32_t E);
+
+/* Per-agent expected SARSA: an agent whose `expected` flag is set learns towards the expectation of Q(s', .) under its own pick,
+ * qp = v, and its target byte (frirl_hip_target_rows) is then not consulted.  At a learning step, let c[0..A-1] be the conclusions of
+ * the fused sweep at s', each the exact-hit consequent or the Shepard quotient exactly as the sweep forms them; g the greedy action,
+ * the first maximum; eps the agent's exploration rate of the episode the step belongs to (frirl_hip_explore_epsilon(epsilon, horizon,
+ * episode) of its exploration row, agent->epsilon without one), and 0 where agent->no_random == 1.  The expectation is taken over what
+ * the pick really does: it takes the random branch with probability eps and then chooses lround(u * A) clamped to A - 1, so action 0
+ * has weight 0.5 / A, action A - 1 has 1.5 / A and the others 1 / A (A == 1: the single weight is 1):
+ *     S = c[0] + c[1] + ... + c[A-1]          (ascending a, FP64)
+ *     M = (S - 0.5 * c[0]) + 0.5 * c[A-1]
+ *     v = (1.0 - eps) * c[g] + (eps / A) * M    where eps != 0     (each operation rounded on its own: no fused multiply-add)
+ *     v = c[g]  (the value itself, no arithmetic) where eps == 0
+ * Nothing else moves: the action taken (the pick's or the teacher's) goes to cur_q_ant, ve2 and action_out, the next pending point is
+ * (s', a'), and in the learner the weight bound of the next step is still formed from the weight sum of a'.  A taught row takes the
+ * teacher's action and learns towards the expectation under its own eps.  With eps == 0 v is c[g]: a non-exploring agent gives the bits
+ * of the Q target, which without a teacher are the bits of SARSA.  This is the reference's frirl_update_sarsa called with gamma 0 and
+ * the reward  reward + gamma * v.
+ * The column is [dev] [E], indexed as the columns of frirl_hip_hparam_rows (the agent's index in the batch, never the launch slot).
+ * A NULL struct pointer = nobody.  Read by frirl_hip_learn_run_expect / _train_expect and frirl_hip_agent_observe_expect only.  Not
+ * built: the flag in the fused demo step (frirl_hip_episode_begin / _step / _steps), frirl_hip_update_sarsa, the lane groups and
+ * frirl_hip_episode_run; in demonstration replay; in merged training and across GPUs (frirl_hip_multi_*). */
+typedef struct frirl_hip_expect_rows {
+    const uint8_t *expected;   /* [dev][E] of 0 / 1, indexed like the other rows; NULL = expected_all */
+    int32_t expected_all;      /* 0 / 1 */
+    uint32_t reserved;         /* 0 */
+} frirl_hip_expect_rows;       /* 16 bytes; NULL struct pointer = nobody learns towards the expectation */
+/* What a valid frirl_hip_expect_rows with a HOST column [E] is (no device is touched): reserved 0, expected_all 0 or 1, every
+ * expected[e] 0 or 1, refused in that order.  FRIRL_HIP_OK, or FRIRL_HIP_EINVAL with the agent named in frirl_hip_last_error (also for
+ * E < 1; NULL host_rows is valid). */
+int frirl_hip_expect_rows_check(const frirl_hip_expect_rows *host_rows, int32_t E);
 
 /* Test probe of the exploration stream, in the form every learning and roll-out kernel calls it.  For key tuple i the global id is
  * agent->env_id_base + env[i] and the word is the SplitMix64 output function of
@@ -941,6 +971,16 @@ int frirl_hip_agent_observe_target(const frirl_hip_tables *t, const frirl_hip_ru
                                    const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target,
                                    const frirl_hip_envs *envs, const frirl_hip_agent_io *io, const int32_t *teacher, void *stream);
 
+/* ---- per-agent expected SARSA: _observe_target with frirl_hip_expect_rows (above) after `target`.  A flagged row takes its action as
+ * in the _explore call and updates towards the expectation v of Q(s', .) under its own exploration rate; its target byte is not
+ * consulted.  expect NULL is the _target call, bit for bit; so is an all-zero column or expected_all 0.  Values are not validated here
+ * (frirl_hip_expect_rows_check does that for a host column).  Refusals as the taught pair, in its order.  There is no _begin_expect:
+ * begin performs no update. */
+int frirl_hip_agent_observe_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent,
+                                   const frirl_hip_hparam_rows *rows, const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target,
+                                   const frirl_hip_expect_rows *expect, const frirl_hip_envs *envs, const frirl_hip_agent_io *io,
+                                   const int32_t *teacher, void *stream);
+
 /* ---- one-launch replay of recorded demonstrations: every agent learns a log of (observation, action, reward, success) records in
  * ONE launch, one workgroup per agent looping over its records; no environment runs.  nant 2..8, A 1..32, any Shepard power.
  * Per record r of agent e (its log starts at record e * agent_stride of every array):
@@ -1224,6 +1264,22 @@ int frirl_hip_learn_train_target(const frirl_hip_tables *t, const frirl_hip_rule
                                  const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work, int64_t *steps_total,
                                  uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out, frirl_hip_learn_chunk_fn on_chunk,
                                  void *user, void *stream);
+/* ... and with per-agent expected SARSA (frirl_hip_expect_rows, above) after `target`: a flagged agent learns towards the expectation
+ * of Q(s', .) under its own pick.  Any of the four structs may be NULL; expect == NULL calls the _target entry point, anything else runs
+ * a fifth kernel family (EXPECT, level 4 of the launch table), which loads the agent's flag with its row values after the rule sweep and
+ * keeps the sum of the A conclusions and the first and last of them beside the greedy one -- a family of its own, so that nobody who
+ * does not ask for it pays for it (profiles/r30_expected.md).  Same shapes, workspace sizes and refusals, in the same order.  With an
+ * all-zero column or expected_all 0 the results are those of the _target call, bit for bit; with every agent flagged,
+ * agent->no_random == 1 and no rows they are those of the unsuffixed call. */
+int frirl_hip_learn_run_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                               const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                               const frirl_hip_envs *envs, const frirl_hip_convergence *conv, const int32_t *live, int32_t nlive, int32_t budget_steps,
+                               int32_t max_episodes, int64_t *work, int64_t *steps_total, void *workspace, size_t workspace_bytes, void *stream);
+int frirl_hip_learn_train_expect(const frirl_hip_tables *t, const frirl_hip_rulebases *b, const frirl_hip_agent *agent, const frirl_hip_hparam_rows *rows,
+                                 const frirl_hip_explore_rows *explore, const frirl_hip_target_rows *target, const frirl_hip_expect_rows *expect,
+                                 const frirl_hip_envs *envs, const frirl_hip_convergence *conv, int32_t budget_steps, int32_t max_episodes, int64_t *work,
+                                 int64_t *steps_total, uint8_t *refused, void *workspace, size_t workspace_bytes, int32_t *launches_out,
+                                 frirl_hip_learn_chunk_fn on_chunk, void *user, void *stream);
 
 /* Persistent form for SMALL rule bases (the demos' learning regime): one wave keeps its environment's rule base,
  * the tables and the episode state in LDS and runs up to nsteps consecutive steps without a global round trip per
@@ -1377,6 +1433,15 @@ int frirl_hip_batch_set_target(frirl_hip_batch *b, const uint8_t *host_target /*
 /* The target a batch trains under, back on the host: host_target HOST [E] is filled with the set column, or with target_all (0 while
  * none is set) for every agent. */
 int frirl_hip_batch_get_target(frirl_hip_batch *b, uint8_t *host_target /* HOST [E] out */);
+/* Per-agent expected SARSA for frirl_hip_batch_train: host_expected holds a HOST column [E] of 0 / 1 (NULL: expected_all for every
+ * agent), validated as frirl_hip_expect_rows_check does and copied; (NULL, 0) clears it.  A rejected call leaves the batch as it was;
+ * the shape restriction is that of frirl_hip_batch_set_hparams.  While the column is set frirl_hip_batch_train goes through
+ * frirl_hip_learn_train_expect (with whatever other rows are set); frirl_hip_batch_episode, _train_merged, _merge_round and _teach
+ * return FRIRL_HIP_EINVAL naming themselves.  frirl_hip_batch_clone(inherit_rows != 0) gathers a set column like any other. */
+int frirl_hip_batch_set_expected(frirl_hip_batch *b, const uint8_t *host_expected /* HOST [E] or NULL */, int32_t expected_all);
+/* The flags a batch trains under, back on the host: host_expected HOST [E] is filled with the set column, or with expected_all (0
+ * while none is set) for every agent. */
+int frirl_hip_batch_get_expected(frirl_hip_batch *b, uint8_t *host_expected /* HOST [E] out */);
 /* rule base of agent e: *R rules, rant HOST [>= *R][nant] (AoS), rconc HOST [>= *R] (pass NULL to query *R only) */
 int frirl_hip_batch_get_rulebase(frirl_hip_batch *b, int32_t e, int32_t *R, double *rant, double *rconc);
 /* Rule bases of all agents to / from one file.  The file is E records back to back, each exactly what
