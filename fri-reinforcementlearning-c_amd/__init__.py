@@ -121,6 +121,28 @@ class SelectResult(C.Structure):
 CLONE_KEPT, CLONE_CLONED, CLONE_BAD_SRC, CLONE_CHAINED, CLONE_BAD_RULES = range(5)      # FRIRL_HIP_CLONE_*
 
 
+class SelectInfo(C.Structure):
+    """struct frirl_hip_select_info (include/frirl_hip.h)."""
+    _fields_ = [("N", C.c_int32), ("status", C.c_int32), ("best", C.c_int32), ("bad_agent", C.c_int32)]
+
+
+PLAN_OK, PLAN_NAN, PLAN_TOO_FEW = range(3)                                              # FRIRL_HIP_PLAN_*
+# FRIRL_HIP_PERTURB_*: the bit of a column in PerturbSpec.columns; 0..4 take (down, up, lo, hi), 5..7 a flip probability
+PERTURB_COLUMNS = ("alpha", "gamma", "weight_significant", "epsilon", "horizon", "skip_rules", "target", "expected")
+
+
+class PerturbSpec(C.Structure):
+    """struct frirl_hip_perturb_spec (include/frirl_hip.h)."""
+    _fields_ = [("columns", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("down", C.c_double * 5), ("up", C.c_double * 5),
+                ("lo", C.c_double * 5), ("hi", C.c_double * 5), ("flip", C.c_double * 3)]
+
+
+class EvolveResult(C.Structure):
+    """struct frirl_hip_evolve_result (include/frirl_hip.h)."""
+    _fields_ = [("best", C.c_int32), ("parents", C.c_int32), ("replaced", C.c_int32), ("perturbed", C.c_int32), ("rules_copied", C.c_int64),
+                ("generation", C.c_int32), ("plan_status", C.c_int32)]
+
+
 class BatchDesc(C.Structure):
     """struct frirl_hip_batch_desc (include/frirl_hip.h)."""
     _fields_ = [("nant", C.c_int32), ("U", C.c_int32), ("E", C.c_int32), ("maxR", C.c_int32), ("u", C.c_void_p), ("ve", C.c_void_p),
@@ -432,6 +454,15 @@ SIGNATURES = {
     "frirl_hip_batch_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
     "frirl_hip_batch_select": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_int, C.POINTER(RolloutScore), C.POINTER(C.c_int32),
                                          C.POINTER(SelectResult)]),
+    "frirl_hip_select_plan_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "frirl_hip_perturb_spec_check": (C.c_int, [C.POINTER(PerturbSpec)]),
+    "frirl_hip_perturb_column_name": (C.c_char_p, [C.c_int32]),
+    "frirl_hip_perturb_rows": (C.c_int, [C.POINTER(PerturbSpec), C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(HparamRowsDesc), C.POINTER(ExploreRowsDesc),
+                                         C.POINTER(TargetRowsDesc), C.POINTER(ExpectRowsDesc), C.c_void_p, C.c_void_p]),
+    "frirl_hip_batch_evolve_step": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_int, C.POINTER(PerturbSpec), C.POINTER(EvolveResult)]),
+    "frirl_hip_batch_evolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_int, C.POINTER(PerturbSpec),
+                                         C.POINTER(EvolveResult)]),
+    "frirl_hip_batch_evolve_best_score": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _DP]),
     "frirl_hip_batch_get_hparams": (C.c_int, [C.c_void_p, C.POINTER(HparamRowsDesc)]),
     "frirl_hip_batch_get_exploration": (C.c_int, [C.c_void_p, C.POINTER(ExploreRowsDesc)]),
     "frirl_hip_batch_merge_round": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -1070,6 +1101,16 @@ class Problem:
               "frirl_hip_clone_agents")
         return status
 
+    def select_plan_device(self, scores, parents, replace, eligible=None, stream=None):
+        """select_plan_device (below) for the E agents of this problem: (src, rank, info) as device tensors."""
+        assert scores.shape[0] == self.E, (tuple(scores.shape), self.E)
+        return select_plan_device(scores, parents, replace, eligible=eligible, stream=stream)
+
+    def perturb_rows(self, spec, generation, status, rows=None, explore=None, target=None, expect=None, stream=None):
+        """perturb_rows (below) for the E agents of this problem: the rows are rewritten in place; returns the count tensor."""
+        assert status.shape == (self.E,), (tuple(status.shape), self.E)
+        return perturb_rows(spec, generation, status, rows=rows, explore=explore, target=target, expect=expect, stream=stream)
+
     def add_rule(self, rant, rconc, active=None, rant_store=None, stream=None):
         """five_hip_add_rule: appends rant[e] -> rconc[e]; returns added [E] int32."""
         import torch
@@ -1648,6 +1689,79 @@ def batch_select(batch, n, parents, replace, start_states=None, inherit_rows=Fal
     check(lib().frirl_hip_batch_select(batch, n, None if st is None else st.ctypes.data_as(_DP), parents, replace, 1 if inherit_rows else 0, scores,
                                        src.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)), "frirl_hip_batch_select")
     return list(scores), src, res
+
+
+def select_plan_device(scores, parents, replace, eligible=None, stream=None):
+    """frirl_hip_select_plan_device: scores is the [E, 40] uint8 device tensor of Problem.rollout_batch(scores=True), eligible a device
+    tensor [E] uint8 / bool or None = all.  Returns (src [E] int32, rank [E] int32 padded with -1, info [4] int32: N, status (PLAN_*),
+    best, bad_agent) on the device.  Does not synchronise."""
+    import torch
+    assert scores.is_cuda and scores.dtype == torch.uint8 and scores.dim() == 2 and scores.shape[1] == C.sizeof(RolloutScore) and scores.is_contiguous()
+    E = scores.shape[0]
+    if eligible is not None:
+        eligible = eligible.view(torch.uint8) if eligible.dtype == torch.bool else eligible
+        assert eligible.is_cuda and eligible.dtype == torch.uint8 and eligible.shape == (E,) and eligible.is_contiguous()
+    src = torch.empty((max(E, 1),), dtype=torch.int32, device=scores.device)
+    rank, info = torch.empty_like(src), torch.empty((4,), dtype=torch.int32, device=scores.device)
+    check(lib().frirl_hip_select_plan_device(_ptr(scores), E, _ptr(eligible), parents, replace, _ptr(src), _ptr(rank), _ptr(info), _stream(stream)),
+          "frirl_hip_select_plan_device")
+    return src, rank, info
+
+
+def perturb_spec(seed=0, **columns):
+    """A PerturbSpec from keywords named as PERTURB_COLUMNS: alpha / gamma / weight_significant / epsilon / horizon take
+    (down, up, lo, hi), skip_rules / target / expected a flip probability.  Only the columns given are enabled."""
+    unknown = set(columns) - set(PERTURB_COLUMNS)
+    if unknown:
+        raise TypeError(f"perturb_spec: unknown column(s) {sorted(unknown)}; the columns are {PERTURB_COLUMNS}")
+    spec = PerturbSpec()
+    spec.seed = int(seed)
+    for name, v in columns.items():
+        c = PERTURB_COLUMNS.index(name)
+        spec.columns |= 1 << c
+        if c < 5:
+            spec.down[c], spec.up[c], spec.lo[c], spec.hi[c] = (float(x) for x in v)
+        else:
+            spec.flip[c - 5] = float(v)
+    return spec
+
+
+def perturb_rows(spec, generation, status, rows=None, explore=None, target=None, expect=None, stream=None):
+    """frirl_hip_perturb_rows: the agents whose status ([E] int32 on the device, as Problem.clone_agents returns it) is CLONE_CLONED get
+    the enabled columns of rows (HparamRows), explore (ExploreRows), target (TargetRows) and expect (ExpectRows) stepped or flipped in
+    place under the draws of (spec.seed, agent, generation, column).  Returns the [1] int32 device tensor counting the agents touched.
+    Does not synchronise."""
+    import torch
+    assert status.is_cuda and status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous()
+    E = status.shape[0]
+    count = torch.empty((1,), dtype=torch.int32, device=status.device)
+    check(lib().frirl_hip_perturb_rows(C.byref(spec), int(generation), E, _ptr(status), _rows(rows, E), _rows(explore, E), _rows(target, E), _rows(expect, E),
+                                       _ptr(count), _stream(stream)), "frirl_hip_perturb_rows")
+    return count
+
+
+def batch_evolve_step(batch, n, parents, replace, start_states=None, inherit_rows=False, spec=None):
+    """frirl_hip_batch_evolve_step on a library-owned batch: evaluate, rank, plan, clone, inherit and (with a PerturbSpec) perturb on the
+    batch's stream, one read-back.  start_states: host [E, n, nant-1] or None = every agent's own.  Returns the EvolveResult."""
+    import numpy as np
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    assert st is None or (st.ndim == 3 and st.shape[:2] == (_batch_agents(batch), n))
+    res = EvolveResult()
+    check(lib().frirl_hip_batch_evolve_step(batch, n, None if st is None else st.ctypes.data_as(_DP), parents, replace, 1 if inherit_rows else 0,
+                                            None if spec is None else C.byref(spec), C.byref(res)), "frirl_hip_batch_evolve_step")
+    return res
+
+
+def batch_evolve(batch, generations, episodes_per_generation, n, parents, replace, start_states=None, inherit_rows=False, spec=None):
+    """frirl_hip_batch_evolve: `generations` times frirl_hip_batch_train for episodes_per_generation more episodes, then
+    batch_evolve_step.  Returns the list of EvolveResult, one per generation."""
+    import numpy as np
+    st = None if start_states is None else np.ascontiguousarray(start_states, dtype=np.float64)
+    assert st is None or (st.ndim == 3 and st.shape[:2] == (_batch_agents(batch), n))
+    res = (EvolveResult * max(generations, 1))()
+    check(lib().frirl_hip_batch_evolve(batch, generations, episodes_per_generation, n, None if st is None else st.ctypes.data_as(_DP), parents, replace,
+                                       1 if inherit_rows else 0, None if spec is None else C.byref(spec), res), "frirl_hip_batch_evolve")
+    return list(res)[:generations]
 
 
 def batch_get_hparams(batch):

@@ -49,6 +49,11 @@ struct frirl_hip_batch {
     uint8_t *d_xp;               // [E] per-agent expected-SARSA flags of frirl_hip_batch_set_expected (allocated on first use)
     frirl_hip_expect_rows xp;    // the device column if one is set, and expected_all
     bool xp_set;                 // flags other than 0 for everybody are set
+    int32_t *d_evo;              // src, rank, status [E] each, then the read-back block of frirl_hip_batch_evolve_step (allocated on first use)
+    uint32_t generation;         // successful evolve steps so far: keys the perturbation draws
+    bool evo_scored;             // evo_successes / evo_reward hold the best agent's score of the last successful step
+    int32_t evo_successes;
+    double evo_reward;
     std::vector<int32_t> h_i;
     std::vector<double> h_d;
 };
@@ -127,7 +132,7 @@ extern "C" void frirl_hip_batch_destroy(frirl_hip_batch *b)
     if (b->s) (void)hipStreamSynchronize(b->s);
     void *ptrs[] = {b->d_u, b->d_ve, b->d_rb, b->d_rant, b->d_grid, b->d_ave, b->d_states, b->d_q_ant, b->d_ep_reward, b->d_start, b->d_prev_reward,
                     b->d_prev_rconc, b->d_tmp, b->d_nrules, b->d_fus, b->d_done, b->d_ep_steps, b->d_status, b->d_episode, b->d_prev_nrules,
-                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h, b->d_tq, b->d_xp};
+                    b->d_prev_steps, b->d_converged, b->d_episodes, b->d_epended, b->d_uidx, b->d_lanes_ws, b->d_learn_ws, b->d_steps_total, b->d_weights, b->d_active, b->d_full, b->d_spread_ant, b->d_spread_R, b->d_hp, b->d_hp_skip, b->d_ex_eps, b->d_ex_h, b->d_tq, b->d_xp, b->d_evo};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (b->s) (void)hipStreamDestroy(b->s);
     delete b;
@@ -790,27 +795,40 @@ extern "C" int frirl_hip_batch_reduce_all_map_orders(frirl_hip_batch *b, int ord
     return batch_reduce_all_map_run(who, b, 0, order_set, n, start_states, only_successful, cap, nullptr, results, after_per_order, totals);
 }
 
-extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)
+// what frirl_hip_batch_evaluate refuses before it looks at the device
+static int evaluate_args_check(const char *who, const frirl_hip_batch *b, int32_t n)
 {
-    static const char *who = "frirl_hip_batch_evaluate";
     if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
     if (n < 1 || (int64_t)b->E * n > INT32_MAX) { set_error("%s: n=%d outside 1..INT32_MAX / E", who, n); return FRIRL_HIP_EINVAL; }
-    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    return FRIRL_HIP_OK;
+}
+
+// The device part of an evaluation: buffers allocated (q.mem, the caller frees it after synchronising), start states uploaded and the
+// greedy roll-outs queued on b->s.  The scores stay on the device, [E] at the start of q.mem.  `he` takes a failed runtime call; the
+// caller synchronises in every case, since `q.own` and `q.mem` may be in use by the upload.
+struct EvalQueued {
+    char *mem = nullptr;
+    std::vector<double> own;
+    frirl_hip_rollout_score *scores() const { return reinterpret_cast<frirl_hip_rollout_score *>(mem); }
+};
+
+static int batch_evaluate_queue(frirl_hip_batch *b, int32_t n, const double *start_states, EvalQueued &q, hipError_t &he)
+{
     const size_t E = (size_t)b->E, ns = (size_t)b->nant - 1, Q = E * (size_t)n;
     // every row at the agent's own start: its desc.start_states row n times (agent.values_def where the batch has none: no array at all)
-    std::vector<double> own;
     if (!start_states && b->d_start) {
         std::vector<double> one(E * ns);
         BCHK(hipMemcpy(one.data(), b->d_start, sizeof(double) * E * ns, hipMemcpyDeviceToHost), "start states download");
-        own.resize(Q * ns);
-        for (size_t q = 0; q < Q; q++) memcpy(&own[q * ns], &one[(q / (size_t)n) * ns], sizeof(double) * ns);
-        start_states = own.data();
+        q.own.resize(Q * ns);
+        for (size_t r = 0; r < Q; r++) memcpy(&q.own[r * ns], &one[(r / (size_t)n) * ns], sizeof(double) * ns);
+        start_states = q.own.data();
     }
     const size_t ws_bytes = frirl_hip_rollout_batch_workspace_bytes(b->nant, b->E, b->maxR, n, b->agent.A);
     const size_t off_reward = (sizeof(frirl_hip_rollout_score) * E + 15) / 16 * 16, off_start = off_reward + sizeof(double) * Q;
     const size_t off_steps = off_start + (start_states ? sizeof(double) * Q * ns : 0), off_ws = (off_steps + sizeof(int32_t) * 2 * Q + 15) / 16 * 16;
     char *mem = nullptr;
     BCHK(hipMalloc(reinterpret_cast<void **>(&mem), off_ws + ws_bytes), "evaluation buffers");
+    q.mem = mem;
     frirl_hip_rollout_batch_rows ro = {};
     ro.n = n;
     ro.reward = reinterpret_cast<double *>(mem + off_reward);
@@ -818,18 +836,30 @@ extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const dou
     ro.success = ro.steps + Q;
     frirl_hip_agent greedy = b->agent;
     greedy.no_random = 1;                                             // an evaluation is greedy (frirl_test_run: reduction_state == 1)
-    std::vector<frirl_hip_rollout_score> sc(E);
     int rc = FRIRL_HIP_OK;
-    hipError_t he = hipSuccess;
     if (start_states) {
         ro.start_states = reinterpret_cast<double *>(mem + off_start);
         he = hipMemcpyAsync(mem + off_start, start_states, sizeof(double) * Q * ns, hipMemcpyHostToDevice, b->s);
     }
-    if (he == hipSuccess) rc = frirl_hip_rollout_batch(&b->t, &b->rb, &greedy, &ro, reinterpret_cast<frirl_hip_rollout_score *>(mem), mem + off_ws, ws_bytes, b->s);
-    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(sc.data(), mem, sizeof(frirl_hip_rollout_score) * E, hipMemcpyDeviceToHost, b->s);
-    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `own` and `mem` may be in use by the upload
+    if (he == hipSuccess) rc = frirl_hip_rollout_batch(&b->t, &b->rb, &greedy, &ro, q.scores(), mem + off_ws, ws_bytes, b->s);
+    return rc;
+}
+
+extern "C" int frirl_hip_batch_evaluate(frirl_hip_batch *b, int32_t n, const double *start_states, frirl_hip_rollout_score *scores, int32_t *best)
+{
+    static const char *who = "frirl_hip_batch_evaluate";
+    if (evaluate_args_check(who, b, n)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    const size_t E = (size_t)b->E;
+    std::vector<frirl_hip_rollout_score> sc(E);
+    EvalQueued q;
+    hipError_t he = hipSuccess;
+    const int rc = batch_evaluate_queue(b, n, start_states, q, he);
+    if (!q.mem) return rc;                                            // nothing was queued
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(sc.data(), q.mem, sizeof(frirl_hip_rollout_score) * E, hipMemcpyDeviceToHost, b->s);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `q.own` and `q.mem` may be in use by the upload
     else (void)hipStreamSynchronize(b->s);
-    (void)hipFree(mem);
+    (void)hipFree(q.mem);
     if (rc) return rc;
     if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
     int32_t win = 0;                                                  // most successes, then the largest reward_sum, then the lowest index
@@ -963,7 +993,47 @@ __global__ void inherit_rows_kernel(const int32_t *__restrict__ src, const int32
     if (b0) b0[e] = b0[s];
     if (b1) b1[e] = b1[s];
 }
+
+// what one frirl_hip_batch_evolve_step reads back: the plan's info, then what the reduction below and the perturbation count
+struct EvolveBlock {
+    frirl_hip_select_info info;
+    int32_t replaced, perturbed;
+    unsigned long long rules_copied;
+    int32_t best_successes, reserved;
+    double best_reward;
+};                                  // 48 bytes
+
+// behind clone and perturbation: agents cloned and the rules they took over (nrules[e] is nrules[src[e]] by now), the best agent's score
+__global__ __launch_bounds__(256) void evolve_reduce_kernel(const int32_t *__restrict__ status, const int32_t *__restrict__ nrules, int E,
+                                                            const frirl_hip_rollout_score *__restrict__ scores, EvolveBlock *__restrict__ out)
+{
+    __shared__ int s_n;
+    __shared__ unsigned long long s_rules;
+    if (threadIdx.x == 0) { s_n = 0; s_rules = 0; }
+    __syncthreads();
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < E && status[e] == FRIRL_HIP_CLONE_CLONED) {
+        atomicAdd(&s_n, 1);
+        atomicAdd(&s_rules, (unsigned long long)nrules[e]);
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (s_n) { atomicAdd(&out->replaced, s_n); atomicAdd(&out->rules_copied, s_rules); }
+    const int best = out->info.best;
+    if (blockIdx.x == 0 && best >= 0 && best < E) { out->best_successes = scores[best].successes; out->best_reward = scores[best].reward_sum; }
+}
 }  // namespace frirl
+
+// frirl_hip_batch_clone(inherit_rows != 0): the gather of every set column, queued behind the clone
+static void queue_inherit_rows(frirl_hip_batch *b, const int32_t *d_src, const int32_t *d_status)
+{
+    if (!(b->hp_set || b->ex_set || b->tq_set || b->xp_set)) return;
+    const frirl_hip_hparam_rows &h = b->hp;
+    hipLaunchKernelGGL(frirl::inherit_rows_kernel, dim3((b->E + 255) / 256), dim3(256), 0, b->s, d_src, d_status, b->E, const_cast<double *>(h.alpha),
+                       const_cast<double *>(h.gamma), const_cast<double *>(h.qdiff_pos_boundary), const_cast<double *>(h.qdiff_neg_boundary),
+                       const_cast<double *>(h.weight_significant), const_cast<double *>(b->ex.epsilon), const_cast<int32_t *>(h.skip_rules),
+                       const_cast<int32_t *>(b->ex.horizon), const_cast<uint8_t *>(b->tq.target), const_cast<uint8_t *>(b->xp.expected));
+}
 
 static int batch_clone_run(const char *who, frirl_hip_batch *b, const int32_t *src, int inherit_rows, int32_t *cloned, int64_t *rules_copied)
 {
@@ -983,13 +1053,7 @@ static int batch_clone_run(const char *who, frirl_hip_batch *b, const int32_t *s
     // no image of a rule base outlives a call (d_lanes_ws and d_learn_ws are imported from rb / uidx at the start of every call that
     // uses them), so there is nothing to invalidate beside the arrays the clone itself rewrites
     if (he == hipSuccess) rc = frirl_hip_clone_agents(&b->rb, b->nant, &b->envs, &b->conv, b->d_weights, d_src, d_status, b->s);
-    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows && (b->hp_set || b->ex_set || b->tq_set || b->xp_set)) {
-        const frirl_hip_hparam_rows &h = b->hp;
-        hipLaunchKernelGGL(frirl::inherit_rows_kernel, dim3((E + 255) / 256), dim3(256), 0, b->s, d_src, d_status, E, const_cast<double *>(h.alpha),
-                           const_cast<double *>(h.gamma), const_cast<double *>(h.qdiff_pos_boundary), const_cast<double *>(h.qdiff_neg_boundary),
-                           const_cast<double *>(h.weight_significant), const_cast<double *>(b->ex.epsilon), const_cast<int32_t *>(h.skip_rules),
-                           const_cast<int32_t *>(b->ex.horizon), const_cast<uint8_t *>(b->tq.target), const_cast<uint8_t *>(b->xp.expected));
-    }
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows) queue_inherit_rows(b, d_src, d_status);
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
     if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemcpyAsync(nr.data(), b->d_nrules, sizeof(int32_t) * E, hipMemcpyDeviceToHost, b->s);
     if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of the call: `src` may be in use by the upload
@@ -1028,6 +1092,103 @@ extern "C" int frirl_hip_batch_select(frirl_hip_batch *b, int32_t n, const doubl
     if (scores) memcpy(scores, sc.data(), sizeof(frirl_hip_rollout_score) * b->E);
     if (src_out) memcpy(src_out, src.data(), sizeof(int32_t) * b->E);
     if (result) *result = frirl_hip_select_result{best, parents, cloned, 0, rules};
+    return FRIRL_HIP_OK;
+}
+
+// ---- population-based training: the selection leg queued on the stream, one read-back (select_device.hip) --------------------------
+// what frirl_hip_batch_evolve_step refuses before it looks at the device
+static int evolve_args_check(const char *who, const frirl_hip_batch *b, int32_t n, int32_t parents, int32_t replace, const frirl_hip_perturb_spec *spec)
+{
+    if (evaluate_args_check(who, b, n)) return FRIRL_HIP_EINVAL;
+    if (parents < 1) { set_error("%s: parents=%d < 1", who, parents); return FRIRL_HIP_EINVAL; }
+    if (replace < 0) { set_error("%s: replace=%d < 0", who, replace); return FRIRL_HIP_EINVAL; }
+    if ((int64_t)parents + replace > b->E) {
+        set_error("%s: parents=%d + replace=%d exceeds the %d agents (a parent would be replaced)", who, parents, replace, b->E);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (!spec) return FRIRL_HIP_OK;
+    if (frirl_hip_perturb_spec_check(spec)) return FRIRL_HIP_EINVAL;
+    const void *set[8] = {b->hp.alpha, b->hp.gamma, b->hp.weight_significant, b->ex.epsilon, b->ex.horizon, b->hp.skip_rules, b->tq.target, b->xp.expected};
+    for (int c = 0; c < 8; c++)
+        if ((spec->columns >> c & 1) && !set[c]) {
+            set_error("%s: the spec perturbs %s, a column this batch has not set (frirl_hip_batch_set_*)", who, frirl_hip_perturb_column_name(c));
+            return FRIRL_HIP_EINVAL;
+        }
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_evolve_step(frirl_hip_batch *b, int32_t n, const double *start_states, int32_t parents, int32_t replace, int inherit_rows,
+                                           const frirl_hip_perturb_spec *spec, frirl_hip_evolve_result *result)
+{
+    static const char *who = "frirl_hip_batch_evolve_step";
+    if (evolve_args_check(who, b, n, parents, replace, spec)) return FRIRL_HIP_EINVAL;
+    DeviceGuard keep_device_; BCHK(hipSetDevice(b->device), "hipSetDevice");
+    const int E = b->E;
+    const size_t block_at = ((size_t)3 * E + 3) / 4 * 4;             // in int32s: the block starts on a 16-byte boundary
+    if (!b->d_evo && !dalloc(&b->d_evo, block_at + sizeof(frirl::EvolveBlock) / sizeof(int32_t))) {
+        set_error("%s: HIP allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return FRIRL_HIP_ELAUNCH;
+    }
+    int32_t *d_src = b->d_evo, *d_rank = d_src + E, *d_status = d_rank + E;
+    frirl::EvolveBlock *d_block = reinterpret_cast<frirl::EvolveBlock *>(b->d_evo + block_at), h = {};
+    EvalQueued q;
+    hipError_t he = hipSuccess;
+    int rc = batch_evaluate_queue(b, n, start_states, q, he);
+    if (!q.mem) return rc;                                            // nothing was queued
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) he = hipMemsetAsync(d_block, 0, sizeof *d_block, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) rc = frirl_hip_select_plan_device(q.scores(), E, nullptr, parents, replace, d_src, d_rank, &d_block->info, b->s);
+    // a plan refused on the device left src at the identity: everything behind it then finds nobody cloned
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) rc = frirl_hip_clone_agents(&b->rb, b->nant, &b->envs, &b->conv, b->d_weights, d_src, d_status, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && inherit_rows) queue_inherit_rows(b, d_src, d_status);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK && spec)
+        rc = frirl_hip_perturb_rows(spec, b->generation, E, d_status, &b->hp, &b->ex, &b->tq, &b->xp, &d_block->perturbed, b->s);
+    if (he == hipSuccess && rc == FRIRL_HIP_OK) {
+        hipLaunchKernelGGL(frirl::evolve_reduce_kernel, dim3((E + 255) / 256), dim3(256), 0, b->s, d_status, b->d_nrules, E, q.scores(), d_block);
+        he = hipMemcpyAsync(&h, d_block, sizeof h, hipMemcpyDeviceToHost, b->s);
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(b->s);            // also on failure of a call: `q.own` and `q.mem` may be in use by the upload
+    else (void)hipStreamSynchronize(b->s);
+    (void)hipFree(q.mem);
+    if (rc) return rc;
+    if (he != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(he)); return FRIRL_HIP_ELAUNCH; }
+    if ((rc = check_launch(who))) return rc;
+    if (h.info.status == FRIRL_HIP_PLAN_NAN) { set_error("%s: agent %d: reward_sum is NaN (nothing was cloned)", who, h.info.bad_agent); return FRIRL_HIP_EINVAL; }
+    if (h.info.status != FRIRL_HIP_PLAN_OK) {
+        set_error("%s: plan status %d: parents=%d + replace=%d exceeds the %d eligible agents, bad_agent %d (nothing was cloned)", who, h.info.status, parents, replace,
+                  h.info.N, h.info.bad_agent);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (result) *result = frirl_hip_evolve_result{h.info.best, parents, h.replaced, h.perturbed, (int64_t)h.rules_copied, (int32_t)b->generation, h.info.status};
+    b->generation++;
+    b->evo_scored = true; b->evo_successes = h.best_successes; b->evo_reward = h.best_reward;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_evolve_best_score(frirl_hip_batch *b, int32_t *successes, double *reward_sum)
+{
+    static const char *who = "frirl_hip_batch_evolve_best_score";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (!b->evo_scored) { set_error("%s: no frirl_hip_batch_evolve_step has succeeded on this batch yet", who); return FRIRL_HIP_EINVAL; }
+    if (successes) *successes = b->evo_successes;
+    if (reward_sum) *reward_sum = b->evo_reward;
+    return FRIRL_HIP_OK;
+}
+
+extern "C" int frirl_hip_batch_evolve(frirl_hip_batch *b, int32_t generations, int32_t episodes_per_generation, int32_t n, const double *start_states,
+                                      int32_t parents, int32_t replace, int inherit_rows, const frirl_hip_perturb_spec *spec, frirl_hip_evolve_result *results)
+{
+    static const char *who = "frirl_hip_batch_evolve";
+    if (!b) { set_error("%s: NULL batch", who); return FRIRL_HIP_EINVAL; }
+    if (generations < 1 || episodes_per_generation < 1) {
+        set_error("%s: generations=%d / episodes_per_generation=%d below 1", who, generations, episodes_per_generation);
+        return FRIRL_HIP_EINVAL;
+    }
+    if (evolve_args_check(who, b, n, parents, replace, spec)) return FRIRL_HIP_EINVAL;      // before anything is trained
+    for (int32_t g = 0; g < generations; g++) {
+        int rc = frirl_hip_batch_train(b, episodes_per_generation + 1, nullptr);
+        if (rc == FRIRL_HIP_OK) rc = frirl_hip_batch_evolve_step(b, n, start_states, parents, replace, inherit_rows, spec, results ? results + g : nullptr);
+        if (rc) return rc;
+    }
     return FRIRL_HIP_OK;
 }
 

@@ -26,6 +26,7 @@ static int usage(const char *what)
                     "       frirl_demo --env NAME --agents N --hparams FILE [--max-episodes M]   (a sweep in one run: FILE holds one set per line, `alpha gamma qdiff_pos qdiff_neg weight_thr skip_rules`, # comments; agent e takes line e mod L)\n"
                     "       frirl_demo --env NAME --agents N --explore FILE [--hparams FILE] [--seed S] [--id-base B] [--max-episodes M]   (an exploration sweep in one run: FILE holds one `epsilon horizon` pair per line, epsilon falling linearly to zero over `horizon` episodes, 0 = constant; agent e takes line e mod L; S seeds the exploration stream, agent e draws under the global id B + e)\n"
                     "       frirl_demo --env NAME --agents N [--hparams FILE] [--explore FILE] --select G --select-episodes M --select-parents P --select-replace K [--select-inherit] [--evaluate n] [--spread F]   (G generations of M episodes; after each, every agent is evaluated from n start states, default 1, and the K worst become copies of the P best, with --select-inherit also of their rows)\n"
+                    "         with --select: [--select-perturb col:down:up:lo:hi]... [--select-flip col:p]... [--select-seed S]   (population-based training: a clone's row value is multiplied by down or up, a coin flip per agent, generation and column, and clamped to [lo, hi]; col = alpha | gamma | weight_significant | skip_rules with --hparams, epsilon | horizon with --explore; a 0 / 1 column flips with probability p)\n"
                     "       frirl_demo --env NAME --agents N [--explore FILE [--seed S] [--id-base B]] --target sarsa|q | --target-rows FILE [--max-episodes M]   (the TD target: every agent learns towards Q(s',a') of the action it takes, sarsa, or towards Q(s',g) of the greedy action, q; FILE holds one 0 (sarsa) or 1 (q) per line, agent e takes line e mod L)\n"
                     "       frirl_demo --env NAME --agents N [--explore FILE [--seed S] [--id-base B]] --expected | --expected-rows FILE [--max-episodes M]   (expected SARSA: a flagged agent learns towards the expectation of Q(s',.) under its own epsilon-greedy pick; FILE holds one 0 or 1 per line, agent e takes line e mod L)\n", what);
     return 2;
@@ -56,7 +57,9 @@ int main(int argc, char **argv)
     const char *expected_rows = NULL; /* --expected-rows FILE: with --agents, agent e is flagged by the 0 / 1 on line e mod L of FILE */
     int select_gen = 0;             /* --select G: generations of train + frirl_hip_batch_select, 0 = not asked for */
     int select_episodes = 0, select_parents = 0, select_replace = -1, select_inherit = 0;
+    struct frirl_demo_perturb perturb;  /* --select-perturb col:down:up:lo:hi, --select-flip col:p, --select-seed S: the clones' rows are perturbed */
     char *fargv[16];
+    memset(&perturb, 0, sizeof perturb);
     fargv[fargc++] = argv[0];
     for (i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--env") && i + 1 < argc) env = argv[++i];
@@ -88,8 +91,31 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--select-parents") && i + 1 < argc) { select_parents = atoi(argv[++i]); if (select_parents < 1) return usage("--select-parents needs P >= 1"); }
         else if (!strcmp(argv[i], "--select-replace") && i + 1 < argc) { select_replace = atoi(argv[++i]); if (select_replace < 0) return usage("--select-replace needs K >= 0"); }
         else if (!strcmp(argv[i], "--select-inherit")) select_inherit = 1;
+        else if (!strcmp(argv[i], "--select-perturb") && i + 1 < argc) {
+            char col[32];
+            double v[4];
+            int used = 0, c;
+            const char *arg = argv[++i];
+            if (sscanf(arg, "%31[^:]:%lf:%lf:%lf:%lf%n", col, &v[0], &v[1], &v[2], &v[3], &used) != 5 || arg[used] || (c = frirl_demo_perturb_column(col)) < 0 || c > 4)
+                return usage("--select-perturb needs col:down:up:lo:hi with col one of alpha, gamma, weight_significant, epsilon, horizon");
+            perturb.columns |= 1u << c;
+            perturb.down[c] = v[0]; perturb.up[c] = v[1]; perturb.lo[c] = v[2]; perturb.hi[c] = v[3];
+        }
+        else if (!strcmp(argv[i], "--select-flip") && i + 1 < argc) {
+            char col[32];
+            double p;
+            int used = 0, c;
+            const char *arg = argv[++i];
+            if (sscanf(arg, "%31[^:]:%lf%n", col, &p, &used) != 2 || arg[used] || (c = frirl_demo_perturb_column(col)) < 5)
+                return usage("--select-flip needs col:p with col one of skip_rules, target, expected");
+            perturb.columns |= 1u << c;
+            perturb.flip[c - 5] = p;
+        }
+        else if (!strcmp(argv[i], "--select-seed") && i + 1 < argc) { char *end; perturb.seed = strtoull(argv[++i], &end, 10); perturb.given = 1; if (*end || end == argv[i]) return usage("--select-seed needs a whole number S >= 0"); }
         else if (fargc < 15) fargv[fargc++] = argv[i];
     }
+    if (perturb.columns) perturb.given = 1;
+    if (perturb.given && select_gen < 1) return usage("--select-perturb / --select-flip / --select-seed go with --select G");
     if (expected_all || expected_rows) {        /* expected SARSA per agent; --explore goes with it */
         const char *opt = expected_rows ? "--expected-rows" : "--expected";
         double *eps = NULL;
@@ -149,6 +175,7 @@ int main(int argc, char **argv)
         if (select_episodes < 1 || select_parents < 1 || select_replace < 0) return usage("--select needs --select-episodes M, --select-parents P and --select-replace K");
         if (select_parents + select_replace > agents) return usage("--select-parents P + --select-replace K exceeds --agents N: a parent would be replaced");
         if (stream_given && !explore) return usage("--seed and --id-base go with --explore FILE");
+        if (perturb.given && frirl_demo_perturb_check(&perturb, hparams != NULL, explore != NULL, err, sizeof err) != 0) return usage(err);
         frirl_parse_cmdline(&fr, fargc, fargv);
         if (frirl_demo_describe(env, &ns, &U, &A, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, &ms) != 0) return 2;
         if (hparams && frirl_demo_parse_hparams(hparams, &sets, &nsets, err, sizeof err) != 0) {
@@ -163,8 +190,12 @@ int main(int argc, char **argv)
         units = malloc(sizeof(double) * (size_t)agents * (size_t)rows * (size_t)ns);
         if (!units) return 1;
         frirl_demo_row_units(agents, rows, ns, units);
-        rc = frirl_demo_batch_run_select(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, select_gen, select_episodes, select_parents, select_replace,
-                                         select_inherit, rows, spread, units, eps, horizon, nx, seed, id_base, sets, nsets, 1);
+        if (perturb.given)
+            rc = frirl_demo_batch_run_evolve(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, select_gen, select_episodes, select_parents, select_replace,
+                                             select_inherit, rows, spread, units, eps, horizon, nx, seed, id_base, sets, nsets, &perturb, 1);
+        else
+            rc = frirl_demo_batch_run_select(env, agents, max_episodes > 0 ? max_episodes : fr.max_episodes, select_gen, select_episodes, select_parents, select_replace,
+                                             select_inherit, rows, spread, units, eps, horizon, nx, seed, id_base, sets, nsets, 1);
         free(units); free(sets); free(eps); free(horizon);
         return rc >= 0 ? 0 : 3;
     }

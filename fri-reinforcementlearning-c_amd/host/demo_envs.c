@@ -1045,10 +1045,11 @@ int frirl_demo_batch_run_expected(const char *env, int agents, int max_episodes,
  * G generations of frirl_hip_batch_train(M + 1) followed by frirl_hip_batch_select (every agent evaluated from `rows` start states, as
  * --evaluate maps them; the `replace` worst become copies of the `parents` best, with `inherit` also of their rows), one `select ENV:
  * generation g ...` line each; then training goes on to max_episodes and the report line follows.  sets / eps + horizon: the sweeps of
- * frirl_demo_batch_run_hparams / _explore, or NULL.  Returns the number of converged agents, or -1. */
-int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
-                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
-                                unsigned long long id_base, const double *sets, int nsets, int verbose)
+ * frirl_demo_batch_run_hparams / _explore, or NULL.  Returns the number of converged agents, or -1.
+ * With spec != NULL (frirl_demo_batch_run_evolve) the selection is frirl_hip_batch_evolve_step and the line ends in ` perturbed K`. */
+static int demo_batch_run_select(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                 int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                 unsigned long long id_base, const double *sets, int nsets, const frirl_hip_perturb_spec *spec, int verbose)
 {
     int nant = 0, ns, episodes = 0, rc, e, k, g;
     frirl_hip_batch_desc d;
@@ -1095,6 +1096,18 @@ int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, i
         frirl_hip_select_result res;
         rc = frirl_hip_batch_train(b, gen_episodes + 1, &episodes);
         if (rc) five_dropin_fatal("frirl_demo_batch_run_select(train)", rc);
+        if (spec) {
+            frirl_hip_evolve_result ev;
+            int32_t successes = 0;
+            double reward = 0.0;
+            rc = frirl_hip_batch_evolve_step(b, rows, start, parents, replace, inherit, spec, &ev);
+            if (rc == 0) rc = frirl_hip_batch_evolve_best_score(b, &successes, &reward);
+            if (rc) five_dropin_fatal("frirl_demo_batch_run_evolve(evolve step)", rc);
+            if (verbose)
+                printf("select %s: generation %d best %d successes %d reward %.6f replaced %d rules_copied %lld perturbed %d\n", env, g, (int)ev.best, (int)successes,
+                       reward, (int)ev.replaced, (long long)ev.rules_copied, (int)ev.perturbed);
+            continue;
+        }
         rc = frirl_hip_batch_select(b, rows, start, parents, replace, inherit, sc, NULL, &res);
         if (rc) five_dropin_fatal("frirl_demo_batch_run_select(select)", rc);
         if (verbose)
@@ -1117,4 +1130,61 @@ int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, i
     demo_desc_free(&mm);
     free(sc); free(col); free(skip); free(start);
     return (int)st.converged;
+}
+
+int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const double *sets, int nsets, int verbose)
+{
+    return demo_batch_run_select(env, agents, max_episodes, generations, gen_episodes, parents, replace, inherit, rows, spread, units, eps, horizon, nx, seed, id_base,
+                                 sets, nsets, NULL, verbose);
+}
+
+/* ---- population-based training: frirl_demo ... --select G ... --select-perturb / --select-flip / --select-seed ------------------------ */
+static void demo_perturb_spec(const struct frirl_demo_perturb *p, frirl_hip_perturb_spec *spec)
+{
+    memset(spec, 0, sizeof *spec);
+    spec->columns = p->columns;
+    spec->seed = p->seed;
+    memcpy(spec->down, p->down, sizeof spec->down); memcpy(spec->up, p->up, sizeof spec->up);
+    memcpy(spec->lo, p->lo, sizeof spec->lo); memcpy(spec->hi, p->hi, sizeof spec->hi);
+    memcpy(spec->flip, p->flip, sizeof spec->flip);
+}
+
+int frirl_demo_perturb_column(const char *name)
+{
+    int c;
+    for (c = 0; name && c < 8; c++)
+        if (!strcmp(name, frirl_hip_perturb_column_name(c))) return c;
+    return -1;
+}
+
+int frirl_demo_perturb_check(const struct frirl_demo_perturb *p, int have_hparams, int have_explore, char *err, size_t err_len)
+{
+    frirl_hip_perturb_spec spec;
+    int c;
+    if (!p || !err || err_len < 1) return -1;
+    demo_perturb_spec(p, &spec);
+    if (frirl_hip_perturb_spec_check(&spec) != 0) { snprintf(err, err_len, "%s", frirl_hip_last_error()); return -1; }
+    for (c = 0; c < 8; c++) {
+        const int with_hparams = c <= FRIRL_HIP_PERTURB_WEIGHT_SIGNIFICANT || c == FRIRL_HIP_PERTURB_SKIP_RULES;
+        const int with_explore = c == FRIRL_HIP_PERTURB_EPSILON || c == FRIRL_HIP_PERTURB_HORIZON;
+        if (!(p->columns >> c & 1)) continue;
+        if (with_hparams ? have_hparams : with_explore ? have_explore : 0) continue;
+        snprintf(err, err_len, "column %s is perturbed but the run does not set it: %s", frirl_hip_perturb_column_name(c),
+                 with_hparams ? "give --hparams FILE" : with_explore ? "give --explore FILE" : "--select goes with neither --target nor --expected");
+        return -1;
+    }
+    return 0;
+}
+
+int frirl_demo_batch_run_evolve(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const double *sets, int nsets, const struct frirl_demo_perturb *perturb, int verbose)
+{
+    frirl_hip_perturb_spec spec;
+    if (!perturb) return -1;
+    demo_perturb_spec(perturb, &spec);
+    return demo_batch_run_select(env, agents, max_episodes, generations, gen_episodes, parents, replace, inherit, rows, spread, units, eps, horizon, nx, seed, id_base,
+                                 sets, nsets, &spec, verbose);
 }

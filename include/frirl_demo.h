@@ -94,6 +94,26 @@ int frirl_demo_batch_run_select(const char *env, int agents, int max_episodes, i
                                 int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
                                 unsigned long long id_base, const double *sets, int nsets, int verbose);
 
+/* Population-based training (frirl_demo ... --select G ... [--select-perturb col:down:up:lo:hi]... [--select-flip col:p]...
+ * [--select-seed S]): the run of frirl_demo_batch_run_select with every generation's selection through frirl_hip_batch_evolve_step,
+ * the clones' rows perturbed as frirl_hip_perturb_rows defines it; the generation line ends in ` perturbed K`.  struct
+ * frirl_demo_perturb holds the fields of frirl_hip_perturb_spec for a host that does not include frirl_hip.h.
+ * frirl_demo_perturb_column: the column index of a name (alpha, gamma, weight_significant, epsilon, horizon, skip_rules, target,
+ * expected), or -1.  frirl_demo_perturb_check: 0, or -1 with err = why the values are refused (frirl_hip_perturb_spec_check) or which
+ * column the run does not set (alpha, gamma, weight_significant, skip_rules come with --hparams, epsilon and horizon with --explore;
+ * a --select run sets neither target nor expected).  No device is touched by either. */
+struct frirl_demo_perturb {
+    unsigned columns;               /* bit c = column c is perturbed */
+    int given;                      /* one of the three flags was given */
+    unsigned long long seed;
+    double down[5], up[5], lo[5], hi[5], flip[3];
+};
+int frirl_demo_perturb_column(const char *name);
+int frirl_demo_perturb_check(const struct frirl_demo_perturb *p, int have_hparams, int have_explore, char *err, size_t err_len);
+int frirl_demo_batch_run_evolve(const char *env, int agents, int max_episodes, int generations, int gen_episodes, int parents, int replace, int inherit,
+                                int rows, double spread, const double *units, const double *eps, const int *horizon, int nx, unsigned long long seed,
+                                unsigned long long id_base, const double *sets, int nsets, const struct frirl_demo_perturb *perturb, int verbose);
+
 /* A TD target per agent in one run (frirl_demo --agents N [--explore FILE] --target sarsa|q, or --target-rows FILE).
  * frirl_demo_parse_target reads FILE: one 0 (FRIRL_HIP_TARGET_SARSA) or 1 (FRIRL_HIP_TARGET_Q) per line, `#` starts a comment, blank
  * lines are skipped; *target = malloc'ed [*n] (the caller frees it).  -1 with err = "line N: why" for the first malformed line (not one

@@ -1577,6 +1577,92 @@ int frirl_hip_batch_select(frirl_hip_batch *b, int32_t n, const double *start_st
 int frirl_hip_batch_get_hparams(frirl_hip_batch *b, const frirl_hip_hparam_rows *host_out);
 int frirl_hip_batch_get_exploration(frirl_hip_batch *b, const frirl_hip_explore_rows *host_out);
 
+/* ---- population-based training on the device: rank, plan, perturb rows (csrc/select_device.hip) ---------------------------------------
+ * frirl_hip_select_plan_device is the contract of frirl_hip_select_plan with every array on the device: it reads nothing back, does
+ * not synchronise and allocates nothing (four launches on `stream`).  N = the eligible agents (eligible: [dev][E] of 0 / 1, NULL =
+ * all).  rank[0..N-1] orders them by most successes, then the largest reward_sum, then the lowest index; reward_sum is compared as a
+ * double, so -0.0 ties with +0.0 (the index decides) and infinities order normally; rank[N..E-1] = -1.  src[e] = e for everybody, then
+ * for k < replace: src[rank[N-1-k]] = rank[k % parents].  info->N = N, info->best = rank[0] (-1 when nothing was ranked).
+ * What the host cannot see is refused on the device, in info->status:
+ *   FRIRL_HIP_PLAN_NAN      an eligible agent's reward_sum is NaN; info->bad_agent = the lowest such index (else -1)
+ *   FRIRL_HIP_PLAN_TOO_FEW  parents + replace > N (a parent would be replaced)
+ * and then src is the identity, rank all -1 and best -1: a frirl_hip_clone_agents queued behind the call clones nothing.  A NaN of
+ * an ineligible agent is not looked at.  FRIRL_HIP_EINVAL naming the cause, before the device is looked for: NULL scores / src / rank /
+ * info, E < 1, parents < 1, replace < 0, parents + replace > E.
+ * The ranking counts, for every agent, the eligible agents that beat it -- E * E key comparisons out of LDS, no sort, no wait between
+ * workgroups; measured in profiles/r31_evolve.md.  Not built: a sorting form for populations far beyond 65 536. */
+typedef struct frirl_hip_select_info { int32_t N, status, best, bad_agent; } frirl_hip_select_info;   /* 16 bytes, [dev] */
+#define FRIRL_HIP_PLAN_OK      0
+#define FRIRL_HIP_PLAN_NAN     1
+#define FRIRL_HIP_PLAN_TOO_FEW 2
+int frirl_hip_select_plan_device(const frirl_hip_rollout_score *scores /* [dev][E] */, int32_t E, const uint8_t *eligible /* [dev][E] or NULL */,
+                                 int32_t parents, int32_t replace, int32_t *src /* [dev][E] out */, int32_t *rank /* [dev][E] out */,
+                                 frirl_hip_select_info *info /* [dev] out */, void *stream);
+
+/* frirl_hip_perturb_rows: the explore step of population-based training.  For every agent e with status[e] == FRIRL_HIP_CLONE_CLONED
+ * (the status array frirl_hip_clone_agents wrote) and every column c that is enabled in spec->columns AND whose device pointer in
+ * hp / ex / tq / xp is not NULL (a NULL struct = all its columns NULL; such a column is skipped):
+ *     u = the exploration stream of frirl_hip_explore_check with keys (spec->seed, global id e, episode `generation`, step c, draw 0);
+ *         e is the agent's index in the batch, NOT offset by env_id_base
+ *     columns 0..3 (double):  f = u < 0.5 ? down[c] : up[c];  v' = fmin(fmax(v * f, lo[c]), hi[c])    one rounded multiplication
+ *     column 4 (horizon):     x = floor((double)h * f + 0.5), clamped to [lo, hi] as above, then converted to int32 (truncated)
+ *     columns 5..7 (0 / 1):   v' = u < flip[c - 5] ? 1 - v : v
+ * Every other agent and every other column stay bit for bit.  A value of exactly 0 stays 0 under a multiplicative step (an epsilon
+ * or horizon of 0 never comes back; give such agents a positive lo if they are to).  *perturbed (or NULL) = the agents touched.  Reads
+ * nothing back, does not synchronise, allocates nothing.  FRIRL_HIP_EINVAL: NULL spec / status, E < 1, a spec that
+ * frirl_hip_perturb_spec_check refuses.
+ * Not built: the qdiff bounds (their pair invariant pos >= neg would need both columns read together), additive steps, resampling
+ * from a prior. */
+#define FRIRL_HIP_PERTURB_ALPHA              0
+#define FRIRL_HIP_PERTURB_GAMMA              1
+#define FRIRL_HIP_PERTURB_WEIGHT_SIGNIFICANT 2
+#define FRIRL_HIP_PERTURB_EPSILON            3
+#define FRIRL_HIP_PERTURB_HORIZON            4
+#define FRIRL_HIP_PERTURB_SKIP_RULES         5
+#define FRIRL_HIP_PERTURB_TARGET             6
+#define FRIRL_HIP_PERTURB_EXPECTED           7
+typedef struct frirl_hip_perturb_spec {
+    uint32_t columns;      /* bit c set = column c is perturbed */
+    uint32_t reserved;     /* 0 */
+    uint64_t seed;
+    double down[5], up[5], lo[5], hi[5];   /* columns 0..4 */
+    double flip[3];                        /* columns 5..7 */
+} frirl_hip_perturb_spec;                  /* 200 bytes */
+/* Host only: reserved == 0 and columns < 256; for the enabled columns down and up in [1/16, 16], lo <= hi and both finite, epsilon
+ * bounds inside [0, 1], weight_significant lo >= 0, horizon bounds inside 0 .. 2^30, flip in [0, 1].  FRIRL_HIP_EINVAL names the
+ * column in frirl_hip_last_error. */
+int frirl_hip_perturb_spec_check(const frirl_hip_perturb_spec *spec);
+const char *frirl_hip_perturb_column_name(int32_t column);      /* "alpha" ... "expected"; NULL outside 0..7 */
+int frirl_hip_perturb_rows(const frirl_hip_perturb_spec *spec, uint32_t generation, int32_t E, const int32_t *status /* [dev][E]: FRIRL_HIP_CLONE_* */,
+                           const frirl_hip_hparam_rows *hp, const frirl_hip_explore_rows *ex, const frirl_hip_target_rows *tq,
+                           const frirl_hip_expect_rows *xp, int32_t *perturbed /* [dev] or NULL */, void *stream);
+
+/* One generation's selection leg on the batch's stream: the evaluation roll-outs of frirl_hip_batch_evaluate(n, start_states),
+ * frirl_hip_select_plan_device over all agents, frirl_hip_clone_agents, with inherit_rows != 0 the row gather of frirl_hip_batch_clone,
+ * with spec != NULL frirl_hip_perturb_rows keyed by the batch's generation counter, and a reduction of replaced / rules_copied /
+ * perturbed -- all queued, then ONE read-back of 48 bytes and one synchronisation.  (With start_states == NULL on a batch that has
+ * own start states those are read back first, as frirl_hip_batch_evaluate does.)  With spec == NULL the batch afterwards is byte for
+ * byte what frirl_hip_batch_select with the same arguments leaves.  The generation counter starts at 0, is returned in
+ * result->generation and advances with every successful step.
+ * Refusals, each leaving rule bases, rows and the generation counter as they were: those of frirl_hip_batch_evaluate; parents < 1,
+ * replace < 0, parents + replace > E; a spec that frirl_hip_perturb_spec_check refuses; a spec that enables a column the batch has
+ * not set (named); a plan status other than OK on the device (FRIRL_HIP_EINVAL naming bad_agent: src was the identity, nothing was
+ * cloned).
+ * frirl_hip_batch_evolve: `generations` times frirl_hip_batch_train(episodes_per_generation + 1) -- that many more episodes -- then
+ * _evolve_step; results[g] (HOST, or NULL) as the step of generation g fills it.  frirl_hip_batch_train still synchronises inside:
+ * only the selection leg is free of host crossings.
+ * Not built: the qdiff bounds, additive steps, selection across GPUs (frirl_hip_multi_*), cloning into another batch. */
+typedef struct frirl_hip_evolve_result { int32_t best, parents, replaced, perturbed; int64_t rules_copied; int32_t generation, plan_status; } frirl_hip_evolve_result;  /* 32 bytes */
+int frirl_hip_batch_evolve_step(frirl_hip_batch *b, int32_t n, const double *start_states /* as frirl_hip_batch_evaluate */, int32_t parents,
+                                int32_t replace, int inherit_rows, const frirl_hip_perturb_spec *spec /* or NULL */,
+                                frirl_hip_evolve_result *result /* or NULL */);
+int frirl_hip_batch_evolve(frirl_hip_batch *b, int32_t generations, int32_t episodes_per_generation, int32_t n, const double *start_states,
+                           int32_t parents, int32_t replace, int inherit_rows, const frirl_hip_perturb_spec *spec /* or NULL */,
+                           frirl_hip_evolve_result *results /* HOST [generations] or NULL */);
+/* successes and reward_sum of result->best in the evaluation of the last successful frirl_hip_batch_evolve_step (they come with its
+ * read-back); FRIRL_HIP_EINVAL before the first one. */
+int frirl_hip_batch_evolve_best_score(frirl_hip_batch *b, int32_t *successes, double *reward_sum);
+
 /* One round of the reference's multi-agent rule-base exchange (frirl_omp_run, frirl_agent.c:426-462) inside the batch: every agent
  * id >= 1 takes over the master's (agent 0's) rules -- all of them in one launch of frirl_hip_merge_rb --, then the master takes
  * over the rules of agent 1, 2, ... in turn.  Agents whose rule base is complete do not send (:432,:444).  *full_agents (or NULL):
